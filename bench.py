@@ -14,10 +14,14 @@ inside the timed region.  Scene upload and acceleration-structure build happen b
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (a torch.distributed.run child,
 spawned before this process touches the GPU) and relays rank 0's JSON line; under an external launcher
-(RANK / WORLD_SIZE in the environment) it is one of the ranks.  With the default --config 2 on one GPU
-the line also carries "configs": one pass each of config 3 and config 4 (both network precisions), the 3-D scenes
-(uniform3d, guided3d), a 2-D scene with a Neumann boundary on the tree (neumann2d), the guiding gain and the variance check
-(--no-extras skips them); at N > 1 it carries one pass of config 5.
+(RANK / WORLD_SIZE in the environment) it is one of the ranks.
+
+A plain run does only what the headline needs: set-up, --warmup passes, --steps timed passes, the outputs of the last
+timed pass when --dump-outputs DIR is given, and the line.  --full adds everything else: the time-to-1spp probe, the CPU
+baseline and the field checked against the oracle (uniform configs), the network-kernel probe and the field checks (guided
+configs), and -- with the default --config 2 on one GPU -- "configs": one pass each of config 3 and config 4 (both network
+precisions), the 3-D scenes (uniform3d, guided3d), a 2-D scene with a Neumann boundary on the tree (neumann2d), the guiding
+gain and the variance check (--no-extras skips them); at N > 1 it carries one pass of config 5.
 
 Rank 0 prints ONE JSON line on stdout, the complete one; when extras follow the headline it also goes to stderr, marked
 "partial", as soon as it is measured (a run that is cut off keeps it in the log).
@@ -76,7 +80,39 @@ def parse_args(argv=None):
     ap.add_argument("--no-1spp", action="store_true", help="skip the time-to-1spp probe (profiling runs)")
     ap.add_argument("--steps-per-round", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="key=value passed to wost_set_option")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the probes, baselines, oracle checks and other configurations beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the field and walk-step count of the last timed pass as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy.  Past DUMP_MAX_BYTES in all, a large array is written as a fixed,
+    seeded sample of its rows (<name>_sample.npy) with the row indices beside it (<name>_sample_rows.npy, float64), so that
+    two runs with the same arguments write the same files."""
+    import numpy as np
+    header = 4096            # bytes allowed for the header of one .npy file
+    os.makedirs(dirname, exist_ok=True)
+    room = DUMP_MAX_BYTES
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes + header <= room:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+            room -= a.nbytes + header
+            continue
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a
+        k = max(0, (room - 2 * header) // (rows[0].nbytes + 8))
+        pick = np.sort(np.random.default_rng(0).choice(len(rows), size=k, replace=False))
+        np.save(os.path.join(dirname, name + "_sample.npy"), rows[pick])
+        np.save(os.path.join(dirname, name + "_sample_rows.npy"), pick.astype(np.float64))
+        room -= k * (rows[0].nbytes + 8) + 2 * header
 
 
 def self_launch(args):
@@ -254,12 +290,12 @@ def run_uniform(env, scene, frame, spp, depth, steps, warmup, args, one_spp=True
     env.barrier()
     elapsed = time.perf_counter() - t0
 
-    tot = torch.tensor([float(steps_local)], dtype=torch.float64, device=env.dev)
+    tot = torch.tensor([float(steps_local), float(st["walk_steps"])], dtype=torch.float64, device=env.dev)
     mx = torch.tensor([elapsed], dtype=torch.float64, device=env.dev)
     env.reduce(tot, env.dist.ReduceOp.SUM)
     env.reduce(mx, env.dist.ReduceOp.MAX)
     elapsed = float(mx[0].item())
-    total_steps = float(tot[0].item())
+    total_steps, last_steps = float(tot[0].item()), float(tot[1].item())
     # The dominant kernel launch of the last timed pass, priced by SURVEY 8(d): 98 algorithmic bytes per walk step x the walk steps
     # THAT launch took / its duration (HIP events around it on the solve's stream, wost_last_launches).  Since round 6 a full-frame
     # solve is one persistent launch of walk_round_kernel (resident lanes take whole pixels, longest expected chain first) plus a
@@ -325,7 +361,7 @@ def run_uniform(env, scene, frame, spp, depth, steps, warmup, args, one_spp=True
                             "step_lane_fill": steps_local / (sched["step_trips"] * 64.0),
                             "trav_trips_per_wave_step": sched["trav_trips"] * 64.0 / steps_local,
                             "step_trips_per_wave_step": sched["step_trips"] * 64.0 / steps_local}
-    res = {"out": out, "field": field, "problem": problem, "depth": depth, "eps": eps, "it": it}
+    res = {"out": out, "field": field, "last_walk_steps": last_steps, "problem": problem, "depth": depth, "eps": eps, "it": it}
     return res
 
 
@@ -371,17 +407,17 @@ def run_guided(env, scene, frame, spp, train_spp, depth, steps, warmup, args, pr
         keys = ("walk_steps", "guided_steps", "train_samples", "optimizer_steps", "net_points", "kernel_launches")
         vals = [float(s.get(k, 0)) for k in keys] + [s["train_ms"], s.get("net_infer_ms", 0.0), s["solve_ms"]]
         agg = vals if agg is None else [a + b for a, b in zip(agg, vals)]
-    tot = torch.tensor(agg[:6], dtype=torch.float64, device=env.dev)
+    tot = torch.tensor(agg[:6] + [float(s["walk_steps"])], dtype=torch.float64, device=env.dev)
     mx = torch.tensor([elapsed] + agg[6:], dtype=torch.float64, device=env.dev)
     env.reduce(tot, env.dist.ReduceOp.SUM)
     env.reduce(mx, env.dist.ReduceOp.MAX)
     elapsed = float(mx[0].item())
-    walk_steps, guided_steps, train_samples, opt_steps, net_points, launches = [float(x) for x in tot.tolist()]
+    walk_steps, guided_steps, train_samples, opt_steps, net_points, launches, last_steps = [float(x) for x in tot.tolist()]
     train_s, infer_s, solve_s = float(mx[1]) / 1e3, float(mx[2]) / 1e3, float(mx[3]) / 1e3
     walk_s = max(elapsed - train_s, 1e-9)
     half = (precision or args.net_precision) == 16
     probe = None
-    if infer_s <= 0 and net_points > 0:
+    if infer_s <= 0 and net_points > 0 and args.full:
         # the solve evaluates the network inside its walk kernel (one launch per sample): the matrix fraction of the
         # network kernel is measured on a short pass of the per-depth path (same network arithmetic, launches timed apart)
         prev = os.environ.get("WOST_GUIDED_FUSED")
@@ -445,7 +481,9 @@ def run_guided(env, scene, frame, spp, train_spp, depth, steps, warmup, args, pr
                           "kernel_s_per_pass": infer_s / steps if infer_s > 0 else None,
                           "probe": None if (infer_s > 0 or probe is None) else {"points": probe_points, "kernel_s": probe_s}},
     }
-    return {"out": out, "field": field, "problem": problem, "depth": depth, "eps": eps}
+    if infer_s <= 0 and not args.full:
+        del out["mfma_probe_of_net_forward_kernel"]      # the probe is a pass of its own: --full only
+    return {"out": out, "field": field, "last_walk_steps": last_steps, "problem": problem, "depth": depth, "eps": eps}
 
 
 REORDERED = (0, 16)      # (pipeline, train_group) of the configs.*_pipelined entries
@@ -702,7 +740,7 @@ def main():
     uniform_field = None
     if cfg["kind"] == "uniform":
         r = run_uniform(env, cfg["scene"], cfg["frame"], cfg["spp"], args.depth, args.steps, args.warmup, args,
-                        one_spp=not args.no_1spp)
+                        one_spp=args.full and not args.no_1spp)
         o = r["out"]
         line.update({"value": o["value"], "ms_per_step": o["ms_per_step"],
                      "config": {"workload": o["workload"], "parallelism": "pixel-tiles x%d" % env.world,
@@ -736,7 +774,7 @@ def main():
             # achieved / peak / frac are the SURVEY 8(d) HBM formula (rounds remain comparable); "what_binds" and "valu" say what the counters
             # say binds the kernel instead
             line["roofline"] = roof
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 # the host baseline is a reported figure at N = 1 only; at N > 1 a short band of the
                 # assembled field is still checked against the oracle
                 base, (b, e, ref_field) = cpu_baseline(r["problem"], cfg["frame"], cfg["spp"], r["depth"], r["eps"],
@@ -759,17 +797,22 @@ def main():
         for k in ("roofline_mfma", "mfma_probe_of_net_forward_kernel"):
             if k in o:
                 line[k] = o[k]
-        if env.rank == 0:
+        if env.rank == 0 and args.full:
             f = r["field"].cpu().numpy()
             line["field_mean"] = float(f.mean())
             line["field_finite"] = bool(np.isfinite(f).all())
+
+    if args.dump_outputs and env.rank == 0:
+        # what a caller of the timed path receives from its last pass: the field (rows x columns x RGB) and the walk-step count
+        dump_outputs(args.dump_outputs, {"field": r["field"].cpu().numpy().reshape(cfg["frame"], cfg["frame"], 3),
+                                         "walk_steps": np.array([r["last_walk_steps"]], np.float64)})
 
     # ---- one pass each of the other single-GPU configurations (driver-run evidence for configs 3, 4, 5) ----
     # The headline is printed as soon as it is measured (a run that is cut off keeps it) and again, complete, at the end; the
     # extras run most important first inside a wall-clock budget (--budget-s, counted from process start): one that would start
     # past it is named in "skipped" instead of run.
     extras = {}
-    want_extras = not args.no_extras and args.config == 2 and not (args.scene or args.frame or args.spp)
+    want_extras = args.full and not args.no_extras and args.config == 2 and not (args.scene or args.frame or args.spp)
     if env.rank == 0 and want_extras:
         # (on stderr: stdout carries exactly one JSON line, the complete one)
         print(json.dumps(dict(line, partial="headline only; the complete line follows on stdout")), file=sys.stderr, flush=True)

@@ -393,7 +393,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "0", "--frame", "128", "--spp", "8", "--backend", "gloo"]
+           "--warmup", "0", "--frame", "128", "--spp", "8", "--backend", "gloo", "--full"]
     r = _run_bench(cmd)
     assert r["n_gpus"] == 2 and r["world_size"] == 2 and r["backend"] == "gloo"
     assert r["metric"] == "walk-steps/s" and r["scaling"] == "strong"
@@ -409,7 +409,7 @@ def test_bench_starts_its_own_ranks():
     import json
     import subprocess
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                          "--frame", "128", "--spp", "8", "--backend", "gloo"], capture_output=True, text=True, timeout=900,
+                          "--frame", "128", "--spp", "8", "--backend", "gloo", "--full"], capture_output=True, text=True, timeout=900,
                          cwd=ROOT, env=env_clean)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -424,7 +424,7 @@ def test_bench_guided_config_two_ranks():
     import sys
     env_clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--gpus", "2", "--steps", "1", "--warmup",
-                          "0", "--frame", "256", "--spp", "6", "--train-spp", "3", "--backend", "gloo"], capture_output=True,
+                          "0", "--frame", "256", "--spp", "6", "--train-spp", "3", "--backend", "gloo", "--full"], capture_output=True,
                          text=True, timeout=900, cwd=ROOT, env=env_clean)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,6 +5,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r06}
 STAGES=${STAGES:-"tests smoke micro bench trace pmc pmc_guided pmc3d pmc3d_1024 pmc_guided3d build3 build2"}
 mkdir -p gpurun_out/$TAG
+OUT=$_        # the directory just made
 has() { [[ " $STAGES " == *" $1 "* ]]; }
 if has tests; then
   # the whole log with the slowest tests named: the driver's limit for this command is 1 200 s, ours 600 s
@@ -14,7 +15,7 @@ if has tests; then
 fi
 if has smoke; then python __graft_entry__.py smoke 2>&1 | tail -3 | tee gpurun_out/$TAG/smoke.log; fi
 if has micro; then ./tools/micro/valu_rate 2>&1 | tee gpurun_out/$TAG/valu_rate.txt; fi
-if has bench; then python bench.py 2>gpurun_out/$TAG/bench.err | grep -v amdgpu.ids | tee gpurun_out/$TAG/bench.json; tail -5 gpurun_out/$TAG/bench.err; fi
+if has bench; then python bench.py --full 2>"$OUT/bench.err" | grep -v amdgpu.ids | tee "$OUT/bench.json"; tail -5 "$OUT/bench.err"; fi
 BARGS="bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-1spp --no-extras"
 if has trace; then
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$TAG/trace -- python3 $BARGS > gpurun_out/$TAG/bench_trace.log 2>&1
