@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wost.h"
@@ -60,8 +61,6 @@ struct WalkQueue {
     float *est;        // written when a persistent launch hands a pixel over mid-way: walk steps the pixel is expected to need still
                        //   (not part of a walker's state: no kernel loads it back; the host orders the next launch by it)
 };
-
-static const int kQueueWords = 17 + 1;  // rng counts twice
 
 // Atomics on one cache line are served one by one by its L2 channel (about 10 ns each: the eight
 // counters of the 16 384 waves of a round cost over a millisecond), so the counters exist in
@@ -623,10 +622,10 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
             // ---- traversal phase: every traversing lane visits one node ----
             ++trav_trips;
 #ifndef WOST_TRAV_BURST
-#define WOST_TRAV_BURST 3       // the burst the kernel is unrolled for (the handle's default trav_burst must equal it)
+#define WOST_TRAV_BURST 3       // the burst the kernel is unrolled for: the automatic one of rounds with a Neumann mesh on the tree (set_schedule)
 #endif
             if (!PERSIST && P.trav_burst == WOST_TRAV_BURST) {
-                // the default burst, unrolled: no loop counter, and the compiler may start a visit's node load early
+                // that burst, unrolled: no loop counter, and the compiler may start a visit's node load early
 #pragma unroll
                 for (int b = 0; b < WOST_TRAV_BURST; ++b) {
                     if (mode == MODE_TRAV) {
@@ -1180,10 +1179,8 @@ struct wost_context {
     int steps_per_round = 0;   // 0 = automatic (see run_solve)
     int thin_waves = 1;        // spread the walkers of an under-full launch over more waves
     int block_size = 256;
-    int wait_weight = 8;
-    bool wait_weight_set = false;   // by wost_set_option: otherwise steps with tree queries on the Neumann side use weight 1
-    int trav_burst = 3;
-    bool trav_burst_set = false;    // by wost_set_option: otherwise the persistent launch runs bursts of 5 with wait weight 6
+    int wait_weight = 0;       // 0 = automatic: this and trav_burst per launch (set_schedule)
+    int trav_burst = 0;        // 0 = automatic
     int time_kernels = 1;
     int refill = -1;       // -1 = automatic (few samples per pixel), 0 = never, 1 = always
     int persist = -1;      // many samples per pixel, more walkers than resident lanes: the first launch is persistent (lanes take pixels,
@@ -1227,23 +1224,38 @@ SceneView scene_view(wost_handle h)
 }
 }  // namespace wost
 
+// The arrays of a queue, in the order they are carved from its one allocation: the 8-byte array first, then the 4-byte arrays.
+// f gets a reference to each pointer (the element size is sizeof(*p)).
+template <class F>
+static void for_each_array(WalkQueue &q, F &&f)
+{
+    f(q.rng); f(q.pix); f(q.x0); f(q.y0); f(q.px); f(q.py); f(q.meta); f(q.nx); f(q.ny);
+    f(q.hint); f(q.thp); f(q.sr); f(q.sg); f(q.sb); f(q.d0_d2); f(q.d0_slot); f(q.est);
+}
+
+// bytes of a queue of n slots
+static size_t queue_bytes(size_t n)
+{
+    WalkQueue q{};
+    size_t bytes = 0;
+    for_each_array(q, [&](auto *&a) { bytes += n * sizeof(*a); });
+    return bytes;
+}
+
 static void carve_queue(void *mem, size_t n, WalkQueue &q)
 {
-    // 8-byte array first, then 4-byte arrays
-    char *p = reinterpret_cast<char *>(mem);
-    q.rng = reinterpret_cast<uint64_t *>(p); p += n * 8;
-    auto take = [&](size_t bytes) { void *r = p; p += bytes; return r; };
-    q.pix = (uint32_t *)take(n * 4);
-    q.x0 = (float *)take(n * 4); q.y0 = (float *)take(n * 4);
-    q.px = (float *)take(n * 4); q.py = (float *)take(n * 4);
-    q.meta = (uint32_t *)take(n * 4);
-    q.nx = (float *)take(n * 4); q.ny = (float *)take(n * 4);
-    q.hint = (int32_t *)take(n * 4);
-    q.thp = (float *)take(n * 4);
-    q.sr = (float *)take(n * 4); q.sg = (float *)take(n * 4); q.sb = (float *)take(n * 4);
-    q.d0_d2 = (float *)take(n * 4);
-    q.d0_slot = (int32_t *)take(n * 4);
-    q.est = (float *)take(n * 4);
+    char *p = static_cast<char *>(mem);
+    for_each_array(q, [&](auto *&a) {
+        a = reinterpret_cast<std::remove_reference_t<decltype(a)>>(p);
+        p += n * sizeof(*a);
+    });
+}
+
+// the queue that starts k slots into q
+static WalkQueue queue_from(WalkQueue q, size_t k)
+{
+    for_each_array(q, [&](auto *&a) { a += k; });
+    return q;
 }
 
 static void destroy_ctx(wost_context *c)
@@ -1422,7 +1434,7 @@ int wost_create(const wost_scene_desc *scene, const wost_settings *settings, int
                            sd.intensity};
         HIP_TRY_C(hipMemcpy(dev, sd.rgb, bytes, hipMemcpyHostToDevice));
     }
-    const size_t qbytes = c->n_pixels * 4 * kQueueWords;
+    const size_t qbytes = queue_bytes(c->n_pixels);
     for (int i = 0; i < 2; ++i) {
         HIP_TRY_C(hipMalloc(&c->queue_mem[i], qbytes));
         carve_queue(c->queue_mem[i], c->n_pixels, c->queue[i]);
@@ -1484,11 +1496,9 @@ int wost_set_option(wost_handle h, const char *key, double value)
     } else if (k == "wait_weight") {
         if (value < 1 || value > 512) return fail(WOST_ERR_INVALID, "wait_weight must be in 1..512");
         h->wait_weight = (int)value;
-        h->wait_weight_set = true;
     } else if (k == "trav_burst") {
         if (value < 1 || value > 16) return fail(WOST_ERR_INVALID, "trav_burst must be in 1..16");
         h->trav_burst = (int)value;
-        h->trav_burst_set = true;
     } else if (k == "spp") {
         if (value < 0 || value >= (1 << 20)) return fail(WOST_ERR_INVALID, "spp must be in 0..2^20-1");
         h->settings.spp = (int32_t)value;
@@ -1545,67 +1555,296 @@ int wost_set_option(wost_handle h, const char *key, double value)
 
 }  // extern "C"
 
-// the instantiation of the round kernel for a launch
-template <bool SLACK>
-static void launch_round(bool has_src, bool refill, bool ntree, bool emissive, unsigned grid, int bs, size_t lds_round, hipStream_t stream,
-                         const RoundParams &rp, bool persist = false)
+// What the launches of a 2-D solve share, fixed by the handle: the block shape, the LDS of a block and how many blocks the chip holds.
+struct LaunchGeometry {
+    int bs, stack_depth;      // threads per block, entries of a lane stack
+    size_t lds, lds_quad;     // the stack columns of a block: one per lane, one per quad (walk_quad_kernel)
+    bool emissive, ntree, has_src;
+    int32_t coop, pool_cap;   // the wave task pools of a Neumann mesh on the tree (RoundParams) ...
+    size_t lds_pools;         // ... and their LDS, behind the stack columns
+    size_t lds_round;         // what a walk_round_kernel block asks for
+    unsigned blocks_per_cu, resident_threads;
+    unsigned resident;        // blocks of a one-launch / persistent launch
+};
+
+static LaunchGeometry launch_geometry(const wost_context *c)
 {
-    if (!SLACK && persist && refill) {
-#define WOST_PERSIST_CASE(E, T, S)                                                                                                           \
-    if (emissive == E && ntree == T && has_src == S) {                                                                                       \
-        hipLaunchKernelGGL((walk_round_kernel<E, T, true, S, false, true>), dim3(grid), dim3(bs), lds_round, stream, rp);                    \
-        return;                                                                                                                              \
+    LaunchGeometry g{};
+    g.bs = c->block_size;
+    const int levels_any = std::max(c->dm.view.n_segs > 0 ? c->dm.view.levels : 1, c->nm.view.n_segs > 0 ? c->nm.view.levels : 1);
+    // closest point: pushes happen on the inner levels 0..L-1, at most 3 per level, and the
+    // branch-free pushes never write beyond entry 3L-1; the Neumann tree queries push up to 4
+    // and pop 1 per inner level: 3L+1 entries
+    g.stack_depth = 3 * levels_any + 1;
+    g.lds = (size_t)g.stack_depth * g.bs * sizeof(uint32_t);
+    g.lds_quad = (size_t)g.stack_depth * (g.bs / 4) * sizeof(uint32_t);
+    g.emissive = c->nm.view.n_segs > 0 && c->nm.view.emissive;
+    g.ntree = c->nm.view.n_segs > WOST_FLAT_MAX;
+    g.has_src = c->src.rgb != nullptr;
+    // a Neumann mesh on the tree: the task pools of every wave behind the stack columns (wost_coop.h)
+    g.coop = (g.ntree && c->coop && c->nm.view.levels <= 11) ? 1 : 0;
+    g.pool_cap = c->pool_cap > 0 ? c->pool_cap : std::min(1024, std::max(384, 128 * c->nm.view.levels));
+    auto pools_bytes = [&](int cap) { return (size_t)(g.bs / 64) * (2 * (size_t)cap + kPoolOwnerWords) * sizeof(uint32_t) + 8; };
+    // (the automatic size gives way to the stack columns of a deep Dirichlet tree; with no room at all: one descent per lane)
+    while (c->pool_cap <= 0 && g.pool_cap > 256 && g.lds + pools_bytes(g.pool_cap) > 64 * 1024) g.pool_cap -= 64;
+    g.lds_pools = g.coop ? pools_bytes(g.pool_cap) : 0;
+    if (g.lds + g.lds_pools > 64 * 1024) { g.coop = 0; g.lds_pools = 0; }
+    // developer experiment: extra LDS per block lowers the number of resident blocks (occupancy sensitivity)
+    g.lds_round = g.lds + g.lds_pools + (getenv("WOST_EXP_LDS_PAD") ? (size_t)atoi(getenv("WOST_EXP_LDS_PAD")) : 0);
+    // blocks a CU holds: the register bound of the instantiation (launch bounds: 6 waves per SIMD, 4 with the tree queries), and
+    // no more than fit its 160 KB of LDS -- with the wave task pools a block asks for about 64 KB (two per CU, not four)
+    const unsigned blocks_by_regs = (unsigned)((g.ntree ? 4 : 6) * 4 * 64 / g.bs);
+    const unsigned blocks_by_lds = (unsigned)std::max<size_t>(1, (size_t)160 * 1024 / std::max<size_t>(g.lds_round, 1));
+    g.blocks_per_cu = std::max(1u, std::min(blocks_by_regs, blocks_by_lds));
+    g.resident_threads = (unsigned)c->n_cus * g.blocks_per_cu * (unsigned)g.bs;
+    g.resident = (unsigned)c->n_cus * g.blocks_per_cu;
+    if (c->resident_blocks > 0) g.resident = std::min((unsigned)c->resident_blocks, g.resident);
+    return g;
+}
+
+// The step scheduling of a walk launch.  A trav_burst / wait_weight set with wost_set_option holds for every launch; the
+// automatic ones (0) are
+//   the persistent launch:  trav_burst 5,              wait_weight ntree ? 1 : 6
+//   every other launch:     trav_burst ntree ? 3 : 5,  wait_weight ntree ? 1 : 8
+// Bursts of five: round 6, + 1-2 % in rounds and shards as well as in the persistent launch (profiles/r06_v_*); there every lane
+// holds a live walker throughout, and an earlier step trip pays too (config 2 222 -> 217 ms, config 3 327 -> 317,
+// profiles/r06_i_burst_variants.txt).  A step that answers its Neumann queries on the tree is long and divergent: served when
+// eight ninths of the busy lanes wait (tools/probes/bench2d_wiggly.py: 3.87 -> 4.40 x 10^8 walk-steps/s on 3000 segments), and
+// its rounds keep the bursts of three that scheduling was tuned with.
+static void set_schedule(const wost_context *c, bool ntree, bool persistent, RoundParams &rp)
+{
+    rp.trav_burst = c->trav_burst > 0 ? c->trav_burst : (ntree && !persistent ? 3 : 5);
+    rp.wait_weight = c->wait_weight > 0 ? c->wait_weight : (ntree ? 1 : (persistent ? 6 : 8));
+}
+
+// The fields of RoundParams that every launch of a solve shares; a launch copies them and sets its queues, counters and lanes.
+static RoundParams base_params(const wost_context *c, const LaunchGeometry &g, float *field_dev, int32_t field_base)
+{
+    RoundParams rp{};
+    rp.dm = c->dm.view; rp.nm = c->nm.view; rp.st = c->dst; rp.probe = c->probe; rp.src = c->src;
+    rp.field = field_dev; rp.field_base = field_base; rp.stats = c->stats;
+    rp.count_far = c->counts + 2; rp.out_capacity = (uint32_t)c->n_pixels;
+    rp.count_long = c->counts + 4; rp.long_steps = c->long_steps > 0 ? (float)c->long_steps : WOST_INF;
+    // a slot regenerates its pixel's next sample inside a round, so rounds are long: 256 steps unless the caller chose
+    // otherwise (shorter rounds only added launches: 128^2 at 1 spp 0.95 -> 1.39 ms with 8-step rounds)
+    rp.steps_per_round = c->steps_per_round > 0 ? c->steps_per_round : 256;
+    rp.stack_stride = g.bs;
+    set_schedule(c, g.ntree, false, rp);
+    rp.coop = g.coop; rp.pool_cap = g.pool_cap; rp.pool_offset = (int32_t)(g.lds / sizeof(uint32_t)); rp.ray_slot_trigger = c->ray_slot_trigger;
+    return rp;
+}
+
+// The walk kernel of a launch (kind WOST_LAUNCH_ROUND / QUAD / ONE / PERSISTENT): the scene's flags become its template
+// arguments E(missive), T(ree), S(ource).  These are all the instantiations there are:
+//   ROUND  walk_round_kernel<E, T, 0, S, slack, 0>    ONE         walk_round_kernel<E, T, 1, 0, 0, 0>  (no source term: launch_ordinary)
+//   QUAD   walk_quad_kernel<E, T, S, slack>           PERSISTENT  walk_round_kernel<E, T, 1, S, 0, 1>
+static void launch_walk(const LaunchGeometry &g, int kind, bool slack, unsigned grid, hipStream_t stream, const RoundParams &rp)
+{
+    auto launch = [&](auto E, auto T, auto S) {
+        constexpr bool e = decltype(E)::value, t = decltype(T)::value, s = decltype(S)::value;
+        if (kind == WOST_LAUNCH_QUAD && slack) hipLaunchKernelGGL((walk_quad_kernel<e, t, s, true>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
+        else if (kind == WOST_LAUNCH_QUAD) hipLaunchKernelGGL((walk_quad_kernel<e, t, s, false>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
+        else if (kind == WOST_LAUNCH_PERSISTENT) hipLaunchKernelGGL((walk_round_kernel<e, t, true, s, false, true>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+        else if (kind == WOST_LAUNCH_ONE) hipLaunchKernelGGL((walk_round_kernel<e, t, true, false, false, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+        else if (slack) hipLaunchKernelGGL((walk_round_kernel<e, t, false, s, true, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+        else hipLaunchKernelGGL((walk_round_kernel<e, t, false, s, false, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+    };
+    auto with_src = [&](auto E, auto T) { g.has_src ? launch(E, T, std::true_type{}) : launch(E, T, std::false_type{}); };
+    auto with_tree = [&](auto E) { g.ntree ? with_src(E, std::true_type{}) : with_src(E, std::false_type{}); };
+    g.emissive ? with_tree(std::true_type{}) : with_tree(std::false_type{});
+}
+
+// Synchronises a side stream when it goes out of scope, if armed: run_solve arms one once it has queued a launch there, so that
+// no return -- an early one on an error included -- leaves that launch reading the queues and counters the next solve rewrites.
+// (The success path orders those launches through far_ev1 / long_ev1 and disarms it.)
+struct SideStreamGuard {
+    hipStream_t stream = nullptr;
+    ~SideStreamGuard() { if (stream) (void)hipStreamSynchronize(stream); }
+};
+
+// One pass of run_solve's loop: one ordinary launch on the solve's stream, and what starts beside it on the side streams.
+struct Pass {
+    int cur;                  // input queue: c->queue[cur]; output queue: c->queue[cur ^ 1]
+    uint32_t n_active;        // walkers in the input queue
+    uint32_t far;             // strayed walkers at its far end, for the launch on far_stream (0 once they joined the long remainders)
+    uint32_t beside_far;      // strayed walkers that joined the long remainders
+    uint32_t n_round;         // walkers of the ordinary launch
+    int kind;                 // ... its WOST_LAUNCH_*, workgroups and parameters
+    unsigned grid;
+    RoundParams rp;
+};
+
+// The hand-over after a persistent launch: it left one partly solved pixel per lane, each with an estimate of the walk steps it
+// still needs (config 2: 387 000 pixels, 12 % of the solve's steps; half of them need 650 steps more, a few thousand over 1 500),
+// and the walkers that strayed beyond the plain visits' range during that launch, parked since with most of their samples
+// ahead of them.  In rounds the few long ones add launch after launch of a nearly empty chip (16 of the 52 ms that followed
+// the persistent launch), so they start NOW and run to their end -- four lanes to a walker, exact at any distance (SLACK: no
+// walker leaves such a launch), the longest a thousand or two four to a wave, the others sixteen -- on long_stream beside the
+// rounds of the rest; and the first round takes the rest sorted by estimate: the walkers of a wave finish together and the
+// wave leaves, instead of a third of the lanes of every wave idling behind finished pixels.
+static int hand_over(wost_context *c, const LaunchGeometry &g, hipStream_t stream, Pass &p, SideStreamGuard &long_guard)
+{
+    const bool beside = c->long_steps > 0;
+    const uint32_t n_far = (beside && p.far <= 1024u && p.far <= (uint32_t)c->long_cap) ? p.far : 0u;
+    const uint32_t n_long = beside ? std::min<uint32_t>(std::min<uint32_t>(c->host_count[4], (uint32_t)c->long_cap - n_far), p.n_active) : 0u;
+    const uint32_t *ord = nullptr;
+    if (p.n_active > 0 && (n_long > 0 || c->tail_sort)) {
+        if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
+        HIP_TRY((hipError_t)order_by_estimate(c->order, c->queue[p.cur].est, p.n_active, stream, &ord));
+        p.rp.order = ord + n_long;
     }
-        WOST_PERSIST_CASE(false, false, false) WOST_PERSIST_CASE(true, false, false) WOST_PERSIST_CASE(false, true, false) WOST_PERSIST_CASE(true, true, false)
-        WOST_PERSIST_CASE(false, false, true) WOST_PERSIST_CASE(true, false, true) WOST_PERSIST_CASE(false, true, true) WOST_PERSIST_CASE(true, true, true)
-#undef WOST_PERSIST_CASE
+    const uint32_t n_beside = n_far + n_long;
+    if (n_beside == 0) return WOST_OK;
+    if (!c->long_mem) {
+        HIP_TRY(hipMalloc(&c->long_mem, queue_bytes((size_t)c->long_cap)));
+        carve_queue(c->long_mem, (size_t)c->long_cap, c->long_queue);
     }
-    if (has_src) {
-        // problems with a source term: the SOURCE instantiations (one extra stage per step)
-        if (ntree) {
-            if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, true, false, true, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-            else hipLaunchKernelGGL((walk_round_kernel<false, true, false, true, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-        } else {
-            if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, false, false, true, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-            else hipLaunchKernelGGL((walk_round_kernel<false, false, false, true, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
+    // the strayed first (most of a pixel ahead of them as a rule), then the long remainders, longest first
+    if (n_far > 0) {
+        hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_far + 255) / 256), dim3(256), 0, stream, queue_from(c->queue[p.cur], c->n_pixels - n_far),
+                           (const uint32_t *)nullptr, n_far, c->long_queue);
+        HIP_TRY(hipGetLastError());
+        p.far = 0; p.beside_far = n_far;
+    }
+    if (n_long > 0) {
+        hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_long + 255) / 256), dim3(256), 0, stream, c->queue[p.cur], ord, n_long, queue_from(c->long_queue, n_far));
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t n_thin = std::min<uint32_t>(n_beside, (uint32_t)std::max(c->long_thin, 0));
+    c->host_count[5] = n_beside;
+    c->host_count[6] = p.n_active - n_long;
+    HIP_TRY(hipMemcpyAsync(c->counts + 5, c->host_count + 5, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->long_ev0, stream));
+    HIP_TRY(hipStreamWaitEvent(c->long_stream, c->long_ev0, 0));
+    RoundParams lp = p.rp;
+    lp.in = c->long_queue; lp.order = nullptr; lp.count_in = c->counts + 5;
+    lp.count_out = lp.count_far = c->counts + 8;       // (nothing comes out: every walker runs to the end of its pixel)
+    lp.steps_per_round = 0x7fffffff; lp.stack_stride = g.stack_depth; lp.lane_shift = 0;
+    const uint32_t quads_per_block = (uint32_t)g.bs / 4u;
+    lp.thin_count = n_thin;
+    lp.thin_blocks = (n_thin * 4u + quads_per_block - 1u) / quads_per_block;
+    const unsigned lgrid = lp.thin_blocks + (n_beside - n_thin + quads_per_block - 1u) / quads_per_block;
+    long_guard.stream = c->long_stream;
+    launch_walk(g, WOST_LAUNCH_QUAD, true, lgrid, c->long_stream, lp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->long_ev1, c->long_stream));
+    p.rp.count_in = c->counts + 6;
+    p.n_round = p.n_active - n_long;
+    return WOST_OK;
+}
+
+// Walkers that left the previous launch at a query beyond the plain kernel's range wait at the far end of its output queue,
+// which is this launch's input queue.  The SLACK instantiation takes them through max_depth steps -- the walk that strayed
+// ends within that many -- on far_stream, next to this launch, and appends them to the same output queue (both kernels only
+// read the input queue and claim output slots from one counter).
+static int launch_strayed(wost_context *c, const LaunchGeometry &g, hipStream_t stream, const Pass &p, SideStreamGuard &far_guard)
+{
+    c->host_count[3] = p.far;
+    HIP_TRY(hipMemcpyAsync(c->counts + 3, c->host_count + 3, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->far_ev0, stream));                      // the counters are ready
+    HIP_TRY(hipStreamWaitEvent(c->far_stream, c->far_ev0, 0));
+    RoundParams fp = p.rp;
+    fp.order = nullptr; fp.in = queue_from(c->queue[p.cur], c->n_pixels - p.far); fp.count_in = c->counts + 3;
+    fp.steps_per_round = std::max(1, c->settings.max_depth);
+    // a few strayed walkers (leaks of a closed scene): one per wave -- a query from very far away is a scan of the whole
+    // mesh by the 64 lanes (closest_point_wave), and the launch lasts as long as its slowest wave; many (an open scene:
+    // every walk that misses the boundary strays): every lane loaded
+    fp.lane_shift = p.far <= 4096u ? 6 : 0;
+    far_guard.stream = c->far_stream;
+    launch_walk(g, WOST_LAUNCH_ROUND, true, (unsigned)((((uint64_t)p.far << fp.lane_shift) + g.bs - 1) / g.bs), c->far_stream, fp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->far_ev1, c->far_stream));
+    // (not counted in `launches`: kernel_ms / kernel_launches stays the average duration of the ordinary launches)
+    return WOST_OK;
+}
+
+// The ordinary launch of a pass, on the solve's stream: its kind, lanes and grid.  The first launch of a solve may drain the
+// queue in ONE launch (few samples per pixel) or be PERSISTENT (many); the others are QUAD (under-filled) or ROUND.
+static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t stream, bool first, Pass &p)
+{
+    RoundParams &rp = p.rp;
+    const int bs = g.bs;
+    // When the walkers left fill less than 1/16 of the resident threads, spread them out: the duration of such a launch is the
+    // latency of its slowest wave, and a wave is as slow as the longest query among its walkers (config 2's last three
+    // launches: 13.1 -> 8.9 ms; with 2 or 4 lanes per walker the extra waves cost more than they save: 9.2 -> 11.8 ms).
+    rp.lane_shift = 0;
+    if (c->thin_waves) {
+        while (rp.lane_shift < 6 && ((uint64_t)p.n_round << (rp.lane_shift + 1)) <= g.resident_threads) ++rp.lane_shift;
+        if (rp.lane_shift < 4) rp.lane_shift = 0;
+    }
+    p.grid = (unsigned)((((uint64_t)p.n_round << rp.lane_shift) + bs - 1) / bs);
+    // REFILL launch: as many resident threads as the chip holds, each draining the input queue.  Worth it when regeneration
+    // cannot keep the lanes busy (measured on config 2's frame: 1 spp 3.5 -> 3.0 ms, 4 spp 8.3 -> 7.9 ms, 8 spp 13.0 -> 13.5 ms)
+    // and the queue is larger than one residency; the 16-bit lane counters bound spp * max_depth.
+    // (the one-launch form of few samples has no instantiation with a source term; the persistent launch has)
+    const bool can_persist = (int64_t)c->settings.spp * c->settings.max_depth < 65535 && first;
+    const bool can_refill = can_persist && !g.has_src;
+    const bool few = can_refill && (c->refill == 1 || (c->refill == -1 && c->settings.spp <= 4 && p.grid > g.resident));
+    // PERSISTENT first launch (many samples per pixel, more walkers than resident lanes): the same resident threads, but the
+    // lanes take whole pixels -- all of a pixel's samples, the pixels in the order of wost_order.h, longest expected chain first
+    // -- until the input queue is dry; then every wave hands what it holds to the output queue and the rest of the solve runs
+    // in rounds.  No lane idles behind a finished pixel and no launch ends while pixels are unread (in rounds, config 2 spent
+    // 108 of its 252 ms in launches where a third of the lanes had finished their pixel, EXPERIMENTS 25); what the rounds
+    // get is the remainder of one pixel per lane.
+    const bool persist = can_persist && !few && c->refill != 1 &&
+                         (c->persist == 1 || (c->persist == -1 && c->settings.spp > 4 && p.n_active > g.resident_threads));
+    if (few || persist) {
+        p.kind = persist ? WOST_LAUNCH_PERSISTENT : WOST_LAUNCH_ONE;
+        rp.lane_shift = 0;
+        p.grid = std::min((unsigned)((p.n_active + bs - 1) / bs), g.resident);
+        c->host_count[1] = p.grid * (unsigned)bs;      // first unread slot (pinned staging word)
+        HIP_TRY(hipMemcpyAsync(c->cursor, c->host_count + 1, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        rp.cursor = c->cursor;
+        rp.steps_per_round = 0x7fffffff;
+        rp.reserve = persist ? 0 : 64;
+        rp.leave_dry = persist ? 1 : 0;
+        if (persist) set_schedule(c, g.ntree, true, rp);
+        if (persist ? c->persist_order : c->few_order) {
+            if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
+            HIP_TRY((hipError_t)order_by_distance(c->order, c->queue[p.cur].d0_d2, p.n_active, stream, &rp.order));
         }
-    } else if (refill) {
-        if (ntree) {
-            if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, true, true, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-            else hipLaunchKernelGGL((walk_round_kernel<false, true, true, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-        } else {
-            if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, false, true, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-            else hipLaunchKernelGGL((walk_round_kernel<false, false, true, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-        }
-    } else if (ntree) {
-        if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, true, false, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-        else hipLaunchKernelGGL((walk_round_kernel<false, true, false, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
+    } else if (p.n_round > 0 &&
+               (c->quad == 1 || (c->quad == -1 && 4.0 * (double)p.n_round <= c->quad_fill * (double)g.resident_threads))) {
+        // Under-filled launch: four lanes per walker (walk_quad_kernel).  Such a launch lasts as long as its longest chain of
+        // dependent node visits; sharing a descent between the lanes of a quad halves that chain.
+        // Few walkers: fewer quads per wave (16 -> 4 -> 1), as long as the waves still fit the chip.
+        p.kind = WOST_LAUNCH_QUAD;
+        rp.lane_shift = 0;
+        while (rp.lane_shift < 4 && ((uint64_t)p.n_round << (2 + rp.lane_shift + 2)) <= g.resident_threads) rp.lane_shift += 2;
+        rp.stack_stride = g.stack_depth;      // entries per (contiguous) quad column
+        p.grid = (unsigned)((((uint64_t)p.n_round << (2 + rp.lane_shift)) + bs - 1) / bs);
     } else {
-        if (emissive) hipLaunchKernelGGL((walk_round_kernel<true, false, false, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
-        else hipLaunchKernelGGL((walk_round_kernel<false, false, false, false, SLACK>), dim3(grid), dim3(bs), lds_round, stream, rp);
+        p.kind = WOST_LAUNCH_ROUND;
     }
+    // (the last strayed walkers can outlive the ordinary queue: then only their launch runs)
+    if (p.n_round > 0) {
+        launch_walk(g, p.kind, false, p.grid, stream, rp);
+        HIP_TRY(hipGetLastError());
+    }
+    return WOST_OK;
 }
 
-// the quad instantiation (four lanes per walker) for an ordinary launch
-template <bool SLACK = false>
-static void launch_quad(bool has_src, bool ntree, bool emissive, unsigned grid, int bs, size_t lds, hipStream_t stream, const RoundParams &rp)
+// The end of a pass: the solve's stream waits for the strayed walkers' launch, the counts (with time_kernels also the
+// counters) come back, and the pass is recorded for wost_last_launches.
+static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint32_t launches, double &kernel_ms)
 {
-#define WOST_QUAD_CASE(E, T, S)                                                                                                  \
-    if (emissive == E && ntree == T && has_src == S) {                                                                           \
-        hipLaunchKernelGGL((walk_quad_kernel<E, T, S, SLACK>), dim3(grid), dim3(bs), lds, stream, rp);                          \
-        return;                                                                                                                  \
-    }
-    WOST_QUAD_CASE(false, false, false) WOST_QUAD_CASE(true, false, false) WOST_QUAD_CASE(false, true, false) WOST_QUAD_CASE(true, true, false)
-    WOST_QUAD_CASE(false, false, true) WOST_QUAD_CASE(true, false, true) WOST_QUAD_CASE(false, true, true) WOST_QUAD_CASE(true, true, true)
-#undef WOST_QUAD_CASE
-}
-
-static WalkQueue queue_from(const WalkQueue &q, size_t k)
-{
-    WalkQueue r = q;
-    r.pix += k; r.x0 += k; r.y0 += k; r.px += k; r.py += k; r.rng += k; r.meta += k; r.nx += k; r.ny += k; r.hint += k; r.thp += k;
-    r.sr += k; r.sg += k; r.sb += k; r.d0_d2 += k; r.d0_slot += k; r.est += k;
-    return r;
+    if (p.far > 0) HIP_TRY(hipStreamWaitEvent(stream, c->far_ev1, 0));
+    if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev1, stream));
+    HIP_TRY(hipMemcpyAsync(c->host_count, c->counts + (p.cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c->host_count + 2, c->counts + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    const bool persist = p.kind == WOST_LAUNCH_PERSISTENT;
+    if (persist) HIP_TRY(hipMemcpyAsync(c->host_count + 4, c->counts + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (c->time_kernels) HIP_TRY(hipMemcpyAsync(c->host_stats, c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (!c->time_kernels) return WOST_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    kernel_ms += ms;
+    wost_launch_info li{p.kind, p.n_round, p.n_active - p.n_round + p.far + p.beside_far, p.n_round > 0 ? p.grid : 0u, ms, 0};
+    for (int k = 0; k < kStatCopies; ++k) li.walk_steps_done += c->host_stats[k].steps;
+    c->last_launches.push_back(li);
+    if (getenv("WOST_TRACE_LAUNCHES")) fprintf(stderr, "launch %d: walkers %u of %u (+ %u strayed) grid %u %.3f ms -> %u left, %u strayed%s\n", launches, p.n_round, p.n_active, p.far, p.grid, ms, c->host_count[0], c->host_count[2], persist ? " (persistent)" : "");
+    return WOST_OK;
 }
 
 // the shared solve driver: field_dev indexed by (pix - field_base)
@@ -1614,37 +1853,16 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
 {
     const auto t_start = std::chrono::high_resolution_clock::now();
     HIP_TRY(hipSetDevice(c->device));
-    const int bs = c->block_size;
-    const int levels = c->dm.view.n_segs > 0 ? c->dm.view.levels : 1;
-    const int levels_any = std::max(levels, c->nm.view.n_segs > 0 ? c->nm.view.levels : 1);
-    // closest point: pushes happen on the inner levels 0..L-1, at most 3 per level, and the
-    // branch-free pushes never write beyond entry 3L-1; the Neumann tree queries push up to 4
-    // and pop 1 per inner level: 3L+1 entries
-    const int stack_depth = 3 * levels_any + 1;
-    const size_t lds = (size_t)stack_depth * bs * sizeof(uint32_t);
+    const LaunchGeometry g = launch_geometry(c);
     HIP_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
 
     const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
-    InitParams ip{};
-    ip.dm = c->dm.view;
-    ip.st = c->dst;
-    ip.probe = c->probe;
-    ip.out = c->queue[0];
-    ip.count_out = c->counts + 0;
-    ip.mask = c->mask;
-    ip.field = field_dev;
-    ip.field_base = field_base;
-    ip.pixel_begin = pixel_begin;
-    ip.pixel_end = pixel_end;
-    ip.shard_index = shard_index;
-    ip.shard_count = shard_count;
-    ip.tiles_x = tiles_x;
-    ip.tiles_y = tiles_y;
-    ip.stack_stride = bs;
+    const InitParams ip{c->dm.view, c->dst, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
+                        pixel_begin, pixel_end, shard_index, shard_count, tiles_x, tiles_y, g.bs};
     const long long n_threads = (long long)tiles_x * tiles_y * 64;
-    const unsigned init_grid = (unsigned)((n_threads + bs - 1) / bs);
-    hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(bs), lds, stream, ip);
+    const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
+    hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->host_count, c->counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1654,250 +1872,31 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
     uint32_t launches = 0;
     int cur = 0;
     c->last_launches.clear();
-    const bool emissive = c->nm.view.n_segs > 0 && c->nm.view.emissive;
-    const bool ntree = c->nm.view.n_segs > WOST_FLAT_MAX;
-    uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (see below)
+    const RoundParams base = base_params(c, g, field_dev, field_base);
+    SideStreamGuard long_guard, far_guard;   // armed: a launch of the long remainders / of strayed walkers was queued
+    uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (launch_strayed)
     bool handed_over = false;     // the previous launch was persistent: queue[cur] holds what it handed over, with estimates
-    bool long_pending = false;    // the launch of the long remainders is under way on long_stream
     while (n_active > 0 || pending_far > 0) {
         const int nxt = cur ^ 1;
         HIP_TRY(hipMemsetAsync(c->counts + nxt, 0, sizeof(uint32_t), stream));
         HIP_TRY(hipMemsetAsync(c->counts + 2, 0, sizeof(uint32_t), stream));
-        RoundParams rp{};
-        rp.count_long = c->counts + 4;
-        rp.long_steps = c->long_steps > 0 ? (float)c->long_steps : WOST_INF;
-        rp.dm = c->dm.view;
-        rp.nm = c->nm.view;
-        rp.st = c->dst;
-        rp.probe = c->probe;
-        rp.src = c->src;
-        rp.in = c->queue[cur];
-        rp.out = c->queue[nxt];
-        rp.count_in = c->counts + cur;
-        rp.count_out = c->counts + nxt;
-        rp.field = field_dev;
-        rp.field_base = field_base;
-        rp.stats = c->stats;
-        rp.count_far = c->counts + 2;
-        rp.out_capacity = (uint32_t)c->n_pixels;
-        // a slot regenerates its pixel's next sample inside a round, so rounds are long: 256 steps
-        // unless the caller chose otherwise (shorter rounds only added launches: 128^2 at 1 spp
-        // 0.95 -> 1.39 ms with 8-step rounds)
-        rp.steps_per_round = c->steps_per_round > 0 ? c->steps_per_round : 256;
-        rp.stack_stride = bs;
-        // a step that answers its Neumann queries on the tree is long and divergent: served when eight ninths of the
-        // busy lanes wait (tools/probes/bench2d_wiggly.py: 3.87 -> 4.40 x 10^8 walk-steps/s on 3000 segments)
-        rp.wait_weight = (ntree && !c->wait_weight_set) ? 1 : c->wait_weight;
-        // bursts of five visits unless the caller chose (round 6: + 1-2 % in rounds and shards as well as in the persistent launch,
-        // profiles/r06_v_*; a Neumann mesh on the tree keeps the three its step scheduling was tuned with)
-        rp.trav_burst = (c->trav_burst_set || ntree) ? c->trav_burst : 5;
-        // a Neumann mesh on the tree: the task pools of every wave behind the stack columns (wost_coop.h)
-        rp.coop = (ntree && c->coop && c->nm.view.levels <= 11) ? 1 : 0;
-        rp.pool_cap = c->pool_cap > 0 ? c->pool_cap : std::min(1024, std::max(384, 128 * c->nm.view.levels));
-        rp.pool_offset = (int32_t)(lds / sizeof(uint32_t));
-        rp.ray_slot_trigger = c->ray_slot_trigger;
-        auto pools_bytes = [&](int cap) { return (size_t)(bs / 64) * (2 * (size_t)cap + kPoolOwnerWords) * sizeof(uint32_t) + 8; };
-        // (the automatic size gives way to the stack columns of a deep Dirichlet tree; with no room at all: one descent per lane)
-        while (c->pool_cap <= 0 && rp.pool_cap > 256 && lds + pools_bytes(rp.pool_cap) > 64 * 1024) rp.pool_cap -= 64;
-        size_t lds_pools = rp.coop ? pools_bytes(rp.pool_cap) : 0;
-        if (lds + lds_pools > 64 * 1024) {
-            rp.coop = 0;
-            lds_pools = 0;
-        }
-        // developer experiment: extra LDS per block lowers the number of resident blocks (occupancy sensitivity)
-        const size_t lds_round = lds + lds_pools + (getenv("WOST_EXP_LDS_PAD") ? (size_t)atoi(getenv("WOST_EXP_LDS_PAD")) : 0);
-        const bool has_src = c->src.rgb != nullptr;
-        // blocks a CU holds: the register bound of the instantiation (launch bounds: 6 waves per SIMD, 4 with the tree queries), and
-        // no more than fit its 160 KB of LDS -- with the wave task pools a block asks for about 64 KB (two per CU, not four)
-        const unsigned blocks_by_regs = (unsigned)((ntree ? 4 : 6) * 4 * 64 / bs);
-        const unsigned blocks_by_lds = (unsigned)std::max<size_t>(1, (size_t)160 * 1024 / std::max<size_t>(lds_round, 1));
-        const unsigned blocks_per_cu = std::max(1u, std::min(blocks_by_regs, blocks_by_lds));
-        const unsigned resident_threads = (unsigned)c->n_cus * blocks_per_cu * (unsigned)bs;
+        Pass p{};
+        p.cur = cur; p.n_active = p.n_round = n_active; p.far = pending_far;
+        p.rp = base;
+        p.rp.in = c->queue[cur]; p.rp.out = c->queue[nxt]; p.rp.count_in = c->counts + cur; p.rp.count_out = c->counts + nxt;
         if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev0, stream));
-        // What a persistent launch handed over: one partly solved pixel per lane, each with an estimate of the walk steps it still
-        // needs (config 2: 387 000 pixels, 12 % of the solve's steps; half of them need 650 steps more, a few thousand over 1 500),
-        // and the walkers that strayed beyond the plain visits' range during that launch, parked since with most of their samples
-        // ahead of them.  In rounds the few long ones add launch after launch of a nearly empty chip (16 of the 52 ms that followed
-        // the persistent launch), so they start NOW and run to their end -- four lanes to a walker, exact at any distance (SLACK: no
-        // walker leaves such a launch), the longest a thousand or two four to a wave, the others sixteen -- on streams of their own
-        // beside the rounds of the rest; and the first round takes the rest sorted by estimate: the walkers of a wave finish
-        // together and the wave leaves, instead of a third of the lanes of every wave idling behind finished pixels.
-        uint32_t n_round = n_active;        // walkers of this iteration's ordinary launch
-        uint32_t beside_far = 0;            // strayed walkers that joined the long remainders
-        if (handed_over && (n_active > 0 || pending_far > 0)) {
-            const bool beside = c->long_steps > 0;
-            const uint32_t n_far = (beside && pending_far <= 1024u && pending_far <= (uint32_t)c->long_cap) ? pending_far : 0u;
-            const uint32_t n_long = beside ? std::min<uint32_t>(std::min<uint32_t>(c->host_count[4], (uint32_t)c->long_cap - n_far), n_active) : 0u;
-            const uint32_t *ord = nullptr;
-            if (n_active > 0 && (n_long > 0 || c->tail_sort)) {
-                if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
-                HIP_TRY((hipError_t)order_by_estimate(c->order, c->queue[cur].est, n_active, stream, &ord));
-                rp.order = ord + n_long;
-            }
-            const uint32_t n_beside = n_far + n_long;
-            if (n_beside > 0) {
-                if (!c->long_mem) {
-                    HIP_TRY(hipMalloc(&c->long_mem, (size_t)c->long_cap * 4 * kQueueWords));
-                    carve_queue(c->long_mem, (size_t)c->long_cap, c->long_queue);
-                }
-                // the strayed first (most of a pixel ahead of them as a rule), then the long remainders, longest first
-                if (n_far > 0) {
-                    hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_far + 255) / 256), dim3(256), 0, stream, queue_from(c->queue[cur], c->n_pixels - n_far),
-                                       (const uint32_t *)nullptr, n_far, c->long_queue);
-                    HIP_TRY(hipGetLastError());
-                    pending_far = 0;
-                    beside_far = n_far;
-                }
-                if (n_long > 0) {
-                    hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_long + 255) / 256), dim3(256), 0, stream, c->queue[cur], ord, n_long, queue_from(c->long_queue, n_far));
-                    HIP_TRY(hipGetLastError());
-                }
-                const uint32_t n_thin = std::min<uint32_t>(n_beside, (uint32_t)std::max(c->long_thin, 0));
-                c->host_count[5] = n_beside;
-                c->host_count[6] = n_active - n_long;
-                HIP_TRY(hipMemcpyAsync(c->counts + 5, c->host_count + 5, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipEventRecord(c->long_ev0, stream));
-                HIP_TRY(hipStreamWaitEvent(c->long_stream, c->long_ev0, 0));
-                RoundParams lp = rp;
-                lp.in = c->long_queue;
-                lp.order = nullptr;
-                lp.count_in = c->counts + 5;
-                lp.count_out = c->counts + 8;       // (nothing comes out: every walker runs to the end of its pixel)
-                lp.count_far = c->counts + 8;
-                lp.steps_per_round = 0x7fffffff;
-                lp.stack_stride = stack_depth;
-                lp.lane_shift = 0;
-                const uint32_t quads_per_block = (uint32_t)bs / 4u;
-                lp.thin_count = n_thin;
-                lp.thin_blocks = (n_thin * 4u + quads_per_block - 1u) / quads_per_block;
-                const unsigned lgrid = lp.thin_blocks + (n_beside - n_thin + quads_per_block - 1u) / quads_per_block;
-                if (lp.thin_blocks == 0u) lp.thin_count = 0u;
-                launch_quad<true>(has_src, ntree, emissive, lgrid, bs, (size_t)stack_depth * (bs / 4) * sizeof(uint32_t), c->long_stream, lp);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(c->long_ev1, c->long_stream));
-                long_pending = true;
-                rp.count_in = c->counts + 6;
-                n_round = n_active - n_long;
-            }
-        }
-        // Walkers that left the previous launch at a query beyond the plain kernel's range wait at the far end of its output queue,
-        // which is this launch's input queue.  The SLACK instantiation takes them through max_depth steps -- the walk that strayed
-        // ends within that many -- on a stream of its own, next to this launch, and appends them to the same output queue (both
-        // kernels only read the input queue and claim output slots from one counter).
-        const uint32_t far_now = pending_far;
-        if (far_now > 0) {
-            c->host_count[3] = far_now;
-            HIP_TRY(hipMemcpyAsync(c->counts + 3, c->host_count + 3, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipEventRecord(c->far_ev0, stream));                      // the counters are ready
-            HIP_TRY(hipStreamWaitEvent(c->far_stream, c->far_ev0, 0));
-            RoundParams fp = rp;
-            fp.order = nullptr;
-            fp.in = queue_from(c->queue[cur], c->n_pixels - far_now);
-            fp.count_in = c->counts + 3;
-            fp.steps_per_round = std::max(1, c->settings.max_depth);
-            // a few strayed walkers (leaks of a closed scene): one per wave -- a query from very far away is a scan of the whole
-            // mesh by the 64 lanes (closest_point_wave), and the launch lasts as long as its slowest wave; many (an open scene:
-            // every walk that misses the boundary strays): every lane loaded
-            fp.lane_shift = far_now <= 4096u ? 6 : 0;
-            launch_round<true>(has_src, false, ntree, emissive, (unsigned)((((uint64_t)far_now << fp.lane_shift) + bs - 1) / bs), bs, lds_round, c->far_stream, fp);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(c->far_ev1, c->far_stream));
-            // (not counted in `launches`: kernel_ms / kernel_launches stays the average duration of the ordinary launches)
-        }
-        // When the walkers left fill less than 1/16 of the resident threads, spread them out: the
-        // duration of such a launch is the latency of its slowest wave, and a wave is as slow as the
-        // longest query among its walkers (config 2's last three launches: 13.1 -> 8.9 ms; with 2 or
-        // 4 lanes per walker the extra waves cost more than they save: 9.2 -> 11.8 ms).
-        rp.lane_shift = 0;
-        if (c->thin_waves) {
-            while (rp.lane_shift < 6 && ((uint64_t)n_round << (rp.lane_shift + 1)) <= resident_threads) ++rp.lane_shift;
-            if (rp.lane_shift < 4) rp.lane_shift = 0;
-        }
-        unsigned grid = (unsigned)((((uint64_t)n_round << rp.lane_shift) + bs - 1) / bs);
-        // REFILL launch: as many resident threads as the chip holds, each draining the input queue.
-        // Worth it when regeneration cannot keep the lanes busy (measured on config 2's frame:
-        // 1 spp 3.5 -> 3.0 ms, 4 spp 8.3 -> 7.9 ms, 8 spp 13.0 -> 13.5 ms) and the queue is larger
-        // than one residency; the 16-bit lane counters bound spp * max_depth.
-        const unsigned resident = c->resident_blocks > 0 ? std::min((unsigned)c->resident_blocks, (unsigned)c->n_cus * blocks_per_cu) : (unsigned)c->n_cus * blocks_per_cu;
-        // (the one-launch form of few samples has no instantiation with a source term; the persistent launch has)
-        const bool can_persist = (int64_t)c->settings.spp * c->settings.max_depth < 65535 && launches == 0;
-        const bool can_refill = can_persist && !has_src;
-        const bool few = can_refill && (c->refill == 1 || (c->refill == -1 && c->settings.spp <= 4 && grid > resident));
-        // PERSISTENT first launch (many samples per pixel, more walkers than resident lanes): the same resident threads, but the
-        // lanes take whole pixels -- all of a pixel's samples, the pixels in the order of wost_order.h, longest expected chain first
-        // -- until the input queue is dry; then every wave hands what it holds to the output queue and the rest of the solve runs
-        // in rounds.  No lane idles behind a finished pixel and no launch ends while pixels are unread (in rounds, config 2 spent
-        // 108 of its 252 ms in launches where a third of the lanes had finished their pixel, EXPERIMENTS 25); what the rounds
-        // get is the remainder of one pixel per lane.
-        const bool persist = can_persist && !few && c->refill != 1 &&
-                             (c->persist == 1 || (c->persist == -1 && c->settings.spp > 4 && n_active > resident_threads));
-        const bool refill = few || persist;
-        if (refill) {
-            rp.lane_shift = 0;
-            grid = std::min((unsigned)((n_active + bs - 1) / bs), resident);
-            c->host_count[1] = grid * (unsigned)bs;      // first unread slot (pinned staging word)
-            HIP_TRY(hipMemcpyAsync(c->cursor, c->host_count + 1, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            rp.cursor = c->cursor;
-            rp.steps_per_round = 0x7fffffff;
-            rp.reserve = 64;
-            if (persist ? c->persist_order : c->few_order) {
-                if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
-                HIP_TRY((hipError_t)order_by_distance(c->order, c->queue[cur].d0_d2, n_active, stream, &rp.order));
-            }
-            if (persist) {
-                rp.reserve = 0;
-                rp.leave_dry = 1;
-                // every lane holds a live walker throughout: longer traversal bursts and an earlier step trip pay here (config 2
-                // 222 -> 217 ms, config 3 327 -> 317, profiles/r06_i_burst_variants.txt), in rounds they do not
-                if (!c->trav_burst_set) rp.trav_burst = 5;
-                if (!c->wait_weight_set && !ntree) rp.wait_weight = 6;
-            }
-        }
-        // Under-filled launch: four lanes per walker (walk_quad_kernel).  Such a launch lasts as long as its longest chain of
-        // dependent node visits; sharing a descent between the lanes of a quad halves that chain.
-        const bool quad = !refill && n_round > 0 &&
-                          (c->quad == 1 || (c->quad == -1 && 4.0 * (double)n_round <= c->quad_fill * (double)resident_threads));
-        // (the last strayed walkers can outlive the ordinary queue: then only their launch runs)
-        if (quad) {
-            // few walkers: fewer quads per wave (16 -> 4 -> 1), as long as the waves still fit the chip
-            rp.lane_shift = 0;
-            while (rp.lane_shift < 4 && ((uint64_t)n_round << (2 + rp.lane_shift + 2)) <= resident_threads) rp.lane_shift += 2;
-            rp.stack_stride = stack_depth;      // entries per (contiguous) quad column
-            grid = (unsigned)((((uint64_t)n_round << (2 + rp.lane_shift)) + bs - 1) / bs);
-            launch_quad(has_src, ntree, emissive, grid, bs, (size_t)stack_depth * (bs / 4) * sizeof(uint32_t), stream, rp);
-            HIP_TRY(hipGetLastError());
-        } else if (n_round > 0) {
-            launch_round<false>(has_src, refill, ntree, emissive, grid, bs, lds_round, stream, rp, persist);
-            HIP_TRY(hipGetLastError());
-        }
-        if (far_now > 0) HIP_TRY(hipStreamWaitEvent(stream, c->far_ev1, 0));
-        if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev1, stream));
-        HIP_TRY(hipMemcpyAsync(c->host_count, c->counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(c->host_count + 2, c->counts + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        if (persist) HIP_TRY(hipMemcpyAsync(c->host_count + 4, c->counts + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        if (c->time_kernels) HIP_TRY(hipMemcpyAsync(c->host_stats, c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        handed_over = persist;
-        if (c->time_kernels) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            kernel_ms += ms;
-            wost_launch_info li{};
-            li.kind = persist ? WOST_LAUNCH_PERSISTENT : (refill ? WOST_LAUNCH_ONE : (quad ? WOST_LAUNCH_QUAD : WOST_LAUNCH_ROUND));
-            li.walkers = n_round;
-            li.walkers_beside = n_active - n_round + far_now + beside_far;
-            li.grid = n_round > 0 ? grid : 0u;
-            li.ms = ms;
-            for (int k = 0; k < kStatCopies; ++k) li.walk_steps_done += c->host_stats[k].steps;
-            c->last_launches.push_back(li);
-            if (getenv("WOST_TRACE_LAUNCHES")) fprintf(stderr, "launch %d: walkers %u of %u (+ %u strayed) grid %u %.3f ms -> %u left, %u strayed%s\n", launches, n_round, n_active, far_now, grid, ms, c->host_count[0], c->host_count[2], persist ? " (persistent)" : "");
-        }
-        if (n_round > 0) ++launches;
+        int rc = handed_over ? hand_over(c, g, stream, p, long_guard) : WOST_OK;
+        if (rc == WOST_OK && p.far > 0) rc = launch_strayed(c, g, stream, p, far_guard);
+        if (rc == WOST_OK) rc = launch_ordinary(c, g, stream, launches == 0, p);
+        if (rc == WOST_OK) rc = finish_pass(c, stream, p, launches, kernel_ms);
+        if (rc != WOST_OK) return rc;
+        handed_over = p.kind == WOST_LAUNCH_PERSISTENT;
+        if (p.n_round > 0) ++launches;
         pending_far = c->host_count[2];
         n_active = c->host_count[0];
         cur = nxt;
     }
-    if (long_pending) {
+    if (long_guard.stream) {
         // the long remainders may outlast the rounds: what is left of their launch counts as kernel time of the solve
         if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev0, stream));
         HIP_TRY(hipStreamWaitEvent(stream, c->long_ev1, 0));
@@ -1907,16 +1906,15 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
             float ms = 0.0f;
             HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
             kernel_ms += ms;
-            wost_launch_info li{};
-            li.kind = WOST_LAUNCH_WAIT;
-            li.ms = ms;
-            c->last_launches.push_back(li);
+            c->last_launches.push_back(wost_launch_info{WOST_LAUNCH_WAIT, 0, 0, 0, ms, 0});
             if (getenv("WOST_TRACE_LAUNCHES")) fprintf(stderr, "waited %.3f ms for the launch of the long remainders\n", ms);
         }
     }
     std::vector<StatsDev> copies(kStatCopies);
     HIP_TRY(hipMemcpyAsync(copies.data(), c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    // the solve's stream has waited for every side launch (far_ev1, long_ev1): nothing is left running
+    long_guard.stream = far_guard.stream = nullptr;
     StatsDev sd{};
     for (const StatsDev &k : copies) {
         sd.steps += k.steps; sd.started += k.started; sd.absorbed += k.absorbed; sd.truncated += k.truncated;
