@@ -780,7 +780,12 @@ static int run_solve3(wost3_context *c, int32_t pixel_begin, int32_t pixel_end, 
         (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
         int per_cu = 4;
         if (const char *w = std::getenv("WOST3_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(w));
-        const unsigned grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * per_cu);
+        unsigned grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * per_cu);
+        // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
+        if (const char *w = std::getenv("WOST3_MAX_BLOCKS")) {
+            const int cap = std::atoi(w);
+            if (cap >= 1) grid = std::min(grid, (unsigned)cap);
+        }
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(bs), lds, stream, P);
         W3_TRY(hipGetLastError());
         W3_TRY(hipEventRecord(c->ev1, stream));

@@ -7,6 +7,8 @@ from conftest import cube_scene3, sphere_scene3
 
 pytestmark = pytest.mark.gpu
 
+COUNTERS = ("walk_steps", "walks_started", "walks_absorbed", "walks_truncated", "neumann_hits")
+
 
 def _it(sd, w, h, spp, depth, eps):
     from elaina_amd import UniformIntegratorSettings
@@ -14,15 +16,49 @@ def _it(sd, w, h, spp, depth, eps):
     return UniformIntegrator3(Problem3.from_dict(sd), UniformIntegratorSettings((w, h), spp, depth, eps))
 
 
+def _same_counters(got, ref):
+    for k in COUNTERS:
+        assert got[k] == ref[k], (k, got[k], ref[k])
+
+
 def _same_solve(oracle, sd, w, h, spp, depth, eps):
     it = _it(sd, w, h, spp, depth, eps)
     it.solve()
     ref = oracle.solve3(sd, w, h, spp, depth, eps, threads=16)
-    for k in ("walk_steps", "walks_started", "walks_absorbed", "walks_truncated", "neumann_hits"):
-        assert it.last_stats[k] == ref[k], k
+    _same_counters(it.last_stats, ref)
     assert np.array_equal(it.solution, ref["field"]), float(np.abs(it.solution - ref["field"]).max())
     it.close()
     return ref
+
+
+def _owned_by_shard(w, h, shard_index, shard_count):
+    """the pixels of shard `shard_index`: whole 8x8 tiles, (w + 7) / 8 of them per row, dealt round robin"""
+    py, px = np.divmod(np.arange(w * h), w)
+    return ((py >> 3) * ((w + 7) >> 3) + (px >> 3)) % shard_count == shard_index
+
+
+def _shards_into_device_buffers(it, w, h, shard_count=3):
+    """every shard solved into a zeroed device buffer of the whole frame -> [(field, stats)]"""
+    import torch
+    out = []
+    for r in range(shard_count):
+        buf = torch.zeros(w * h * 3, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        st = dict(it.solve_sharded(r, shard_count, buf.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        out.append((buf.cpu().numpy().reshape(-1, 3), st))
+    return out
+
+
+def _same_shards(parts, ref, w, h):
+    """each shard equals the oracle's full field on its own tiles and is zero elsewhere; the counters add up to the oracle's"""
+    for r, (f, _) in enumerate(parts):
+        own = _owned_by_shard(w, h, r, len(parts))
+        assert own.any() and not own.all()
+        assert np.array_equal(f[own], ref["field"][own]), (r, float(np.abs(f[own] - ref["field"][own]).max()))
+        assert np.all(f[~own] == 0.0), r
+    for k in COUNTERS:
+        assert sum(st[k] for _, st in parts) == ref[k], k
 
 
 @pytest.mark.parametrize("subdiv", [0, 2, 3])
@@ -106,7 +142,127 @@ def test_3d_sharded_solve_sums_to_the_full_field(oracle):
         torch.cuda.synchronize()
         acc += part
     assert np.array_equal(acc.cpu().numpy().reshape(-1, 3), full)
+    # each shard against the oracle: its own tiles, zeros elsewhere, counters that add up
+    _same_shards(_shards_into_device_buffers(it, 40, 24), oracle.solve3(sd, 40, 24, 6, 64, 2e-3, threads=16), 40, 24)
     it.close()
+
+
+# ---- one lane, many pixels: the walk launch capped at WOST3_MAX_BLOCKS blocks of 256 lanes -----------------------------------
+# Frames of the other tests hold fewer pixels than the persistent grid has lanes, so the first grab of every wave hands out the
+# whole frame.  Under the cap every lane finishes a pixel and refills about seven times: the wave's leftover pool, the fold of
+# the finished pixel's counters into the lane totals, the reset of the lane and the tile order of the slots all matter.
+
+def _refill_scene(name, w, h):
+    if name == "sphere":
+        return sphere_scene3(subdiv=3, value=lambda x, y, z: x * y + z)
+    if name == "masked_cube":
+        sd = cube_scene3(n=2, d_faces=(0, 1), n_faces=(2, 3, 4, 5), value=lambda x, y, z: x, flux=lambda x, y, z, f: 0.0)
+        sd["mask"] = (np.random.default_rng(w * h).uniform(size=w * h) >= 0.3).astype(np.uint8)         # 30 % masked
+        return sd
+    if name == "shell":
+        return _shell_scene(2, 3)
+    if name == "emissive_shell":
+        return _shell_scene(2, 3, flux=lambda x, y, z: 0.3 * y)
+    if name == "source":
+        from test_oracle_3d import _unit_source
+        sd = sphere_scene3(subdiv=2, value=lambda x, y, z: 0.25 * x)
+        sd["probe"] = (0.5, (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), (1.0, 0.0, 0.0))
+        sd["source"] = _unit_source()
+        return sd
+    raise ValueError(name)
+
+
+@pytest.mark.parametrize("blocks,scene,w,h,spp,depth,knobs", [
+    (1, "sphere", 48, 40, 1, 64, {}),
+    (2, "sphere", 69, 53, 8, 64, {}),
+    (1, "masked_cube", 45, 37, 8, 48, {}),
+    (2, "masked_cube", 72, 56, 1, 48, {}),
+    (1, "shell", 48, 40, 8, 64, {}),                            # Neumann mesh on the tree: pools on (coop 2)
+    (2, "shell", 69, 53, 1, 48, {}),
+    (1, "emissive_shell", 45, 37, 2, 48, {}),
+    (2, "source", 72, 56, 8, 64, {}),
+    (1, "source", 45, 37, 1, 64, {}),
+    (1, "sphere", 45, 37, 8, 64, {"WOST3_WAVE": "0"}),          # the lane machine refills apart from the wave's queries
+])
+def test_3d_lanes_that_take_many_pixels_match_oracle(oracle, monkeypatch, blocks, scene, w, h, spp, depth, knobs):
+    """tiled (48x40, 72x56) and ragged (45x37, 69x53: slots in row order) frames of about seven pixels per lane, one sample
+    (many short pixels per lane) and eight (large per-pixel counters): the oracle's field and all five counters"""
+    assert w * h > 6 * 256 * blocks
+    monkeypatch.setenv("WOST3_MAX_BLOCKS", str(blocks))
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    ref = _same_solve(oracle, _refill_scene(scene, w, h), w, h, spp, depth, 2e-3)
+    assert ref["walks_started"] > 0 and np.any(ref["field"] != 0)
+
+
+def test_3d_pixel_ranges_of_a_capped_ragged_frame_match_oracle(oracle, monkeypatch):
+    """wost3_solve over part of the frame (the untiled order, the field written from `pixel_begin` on): pieces that put
+    together give the oracle's whole field, each with the oracle's counters of that range; ranges outside the frame refused"""
+    import ctypes as C
+    from elaina_amd import capi
+    monkeypatch.setenv("WOST3_MAX_BLOCKS", "1")
+    w, h, spp, depth, eps = 45, 37, 4, 48, 2e-3
+    n = w * h
+    sd = _refill_scene("masked_cube", w, h)
+    full = oracle.solve3(sd, w, h, spp, depth, eps, threads=16)
+    it = _it(sd, w, h, spp, depth, eps)
+    pieces, totals = [], dict.fromkeys(COUNTERS, 0)
+    for b, e in ((0, 1), (1, 700), (700, 700), (700, n)):
+        it.solve(b, e)
+        assert it.solution.shape == (e - b, 3)
+        _same_counters(it.last_stats, oracle.solve3(sd, w, h, spp, depth, eps, pixel_begin=b, pixel_end=e, threads=16))
+        for k in COUNTERS:
+            totals[k] += it.last_stats[k]
+        pieces.append(it.solution.copy())
+    assert np.array_equal(np.concatenate(pieces), full["field"])
+    _same_counters(totals, full)
+    buf = np.full((n + 2, 3), 7.0, np.float32)
+    for b, e in ((-1, 10), (0, n + 1), (10, 5), (n + 1, n + 1)):
+        st = capi.Stats()
+        with pytest.raises(capi.WostError):
+            capi._check(it.lib.wost3_solve(it._handle, b, e, capi._fp(buf), C.byref(st)), "wost3_solve")
+    assert np.all(buf == 7.0)
+    it.close()
+
+
+def test_3d_shards_of_a_capped_ragged_frame_match_oracle(oracle, monkeypatch):
+    """3 shards of a 45x37 frame (6 tiles per row, the last one ragged) into device buffers, one block of lanes that skips
+    the pixels of the other shards: the oracle's full field on the shard's own tiles, zeros elsewhere, counters that add up"""
+    monkeypatch.setenv("WOST3_MAX_BLOCKS", "1")
+    w, h, spp, depth, eps = 45, 37, 2, 48, 2e-3
+    sd = _refill_scene("emissive_shell", w, h)
+    sd["mask"] = (np.random.default_rng(3).uniform(size=w * h) >= 0.3).astype(np.uint8)
+    it = _it(sd, w, h, spp, depth, eps)
+    _same_shards(_shards_into_device_buffers(it, w, h), oracle.solve3(sd, w, h, spp, depth, eps, threads=16), w, h)
+    it.close()
+
+
+@pytest.mark.parametrize("case", ["shell_1024x512", "ragged_sphere_1000x700"])
+def test_3d_production_size_frame_with_more_pixels_than_lanes(oracle, case):
+    """the default grid (4 blocks per CU) on frames of about two pixels per lane, no knobs: three 8-row bands (the first,
+    middle and last rows -- in the tiled order the last slots are the last tiles) against the oracle, the counter identities,
+    a second solve with the same bits and counters, three shards that add up to the full field"""
+    if case == "shell_1024x512":
+        sd, w, h = _shell_scene(2, 3), 1024, 512
+    else:
+        sd, w, h = sphere_scene3(subdiv=3, value=lambda x, y, z: x * y + z), 1000, 700
+    spp, depth, eps = 2, 64, 2e-3
+    it = _it(sd, w, h, spp, depth, eps)
+    it.solve()
+    f, s = it.solution.copy(), dict(it.last_stats)
+    assert s["walks_started"] == w * h * spp == s["walks_absorbed"] + s["walks_truncated"]
+    for row in (0, h // 2 - 4, h - 8):
+        b, e = row * w, (row + 8) * w
+        ref = oracle.solve3(sd, w, h, spp, depth, eps, pixel_begin=b, pixel_end=e, threads=16)
+        assert np.array_equal(f[b:e], ref["field"]), (row, float(np.abs(f[b:e] - ref["field"]).max()))
+    it.solve()
+    assert np.array_equal(it.solution, f)
+    _same_counters(it.last_stats, s)
+    parts = _shards_into_device_buffers(it, w, h)
+    it.close()
+    assert np.array_equal(parts[0][0] + parts[1][0] + parts[2][0], f)
+    for k in COUNTERS:
+        assert sum(st[k] for _, st in parts) == s[k], k
 
 
 def _shell_scene(subdiv_d, subdiv_n, flux=None):
@@ -313,7 +469,8 @@ def test_3d_queries_and_walks_far_outside_the_meshes(oracle):
 
 def test_3d_random_scenes_match_the_oracle():
     """tools/fuzz/fuzz_parity3d.py: random bumpy icospheres of 20 .. 1280 triangles on either boundary kind, holes, emissive or
-    not, doubled and zero-area triangles, scales 1e-3 .. 1e3, probes that look at the scene from 40 scene sizes away"""
+    not, doubled and zero-area triangles, scales 1e-3 .. 1e3, probes that look at the scene from 40 scene sizes away, the walk
+    launch capped at one or two blocks on frames of about seven pixels per lane"""
     import os
     import subprocess
     import sys

@@ -77,7 +77,7 @@ def main():
             sd["mask"] = (rng.uniform(size=w * h) < 0.7).astype(np.uint8)
         # how the tree queries are answered -- by the wave through its task pools (default), per lane, pools too small for a trip
         # (the waves then answer the old way), slot tasks served eagerly -- must not change a bit
-        for k in ("WOST3_WAVE", "WOST3_COOP", "WOST3_POOL_CAP", "WOST3_RAY_TRIGGER", "WOST3_CP_TRIGGER"):
+        for k in ("WOST3_WAVE", "WOST3_COOP", "WOST3_POOL_CAP", "WOST3_RAY_TRIGGER", "WOST3_CP_TRIGGER", "WOST3_MAX_BLOCKS"):
             os.environ.pop(k, None)
         if rng.uniform() < 0.5:
             knobs = {"WOST3_WAVE": str(int(rng.choice([0, 1, 1]))), "WOST3_COOP": str(int(rng.choice([0, 1, 1]))),
@@ -85,6 +85,18 @@ def main():
                      "WOST3_CP_TRIGGER": str(int(rng.choice([1, 64])))}
             feat.append(str(knobs))
             os.environ.update(knobs)
+        # the walk launch capped at one or two blocks of 256 lanes on a frame scaled up to about seven pixels per lane, its
+        # right and bottom edges mostly cut ragged (the untiled order): every lane takes pixel after pixel through the refill.
+        # Drawn after everything else, so that each seed keeps its scene and knobs.
+        blocks = int(rng.choice([0, 0, 0, 1, 2]))
+        if blocks:
+            k = int(np.ceil(np.sqrt(7 * 256 * blocks / (w * h))))
+            w2, h2 = w * k - int(rng.integers(0, 8)), h * k - int(rng.integers(0, 8))
+            if "mask" in sd:
+                sd["mask"] = np.ascontiguousarray(np.tile(sd["mask"].reshape(h, w), (k, k))[:h2, :w2].reshape(-1))
+            w, h = w2, h2
+            feat.append("max blocks %d frame %dx%d" % (blocks, w, h))
+            os.environ["WOST3_MAX_BLOCKS"] = str(blocks)
         it = UniformIntegrator3(Problem3.from_dict(sd), UniformIntegratorSettings((w, h), spp, depth, eps))
         it.solve()
         ref = oracle.solve3(sd, w, h, spp, depth, eps, threads=os.cpu_count() or 8)
