@@ -1551,6 +1551,7 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
 
     // one launch of the fused sample kernel on `st` with the network image `Fn` and the launch state in P
     const uint32_t *walk_order = nullptr;     // built once per solve, when the cache of the evaluation points' queries is full
+    unsigned last_grid = 0;                   // blocks of the last launch (WOST_GUIDED_DEBUG prints them)
     auto launch_walk = [&](const FusedNet &Fn, hipStream_t st) -> int {
         G_TRY(hipMemsetAsync(g->cursor, 0, sizeof(uint32_t), st));
         // (not for the launches of several samples per pixel, whose drain is one walk whatever the order, nor for one rank's shard:
@@ -1575,7 +1576,13 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
             if (P.training) G_TRY(hipMemsetAsync(g->cur_depth, 0, (size_t)N * (size_t)P.n_samples * sizeof(uint32_t), st));
             launches += 2;
         }
-        const unsigned gridf = (unsigned)std::min<size_t>(256, ((size_t)N + n_fused_threads - 1) / n_fused_threads);
+        unsigned gridf = (unsigned)std::min<size_t>(256, ((size_t)N + n_fused_threads - 1) / n_fused_threads);
+        // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
+        if (const char *w = std::getenv("WOST_GUIDED_MAX_BLOCKS")) {
+            const int cap = std::atoi(w);
+            if (cap >= 1) gridf = std::min(gridf, (unsigned)cap);
+        }
+        last_grid = gridf;
 #define LAUNCH_FUSED(E, T)                                                                                                      \
     do {                                                                                                                        \
         auto kfn = v.src.rgb ? (fused_half ? guided_sample_kernel<E, T, true, true> : guided_sample_kernel<E, T, true, false>)    \
@@ -1843,8 +1850,8 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
             if (dbg) {
                 unsigned long long t[4];
                 G_TRY(hipMemcpy(t, g->dbg, sizeof(t), hipMemcpyDeviceToHost));
-                std::fprintf(stderr, "[fused sample %d x%d] first wave out of pixels at %.1f us, last at %.1f us, end %.1f us\n", sample, n_run,
-                             (double)(t[1] - t[0]) / 100.0, (double)(t[2] - t[0]) / 100.0, (double)(t[3] - t[0]) / 100.0);
+                std::fprintf(stderr, "[fused sample %d x%d] %u blocks: first wave out of pixels at %.1f us, last at %.1f us, end %.1f us\n", sample,
+                             n_run, last_grid, (double)(t[1] - t[0]) / 100.0, (double)(t[2] - t[0]) / 100.0, (double)(t[3] - t[0]) / 100.0);
             }
             sample += n_run - 1;     // the index of the last sample this launch has run
             d0_valid = true;

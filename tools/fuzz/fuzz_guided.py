@@ -45,6 +45,21 @@ def main():
         if rng.uniform() < 0.25:
             feat.append("mask")
             p.mask = (rng.uniform(size=w * h) < 0.75).astype(np.uint8)
+        # the fused kernel's grid capped at one or two blocks (640 lanes each in fp32, 768 in half precision) on a frame of 48 to 80
+        # pixels a side, mostly ragged (the row-major order): every lane of a one-sample launch takes pixel after pixel.  Drawn
+        # after everything else, so that each seed keeps its scene and settings.
+        os.environ.pop("WOST_GUIDED_MAX_BLOCKS", None)
+        blocks = int(rng.choice([0, 0, 0, 1, 2]))
+        if blocks:
+            w2, h2 = int(rng.integers(48, 81)), int(rng.integers(48, 81))
+            if rng.uniform() < 0.25:
+                w2, h2 = w2 // 8 * 8, h2 // 8 * 8
+            if p.mask is not None:
+                k = int(np.ceil(max(w2 / w, h2 / h)))
+                p.mask = np.ascontiguousarray(np.tile(p.mask.reshape(h, w), (k, k))[:h2, :w2].reshape(-1))
+            w, h = w2, h2
+            feat.append("max blocks %d frame %dx%d" % (blocks, w, h))
+            os.environ["WOST_GUIDED_MAX_BLOCKS"] = str(blocks)
         feat.append("mgd %s stride %d+%d" % (mgd, stride, offset))
         st = GuidedIntegratorSettings(frameSize=(w, h), samplesPerPixel=spp, trainSppCount=train, maxWalkingDepth=depth, epsilonShell=eps,
                                       uniformFractionInTrainingPhase=uf[0], uniformFractionInGuidingPhase=uf[1],
