@@ -538,15 +538,65 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                 }
             }
         }
-        const int n_trav = __popcll(__ballot(mode == MODE_TRAV));
-        const int n_wait = __popcll(__ballot(mode == MODE_WAIT));
+        int n_trav = __popcll(__ballot(mode == MODE_TRAV));
+        int n_wait = __popcll(__ballot(mode == MODE_WAIT));
         if (n_trav + n_wait == 0) {
             if (REFILL && __ballot(mode == MODE_REFILL)) continue;
             break;
         }
-        if (n_wait * P.wait_weight >= n_trav * 8) {
-            ++step_trips;
+        if (n_wait * P.wait_weight < n_trav * 8) {
+            // ---- traversal phase: every traversing lane visits one node ----
+            // The phase is a loop of its own: after a burst the scheduler's test is made right here, and while it still
+            // prefers traversal the next burst follows without a trip through the outer loop.  The outer loop carries the
+            // whole lane state (Lane, Trav, mode, counters) and the compiler gives that state one home in registers across
+            // the back edge and another inside each body, with copies in and out; about two of three traversal trips follow
+            // a traversal trip, and those now pay none of them (EXPERIMENTS "Register copies around the scheduler loop").
+            // Same ballots, same test, same counters: the sequence of bodies a wave runs is what it was.  A lane that waits
+            // for a refill (a REFILL launch took a pixel with no sample left) is served at the head of the outer loop, so
+            // such a wave goes back there after every burst as before; no lane turns to MODE_REFILL inside this phase.
+            const bool refill_waiting = REFILL && __ballot(mode == MODE_REFILL) != 0ull;
+            for (;;) {
+                ++trav_trips;
+#ifndef WOST_TRAV_BURST
+#define WOST_TRAV_BURST 3       // the burst the kernel is unrolled for: the automatic one of rounds with a Neumann mesh on the tree (set_schedule)
+#endif
+                if (!PERSIST && P.trav_burst == WOST_TRAV_BURST) {
+                    // that burst, unrolled: no loop counter, and the compiler may start a visit's node load early
+#pragma unroll
+                    for (int b = 0; b < WOST_TRAV_BURST; ++b) {
+                        if (mode == MODE_TRAV) {
+                            S.visits++;
+                            WOST_TRACK_VISIT_PRE();
+                            if (!trav_visit<SLACK>(P.dm, L.px, L.py, T, stk)) mode = MODE_WAIT;
+                            WOST_TRACK_VISIT_POST();
+                        }
+                    }
+                } else {
+                    for (int b = 0; b < P.trav_burst; ++b) {
+                        if (mode == MODE_TRAV) {
+                            S.visits++;
+                            WOST_TRACK_VISIT_PRE();
+                            if (!trav_visit<SLACK>(P.dm, L.px, L.py, T, stk)) mode = MODE_WAIT;
+                            WOST_TRACK_VISIT_POST();
+                        }
+                    }
+                }
+                if (refill_waiting) break;
+                n_trav = __popcll(__ballot(mode == MODE_TRAV));
+                n_wait = __popcll(__ballot(mode == MODE_WAIT));
+                if (n_wait * P.wait_weight >= n_trav * 8) break;      // (also when no lane is left in either mode)
+            }
+            // The test prefers the step phase now, and it is the test the next trip would make on the same modes: the step phase
+            // follows at once, in this trip, with the state where the traversal left it -- not after a round through the back
+            // edge, which moved every value to its register of the loop head and back.  Only a wave with nothing left to do, or
+            // with a lane waiting for a refill, goes to the head.
+            // (Not in the persistent launch, which lives on 80 registers: with both phases in one trip its scratch grew from
+            // 44 to 104 bytes per lane, spill code inside the loop.  It goes to the head, which makes the same test again.)
+            if (PERSIST || refill_waiting || n_trav + n_wait == 0) continue;
+        }
+        {
             // ---- step phase ----
+            ++step_trips;
             uint32_t wave_status = 0u;
             if (NEUMANN_TREE && P.coop) {
                 // (8-byte LDS atomics: the pools start at an 8-byte boundary whatever lies before the dynamic segment)
@@ -555,8 +605,10 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                 const WavePool W{pw + kPoolOwnerWords, pw + kPoolOwnerWords + P.pool_cap, pw, P.pool_cap};
                 wave_status = step_finish_wave<NEUMANN_EMISSIVE, SOURCE>(P.dm, P.nm, P.st, L, T.best, mode == MODE_WAIT && !fresh, W, stk, P.ray_slot_trigger, P.src);
             }
-            if (mode == MODE_WAIT) {
-                if (!fresh) {
+            // (two branches side by side, not one inside the other: nested, every value that only the inner one changes was
+            // copied to its register of the join twice, once in front of each)
+            if (mode == MODE_WAIT && !fresh) {
+                {
                     const uint32_t status = (NEUMANN_TREE && P.coop) ? wave_status
                                                                      : step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src);
                     const bool ended = (status & STEP_ENDED) != 0u;
@@ -574,6 +626,8 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                     }
                     --budget;
                 }
+            }
+            if (mode == MODE_WAIT) {
                 fresh = false;
                 if (alive && budget > 0) {
                     if (!has_d || L.depth == 0) {
@@ -616,33 +670,6 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                         mode = MODE_WAIT;
                     }
                     hb &= hb - 1;
-                }
-            }
-        } else {
-            // ---- traversal phase: every traversing lane visits one node ----
-            ++trav_trips;
-#ifndef WOST_TRAV_BURST
-#define WOST_TRAV_BURST 3       // the burst the kernel is unrolled for: the automatic one of rounds with a Neumann mesh on the tree (set_schedule)
-#endif
-            if (!PERSIST && P.trav_burst == WOST_TRAV_BURST) {
-                // that burst, unrolled: no loop counter, and the compiler may start a visit's node load early
-#pragma unroll
-                for (int b = 0; b < WOST_TRAV_BURST; ++b) {
-                    if (mode == MODE_TRAV) {
-                        S.visits++;
-                        WOST_TRACK_VISIT_PRE();
-                        if (!trav_visit<SLACK>(P.dm, L.px, L.py, T, stk)) mode = MODE_WAIT;
-                        WOST_TRACK_VISIT_POST();
-                    }
-                }
-            } else {
-                for (int b = 0; b < P.trav_burst; ++b) {
-                    if (mode == MODE_TRAV) {
-                        S.visits++;
-                        WOST_TRACK_VISIT_PRE();
-                        if (!trav_visit<SLACK>(P.dm, L.px, L.py, T, stk)) mode = MODE_WAIT;
-                        WOST_TRACK_VISIT_POST();
-                    }
                 }
             }
         }
@@ -762,13 +789,30 @@ __global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
     Trav T = trav_begin(Closest{WOST_INF, -1});
     uint32_t trav_trips = 0, step_trips = 0;
     for (;;) {
-        const int n_trav = __popcll(__ballot(mode == MODE_TRAV));
-        const int n_wait = __popcll(__ballot(mode == MODE_WAIT));
+        int n_trav = __popcll(__ballot(mode == MODE_TRAV));
+        int n_wait = __popcll(__ballot(mode == MODE_WAIT));
         if (n_trav + n_wait == 0) break;
-        if (n_wait * P.wait_weight >= n_trav * 8) {
+        if (n_wait * P.wait_weight < n_trav * 8) {
+            // the traversal phase lasts while the scheduler's test prefers it, and the step phase follows it in the same trip
+            // (see walk_round_kernel)
+            for (;;) {
+                ++trav_trips;
+                for (int b = 0; b < P.trav_burst; ++b) {
+                    if (mode == MODE_TRAV) {
+                        S.visits++;
+                        if (!quad_visit<SLACK>(P.dm, L.px, L.py, T, stk, j)) mode = MODE_WAIT;
+                    }
+                }
+                n_trav = __popcll(__ballot(mode == MODE_TRAV));
+                n_wait = __popcll(__ballot(mode == MODE_WAIT));
+                if (n_wait * P.wait_weight >= n_trav * 8) break;
+            }
+            if (n_trav + n_wait == 0) break;
+        }
+        {
             ++step_trips;
-            if (mode == MODE_WAIT) {
-                if (!fresh) {
+            if (mode == MODE_WAIT && !fresh) {       // (beside the next branch, not around it: see walk_round_kernel)
+                {
                     const uint32_t status = step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src);
                     const bool ended = (status & STEP_ENDED) != 0u;
                     S.b += ((status >> 1) & 1u) | (((status >> 2) & 1u) << 16);
@@ -783,6 +827,8 @@ __global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
                     }
                     --budget;
                 }
+            }
+            if (mode == MODE_WAIT) {
                 fresh = false;
                 if (alive && budget > 0) {
                     if (!has_d || L.depth == 0) {
@@ -812,14 +858,6 @@ __global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
                         mode = MODE_WAIT;
                     }
                     hb &= ~(0xfull << (src & ~3));
-                }
-            }
-        } else {
-            ++trav_trips;
-            for (int b = 0; b < P.trav_burst; ++b) {
-                if (mode == MODE_TRAV) {
-                    S.visits++;
-                    if (!quad_visit<SLACK>(P.dm, L.px, L.py, T, stk, j)) mode = MODE_WAIT;
                 }
             }
         }
