@@ -1177,12 +1177,11 @@ struct wost_guided {
     void *frame_user = nullptr;
     int32_t frame_spp_every = 0, frame_spp_until = 0, frame_time_every = 0;
     EventRing net_events;              // timing of the network-evaluating launches
-    // opt-in pipelined training order (wost_guided_set_option "pipeline"): the training pass of sample k runs on its own
-    // stream while sample k + 1 walks with a frozen copy of the weights of pass k - 1
-    int pipeline = 0;
-    // opt-in "train_group" S: a training launch walks S samples of every pixel back to back (one record set per sample) and the S
-    // training passes follow the launch: the drain of the longest walks is paid once per S samples; S = 1 is the reference's order
-    int train_group = 1;
+    // opt-in training orders (wost_guided_set_option; GuidedPlan).  "train_group" S: a training launch walks S samples of every pixel
+    // back to back (one record set per sample) and the S training passes follow the launch: the drain of the longest walks is paid once
+    // per S samples; S = 1 is the reference's order.  "pipeline" 1: the passes of a group run on their own stream while the next group
+    // walks with a frozen copy of the weights that the passes of the group before left.
+    int pipeline = 0, train_group = 1;
     // the pixels of a fused launch in the order of wost_order.h -- longest expected walk first, by the cached distance of the
     // evaluation points -- from the second launch of a solve on (the first fills the cache): the drain of a launch is its longest
     // walks, and they start first (the uniform one-launch path: 2.64 -> 2.48 ms at 1 spp)
@@ -1191,7 +1190,7 @@ struct wost_guided {
     int rec_sets = 1;                     // record sets rec / cur_depth are allocated for
     std::vector<TrainSet> ts_more;        // training-set arrays of the sets 1 .. (pipelined groups train while the next group walks)
     hipStream_t train_stream = nullptr;
-    void *snap[2] = {nullptr, nullptr};   // frozen inference images, used alternately
+    uint8_t *snap[2] = {nullptr, nullptr};   // frozen inference images, used alternately
     hipEvent_t ev_ts = nullptr;           // the training set of a sample is complete (walk stream)
     hipEvent_t ev_train[2] = {nullptr, nullptr};   // training pass k is complete and its weights are in snap[k % 2] (training stream)
     EventRing train_events;               // device time of the training passes in that mode
@@ -1377,14 +1376,9 @@ int wost_guided_set_option(wost_guided_handle h, const char *key, double value)
 {
     if (!h || !key) return set_error(WOST_ERR_INVALID, "null argument");
     const std::string k(key);
-    if (k == "pipeline") {
-        if (!(value == 0.0 || value == 1.0)) return set_error(WOST_ERR_INVALID, "pipeline is 0 or 1");
-        h->pipeline = (int)value;
-        return WOST_OK;
-    }
-    if (k == "walk_order") {
-        if (!(value == 0.0 || value == 1.0)) return set_error(WOST_ERR_INVALID, "walk_order is 0 or 1");
-        h->walk_order = (int)value;
+    if (k == "pipeline" || k == "walk_order") {
+        if (!(value == 0.0 || value == 1.0)) return set_error(WOST_ERR_INVALID, k + " is 0 or 1");
+        (k == "pipeline" ? h->pipeline : h->walk_order) = (int)value;
         return WOST_OK;
     }
     if (k == "train_group") {
@@ -1433,556 +1427,562 @@ int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, fl
 
 }  // extern "C"
 
-// the shared driver: field_host (n_pixels*3, may be null) and/or field_dev (device, n_pixels*3)
-static int run_guided(wost_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev,
-                      wost_guided_stats *stats)
+// ---- the solve driver.  First everything that is fixed for one solve.  guided_plan() fills it once per solve and is the only place that reads the driver's
+// environment switches -- at solve time, not at handle creation: they may change between two solves on one handle.
+struct GuidedPlan {
+    bool emissive, tree, source;      // the scene's flags = the template arguments of the walk kernels
+    int stack_words;                  // a lane's traversal stack in the kernels per depth ...
+    size_t lds, lds_fused;            // ... and the LDS of their 256-lane blocks; of a block of the fused kernel
+    // a whole sample is one launch whenever the network has the reference's shape -- with the half-precision image when "precision"
+    // is 16, with the fp32 fragments otherwise -- and WOST_GUIDED_FUSED=0 does not ask for the path per depth (same field, same records)
+    bool fused, fused_half;
+    FusedNet F;                       // the network's own images
+    int n_fused_threads, fused_stack_words;      // (the fused kernel's columns also hold a walker's mixture)
+    unsigned grid_fused;              // WOST_GUIDED_MAX_BLOCKS caps it, so that every lane takes many pixels one after another (tests)
+    int wait_weight, trav_burst, tail_chunk, tail_margin_pct;      // WOST_GUIDED_WAIT_WEIGHT / TRAV_BURST / TAIL_CHUNK / TAIL_MARGIN
+    int samples_per_launch;           // of a launch that trains nothing: WOST_GUIDED_SAMPLES_PER_LAUNCH [64]
+    bool dbg;                         // WOST_GUIDED_DEBUG
+    uint32_t train_offset;            // trainPixelOffset of this solve
+    int n_train_pixels, n_train_blocks;
+    // The opt-in training orders (never the parity mode).  The estimator is unbiased for ANY network state (a step's direction and its
+    // one-sample MIS density come from the same weights, and a training record carries the density it was drawn with): the only change is
+    // that the network a sample sees is a few training passes older.  Both need the fused kernel; a solve with intermediate frames keeps the reference's order.
+    int n_trained, group;
+    bool reordered;
+};
+
+// the guiding state of a sample (ctor state integrator.cu:1158-1160, prepareSolve :125-126, the switch :991-996)
+struct GuidePhase { bool training; float uniform_fraction; int max_guided_depth; };
+static GuidePhase phase_at(const wost_guided_settings &s, int sample)
 {
-    const auto t_start = std::chrono::high_resolution_clock::now();
-    G_TRY(hipSetDevice(g->device));
-    const wost_guided_settings &s = g->gs;
-    const SceneView &v = g->view;
-    hipStream_t stream = v.stream;
-    const int N = (int)g->n_pixels;
-    const bool emissive = v.nm.n_segs > 0 && v.nm.emissive;
-    const bool tree = v.nm.n_segs > WOST_FLAT_MAX;
-    const int d_levels = v.dm.n_segs > 0 ? v.dm.levels : 1, n_levels = v.nm.n_segs > 0 ? v.nm.levels : 1;
-    const int stack_words = 3 * std::max(d_levels, n_levels) + 1;
-    const size_t lds = (size_t)stack_words * 256 * sizeof(uint32_t);
-    uint32_t launches = 0;
-    const uint64_t net_launches_before = net_launch_count(g->net);
+    if (sample < s.train_spp_count) return {true, s.uniform_fraction_training, s.max_guided_depth_training};
+    return {false, s.uniform_fraction_guiding, s.max_guided_depth_guiding};
+}
+
+// what the steps of a solve count and hand to each other
+struct GuidedRun {
+    std::chrono::high_resolution_clock::time_point t_start;
+    uint64_t net_launches_before; int opt_before;      // the network's counters when the solve began
+    uint32_t launches = 0;                  // of this file; the network counts its own
     double train_ms = 0.0;
     uint64_t train_samples = 0;
-    const int opt_before = net_optimizer_steps(g->net);
+    const uint32_t *walk_order = nullptr;   // built once per solve, when the cache of the evaluation points' queries is full ...
+    bool d0_valid = false;                  // ... which the first fused launch of the solve fills
+};
 
-    G_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
-    if (g->sync) {
-        // shared network: the summed gradients are divided by the number of ranks (include/wost.h)
-        // (WOST_SYNC_RANKS_I64_HOST was added to the callback's ops in library version 0.2: a callback written against 0.1
-        // answers WOST_SYNC_UNSUPPORTED and keeps the old behaviour -- the summed gradient is used undivided; any other
-        // non-zero return is a failure and ends the solve)
-        int64_t ranks = 1;
-        const int src = g->sync(g->sync_user, WOST_SYNC_RANKS_I64_HOST, &ranks, 1);
-        if (src == WOST_SYNC_UNSUPPORTED) {
-            fprintf(stderr, "wost: the sync callback does not know WOST_SYNC_RANKS_I64_HOST; shared gradients stay undivided\n");
-            ranks = 1;
-        } else if (src != 0 || ranks < 1) {
-            // a genuine failure (or a nonsensical answer) must not train on: the other ranks would step with another gradient
-            return set_error(WOST_ERR_DEVICE, "sync callback failed (rank count)");
-        }
-        net_set_gradient_divisor(g->net, (float)ranks);
-    } else {
-        net_set_gradient_divisor(g->net, 1.0f);
+// The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource), the network's precision
+// H(alf).  These are all the walk instantiations there are:
+//   G_FUSED  guided_sample_kernel<E, T, S, H>   G_SEPARATE  separate_kernel<E, T, S>   G_TAIL  tail_kernel<E, T, S>   G_SAMPLE  sample_kernel<T>
+enum GKernel { G_FUSED, G_SEPARATE, G_TAIL, G_SAMPLE };
+template <bool E, bool T, bool S>
+static const void *guided_kernel_of(GKernel kind, bool half)
+{
+    if (kind == G_FUSED) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false>);
+    if (kind == G_SEPARATE) return reinterpret_cast<const void *>(separate_kernel<E, T, S>);
+    return kind == G_TAIL ? reinterpret_cast<const void *>(tail_kernel<E, T, S>) : reinterpret_cast<const void *>(sample_kernel<T>);
+}
+static const void *guided_kernel(GKernel k, const GuidedPlan &pl)
+{
+    const bool h = pl.fused_half;
+    if (pl.emissive && pl.tree) return pl.source ? guided_kernel_of<true, true, true>(k, h) : guided_kernel_of<true, true, false>(k, h);
+    if (pl.emissive) return pl.source ? guided_kernel_of<true, false, true>(k, h) : guided_kernel_of<true, false, false>(k, h);
+    if (pl.tree) return pl.source ? guided_kernel_of<false, true, true>(k, h) : guided_kernel_of<false, true, false>(k, h);
+    return pl.source ? guided_kernel_of<false, false, true>(k, h) : guided_kernel_of<false, false, false>(k, h);
+}
+// one launch of a walk kernel, counted; Fn: the network image of a G_FUSED launch (the kernels per depth take P alone)
+static void launch_guided(GKernel kind, const GuidedPlan &pl, GuidedRun &run, unsigned grid, hipStream_t st, GParams P, FusedNet Fn = FusedNet{})
+{
+    void *args[] = {&P, &Fn};
+    const bool f = kind == G_FUSED;
+    ++run.launches;
+    (void)hipLaunchKernel(guided_kernel(kind, pl), dim3(grid), dim3(f ? pl.n_fused_threads : 256), args, f ? pl.lds_fused : pl.lds, st);
+}
+
+// the members of F that describe the network's shape; false when the fused kernel does not exist for it
+static bool fused_shape(const NetLayout *L, FusedNet &Fn)
+{
+    if (!(L && L->n_levels == 8 && L->n_features == 4 && L->enc == 32 && L->n_neurons == 64 && L->n_hidden == 3 && L->n_out_padded == 48 && L->n_out == 33))
+        return false;
+    Fn.n_frag = L->n_mlp / 4; Fn.n_mlp = L->n_mlp;
+    for (int l = 0; l < 4; ++l) { Fn.w_off[l] = L->w_off[l]; Fn.w_off4[l] = L->w_off[l] / 4; }
+    for (int l = 0; l < 8; ++l) { Fn.scale[l] = L->scale[l]; Fn.res[l] = (uint32_t)L->res[l]; }
+    for (int l = 0; l <= 8; ++l) Fn.off[l] = L->level_off[l];
+    return true;
+}
+
+static int env_int(const char *name, int fallback, int at_least)
+{
+    const char *w = std::getenv(name);
+    return w ? std::max(at_least, std::atoi(w)) : fallback;
+}
+
+static GuidedPlan guided_plan(wost_guided *g)
+{
+    const wost_guided_settings &s = g->gs;
+    const SceneView &v = g->view;
+    const size_t N = g->n_pixels;
+    GuidedPlan pl{};
+    pl.emissive = v.nm.n_segs > 0 && v.nm.emissive; pl.tree = v.nm.n_segs > WOST_FLAT_MAX; pl.source = v.src.rgb != nullptr;
+    pl.stack_words = 3 * std::max(v.dm.n_segs > 0 ? v.dm.levels : 1, v.nm.n_segs > 0 ? v.nm.levels : 1) + 1;
+    pl.lds = (size_t)pl.stack_words * 256 * sizeof(uint32_t);
+    // prepareSolve (integrator.cu:126): trainPixelOffset = stride <= 1 ? 0 : sampler.get1D() * stride, one draw per
+    // solve from the integrator's host sampler; a caller-fixed offset (>= 0) overrides the draw
+    if (s.train_pixel_stride > 1 && s.train_pixel_offset >= 0) pl.train_offset = (uint32_t)s.train_pixel_offset;
+    else if (s.train_pixel_stride > 1) {
+        union { uint32_t u; float f; } x;
+        x.u = (host_pcg_next(g) >> 9) | 0x3f800000u;
+        pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
+    g->last_train_offset = pl.train_offset;
+    pl.n_train_pixels = (int)((N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride);
+    pl.n_train_blocks = (pl.n_train_pixels + 255) / 256;
+    const char *env = std::getenv("WOST_GUIDED_FUSED");
+    const bool wanted = !(env && env[0] == '0');
+    HalfNetView hv{}; F32NetView fv{};
+    const NetLayout *L = nullptr;
+    if (wanted && net_half_view(g->net, &hv) == WOST_OK) { L = &hv.L; pl.fused_half = true; pl.F.image = hv.image; }
+    else if (wanted && net_f32_view(g->net, &fv) == WOST_OK) { L = &fv.L; pl.F.frag32 = fv.frag; pl.F.grid32 = fv.grid; }
+    pl.fused = fused_shape(L, pl.F);
+    pl.fused_stack_words = std::max(pl.stack_words, kVmmColWords);
+    pl.wait_weight = env_int("WOST_GUIDED_WAIT_WEIGHT", 4, 1);      // measured on config 4 (a sweep over both constants)
+    pl.trav_burst = env_int("WOST_GUIDED_TRAV_BURST", 10, 1);
+    pl.tail_chunk = env_int("WOST_GUIDED_TAIL_CHUNK", 4, 0);        // a sweep over both, DESIGN.md 4.9: 3.52 -> 3.37 ms per trained sample of config 4
+    pl.tail_margin_pct = env_int("WOST_GUIDED_TAIL_MARGIN", 300, 0);
+    // a pixel's samples run one after the other in one lane, so the last pixels taken keep a few lanes busy for n walks while
+    // the chip idles: bounded launches keep that tail short against the launch itself
+    pl.samples_per_launch = env_int("WOST_GUIDED_SAMPLES_PER_LAUNCH", 64, 1);
+    pl.dbg = std::getenv("WOST_GUIDED_DEBUG") != nullptr;
+    pl.n_fused_threads = fused_threads(pl.fused_half);
+    pl.lds_fused = ((size_t)pl.fused_stack_words * pl.n_fused_threads + (size_t)(pl.n_fused_threads / 64) * fused_xch_words(pl.fused_half) +
+                    (pl.fused_half ? (size_t)2 * pl.F.n_frag : (size_t)pl.F.n_mlp)) * sizeof(uint32_t);
+    pl.grid_fused = (unsigned)std::min<size_t>(256, (N + pl.n_fused_threads - 1) / pl.n_fused_threads);
+    if (const int cap = env_int("WOST_GUIDED_MAX_BLOCKS", 0, 0)) pl.grid_fused = std::min(pl.grid_fused, (unsigned)cap);
+    if (pl.fused) {
+        // the stack columns grow with the depth of the trees: when the fused kernel's LDS no longer fits a block (the fp32 fragments with a 10-level
+        // tree), or the device refuses it to the one instantiation this solve launches, the solve takes the path per depth instead of failing at the launch
+        int max_lds = 0, dev_optin = 0;
+        if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, g->device) != hipSuccess || max_lds <= 0) max_lds = 64 * 1024;
+        if (hipDeviceGetAttribute(&dev_optin, hipDeviceAttributeSharedMemPerBlockOptin, g->device) == hipSuccess && dev_optin > max_lds) max_lds = dev_optin;
+        const bool fits = pl.lds_fused <= (size_t)max_lds;
+        pl.fused = fits && hipFuncSetAttribute(guided_kernel(G_FUSED, pl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_fused) == hipSuccess;
+        if (fits && !pl.fused) (void)hipGetLastError();
+    }
+    pl.n_trained = std::min(s.spp, s.train_spp_count);
+    pl.reordered = pl.fused && pl.n_trained > 0 && !g->frame_fn && !pl.dbg && (g->pipeline || g->train_group > 1);
+    pl.group = pl.reordered ? std::min(std::max(g->train_group, 1), pl.n_trained) : 1;
+    return pl;
+}
+
+// The groups grow with the training: the launch that starts at sample s covers min(S, max(1, s / 2)) samples -- never more than half of what has
+// been trained before it.  The network learns fastest from its first samples; with fixed groups of 16 the first sixteen samples of a solve all walked
+// with the untrained network (on config 4: rel-L2 against a 4096-sample field 0.0262, worse than the uniform integrator's 0.0248; the reference's order 0.0244).
+static int group_at(const GuidedPlan &pl, int first_sample)
+{
+    return std::min(std::min(pl.group, std::max(1, first_sample / 2)), pl.n_trained - first_sample);
+}
+
+// The GParams fields that every launch of a solve shares (built after grow_record_sets).  A launch per depth adds its queues,
+// counters and depth (walk_per_depth); a fused launch adds what launch_fused sets.
+static GParams base_params(const wost_guided *g, const GuidedPlan &pl, int shard_index, int shard_count)
+{
+    const SceneView &v = g->view;
+    const size_t N = g->n_pixels;
     GParams P{};
     P.dm = v.dm; P.nm = v.nm; P.st = v.st; P.probe = v.probe; P.src = v.src; P.box = g->box; P.mask = v.mask;
     P.rng = g->rng; P.sol = g->sol; P.cur_depth = g->cur_depth; P.rec = g->rec; P.hint0 = g->hint0;
-    P.rec_ld = (size_t)N; P.net_in = g->net_in; P.net_out = g->net_out; P.net_ld = (size_t)N; P.stats = g->stats; P.n_pixels = N; P.stack_stride = 256;
-    P.max_train_depth = s.max_train_depth;
-    // prepareSolve (integrator.cu:126): trainPixelOffset = stride <= 1 ? 0 : sampler.get1D() * stride, one draw per
-    // solve from the integrator's host sampler; a caller-fixed offset (>= 0) overrides the draw
-    uint32_t train_offset = 0;
-    if (s.train_pixel_stride > 1) {
-        if (s.train_pixel_offset >= 0) train_offset = (uint32_t)s.train_pixel_offset;
-        else {
-            union { uint32_t u; float f; } x;
-            x.u = (host_pcg_next(g) >> 9) | 0x3f800000u;
-            train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
-        }
-    }
-    g->last_train_offset = train_offset;
-    const int n_train_pixels = (int)(((size_t)N - train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride);
-    const int n_train_blocks = (n_train_pixels + 255) / 256;
-    P.train_offset = train_offset; P.train_stride = (uint32_t)s.train_pixel_stride;
-    P.shard_index = shard_index; P.shard_count = shard_count;
+    P.rec_ld = N * (size_t)g->rec_sets; P.net_in = g->net_in; P.net_out = g->net_out; P.net_ld = N; P.stats = g->stats; P.n_pixels = (int32_t)N; P.stack_stride = 256;
+    P.max_train_depth = g->gs.max_train_depth; P.train_offset = pl.train_offset; P.train_stride = (uint32_t)g->gs.train_pixel_stride; P.shard_index = shard_index; P.shard_count = shard_count;
+    P.d0_d2 = g->d0_d2; P.cursor = g->cursor; P.pstate = g->pstate; P.stack_words = pl.fused_stack_words;
+    P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.tail_chunk = pl.tail_chunk; P.tail_margin_pct = pl.tail_margin_pct;
+    return P;
+}
 
-    // A whole sample is one launch (guided_sample_kernel, the network evaluated inside the wave) whenever the network has
-    // the reference's shape: with the half-precision image when "precision" is 16, with the fp32 fragments otherwise.
-    // WOST_GUIDED_FUSED=0 keeps the one-launch-per-depth path for comparison (same field, same records).
-    bool fused = false, fused_half = false;
-    FusedNet F{};
-    // the members of F that describe the network's shape; false when the fused kernel does not exist for it
-    auto fused_shape = [](const NetLayout *L, FusedNet &Fn) {
-        if (!(L && L->n_levels == 8 && L->n_features == 4 && L->enc == 32 && L->n_neurons == 64 && L->n_hidden == 3 && L->n_out_padded == 48 &&
-              L->n_out == 33))
-            return false;
-        Fn.n_frag = L->n_mlp / 4;
-        Fn.n_mlp = L->n_mlp;
-        for (int l = 0; l < 4; ++l) { Fn.w_off[l] = L->w_off[l]; Fn.w_off4[l] = L->w_off[l] / 4; }
-        for (int l = 0; l < 8; ++l) { Fn.scale[l] = L->scale[l]; Fn.res[l] = (uint32_t)L->res[l]; }
-        for (int l = 0; l <= 8; ++l) Fn.off[l] = L->level_off[l];
-        return true;
-    };
-    {
-        const char *env = std::getenv("WOST_GUIDED_FUSED");
-        HalfNetView hv{};
-        F32NetView fv{};
-        const NetLayout *L = nullptr;
-        if (env && env[0] == '0') {
-        } else if (net_half_view(g->net, &hv) == WOST_OK) {
-            L = &hv.L;
-            fused_half = true;
-            F.image = hv.image;
-        } else if (net_f32_view(g->net, &fv) == WOST_OK) {
-            L = &fv.L;
-            F.frag32 = fv.frag;
-            F.grid32 = fv.grid;
-        }
-        fused = fused_shape(L, F);
+// Shared network: the summed gradients are divided by the number of ranks (include/wost.h).  WOST_SYNC_RANKS_I64_HOST was added
+// to the callback's ops in library version 0.2: a callback written against 0.1 answers WOST_SYNC_UNSUPPORTED and keeps the old
+// behaviour -- the summed gradient is used undivided; any other non-zero return is a failure and ends the solve.
+static int sync_rank_count(wost_guided *g)
+{
+    int64_t ranks = 1;
+    const int src = g->sync ? g->sync(g->sync_user, WOST_SYNC_RANKS_I64_HOST, &ranks, 1) : 0;
+    if (src == WOST_SYNC_UNSUPPORTED) {
+        fprintf(stderr, "wost: the sync callback does not know WOST_SYNC_RANKS_I64_HOST; shared gradients stay undivided\n");
+        ranks = 1;
+    } else if (src != 0 || ranks < 1) {
+        // a genuine failure (or a nonsensical answer) must not train on: the other ranks would step with another gradient
+        return set_error(WOST_ERR_DEVICE, "sync callback failed (rank count)");
     }
-    P.d0_d2 = g->d0_d2; P.cursor = g->cursor; P.stack_words = std::max(stack_words, kVmmColWords);      // the fused kernel's columns also hold a walker's mixture
-    P.wait_weight = 4; P.trav_burst = 10;     // measured on config 4 (a sweep over both constants)
-    if (const char *w = std::getenv("WOST_GUIDED_WAIT_WEIGHT")) P.wait_weight = std::max(1, std::atoi(w));
-    if (const char *w = std::getenv("WOST_GUIDED_TRAV_BURST")) P.trav_burst = std::max(1, std::atoi(w));
-    P.tail_chunk = 4; P.tail_margin_pct = 300;      // a sweep over both, DESIGN.md 4.9: 3.52 -> 3.37 ms per trained sample of config 4
-    if (const char *w = std::getenv("WOST_GUIDED_TAIL_CHUNK")) P.tail_chunk = std::max(0, std::atoi(w));
-    if (const char *w = std::getenv("WOST_GUIDED_TAIL_MARGIN")) P.tail_margin_pct = std::max(0, std::atoi(w));
-    const int n_fused_threads = fused_threads(fused_half);
-    const size_t lds_fused = ((size_t)P.stack_words * n_fused_threads + (size_t)(n_fused_threads / 64) * fused_xch_words(fused_half) +
-                              (fused_half ? (size_t)2 * F.n_frag : (size_t)F.n_mlp)) * sizeof(uint32_t);
-    if (fused) {
-        // the stack columns grow with the depth of the trees: when the fused kernel's LDS no longer fits a block (the fp32
-        // fragments with a 10-level tree), the solve takes the one-launch-per-depth path instead of failing at the launch
-        int max_lds = 0;
-        if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, g->device) != hipSuccess || max_lds <= 0) max_lds = 64 * 1024;
-        int dev_optin = 0;
-        if (hipDeviceGetAttribute(&dev_optin, hipDeviceAttributeSharedMemPerBlockOptin, g->device) == hipSuccess && dev_optin > max_lds) max_lds = dev_optin;
-        if (lds_fused > (size_t)max_lds) fused = false;
+    net_set_gradient_divisor(g->net, (float)ranks);
+    return WOST_OK;
+}
+// ... and the rank count belongs to that solve: whichever way run_guided returns, a later wost_net_train_step on the handle's network is a plain step
+struct DivisorGuard { wost_net_handle net; ~DivisorGuard() { net_set_gradient_divisor(net, 1.0f); } };
+
+// One launch of the fused sample kernel on `st` with the network image `Fn`: `n_samples` samples of every pixel, from `sample` on.
+static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GParams P, const FusedNet &Fn, hipStream_t st,
+                        const GuidePhase &ph, int sample, int n_samples)
+{
+    const int N = (int)g->n_pixels;
+    if (pl.dbg) {
+        const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
+        G_TRY(hipMemcpyAsync(g->dbg, init, sizeof(init), hipMemcpyHostToDevice, st));
+        G_TRY(hipStreamSynchronize(st));
     }
-
-    // one launch of the fused sample kernel on `st` with the network image `Fn` and the launch state in P
-    const uint32_t *walk_order = nullptr;     // built once per solve, when the cache of the evaluation points' queries is full
-    unsigned last_grid = 0;                   // blocks of the last launch (WOST_GUIDED_DEBUG prints them)
-    auto launch_walk = [&](const FusedNet &Fn, hipStream_t st) -> int {
-        G_TRY(hipMemsetAsync(g->cursor, 0, sizeof(uint32_t), st));
-        // (not for the launches of several samples per pixel, whose drain is one walk whatever the order, nor for one rank's shard:
-        // seven of eight pixels of the order belong to other ranks and a lane asks eight times for one -- shard 0 of 8 of config 5
-        // 0.219 -> 0.246 s; the whole frame, one sample per launch: config 4 1.420 -> 1.400 s in half precision, 2.206 -> 2.174 in fp32)
-        const bool ordered = g->walk_order && P.d0_valid && v.dm.n_segs > 0 && P.n_samples == 1 && P.shard_count == 1;
-        if (ordered && !walk_order) {
-            if (g->order.cap < (size_t)N) G_TRY((hipError_t)order_alloc(g->order, (size_t)N));
-            G_TRY((hipError_t)order_by_distance(g->order, g->d0_d2, (uint32_t)N, st, &walk_order));
-            launches += 2;
-        }
-        P.order = ordered ? walk_order : nullptr;
-        P.pstate = g->pstate;
-        if (P.n_samples > 1) {
-            // several samples of every pixel in one launch: the pixel state words start at zero, and what a one-sample launch
-            // sets on the fly is set before the launch
-            G_TRY(hipMemsetAsync(g->pstate, 0, (size_t)N * sizeof(uint32_t), st));
-            if (P.first_sample) {
-                hipLaunchKernelGGL(guided_init_kernel, dim3((N + 255) / 256), dim3(256), 0, st, P);
-                ++launches;
-            }
-            if (P.training) G_TRY(hipMemsetAsync(g->cur_depth, 0, (size_t)N * (size_t)P.n_samples * sizeof(uint32_t), st));
-            launches += 2;
-        }
-        unsigned gridf = (unsigned)std::min<size_t>(256, ((size_t)N + n_fused_threads - 1) / n_fused_threads);
-        // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
-        if (const char *w = std::getenv("WOST_GUIDED_MAX_BLOCKS")) {
-            const int cap = std::atoi(w);
-            if (cap >= 1) gridf = std::min(gridf, (unsigned)cap);
-        }
-        last_grid = gridf;
-#define LAUNCH_FUSED(E, T)                                                                                                      \
-    do {                                                                                                                        \
-        auto kfn = v.src.rgb ? (fused_half ? guided_sample_kernel<E, T, true, true> : guided_sample_kernel<E, T, true, false>)    \
-                             : (fused_half ? guided_sample_kernel<E, T, false, true> : guided_sample_kernel<E, T, false, false>); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused); \
-        hipLaunchKernelGGL(kfn, dim3(gridf), dim3(n_fused_threads), lds_fused, st, P, Fn);                                       \
-    } while (0)
-        if (emissive) { if (tree) LAUNCH_FUSED(true, true); else LAUNCH_FUSED(true, false); }
-        else          { if (tree) LAUNCH_FUSED(false, true); else LAUNCH_FUSED(false, false); }
-#undef LAUNCH_FUSED
-        ++launches;
-        G_TRY(hipGetLastError());
-        return WOST_OK;
-    };
-    // the training set of record set j of the launch that has just walked, in (pixel, record) order, into `ts`; its size
-    // arrives in host_counts[1 + j]
-    auto enqueue_train_set = [&](hipStream_t st, int j, const TrainSet &ts) -> int {
-        TParams T{};
-        T.box = g->box; T.cur_depth = g->cur_depth + (size_t)j * (size_t)N; T.rec = g->rec + (size_t)j * (size_t)N; T.rec_ld = P.rec_ld; T.n_pixels = N;
-        T.train_offset = train_offset; T.train_stride = (uint32_t)s.train_pixel_stride;
-        T.n_train_pixels = n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
-        hipLaunchKernelGGL((train_set_kernel<false>), dim3(n_train_blocks), dim3(256), 0, st, T);
-        hipLaunchKernelGGL(train_scan_kernel, dim3(1), dim3(256), 0, st, g->block_sums, n_train_blocks);
-        hipLaunchKernelGGL((train_set_kernel<true>), dim3(n_train_blocks), dim3(256), 0, st, T);
-        launches += 3;
-        G_TRY(hipGetLastError());
-        G_TRY(hipMemcpyAsync(g->host_counts + 1 + j, g->block_sums + n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        return WOST_OK;
-    };
-    // trainStep (:618-668): up to batches_per_spp Adam steps on the n entries of the training set `ts`
-    auto train_passes = [&](size_t n, hipStream_t st, const TrainSet &ts) -> int {
-        g->last_train_n = (uint32_t)n;
-        train_samples += n;
-        const size_t bs = (size_t)s.batch_size;
-        size_t n_batches = std::min<size_t>(n / bs + 1, (size_t)s.batches_per_spp);
-        if (g->sync) {
-            // shared network: every rank must take the same number of steps -- the smallest
-            // number of full batches any rank has
-            size_t usable = 0;
-            for (size_t it = 0; it < n_batches; ++it) {
-                size_t local = std::min(n - it * bs, bs);
-                local -= local % 128;
-                if (local < (size_t)s.min_batch_size) break;
-                ++usable;
-            }
-            int64_t vmin = (int64_t)usable;
-            if (g->sync(g->sync_user, WOST_SYNC_MIN_I64_HOST, &vmin, 1) != 0)
-                return set_error(WOST_ERR_DEVICE, "sync callback failed (batch count)");
-            n_batches = (size_t)std::max<int64_t>(vmin, 0);
-        }
-        for (size_t it = 0; it < n_batches; ++it) {
-            size_t local = std::min(n - it * bs, bs);
-            local -= local % 128;
-            if (local < (size_t)s.min_batch_size) break;
-            const size_t o = it * bs;
-            float *raw = nullptr, *dl = nullptr;
-            int rc = net_forward_train_dev(g->net, ts.xy + 2 * o, (int)local, st, &raw, &dl);
-            if (rc != WOST_OK) return rc;
-            launch_vmm_loss_gradients(st, raw, ts.dir + 2 * o, ts.li + o, ts.pdf + o, ts.onn + o, ts.nrm + 2 * o, (int)local, s.loss_scale, dl, nullptr);
-            ++launches;      // the loss-gradient kernel; the network's own launches are counted by the network
-            rc = net_backward_update_dev(g->net, ts.xy + 2 * o, (int)local, s.loss_scale, g->sync ? 0 : 1, st);
-            if (rc != WOST_OK) return rc;
-            if (g->sync) {
-                // sum the fixed-point gradients of all ranks (integer sums: the same network
-                // everywhere, bit for bit), then step
-                G_TRY(hipStreamSynchronize(st));
-                uint64_t count = 0;
-                void *gbuf = net_gradient_buffer(g->net, &count);
-                if (g->sync(g->sync_user, WOST_SYNC_SUM_I64_DEVICE, gbuf, count) != 0)
-                    return set_error(WOST_ERR_DEVICE, "sync callback failed (gradient all-reduce)");
-                rc = net_apply_update_dev(g->net, s.loss_scale, st);
-                if (rc != WOST_OK) return rc;
-            }
-        }
-        return WOST_OK;
-    };
-
-    bool d0_valid = false;
-    // ctor state (integrator.cu:1158-1160), prepareSolve (:125-126)
-    bool training = true;
-    float uniform_fraction = s.uniform_fraction_training;
-    int max_guided_depth = s.max_guided_depth_training;
-    const bool dbg = std::getenv("WOST_GUIDED_DEBUG") != nullptr;
-
-    // ---- opt-in training orders (never the parity mode) ---------------------------------------------------------------
-    // "train_group" S: a training launch walks S samples of every pixel (each with its own record set), then the S training
-    // passes follow.  "pipeline" 1: the passes of group g run on a second stream while group g + 1 walks with a frozen copy
-    // of the weights that the passes of group g - 1 left.  The estimator is unbiased for ANY network state (a step's
-    // direction and its one-sample MIS density come from the same weights, and a training record carries the density it was
-    // drawn with): the only change is that the network a sample sees is a few training passes older.  Both need the fused
-    // sample kernel; a solve with intermediate frames keeps the reference's order.
-    const int n_trained = std::min(s.spp, s.train_spp_count);
-    const bool reordered = fused && n_trained > 0 && !g->frame_fn && !dbg && (g->pipeline || g->train_group > 1);
-    const int group = reordered ? std::min(std::max(g->train_group, 1), n_trained) : 1;
-    // The groups grow with the training: the launch that starts at sample s covers min(S, max(1, s / 2)) samples -- never more than
-    // half of what has been trained before it.  The network learns fastest from its first samples; with fixed groups of 16 the first
-    // sixteen samples of a solve all walked with the untrained network (on config 4: rel-L2 against a 4096-sample field 0.0262, worse than
-    // the uniform integrator's 0.0248; the reference's order 0.0244).
-    auto group_at = [&](int first_sample) { return std::min(std::min(group, std::max(1, first_sample / 2)), n_trained - first_sample); };
-    if (group > g->rec_sets) {
-        // one record set per sample of a training launch (201 MB each at 1024^2: sized for 288 GB of HBM)
-        float *rec = nullptr;
-        uint32_t *cd = nullptr;
-        // (the smaller set goes first: nothing on the device uses it between two solves, and group 16 would otherwise hold
-        // 3.2 GB next to the 201 MB it replaces until the handle is destroyed)
-        G_TRY(hipStreamSynchronize(stream));
-        gfree_one(g, g->rec);
-        gfree_one(g, g->cur_depth);
-        g->rec = nullptr; g->cur_depth = nullptr; g->rec_sets = 0;
-        G_TRY(galloc(g, &rec, (size_t)kMaxTrainDepth * kRecFields * (size_t)N * group));
-        G_TRY(galloc(g, &cd, (size_t)N * group));
-        g->rec = rec; g->cur_depth = cd; g->rec_sets = group;
-        P.rec = g->rec; P.cur_depth = g->cur_depth;
+    G_TRY(hipMemsetAsync(g->cursor, 0, sizeof(uint32_t), st));
+    // the pixels in the order of wost_order.h (not for the launches of several samples per pixel, whose drain is one walk whatever the order, nor for one rank's shard:
+    // seven of eight pixels of the order belong to other ranks and a lane asks eight times for one -- shard 0 of 8 of config 5
+    // 0.219 -> 0.246 s; the whole frame, one sample per launch: config 4 1.420 -> 1.400 s in half precision, 2.206 -> 2.174 in fp32)
+    const bool ordered = g->walk_order && run.d0_valid && g->view.dm.n_segs > 0 && n_samples == 1 && P.shard_count == 1;
+    if (ordered && !run.walk_order) {
+        if (g->order.cap < (size_t)N) G_TRY((hipError_t)order_alloc(g->order, (size_t)N));
+        G_TRY((hipError_t)order_by_distance(g->order, g->d0_d2, (uint32_t)N, st, &run.walk_order));
+        run.launches += 2;
     }
-    P.rec_ld = (size_t)N * (size_t)g->rec_sets;
-    int sample0 = 0;
-    if (reordered && g->pipeline) {
-        const size_t snap_bytes = net_snapshot_bytes(g->net);
-        if (snap_bytes == 0) return set_error(WOST_ERR_UNSUPPORTED, "pipelined training needs a network image");
-        if (!g->train_stream) {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);       // lo = least urgent: the training fills what the walk leaves idle
-            G_TRY(hipStreamCreateWithPriority(&g->train_stream, hipStreamNonBlocking, lo));
-            G_TRY(hipEventCreateWithFlags(&g->ev_ts, hipEventDisableTiming));
-            for (hipEvent_t &e : g->ev_train) G_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            G_TRY(g->train_events.init(64));
-            for (void *&p : g->snap) {
-                uint8_t *q = nullptr;
-                G_TRY(galloc(g, &q, snap_bytes));
-                p = q;
-            }
-        }
-        // the passes of a group read their training sets while the next group walks over the record sets: one array set per sample
-        while ((int)g->ts_more.size() + 1 < group) {
-            TrainSet t{};
-            const size_t M = (size_t)g->n_train_pixels * kMaxTrainDepth;
-            G_TRY(galloc(g, &t.xy, 2 * M)); G_TRY(galloc(g, &t.dir, 2 * M)); G_TRY(galloc(g, &t.sol, 3 * M)); G_TRY(galloc(g, &t.li, M));
-            G_TRY(galloc(g, &t.pdf, M)); G_TRY(galloc(g, &t.nrm, 2 * M)); G_TRY(galloc(g, &t.onn, M));
-            g->ts_more.push_back(t);
-        }
-        auto ts_of = [&](int j) -> const TrainSet & { return j == 0 ? g->ts : g->ts_more[(size_t)j - 1]; };
-        hipStream_t B = g->train_stream;
-        // an error return below must not leave training passes in flight on the second stream behind the caller's back
-        struct DrainOnError {
-            hipStream_t s;
-            bool armed;
-            ~DrainOnError() { if (armed) (void)hipStreamSynchronize(s); }
-        } drain{B, true};
-        FusedNet Fs[2] = {F, F};
-        for (int k = 0; k < 2; ++k) {
-            int rc = net_snapshot_dev(g->net, g->snap[k], stream);      // both copies start as the weights the solve starts with
-            if (rc != WOST_OK) return rc;
-            bool half = false;
-            HalfNetView hv{};
-            F32NetView fv{};
-            rc = net_snapshot_views(g->net, g->snap[k], &half, &hv, &fv);
-            if (rc != WOST_OK || half != fused_half) return set_error(WOST_ERR_UNSUPPORTED, "pipelined training: no view of the network image");
-            if (half) Fs[k].image = hv.image;
-            else { Fs[k].frag32 = fv.frag; Fs[k].grid32 = fv.grid; }
-        }
-        std::vector<int> group_size;
-        for (int first = 0; first < n_trained; first += group_size.back()) group_size.push_back(group_at(first));
-        const int n_groups = (int)group_size.size();
-        auto size_of = [&](int k) { return group_size[(size_t)k]; };
-        P.training = 1; P.uniform_fraction = uniform_fraction; P.max_guided_depth = max_guided_depth; P.dbg = nullptr;
-        auto walk = [&](int k) -> int {
-            P.first_sample = k == 0;
-            P.d0_valid = k > 0 ? 1 : 0;
-            P.n_samples = size_of(k);
-            return launch_walk(Fs[k & 1], stream);
-        };
-        auto train_sets = [&](int k) -> int {
-            for (int j = 0; j < size_of(k); ++j) {
-                const int rc = enqueue_train_set(stream, j, ts_of(j));
-                if (rc != WOST_OK) return rc;
-            }
-            return WOST_OK;
-        };
-        // (the training stream starts behind whatever the walk stream has been given so far)
-        G_TRY(hipEventRecord(g->ev_ts, stream));
-        G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
-        int rc = walk(0);
-        if (rc == WOST_OK) rc = train_sets(0);
+    // what varies between the fused launches of a solve: these eight fields, set here and nowhere else
+    P.first_sample = sample == 0; P.d0_valid = run.d0_valid ? 1 : 0; P.n_samples = n_samples;
+    P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.max_guided_depth = ph.max_guided_depth;
+    P.order = ordered ? run.walk_order : nullptr; P.dbg = pl.dbg ? g->dbg : nullptr;
+    if (n_samples > 1) {
+        // several samples of every pixel in one launch: the pixel state words start at zero, and what a one-sample launch sets on the fly is set before the launch
+        G_TRY(hipMemsetAsync(g->pstate, 0, (size_t)N * sizeof(uint32_t), st));
+        if (P.first_sample) hipLaunchKernelGGL(guided_init_kernel, dim3((N + 255) / 256), dim3(256), 0, st, P);
+        if (P.training) G_TRY(hipMemsetAsync(g->cur_depth, 0, (size_t)N * (size_t)n_samples * sizeof(uint32_t), st));
+        run.launches += P.first_sample ? 3 : 2;
+    }
+    launch_guided(G_FUSED, pl, run, pl.grid_fused, st, P, Fn);
+    G_TRY(hipGetLastError());
+    run.d0_valid = true;
+    if (pl.dbg) {
+        unsigned long long t[4];
+        G_TRY(hipMemcpy(t, g->dbg, sizeof(t), hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[fused sample %d x%d] %u blocks: first wave out of pixels at %.1f us, last at %.1f us, end %.1f us\n", sample,
+                     n_samples, pl.grid_fused, (double)(t[1] - t[0]) / 100.0, (double)(t[2] - t[0]) / 100.0, (double)(t[3] - t[0]) / 100.0);
+    }
+    return WOST_OK;
+}
+
+// the training set of record set j of the launch that has just walked, in (pixel, record) order, into `ts`; its size arrives in host_counts[1 + j]
+static int enqueue_train_set(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, hipStream_t st, int j, const TrainSet &ts)
+{
+    const size_t N = g->n_pixels;
+    TParams T{};
+    T.box = g->box; T.cur_depth = g->cur_depth + (size_t)j * N; T.rec = g->rec + (size_t)j * N; T.rec_ld = N * (size_t)g->rec_sets; T.n_pixels = (int)N;
+    T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->gs.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
+    hipLaunchKernelGGL((train_set_kernel<false>), dim3(pl.n_train_blocks), dim3(256), 0, st, T);
+    hipLaunchKernelGGL(train_scan_kernel, dim3(1), dim3(256), 0, st, g->block_sums, pl.n_train_blocks);
+    hipLaunchKernelGGL((train_set_kernel<true>), dim3(pl.n_train_blocks), dim3(256), 0, st, T);
+    run.launches += 3;
+    G_TRY(hipGetLastError());
+    G_TRY(hipMemcpyAsync(g->host_counts + 1 + j, g->block_sums + pl.n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return WOST_OK;
+}
+
+// entries of batch `it` of a training set of n: what is left of the set, rounded down to 128; 0 = no further batch
+static size_t batch_len(size_t n, size_t it, const wost_guided_settings &s)
+{
+    const size_t bs = (size_t)s.batch_size;
+    if (it * bs > n) return 0;
+    const size_t local = std::min(n - it * bs, bs) / 128 * 128;
+    return local < (size_t)s.min_batch_size ? 0 : local;
+}
+
+// trainStep (:618-668): up to batches_per_spp Adam steps on the n entries of the training set `ts`
+static int train_passes(wost_guided *g, GuidedRun &run, size_t n, hipStream_t st, const TrainSet &ts)
+{
+    const wost_guided_settings &s = g->gs;
+    g->last_train_n = (uint32_t)n; run.train_samples += n;
+    const size_t bs = (size_t)s.batch_size;
+    size_t n_batches = std::min<size_t>(n / bs + 1, (size_t)s.batches_per_spp);
+    if (g->sync) {
+        // shared network: every rank must take the same number of steps -- the smallest number of full batches any rank has
+        int64_t vmin = 0;
+        while ((size_t)vmin < n_batches && batch_len(n, (size_t)vmin, s)) ++vmin;
+        if (g->sync(g->sync_user, WOST_SYNC_MIN_I64_HOST, &vmin, 1) != 0) return set_error(WOST_ERR_DEVICE, "sync callback failed (batch count)");
+        n_batches = (size_t)std::max<int64_t>(vmin, 0);
+    }
+    for (size_t it = 0; it < n_batches; ++it) {
+        const size_t local = batch_len(n, it, s), o = it * bs;
+        if (!local) break;
+        float *raw = nullptr, *dl = nullptr;
+        int rc = net_forward_train_dev(g->net, ts.xy + 2 * o, (int)local, st, &raw, &dl);
         if (rc != WOST_OK) return rc;
-        G_TRY(hipEventRecord(g->ev_ts, stream));
-        for (int k = 0; k < n_groups; ++k) {
-            if (k + 1 < n_groups) {
-                // walk(k + 1) reads snap[(k + 1) % 2] = the weights after the passes of group k - 1
-                if (k >= 1) G_TRY(hipStreamWaitEvent(stream, g->ev_train[(k - 1) & 1], 0));
-                rc = walk(k + 1);
-                if (rc != WOST_OK) return rc;
-            }
-            G_TRY(hipEventSynchronize(g->ev_ts));          // the training sets of group k are complete; their sizes have arrived
-            size_t n_of[16];
-            for (int j = 0; j < size_of(k); ++j) n_of[j] = g->host_counts[1 + j];
-            G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
-            const size_t ev = g->train_events.begin(B);
-            for (int j = 0; j < size_of(k) && rc == WOST_OK; ++j) rc = train_passes(n_of[j], B, ts_of(j));
-            if (rc == WOST_OK) rc = net_snapshot_dev(g->net, g->snap[k & 1], B);
-            g->train_events.end(ev, B);
-            if (rc != WOST_OK) return rc;
-            G_TRY(hipEventRecord(g->ev_train[k & 1], B));
-            if (k + 1 < n_groups) {
-                G_TRY(hipStreamWaitEvent(stream, g->ev_train[k & 1], 0));     // the arrays of the training sets are free again
-                rc = train_sets(k + 1);
-                if (rc != WOST_OK) return rc;
-                G_TRY(hipEventRecord(g->ev_ts, stream));
-            }
-        }
-        // what follows (the guiding phase, the resolve) reads the network's own images
-        G_TRY(hipStreamWaitEvent(stream, g->ev_train[(n_groups - 1) & 1], 0));
-        G_TRY(hipStreamSynchronize(B));
-        drain.armed = false;
-        train_ms += g->train_events.drain();
-        sample0 = n_trained;
-        d0_valid = true;
+        launch_vmm_loss_gradients(st, raw, ts.dir + 2 * o, ts.li + o, ts.pdf + o, ts.onn + o, ts.nrm + 2 * o, (int)local, s.loss_scale, dl, nullptr);
+        ++run.launches;      // the loss-gradient kernel; the network's own launches are counted by the network
+        rc = net_backward_update_dev(g->net, ts.xy + 2 * o, (int)local, s.loss_scale, g->sync ? 0 : 1, st);
+        if (rc != WOST_OK) return rc;
+        if (!g->sync) continue;
+        // sum the fixed-point gradients of all ranks (integer sums: the same network everywhere, bit for bit), then step
+        G_TRY(hipStreamSynchronize(st));
+        uint64_t count = 0;
+        void *gbuf = net_gradient_buffer(g->net, &count);
+        if (g->sync(g->sync_user, WOST_SYNC_SUM_I64_DEVICE, gbuf, count) != 0)
+            return set_error(WOST_ERR_DEVICE, "sync callback failed (gradient all-reduce)");
+        rc = net_apply_update_dev(g->net, s.loss_scale, st);
+        if (rc != WOST_OK) return rc;
     }
+    return WOST_OK;
+}
 
-    for (int sample = sample0; sample < s.spp; ++sample) {
-        if (sample >= s.train_spp_count && training) {       // :991-996
-            training = false;
-            uniform_fraction = s.uniform_fraction_guiding;
-            max_guided_depth = s.max_guided_depth_guiding;
+// one record set per sample of a training launch (201 MB each at 1024^2: sized for 288 GB of HBM)
+static int grow_record_sets(wost_guided *g, int sets, hipStream_t stream)
+{
+    if (sets <= g->rec_sets) return WOST_OK;
+    // (the smaller set goes first: nothing on the device uses it between two solves, and group 16 would otherwise hold
+    // 3.2 GB next to the 201 MB it replaces until the handle is destroyed)
+    G_TRY(hipStreamSynchronize(stream));
+    gfree_one(g, g->rec); gfree_one(g, g->cur_depth);
+    g->rec = nullptr; g->cur_depth = nullptr; g->rec_sets = 0;
+    G_TRY(galloc(g, &g->rec, (size_t)kMaxTrainDepth * kRecFields * g->n_pixels * sets));
+    G_TRY(galloc(g, &g->cur_depth, g->n_pixels * sets));
+    g->rec_sets = sets;
+    return WOST_OK;
+}
+
+// Synchronises the training stream when it goes out of scope, if armed: no return of train_pipelined -- an early one on an error included -- leaves
+// training passes in flight on the second stream behind the caller's back.  (The success path has waited for them itself and disarms it.)
+struct TrainStreamGuard {
+    hipStream_t stream = nullptr;
+    ~TrainStreamGuard() { if (stream) (void)hipStreamSynchronize(stream); }
+};
+static const TrainSet &train_set_of(const wost_guided *g, int j) { return j == 0 ? g->ts : g->ts_more[(size_t)j - 1]; }
+
+// "pipeline" 1: all trained samples of the solve.  Group k walks on `stream` with snap[k % 2], the weights after the passes of
+// group k - 2, and its passes run on the training stream while group k + 1 walks.
+static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, const GParams &P, hipStream_t stream)
+{
+    const size_t snap_bytes = net_snapshot_bytes(g->net);
+    if (snap_bytes == 0) return set_error(WOST_ERR_UNSUPPORTED, "pipelined training needs a network image");
+    if (!g->train_stream) {
+        int lo = 0, hi = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);       // lo = least urgent: the training fills what the walk leaves idle
+        G_TRY(hipStreamCreateWithPriority(&g->train_stream, hipStreamNonBlocking, lo));
+        G_TRY(hipEventCreateWithFlags(&g->ev_ts, hipEventDisableTiming));
+        for (hipEvent_t &e : g->ev_train) G_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        G_TRY(g->train_events.init(64));
+        for (uint8_t *&p : g->snap) G_TRY(galloc(g, &p, snap_bytes));
+    }
+    // the passes of a group read their training sets while the next group walks over the record sets: one array set per sample
+    while ((int)g->ts_more.size() + 1 < pl.group) {
+        TrainSet t{};
+        const size_t M = (size_t)g->n_train_pixels * kMaxTrainDepth;
+        G_TRY(galloc(g, &t.xy, 2 * M)); G_TRY(galloc(g, &t.dir, 2 * M)); G_TRY(galloc(g, &t.sol, 3 * M)); G_TRY(galloc(g, &t.li, M));
+        G_TRY(galloc(g, &t.pdf, M)); G_TRY(galloc(g, &t.nrm, 2 * M)); G_TRY(galloc(g, &t.onn, M));
+        g->ts_more.push_back(t);
+    }
+    hipStream_t B = g->train_stream;
+    TrainStreamGuard drain{B};
+    FusedNet Fs[2] = {pl.F, pl.F};
+    for (int k = 0; k < 2; ++k) {
+        int rc = net_snapshot_dev(g->net, g->snap[k], stream);      // both copies start as the weights the solve starts with
+        if (rc != WOST_OK) return rc;
+        bool half = false;
+        HalfNetView hv{}; F32NetView fv{};
+        rc = net_snapshot_views(g->net, g->snap[k], &half, &hv, &fv);
+        if (rc != WOST_OK || half != pl.fused_half) return set_error(WOST_ERR_UNSUPPORTED, "pipelined training: no view of the network image");
+        if (half) Fs[k].image = hv.image;
+        else { Fs[k].frag32 = fv.frag; Fs[k].grid32 = fv.grid; }
+    }
+    std::vector<int> first(1, 0);      // group k: the samples first[k] .. first[k + 1] - 1
+    while (first.back() < pl.n_trained) first.push_back(first.back() + group_at(pl, first.back()));
+    const int n_groups = (int)first.size() - 1;
+    const GuidePhase ph = phase_at(g->gs, 0);
+    // (the training stream starts behind whatever the walk stream has been given so far)
+    G_TRY(hipEventRecord(g->ev_ts, stream));
+    G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
+    int rc = launch_fused(g, pl, run, P, Fs[0], stream, ph, 0, first[1]);
+    for (int j = 0; j < first[1] && rc == WOST_OK; ++j) rc = enqueue_train_set(g, pl, run, stream, j, train_set_of(g, j));
+    if (rc != WOST_OK) return rc;
+    G_TRY(hipEventRecord(g->ev_ts, stream));
+    for (int k = 0; k < n_groups; ++k) {
+        const int size = first[k + 1] - first[k], next_size = k + 1 < n_groups ? first[k + 2] - first[k + 1] : 0;
+        if (k + 1 < n_groups) {
+            // the walk of group k + 1 reads snap[(k + 1) % 2] = the weights after the passes of group k - 1
+            if (k >= 1) G_TRY(hipStreamWaitEvent(stream, g->ev_train[(k - 1) & 1], 0));
+            rc = launch_fused(g, pl, run, P, Fs[(k + 1) & 1], stream, ph, first[k + 1], next_size);
+            if (rc != WOST_OK) return rc;
         }
-        P.training = training ? 1 : 0;
-        P.uniform_fraction = uniform_fraction;
-        P.first_sample = sample == 0;
-        int n_run = 1;      // samples this iteration covers
-        // both paths give the same results and could alternate within a solve; the fused one is used whenever it exists
-        const bool fused_now = fused;
-        if (fused_now) {
-            if (training) {
-                n_run = group_at(sample);      // 1 unless "train_group" asks for more
-            } else {
-                // nothing is trained between the remaining samples: one launch runs them all, up to the next
-                // intermediate frame the caller asked for
-                int last = s.spp - 1;
-                if (g->frame_fn) {
-                    for (int j = sample; j < s.spp; ++j) {
-                        const bool by_spp = g->frame_spp_every > 0 && j % g->frame_spp_every == 0 && j < g->frame_spp_until;
-                        const bool by_time = g->frame_time_every > 0 && j % g->frame_time_every == 0;
-                        if (by_spp || by_time) { last = j; break; }
-                    }
-                }
-                n_run = last - sample + 1;
-                // a pixel's samples run one after the other in one lane, so the last pixels taken keep a few lanes busy for
-                // n_run walks while the chip idles: bounded launches keep that tail short against the launch itself
-                int cap = 64;
-                if (const char *w = std::getenv("WOST_GUIDED_SAMPLES_PER_LAUNCH")) cap = std::max(1, std::atoi(w));
-                n_run = std::min(n_run, cap);
-            }
-            n_run = std::min(n_run, 0xffff);      // a pixel's state word counts the samples of a launch in 16 bits (arrived << 16 | complete)
-            n_run = (int)std::min<uint64_t>((uint64_t)n_run, std::max<uint64_t>(1, 0xffffffffull / (uint64_t)std::max(N, 1)));      // (items of a launch are counted in 32 bits)
-            P.n_samples = n_run;
-            P.d0_valid = d0_valid ? 1 : 0;
-            P.max_guided_depth = max_guided_depth;
-            P.dbg = dbg ? g->dbg : nullptr;
-            if (dbg) {
-                const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
-                G_TRY(hipMemcpyAsync(g->dbg, init, sizeof(init), hipMemcpyHostToDevice, stream));
-                G_TRY(hipStreamSynchronize(stream));
-            }
-            const int rcw = launch_walk(F, stream);
-            if (rcw != WOST_OK) return rcw;
-            if (dbg) {
-                unsigned long long t[4];
-                G_TRY(hipMemcpy(t, g->dbg, sizeof(t), hipMemcpyDeviceToHost));
-                std::fprintf(stderr, "[fused sample %d x%d] %u blocks: first wave out of pixels at %.1f us, last at %.1f us, end %.1f us\n", sample,
-                             n_run, last_grid, (double)(t[1] - t[0]) / 100.0, (double)(t[2] - t[0]) / 100.0, (double)(t[3] - t[0]) / 100.0);
-            }
-            sample += n_run - 1;     // the index of the last sample this launch has run
-            d0_valid = true;
-        }
-        int cur = 0;     // queue holding the evaluation points of this depth
-        if (!fused_now) {
-        G_TRY(hipMemsetAsync(g->counts + cur, 0, sizeof(uint32_t), stream));
-        P.out = g->q[cur]; P.count_out = g->counts + cur;
-        hipLaunchKernelGGL(begin_sample_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, P);
-        ++launches;
-        }
-        // The queue only shrinks from depth to depth, so ANY earlier size bounds it.  The sizes come
-        // back through pinned memory without the host waiting for them (every kernel reads the exact
-        // size on the device); the launches of a sample are issued back to back.
-        uint32_t n_cur = (uint32_t)N;
-        int polled = -1;                 // last depth whose queue size has arrived
-        for (int depth = 0; depth < s.max_depth && !fused_now; ++depth) {
-            const int nxt = cur ^ 1;
-            P.depth = depth;
-            P.guiding = depth < max_guided_depth ? 1 : 0;
-            P.last_depth = depth == s.max_depth - 1;
-            P.in = g->q[cur]; P.count_in = g->counts + cur;
-            P.out = g->q[nxt]; P.count_out = g->counts + nxt;
-            const unsigned grid = (n_cur + 255) / 256;
-            if (!P.guiding) {
-                // no network from here on: every remaining walker runs to its end in one launch
-#define LAUNCH_TAIL(E, T)                                                                                            \
-    do {                                                                                                             \
-        if (v.src.rgb) hipLaunchKernelGGL((tail_kernel<E, T, true>), dim3(grid), dim3(256), lds, stream, P);           \
-        else hipLaunchKernelGGL((tail_kernel<E, T, false>), dim3(grid), dim3(256), lds, stream, P);                     \
-    } while (0)
-                if (emissive) { if (tree) LAUNCH_TAIL(true, true); else LAUNCH_TAIL(true, false); }
-                else          { if (tree) LAUNCH_TAIL(false, true); else LAUNCH_TAIL(false, false); }
-#undef LAUNCH_TAIL
-                ++launches;
-                G_TRY(hipGetLastError());
-                break;
-            }
-            G_TRY(hipMemsetAsync(g->counts + nxt, 0, sizeof(uint32_t), stream));
-#define LAUNCH_SEP(E, T)                                                                                             \
-    do {                                                                                                             \
-        if (v.src.rgb) hipLaunchKernelGGL((separate_kernel<E, T, true>), dim3(grid), dim3(256), lds, stream, P);       \
-        else hipLaunchKernelGGL((separate_kernel<E, T, false>), dim3(grid), dim3(256), lds, stream, P);                 \
-    } while (0)
-            if (emissive) { if (tree) LAUNCH_SEP(true, true); else LAUNCH_SEP(true, false); }
-            else          { if (tree) LAUNCH_SEP(false, true); else LAUNCH_SEP(false, false); }
-#undef LAUNCH_SEP
-            ++launches;
-            // the out-of-shell queue is the input of the network and of the sampling kernel
-            G_TRY(hipMemcpyAsync(g->depth_counts + depth, g->counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            G_TRY(hipEventRecord(g->depth_events[depth], stream));
-            while (polled < depth && hipEventQuery(g->depth_events[polled + 1]) == hipSuccess) n_cur = g->depth_counts[++polled];
-            if (polled == depth && n_cur == 0) break;      // known to be empty
-            const uint32_t n_out = n_cur;                  // an upper bound
-            if (P.guiding) {
-                const size_t ev = g->net_events.begin(stream);
-                int rc = net_inference_dev(g->net, g->net_in, g->counts + nxt, (int)n_out, g->net_out, true, stream, (size_t)N);
-                g->net_events.end(ev, stream);
-                if (rc != WOST_OK) return rc;      // (counted by the network)
-            }
-            P.in = g->q[nxt]; P.count_in = g->counts + nxt;
-            const unsigned grid2 = (n_out + 255) / 256;
-            if (tree) hipLaunchKernelGGL((sample_kernel<true>), dim3(grid2), dim3(256), lds, stream, P);
-            else hipLaunchKernelGGL((sample_kernel<false>), dim3(grid2), dim3(256), lds, stream, P);
-            ++launches;
-            G_TRY(hipGetLastError());
-            cur = nxt;
-            n_cur = n_out;
-        }
-        // ---- trainStep (:618-668) ----
-        if (training) {
-            G_TRY(hipStreamSynchronize(stream));     // the walk phase ends here; train_ms counts the training only
-            const auto t0 = std::chrono::high_resolution_clock::now();
-            for (int j = 0; j < n_run; ++j) {        // (one record set per sample of the launch; one unless "train_group" is set)
-                int rc = enqueue_train_set(stream, j, g->ts);
-                if (rc != WOST_OK) return rc;
-                G_TRY(hipStreamSynchronize(stream));
-                rc = train_passes((size_t)g->host_counts[1 + j], stream, g->ts);
-                if (rc != WOST_OK) return rc;
-            }
-            G_TRY(hipStreamSynchronize(stream));
-            train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-        }
-        // intermediate frames (reference integrator.cu:1049-1081)
-        if (g->frame_fn) {
-            const bool by_spp = g->frame_spp_every > 0 && sample % g->frame_spp_every == 0 && sample < g->frame_spp_until;
-            const bool by_time = g->frame_time_every > 0 && sample % g->frame_time_every == 0;
-            if (by_spp || by_time) {
-                hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)(sample + 1),
-                                   g->field);
-                std::vector<float> frame((size_t)N * 3);
-                G_TRY(hipMemcpyAsync(frame.data(), g->field, frame.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-                G_TRY(hipStreamSynchronize(stream));
-                const double ms =
-                    std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t_start).count();
-                if (by_spp && g->frame_fn(g->frame_user, 0, sample, ms, frame.data()) != 0)
-                    return set_error(WOST_ERR_INVALID, "frame callback asked to stop");
-                if (by_time && g->frame_fn(g->frame_user, 1, sample, ms, frame.data()) != 0)
-                    return set_error(WOST_ERR_INVALID, "frame callback asked to stop");
-            }
+        G_TRY(hipEventSynchronize(g->ev_ts));          // the training sets of group k are complete; their sizes have arrived
+        size_t n_of[16];
+        for (int j = 0; j < size; ++j) n_of[j] = g->host_counts[1 + j];
+        G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
+        const size_t ev = g->train_events.begin(B);
+        for (int j = 0; j < size && rc == WOST_OK; ++j) rc = train_passes(g, run, n_of[j], B, train_set_of(g, j));
+        if (rc == WOST_OK) rc = net_snapshot_dev(g->net, g->snap[k & 1], B);
+        g->train_events.end(ev, B);
+        if (rc != WOST_OK) return rc;
+        G_TRY(hipEventRecord(g->ev_train[k & 1], B));
+        if (k + 1 < n_groups) {
+            G_TRY(hipStreamWaitEvent(stream, g->ev_train[k & 1], 0));     // the arrays of the training sets are free again
+            for (int j = 0; j < next_size && rc == WOST_OK; ++j) rc = enqueue_train_set(g, pl, run, stream, j, train_set_of(g, j));
+            if (rc != WOST_OK) return rc;
+            G_TRY(hipEventRecord(g->ev_ts, stream));
         }
     }
-    hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)s.spp, g->field);
+    // what follows (the guiding phase, the resolve) reads the network's own images
+    G_TRY(hipStreamWaitEvent(stream, g->ev_train[(n_groups - 1) & 1], 0));
+    G_TRY(hipStreamSynchronize(B));
+    drain.stream = nullptr;
+    run.train_ms += g->train_events.drain();
+    return WOST_OK;
+}
+
+// intermediate frames (reference integrator.cu:1049-1081): bit 0 = the spp schedule asks for one after sample j, bit 1 = the time schedule
+static int frame_due(const wost_guided *g, int j)
+{
+    if (!g->frame_fn) return 0;
+    const bool by_spp = g->frame_spp_every > 0 && j % g->frame_spp_every == 0 && j < g->frame_spp_until;
+    const bool by_time = g->frame_time_every > 0 && j % g->frame_time_every == 0;
+    return (by_spp ? 1 : 0) | (by_time ? 2 : 0);
+}
+
+// ... and the frame after `sample`, if one is due
+static int emit_frame(wost_guided *g, const GuidedRun &run, hipStream_t stream, int sample)
+{
+    const int N = (int)g->n_pixels, due = frame_due(g, sample);
+    if (!due) return WOST_OK;
+    hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)(sample + 1), g->field);
+    std::vector<float> frame((size_t)N * 3);
+    G_TRY(hipMemcpyAsync(frame.data(), g->field, frame.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    G_TRY(hipStreamSynchronize(stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
+    for (int kind = 0; kind < 2; ++kind)      // 0: by spp, 1: by time
+        if (((due >> kind) & 1) && g->frame_fn(g->frame_user, kind, sample, ms, frame.data()) != 0)
+            return set_error(WOST_ERR_INVALID, "frame callback asked to stop");
+    return WOST_OK;
+}
+
+// samples the fused launch that starts at `sample` covers
+static int samples_this_launch(const wost_guided *g, const GuidedPlan &pl, const GuidePhase &ph, int sample)
+{
+    int n_run = ph.training ? group_at(pl, sample) : 1;      // 1 unless "train_group" asks for more
+    if (!ph.training) {
+        // nothing is trained between the remaining samples: one launch runs them all, up to the next intermediate frame the caller asked for
+        int last = sample;
+        while (last < g->gs.spp - 1 && !frame_due(g, last)) ++last;
+        n_run = std::min(last - sample + 1, pl.samples_per_launch);
+    }
+    n_run = std::min(n_run, 0xffff);      // a pixel's state word counts the samples of a launch in 16 bits (arrived << 16 | complete)
+    return (int)std::min<uint64_t>((uint64_t)n_run, std::max<uint64_t>(1, 0xffffffffull / std::max<uint64_t>(g->n_pixels, 1)));      // (items of a launch are counted in 32 bits)
+}
+
+// One sample on the one-launch-per-depth path: begin, then per depth separate / network / sample, and the tail once nothing
+// needs the network any more.
+static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GParams P, const GuidePhase &ph, int sample, hipStream_t stream)
+{
+    const wost_guided_settings &s = g->gs;
+    const int N = (int)g->n_pixels;
+    P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.first_sample = sample == 0;
+    int cur = 0;     // queue holding the evaluation points of this depth
+    G_TRY(hipMemsetAsync(g->counts + cur, 0, sizeof(uint32_t), stream));
+    P.out = g->q[cur]; P.count_out = g->counts + cur;
+    hipLaunchKernelGGL(begin_sample_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, P);
+    ++run.launches;
+    // The queue only shrinks from depth to depth, so ANY earlier size bounds it.  The sizes come back through pinned memory without the
+    // host waiting for them (every kernel reads the exact size on the device); the launches of a sample are issued back to back.
+    uint32_t n_cur = (uint32_t)N;
+    int polled = -1;                 // last depth whose queue size has arrived
+    for (int depth = 0; depth < s.max_depth; ++depth) {
+        const int nxt = cur ^ 1;
+        P.depth = depth; P.guiding = depth < ph.max_guided_depth ? 1 : 0; P.last_depth = depth == s.max_depth - 1;
+        P.in = g->q[cur]; P.count_in = g->counts + cur; P.out = g->q[nxt]; P.count_out = g->counts + nxt;
+        const unsigned grid = (n_cur + 255) / 256;
+        if (!P.guiding) {
+            // no network from here on: every remaining walker runs to its end in one launch
+            launch_guided(G_TAIL, pl, run, grid, stream, P);
+            G_TRY(hipGetLastError());
+            break;
+        }
+        G_TRY(hipMemsetAsync(g->counts + nxt, 0, sizeof(uint32_t), stream));
+        launch_guided(G_SEPARATE, pl, run, grid, stream, P);
+        // the out-of-shell queue is the input of the network and of the sampling kernel
+        G_TRY(hipMemcpyAsync(g->depth_counts + depth, g->counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        G_TRY(hipEventRecord(g->depth_events[depth], stream));
+        while (polled < depth && hipEventQuery(g->depth_events[polled + 1]) == hipSuccess) n_cur = g->depth_counts[++polled];
+        if (polled == depth && n_cur == 0) break;      // known to be empty
+        const uint32_t n_out = n_cur;                  // an upper bound
+        const size_t ev = g->net_events.begin(stream);
+        const int rc = net_inference_dev(g->net, g->net_in, g->counts + nxt, (int)n_out, g->net_out, true, stream, (size_t)N);
+        g->net_events.end(ev, stream);
+        if (rc != WOST_OK) return rc;      // (counted by the network)
+        P.in = g->q[nxt]; P.count_in = g->counts + nxt;
+        launch_guided(G_SAMPLE, pl, run, (n_out + 255) / 256, stream, P);
+        G_TRY(hipGetLastError());
+        cur = nxt; n_cur = n_out;
+    }
+    return WOST_OK;
+}
+
+// trainStep (:618-668) after a launch that walked n_run samples: one record set and one training pass per sample, in order
+static int train_after_walk(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, hipStream_t stream, int n_run)
+{
+    G_TRY(hipStreamSynchronize(stream));     // the walk phase ends here; train_ms counts the training only
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (int j = 0; j < n_run; ++j) {
+        int rc = enqueue_train_set(g, pl, run, stream, j, g->ts);
+        if (rc != WOST_OK) return rc;
+        G_TRY(hipStreamSynchronize(stream));
+        rc = train_passes(g, run, (size_t)g->host_counts[1 + j], stream, g->ts);
+        if (rc != WOST_OK) return rc;
+    }
+    G_TRY(hipStreamSynchronize(stream));
+    run.train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    return WOST_OK;
+}
+
+// resolve, the copies of the field, the counters folded and the stats
+static int finish_guided(wost_guided *g, const GuidedRun &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
+{
+    const int N = (int)g->n_pixels;
+    hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)g->gs.spp, g->field);
     G_TRY(hipGetLastError());
     if (field_host) G_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) G_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     std::vector<GStatsDev> copies(kStatCopies);
     G_TRY(hipMemcpyAsync(copies.data(), g->stats, kStatCopies * sizeof(GStatsDev), hipMemcpyDeviceToHost, stream));
     G_TRY(hipStreamSynchronize(stream));
-    GStatsDev hs{};
+    wost_guided_stats out{};
     for (const GStatsDev &c : copies) {
-        hs.steps += c.steps; hs.started += c.started; hs.absorbed += c.absorbed;
-        hs.truncated += c.truncated; hs.nhits += c.nhits; hs.guided += c.guided; hs.net_points += c.net_points;
+        out.walk_steps += c.steps; out.walks_started += c.started; out.walks_absorbed += c.absorbed; out.walks_truncated += c.truncated;
+        out.neumann_hits += c.nhits; out.guided_steps += c.guided; out.net_points += c.net_points;
     }
-    const double net_infer_ms = g->net_events.drain();
-    net_set_gradient_divisor(g->net, 1.0f);      // the rank count belongs to this solve: a later wost_net_train_step on the handle is a plain step
-    if (stats) {
-        *stats = wost_guided_stats{};
-        stats->walk_steps = hs.steps; stats->walks_started = hs.started; stats->walks_absorbed = hs.absorbed;
-        stats->walks_truncated = hs.truncated; stats->neumann_hits = hs.nhits; stats->guided_steps = hs.guided;
-        stats->train_samples = train_samples;
-        stats->optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - opt_before);
-        stats->train_ms = train_ms;
-        stats->kernel_launches = launches + (uint32_t)(net_launch_count(g->net) - net_launches_before);
-        stats->net_points = hs.net_points;
-        stats->reserved = g->last_train_offset;
-        stats->net_infer_ms = net_infer_ms;
-        stats->solve_ms =
-            std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t_start).count();
-    }
+    out.train_samples = run.train_samples; out.train_ms = run.train_ms; out.net_infer_ms = g->net_events.drain();
+    out.optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - run.opt_before); out.reserved = g->last_train_offset;
+    out.kernel_launches = run.launches + (uint32_t)(net_launch_count(g->net) - run.net_launches_before);
+    out.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
+    if (stats) *stats = out;
     return WOST_OK;
+}
+
+// the shared driver: field_host (n_pixels*3, may be null) and/or field_dev (device, n_pixels*3)
+static int run_guided(wost_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats)
+{
+    GuidedRun run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
+    DivisorGuard divisor{g->net};
+    G_TRY(hipSetDevice(g->device));
+    hipStream_t stream = g->view.stream;
+    G_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
+    int rc = sync_rank_count(g);      // (before the plan: a solve that ends here has drawn nothing from the host sampler)
+    if (rc != WOST_OK) return rc;
+    const GuidedPlan pl = guided_plan(g);
+    rc = grow_record_sets(g, pl.group, stream);
+    if (rc != WOST_OK) return rc;
+    const GParams P = base_params(g, pl, shard_index, shard_count);
+    int sample = 0;
+    if (pl.reordered && g->pipeline) {
+        rc = train_pipelined(g, pl, run, P, stream);
+        if (rc != WOST_OK) return rc;
+        sample = pl.n_trained;
+    }
+    for (; sample < g->gs.spp; ++sample) {
+        const GuidePhase ph = phase_at(g->gs, sample);
+        // both paths give the same results; the fused one is used whenever it exists
+        const int n_run = pl.fused ? samples_this_launch(g, pl, ph, sample) : 1;      // samples this iteration covers
+        rc = pl.fused ? launch_fused(g, pl, run, P, pl.F, stream, ph, sample, n_run) : walk_per_depth(g, pl, run, P, ph, sample, stream);
+        if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, stream, n_run);
+        sample += n_run - 1;     // the index of the last sample this iteration has run
+        if (rc == WOST_OK) rc = emit_frame(g, run, stream, sample);
+        if (rc != WOST_OK) return rc;
+    }
+    return finish_guided(g, run, stream, field_host, field_dev, stats);
 }
 
 extern "C" {

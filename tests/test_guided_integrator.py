@@ -1102,3 +1102,43 @@ def test_gpu_sync_callback_failures_end_the_solve():
                 {capi.SYNC_SUM_I64_DEVICE: capi.SYNC_UNSUPPORTED}):
         with pytest.raises(WostError, match="sync callback failed"):
             solve_with(bad)
+
+
+@pytest.mark.gpu
+def test_gpu_failed_shared_solve_leaves_a_plain_network():
+    """The rank count of a shared-network solve belongs to that solve, also when the solve ends in an error: a sync
+    callback answers 3 ranks and then fails at the gradient all-reduce, before any optimizer step.  A
+    wost_net_train_step on the handle's network afterwards must be the plain step a never-solved handle takes, bit for
+    bit (the optimizer divides the gradient by the rank count, and a division by 3 rounds)"""
+    import ctypes as C
+    from elaina_amd import capi
+    from elaina_amd.capi import WostError
+    from elaina_amd.guided import GuidedIntegrator, GuidedIntegratorSettings
+    prob = laplace_box()
+    st = GuidedIntegratorSettings(frameSize=(32, 32), samplesPerPixel=2, trainSppCount=2, maxWalkingDepth=16, epsilonShell=EPS,
+                                  batchSize=1024, minBatchSize=512)
+
+    def sync(user, op, data, count):
+        if op == capi.SYNC_RANKS_I64_HOST:
+            C.cast(data, C.POINTER(C.c_int64))[0] = 3
+        return 1 if op == capi.SYNC_SUM_I64_DEVICE else 0
+
+    fresh = GuidedIntegrator(prob, st, AABB, seed=2)
+    gi = GuidedIntegrator(prob, st, AABB, seed=2)
+    fn = capi.SYNC_FN(sync)
+    capi._check(gi.lib.wost_guided_set_sync(gi._handle, fn, None), "wost_guided_set_sync")
+    try:
+        with pytest.raises(WostError, match="gradient all-reduce"):
+            gi.solve()
+        assert np.array_equal(gi.network.params(), fresh.network.params())      # the solve ended before its first step
+        rng = np.random.default_rng(11)
+        xy = rng.random((256, 2), dtype=np.float32)
+        dl = (0.01 * rng.standard_normal((256, 33))).astype(np.float32)
+        p0 = fresh.network.params()
+        for it in (gi, fresh):
+            it.network.train_step(xy, dl)
+        assert not np.array_equal(fresh.network.params(), p0)                   # (the step is a step)
+        assert np.array_equal(gi.network.params(), fresh.network.params())
+    finally:
+        gi.close()
+        fresh.close()
