@@ -14,7 +14,8 @@
 //     activations in a per-lane LDS column, wave-uniform weights through scalar loads;
 //   * gradients are sums over the training points and are accumulated in 64-bit fixed point
 //     with integer atomics, hence independent of the order in which blocks arrive.
-// DESIGN.md section 4.7 has the numbers.
+// Host side of an Adam step: a TrainPlan made once per network (make_train_plan), then net_backward_update_dev = backward_pass,
+// grid_gradient, weight_gradients, net_apply_update_dev.  DESIGN.md section 4.7 has the numbers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1531,6 +1532,110 @@ __global__ void optimizer_kernel(NetLayout L, uint32_t n, float *params, float *
 
 using namespace wost;
 
+// ---- the gradient launches of a training step, planned once per network (make_train_plan) from the layout and the WOST_GRID_GRAD_*
+// knobs; grid_gradient() adds what depends on the batch size.  One strategy runs: groups (two inputs), bin3 (three), else fallback.  A level
+// group: levels [lv0, lv1), features [q0, q1), LDS accumulators of `bytes` x replicas (use_lds 0: straight to global memory)
+struct GridGradStep { int lv0, lv1, q0, q1; size_t bytes; int use_lds, replicas; };
+struct TrainPlan {
+    GridGradPlan groups{};               // grid_grad_plan_kernel: every level group in one launch; n_groups == 0: does not hold
+    size_t plan_bytes = 0;               // its LDS: the largest group with its replicas
+    GridBin3Plan bin3{};                 // grid_bin3_*: extents, offsets, chunk; bins == 0: off, or no box size fits
+    std::vector<GridGradStep> fallback;  // grid_grad_kernel: one launch per level group
+};
+
+static int env_int(const char *name, int unset) { const char *e = std::getenv(name); return e ? std::atoi(e) : unset; }
+// LDS of a group's 8-byte accumulators: 72 KB (two blocks per CU), a larger level alone up to 150 KB (one block); all levels of a box
+constexpr size_t kGroupSmall = 72 * 1024, kGroupBig = 150 * 1024, kBin3LdsCap = 152 * 1024;
+static size_t level_bytes(const NetLayout &L, int l, int nq) { return (size_t)(L.level_off[l + 1] - L.level_off[l]) * nq * sizeof(fx_t); }
+// Consecutive levels grouped while their accumulators fit kGroupSmall; a level that does not, in feature slices.  one_launch (the groups of
+// grid_grad_plan_kernel): levels below 1024 cells apart, within kGroupSmall / coarse_copies, replicas where there is room; empty when a feature of a
+// level does not fit, or past 16 groups.  Else (grid_grad_kernel) a level alone may take kGroupBig, and levels too large even for that share one launch.
+static std::vector<GridGradStep> level_groups(const NetLayout &L, bool one_launch, int coarse_copies)
+{
+    std::vector<GridGradStep> steps;
+    const int nf = L.n_features;
+    const size_t alone = one_launch ? kGroupSmall : kGroupBig;
+    auto is_coarse = [&](int l) { return one_launch && L.level_off[l + 1] - L.level_off[l] < 1024u; };
+    for (int lv = 0; lv < L.n_levels;) {
+        int end = lv;
+        size_t bytes = 0;
+        const bool coarse = is_coarse(lv);
+        const size_t budget = coarse ? kGroupSmall / (size_t)coarse_copies : kGroupSmall;
+        while (end < L.n_levels && is_coarse(end) == coarse && bytes + level_bytes(L, end, nf) <= budget) bytes += level_bytes(L, end++, nf);
+        if (end == lv && coarse && level_bytes(L, lv, nf) <= kGroupSmall) bytes = level_bytes(L, end++, nf);      // alone, fewer copies
+        if (end > lv) {
+            int copies = 1;
+            while (one_launch && copies < 8 && (size_t)(2 * copies) * bytes <= kGroupSmall) copies *= 2;
+            steps.push_back({lv, end, 0, nf, bytes, 1, copies});
+        } else if (level_bytes(L, lv, 1) > alone) {
+            if (one_launch) return {};
+            while (end < L.n_levels && level_bytes(L, end, 1) > alone) ++end;
+            steps.push_back({lv, end, 0, nf, 0, 0, 1});
+        } else {
+            int slices = 1;
+            while (level_bytes(L, lv, (nf + slices - 1) / slices) > alone) ++slices;
+            const int per = (nf + slices - 1) / slices;
+            for (int q0 = 0; q0 < nf; q0 += per) steps.push_back({lv, lv + 1, q0, std::min(nf, q0 + per), level_bytes(L, lv, std::min(nf, q0 + per) - q0), 1, 1});
+            end = lv + 1;
+        }
+        lv = end;
+    }
+    if (one_launch && steps.size() > 16) steps.clear();
+    return steps;
+}
+// what depends on the batch size: chunk[g] x (levels x features of g) about the same for every group, ~ 448 blocks (two per CU) -> blocks
+static int grid_grad_chunks(GridGradPlan &plan, int n)
+{
+    double total = 0.0;
+    for (int g = 0; g < plan.n_groups; ++g) total += (double)(plan.lv1[g] - plan.lv0[g]) * (plan.q1[g] - plan.q0[g]);
+    const double per_block = total * (double)n / 448.0;
+    int blocks = 0;
+    for (int g = 0; g < plan.n_groups; ++g) {
+        const double w = (double)(plan.lv1[g] - plan.lv0[g]) * (plan.q1[g] - plan.q0[g]);
+        long long chunk_g = (long long)(per_block / w);
+        chunk_g = std::max<long long>(1024, (chunk_g + 63) / 64 * 64);
+        chunk_g = std::min<long long>(chunk_g, ((long long)n + 63) / 64 * 64);
+        plan.chunk[g] = (int32_t)chunk_g;
+        plan.first_block[g] = blocks;
+        blocks += (int)(((long long)n + chunk_g - 1) / chunk_g);
+    }
+    plan.first_block[plan.n_groups] = blocks;
+    return blocks;
+}
+// three inputs: the per-level extents of a box's accumulators, for the first of 8 or 16 boxes per axis at which they fit LDS (bins 0: neither)
+static GridBin3Plan grid_bin3_plan(const NetLayout &L, int chunk)
+{
+    GridBin3Plan bp{};
+    bp.chunk = chunk;
+    for (int bins : {8, 16}) {
+        int total = 0;
+        for (int l = 0; l < L.n_levels; ++l) {
+            bp.ext[l] = (int)std::floor(L.scale[l] / (float)bins) + 3;
+            bp.acc_off[l] = total;
+            total += bp.ext[l] * bp.ext[l] * bp.ext[l];
+        }
+        bp.acc_off[L.n_levels] = bp.n_acc = total;
+        if ((bp.bins = (size_t)total * L.n_features * sizeof(fx_t) <= kBin3LdsCap ? bins : 0)) break;
+    }
+    return bp;
+}
+// the knobs: WOST_GRID_GRAD_PLAN=0 / _BINS=0 (only the fallback list remains), _COPIES (4; 1, 2, 4 or 8), _BIN_CHUNK (2048, at least 64)
+static TrainPlan make_train_plan(const NetLayout &L)
+{
+    TrainPlan P;
+    int copies = std::max(1, std::min(8, env_int("WOST_GRID_GRAD_COPIES", 4)));
+    while (copies & (copies - 1)) --copies;
+    if (L.dims == 2 && env_int("WOST_GRID_GRAD_PLAN", 1) != 0)      // (the grids of three inputs are far larger than LDS)
+        for (const GridGradStep &s : level_groups(L, true, copies)) {
+            const int g = P.groups.n_groups++;
+            P.groups.lv0[g] = s.lv0; P.groups.lv1[g] = s.lv1; P.groups.q0[g] = s.q0; P.groups.q1[g] = s.q1; P.groups.replicas[g] = s.replicas;
+            P.plan_bytes = std::max(P.plan_bytes, s.bytes * (size_t)s.replicas);
+        }
+    if (L.dims == 3 && env_int("WOST_GRID_GRAD_BINS", 1) != 0) P.bin3 = grid_bin3_plan(L, std::max(64, env_int("WOST_GRID_GRAD_BIN_CHUNK", 2048)));
+    P.fallback = level_groups(L, false, 1);
+    return P;
+}
+
 struct wost_net {
     int device = 0;
     wost_net_config cfg{};
@@ -1549,6 +1654,7 @@ struct wost_net {
     uint2 *params_h = nullptr, *params_hb = nullptr;   // f16 fragments of the training weights and of their transposes
     float *train_partial = nullptr;                    // per-block sums of the matrix gradients (net_train_h_kernel), 256 rows
     bool fused_backward = true;      // net_backward_wgrad_kernel (WOST_NET_FUSED=0: backward and weight gradients apart)
+    TrainPlan plan;                  // the gradient launches of a training step (make_train_plan, at creation)
     int step = 0;
     uint64_t n_launches = 0;           // kernels and fills issued by the *_dev entry points (wost_guided_stats.kernel_launches)
     uint32_t *param_steps = nullptr;   // Adam steps taken by each parameter (tiny-cuda-nn adam_step)
@@ -1567,6 +1673,9 @@ struct wost_net {
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// the shape the MFMA kernels are instantiated for (eight_by_four: as 8 levels x 4 features, which the half-precision kernels need on top)
+static bool reference_shape(const NetLayout &L, bool eight_by_four) { return L.enc == 32 && L.n_neurons == 64 && L.n_hidden == 3 && L.n_out_padded == 48 && (!eight_by_four || (L.n_features == 4 && L.n_levels == 8)); }
 
 // entries of the half-precision image of one parameter set: MFMA fragments of the matrices, then the grid
 static size_t half_image_entries(const NetLayout &L) { return (size_t)L.n_mlp / 4 + L.level_off[L.n_levels]; }
@@ -1595,6 +1704,28 @@ static void refresh_half(wost_net *h, hipStream_t stream)
         hipLaunchKernelGGL(fragment_mlp_h_kernel, dim3(gh), dim3(256), 0, stream, h->L, h->params, h->params_h);
         hipLaunchKernelGGL(fragment_mlp_hb_kernel, dim3(gh), dim3(256), 0, stream, h->L, h->params, h->params_hb);
     }
+}
+
+// precision / train_precision 16: the shape and LDS checks, the f16 images (allocated once), their first contents
+static int enable_half(wost_net *h, bool training)
+{
+    const NetLayout &L = h->L;
+    if (!reference_shape(L, true))
+        return set_error(WOST_ERR_UNSUPPORTED, std::string("half-precision ") + (training ? "training" : "inference") +
+                                                   " is built for the reference's network shape only (8 levels x 4 features, 3 x 64, two or three inputs)");
+    NET_TRY(hipSetDevice(h->device));
+    const size_t image = half_image_entries(L) * sizeof(uint2);
+    if (L.dims == 2 && image > 158 * 1024)
+        return set_error(WOST_ERR_UNSUPPORTED, "half-precision network: weights and grid must fit into 158 KB of LDS");
+    if (!training && !h->inference_h) NET_TRY(hipMalloc((void **)&h->inference_h, image));
+    if (training && !h->params_h) NET_TRY(hipMalloc((void **)&h->params_h, image));
+    if (training && !h->params_hb) NET_TRY(hipMalloc((void **)&h->params_hb, (size_t)L.n_mlp / 4 * sizeof(uint2)));
+    if (training && !h->train_partial) NET_TRY(hipMalloc((void **)&h->train_partial, (size_t)256 * L.n_mlp * sizeof(float)));
+    (training ? h->train_precision : h->precision) = 16;
+    refresh_half(h, nullptr);
+    NET_TRY(hipGetLastError());
+    NET_TRY(hipDeviceSynchronize());
+    return WOST_OK;
 }
 
 static int refresh_transposed(wost_net *h, hipStream_t stream)
@@ -1676,157 +1807,12 @@ static int ensure_points(wost_net *h, size_t n)
     NET_TRY(hipMalloc((void **)&h->d_mask, n * 4 * sizeof(unsigned long long)));
     if (h->d_bin_order) { (void)hipFree(h->d_bin_order); h->d_bin_order = nullptr; }
     if (L.dims == 3) NET_TRY(hipMalloc((void **)&h->d_bin_order, n * sizeof(uint32_t)));
+    if (h->plan.bin3.bins && !h->d_bin_tab) NET_TRY(hipMalloc((void **)&h->d_bin_tab, (2 * 4096 + 1 + 2 * 4097) * sizeof(uint32_t)));      // box tables, up to 16^3 boxes
     h->cap_points = n;
     return WOST_OK;
 }
 
-// WOST_NET_CHECK3=1 (developer self check, EXPERIMENTS 20): the half-precision training kernels of every Adam step launched three times
-// on the same inputs, the three results compared word by word on the device; the counts go to stderr when the network is destroyed
-__global__ void check3_kernel(const uint32_t *a, const uint32_t *b, const uint32_t *c, size_t n, unsigned long long *out, uint32_t *log)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t x = a[i], y = b[i], z = c[i];
-    if (x == y && y == z) return;
-    const unsigned long long k = atomicAdd(&out[0], 1ull);
-    atomicAdd(&out[1 + (y == z ? 0 : x == z ? 1 : x == y ? 2 : 3)], 1ull);
-    if (log && k < 65536ull) log[k] = (uint32_t)i;
-}
-struct Check3 {
-    bool on = false, asked = false;
-    unsigned long long *dev = nullptr;       // [kernel 0 forward / 1 train][words differing, odd launch 0 1 2, all differ] + launches with a difference
-    void *scratch[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[4] = {0, 0, 0, 0};
-    unsigned long long steps = 0;
-    uint32_t *log = nullptr;                 // word indices of the forward kernel's first 65 536 differing words
-    int n_out = 33;
-};
-static Check3 g_check3;
-
-// ---- what runs in FRONT of the three launches of the self check (WOST_NET_CHECK3_PRE, EXPERIMENTS 20 / 26) ----------------------
-// The first-tile deviation of net_forward_h_kernel appears when the kernel follows a different kernel.  Two readings: a transient of
-// the matrix pipe at the start of matrix work, or state the previous launch left behind (LDS is never cleared between launches, the
-// instruction cache holds the previous kernel).  These kernels set up one or the other in front of chosen launches:
-//   "lds"      every LDS byte of every CU filled with half-precision NaNs in front of ALL three launches
-//   "lds23"    ... in front of launches 2 and 3 only (which never deviate as things stand)
-//   "burn1"    a heavy matrix kernel of another kind in front of launch 1 (a warm matrix pipe, foreign LDS / instruction cache)
-//   "icache23" the instruction caches invalidated in front of launches 2 and 3
-__global__ __launch_bounds__(1024) void check3_lds_fill_kernel(uint32_t pattern, uint32_t n_words, uint32_t *sink)
-{
-    extern __shared__ uint32_t s_fill[];
-    for (uint32_t i = threadIdx.x; i < n_words; i += blockDim.x) s_fill[i] = pattern;
-    __syncthreads();
-    if (s_fill[(threadIdx.x * 977u) % n_words] != pattern) atomicAdd(sink, 1u);
-}
-__global__ void check3_icache_kernel()
-{
-    asm volatile("s_icache_inv\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-}
-__global__ __launch_bounds__(1024) void check3_burn_kernel(int iters, float *sink)
-{
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    f32x16 acc[4];
-    for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < 16; ++j) acc[k][j] = 0.0f;
-    const h4 a = {(_Float16)(threadIdx.x & 7), (_Float16)1.0f, (_Float16)0.5f, (_Float16)0.25f}, b = {(_Float16)1.0f, (_Float16)(threadIdx.x & 3), (_Float16)2.0f, (_Float16)0.125f};
-    for (int i = 0; i < iters; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[k] = __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, acc[k], 0, 0, 0);
-    float t = 0.0f;
-    for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < 16; ++j) t += acc[k][j];
-    if (t == 12345.678f) sink[0] = t;
-}
-static uint32_t check3_pre_mask()
-{
-    // bit k (0..2): lds in front of launch k; bit 3: burn in front of launch 0; bits 4, 5: icache in front of launches 1 and 2
-    static int mask = -1;
-    if (mask < 0) {
-        mask = 0;
-        const char *e = std::getenv("WOST_NET_CHECK3_PRE");
-        const std::string v = e ? e : "";
-        if (v.find("lds23") != std::string::npos) mask |= 6;
-        else if (v.find("lds") != std::string::npos) mask |= 7;
-        if (v.find("burn1") != std::string::npos) mask |= 8;
-        if (v.find("icache23") != std::string::npos) mask |= 48;
-    }
-    return (uint32_t)mask;
-}
-static void check3_pre(int launch, hipStream_t stream)
-{
-    const uint32_t m = check3_pre_mask();
-    if (!m || !g_check3.dev) return;
-    uint32_t *sink = reinterpret_cast<uint32_t *>(g_check3.dev + 15);
-    if (m & (1u << launch)) {
-        const uint32_t bytes = 156u * 1024u;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(check3_lds_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        hipLaunchKernelGGL(check3_lds_fill_kernel, dim3(512), dim3(1024), bytes, stream, 0x7e007e00u, bytes / 4u, sink);
-    }
-    if (launch == 0 && (m & 8u)) hipLaunchKernelGGL(check3_burn_kernel, dim3(512), dim3(1024), 0, stream, 400, reinterpret_cast<float *>(sink));
-    if ((launch == 1 && (m & 16u)) || (launch == 2 && (m & 32u))) hipLaunchKernelGGL(check3_icache_kernel, dim3(4096), dim3(64), 0, stream);
-}
-static bool check3_on()
-{
-    if (!g_check3.asked) {
-        g_check3.asked = true;
-        const char *e = std::getenv("WOST_NET_CHECK3");
-        g_check3.on = e && std::atoi(e) != 0;
-        if (g_check3.on && (hipMalloc((void **)&g_check3.log, 65536 * 4) != hipSuccess || hipMalloc((void **)&g_check3.dev, 16 * sizeof(unsigned long long)) != hipSuccess ||
-                            hipMemset(g_check3.dev, 0, 16 * sizeof(unsigned long long)) != hipSuccess))
-            g_check3.on = false;
-    }
-    return g_check3.on;
-}
-static void *check3_scratch(int k, size_t bytes)
-{
-    if (g_check3.scratch_bytes[k] < bytes) {
-        if (g_check3.scratch[k]) (void)hipFree(g_check3.scratch[k]);
-        g_check3.scratch[k] = nullptr;
-        if (hipMalloc(&g_check3.scratch[k], bytes) != hipSuccess) return nullptr;
-        g_check3.scratch_bytes[k] = bytes;
-    }
-    return g_check3.scratch[k];
-}
-static void check3_compare(int kernel, const void *a, const void *b, const void *c, size_t bytes, hipStream_t stream)
-{
-    const size_t words = bytes / 4;
-    hipLaunchKernelGGL(check3_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const uint32_t *>(a),
-                       reinterpret_cast<const uint32_t *>(b), reinterpret_cast<const uint32_t *>(c), words, g_check3.dev + 8 * kernel, kernel == 0 ? g_check3.log : nullptr);
-}
-static void check3_report()
-{
-    if (!g_check3.on || !g_check3.dev) return;
-    unsigned long long v[16];
-    if (hipMemcpy(v, g_check3.dev, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
-#ifdef WOST_H_NO_REDO
-    std::fprintf(stderr, "CHECK3 build: net_forward_h_kernel WITHOUT the recomputed first tile (WOST_H_NO_REDO)\n");
-#else
-    std::fprintf(stderr, "CHECK3 build: net_forward_h_kernel recomputes a wave's first tile\n");
-#endif
-    std::fprintf(stderr, "CHECK3 after %llu training steps: forward words differing %llu (odd launch 0/1/2/all: %llu %llu %llu %llu); train kernel words differing %llu (%llu %llu %llu %llu)\n",
-                 g_check3.steps, v[0], v[1], v[2], v[3], v[4], v[8], v[9], v[10], v[11], v[12]);
-    // where in the launch the forward kernel's differing units lie: a wave takes the tiles blockIdx * waves + wave + k * (256 * waves), k = 0, 1, ...
-    const size_t n_log = (size_t)std::min<unsigned long long>(v[0], 65536ull);
-    if (n_log) {
-        std::vector<uint32_t> idx(n_log);
-        if (hipMemcpy(idx.data(), g_check3.log, n_log * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
-        const int waves = kHalfFwdThreads / 64;
-        std::vector<char> seen;
-        size_t hist[16] = {0}, units = 0;
-        for (uint32_t w : idx) {
-            const size_t unit = (size_t)w / (size_t)g_check3.n_out / 16;
-            if (seen.size() <= unit) seen.resize(unit + 1, 0);
-            if (seen[unit]) continue;
-            seen[unit] = 1;      // (a unit that fails in two different steps is counted once: rare)
-            ++units;
-            hist[std::min<size_t>(15, unit / 2 / (size_t)(256 * waves))]++;
-        }
-        std::fprintf(stderr, "CHECK3 forward: %zu distinct units among the first %zu differing words; by the wave's iteration k: ", units, n_log);
-        for (int k = 0; k < 16; ++k) std::fprintf(stderr, "%zu ", hist[k]);
-        std::fprintf(stderr, "\n");
-    }
-}
+#include "wost_net_check3.h"
 
 static void net_free(wost_net *h)
 {
@@ -1836,15 +1822,9 @@ static void net_free(wost_net *h)
     for (float *p : {h->params, h->inference, h->params_t, h->inference_t, h->params_f, h->inference_f, h->params_fb, h->m1, h->m2, h->ema_raw, h->d_xy, h->d_out, h->d_dl, h->d_acts, h->d_deltas, h->d_denc})
         if (p) (void)hipFree(p);
     if (h->grad && h->grad_owned) (void)hipFree(h->grad);
-    if (h->d_mask) (void)hipFree(h->d_mask);
-    if (h->d_bin_order) (void)hipFree(h->d_bin_order);
-    if (h->d_bin_tab) (void)hipFree(h->d_bin_tab);
-    if (h->param_steps) (void)hipFree(h->param_steps);
-    if (h->lr_table) (void)hipFree(h->lr_table);
-    if (h->inference_h) (void)hipFree(h->inference_h);
-    if (h->params_h) (void)hipFree(h->params_h);
-    if (h->params_hb) (void)hipFree(h->params_hb);
-    if (h->train_partial) (void)hipFree(h->train_partial);
+    for (void *p : {(void *)h->d_mask, (void *)h->d_bin_order, (void *)h->d_bin_tab, (void *)h->param_steps, (void *)h->lr_table, (void *)h->inference_h,
+                    (void *)h->params_h, (void *)h->params_hb, (void *)h->train_partial})
+        if (p) (void)hipFree(p);
     delete h;
 }
 
@@ -1857,273 +1837,18 @@ int net_inference_dev(wost_net *h, const float *xy_dev, const uint32_t *count_de
     return launch_forward(h, use_inference_params, xy_dev, max_n, count_dev, out_dev, nullptr, stream, feature_stride);
 }
 
-// forward with the training parameters, keeping activations; *out_dev = raw outputs
-// (n x n_output), *dl_dev = where the caller writes dL/dout before net_backward_update_dev
+// forward with the training parameters, keeping activations (half precision: the inference kernel, keeping the f16 encoding of every point,
+// 64 bytes); *out_dev = raw outputs (n x n_output), *dl_dev = where the caller writes dL/dout before net_backward_update_dev
 int net_forward_train_dev(wost_net *h, const float *xy_dev, int n, hipStream_t stream, float **out_dev, float **dl_dev)
 {
     int rc = ensure_points(h, (size_t)n);
     if (rc != WOST_OK) return rc;
-    if (h->train_precision == 16) {
-        // the inference kernel on the training weights; the f16 encoding of every point (64 bytes) is kept
-        if (check3_on() && h->L.dims == 2 && std::atoi(std::getenv("WOST_NET_CHECK3")) == 2) {
-            // variant 2: a discarded launch in front (is it the launch that follows OTHER kernels that differs, whatever it computes?)
-            const size_t ob = (size_t)n * h->L.n_out * 4, eb = (size_t)((n + 31) / 32 * 2) * 2 * 64 * 8;
-            float *o3 = (float *)check3_scratch(3, ob);
-            uint2 *e1 = (uint2 *)check3_scratch(2, eb);
-            if (o3 && e1) (void)launch_forward_h(h, h->params, h->params_h, xy_dev, n, nullptr, o3, (size_t)h->L.n_out, 1, e1, stream);
-        }
-        if (check3_on()) check3_pre(0, stream);
-        rc = launch_forward_h(h, h->params, h->params_h, xy_dev, n, nullptr, h->d_out, (size_t)h->L.n_out, 1, reinterpret_cast<uint2 *>(h->d_acts), stream);
-        if (rc != WOST_OK) return rc;
-        if (check3_on()) {
-            g_check3.n_out = h->L.n_out;
-            const size_t ob = (size_t)n * h->L.n_out * 4, eb = (size_t)((n + 31) / 32 * 2) * 2 * 64 * 8;
-            float *o1 = (float *)check3_scratch(0, ob), *o2 = (float *)check3_scratch(1, ob);
-            uint2 *e1 = (uint2 *)check3_scratch(2, eb);
-            if (o1 && o2 && e1) {
-                check3_pre(1, stream);
-                (void)launch_forward_h(h, h->params, h->params_h, xy_dev, n, nullptr, o1, (size_t)h->L.n_out, 1, e1, stream);
-                check3_pre(2, stream);
-                (void)launch_forward_h(h, h->params, h->params_h, xy_dev, n, nullptr, o2, (size_t)h->L.n_out, 1, e1, stream);
-                check3_compare(0, h->d_out, o1, o2, ob, stream);
-                ++g_check3.steps;
-            }
-        }
-    } else {
-        rc = launch_forward(h, false, xy_dev, n, nullptr, h->d_out, h->d_acts, stream);
-        if (rc != WOST_OK) return rc;
-    }
+    if (h->train_precision != 16) rc = launch_forward(h, false, xy_dev, n, nullptr, h->d_out, h->d_acts, stream);
+    else if (check3_on()) rc = check3_forward(h, xy_dev, n, stream);      // the launch of the line below among its repeats
+    else rc = launch_forward_h(h, h->params, h->params_h, xy_dev, n, nullptr, h->d_out, (size_t)h->L.n_out, 1, reinterpret_cast<uint2 *>(h->d_acts), stream);
+    if (rc != WOST_OK) return rc;
     *out_dev = h->d_out;
     *dl_dev = h->d_dl;
-    return WOST_OK;
-}
-
-int net_apply_update_dev(wost_net *h, float loss_scale, hipStream_t stream);
-
-int net_backward_update_dev(wost_net *h, const float *xy_dev, int n, float loss_scale, int apply_update, hipStream_t stream)
-{
-    const NetLayout &L = h->L;
-    NET_TRY(hipMemsetAsync(h->grad, 0, (size_t)h->n_params * sizeof(fx_t), stream));
-    ++h->n_launches;
-    const bool half = h->train_precision == 16;
-    const bool fused = h->fused_backward || half;
-    if (half) {
-        // recompute the hidden layers from the stored encoding, backward pass, all weight gradients in registers
-        const size_t lds = (size_t)L.n_mlp / 4 * sizeof(uint2) * 2;
-        const int n_units = (n + 15) / 16;
-        const unsigned gridb = (unsigned)std::min((n_units + kHalfThreads / 64 - 1) / (kHalfThreads / 64), 256);
-        int k = 0;
-        while (k < 10 && (n >> (k + 10)) > 0) ++k;          // 2^k ~ n / 512, between 1 and 1024
-        hipLaunchKernelGGL(net_train_h_kernel, dim3(gridb), dim3(kHalfThreads), lds, stream, L, h->params_h, h->params_hb,
-                           reinterpret_cast<const uint2 *>(h->d_acts), h->d_dl, n, (float)(1 << k), h->d_denc, h->train_partial);
-        if (check3_on() && L.dims == 2) {
-            const size_t db = (size_t)n * L.enc * 4, pb = (size_t)gridb * L.n_mlp * 4;
-            float *d1 = (float *)check3_scratch(0, db), *d2 = (float *)check3_scratch(1, db), *p1 = (float *)check3_scratch(2, pb), *p2 = (float *)check3_scratch(3, pb);
-            if (d1 && d2 && p1 && p2) {
-                for (int rep = 0; rep < 2; ++rep)
-                    hipLaunchKernelGGL(net_train_h_kernel, dim3(gridb), dim3(kHalfThreads), lds, stream, L, h->params_h, h->params_hb,
-                                       reinterpret_cast<const uint2 *>(h->d_acts), h->d_dl, n, (float)(1 << k), rep ? d2 : d1, rep ? p2 : p1);
-                check3_compare(1, h->d_denc, d1, d2, db, stream);
-                check3_compare(1, h->train_partial, p1, p2, pb, stream);
-            }
-        }
-        hipLaunchKernelGGL(net_train_h_reduce_kernel, dim3((L.n_mlp + 255) / 256, (gridb + 15) / 16), dim3(256), 0, stream, L, h->train_partial, (int)gridb,
-                           h->grad);
-        h->n_launches += 2;
-    } else if (h->use_mfma && fused) {
-        // backward pass and weight gradients of a 1024-point chunk in one block (deltas stay on chip)
-        const size_t lds = ((size_t)L.n_mlp + 4 * 64 * kTileStride + 3 * 64 * 64) * sizeof(float);
-        auto kfn = net_backward_wgrad_kernel<32, 64, 3, 48>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)((n + 1023) / 1024)), dim3(256), lds, stream, L, h->params_fb, h->d_dl, h->d_mask, n,
-                           h->d_acts, h->d_denc, h->grad);
-        ++h->n_launches;
-    } else if (h->use_mfma) {
-        const size_t lds = (size_t)L.n_mlp * sizeof(float);
-        const int n_tiles = (n + 63) / 64 * 4 / kMfmaSub;
-        const unsigned gridb = (unsigned)std::min((n_tiles + kBwdThreads / 64 - 1) / (kBwdThreads / 64), 256);
-        hipLaunchKernelGGL((net_backward_mfma_kernel<32, 64, 3, 48, kBwdThreads>), dim3(gridb), dim3(kBwdThreads), lds, stream, L,
-                           h->params_fb, h->d_dl, h->d_mask, n, h->d_deltas, h->d_denc);
-        ++h->n_launches;
-    } else {
-        const size_t lds = 2 * 64 * kNetBlock * sizeof(float);
-        const unsigned gridp = (unsigned)((n + kNetBlock - 1) / kNetBlock);
-        hipLaunchKernelGGL(net_backward_kernel, dim3(gridp), dim3(kNetBlock), lds, stream, L, h->params, xy_dev, h->d_dl, h->d_acts,
-                           n, h->d_deltas, h->d_denc);
-        ++h->n_launches;
-    }
-    NET_TRY(hipGetLastError());
-    {
-        // group consecutive levels so that each group's 8-byte accumulators fit into LDS: up to
-        // 72 KB per group (two blocks per CU), a single larger level alone up to 150 KB (one block
-        // per CU), and a level larger than that in feature slices
-        const size_t small = 72 * 1024, big = 150 * 1024;
-        auto level_bytes = [&](int l, int nq) { return (size_t)(L.level_off[l + 1] - L.level_off[l]) * nq * sizeof(fx_t); };
-        auto launch = [&](int lv0, int lv1, int q0, int q1, size_t bytes, int use_lds) {
-            const int gchunk = bytes > small ? 4096 : 2048;
-            if (bytes > 48 * 1024)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)big);
-            const size_t ld_point = half ? (size_t)L.n_features : (size_t)L.enc, ld_level = half ? (size_t)n * L.n_features : (size_t)L.n_features;
-            hipLaunchKernelGGL(grid_grad_kernel, dim3((unsigned)((n + gchunk - 1) / gchunk)), dim3(kGridGradBlock), bytes, stream, L, xy_dev,
-                               h->d_denc, ld_point, ld_level, n, gchunk, lv0, lv1, q0, q1, use_lds, h->grad);
-            ++h->n_launches;
-        };
-        // one launch for all groups when every group fits the budget of two blocks per CU (two-input networks: the three-input
-        // grids are far larger than LDS); WOST_GRID_GRAD_PLAN=0: the launches per group below
-        GridGradPlan plan{};
-        size_t plan_bytes = 0;
-        bool planned = L.dims == 2 && !(std::getenv("WOST_GRID_GRAD_PLAN") && std::atoi(std::getenv("WOST_GRID_GRAD_PLAN")) == 0);
-        int coarse_copies = 4;       // copies of the accumulators of levels below 1024 cells (WOST_GRID_GRAD_COPIES)
-        if (const char *w = std::getenv("WOST_GRID_GRAD_COPIES")) coarse_copies = std::max(1, std::min(8, std::atoi(w)));
-        while (coarse_copies & (coarse_copies - 1)) --coarse_copies;
-        for (int lv = 0; planned && lv < L.n_levels;) {
-            int end = lv;
-            size_t bytes = 0;
-            const bool coarse = L.level_off[lv + 1] - L.level_off[lv] < 1024u;
-            const size_t budget = coarse ? small / (size_t)coarse_copies : small;
-            while (end < L.n_levels && (L.level_off[end + 1] - L.level_off[end] < 1024u) == coarse && bytes + level_bytes(end, L.n_features) <= budget)
-                bytes += level_bytes(end++, L.n_features);
-            if (end == lv && coarse && level_bytes(lv, L.n_features) <= small) bytes = level_bytes(end++, L.n_features);      // alone, fewer copies
-            if (end > lv) {
-                if (plan.n_groups >= 16) { planned = false; break; }
-                const int g = plan.n_groups++;
-                plan.lv0[g] = lv; plan.lv1[g] = end; plan.q0[g] = 0; plan.q1[g] = L.n_features;
-                int copies = 1;
-                while (copies < 8 && (size_t)(2 * copies) * bytes <= small) copies *= 2;
-                plan.replicas[g] = copies;
-                plan_bytes = std::max(plan_bytes, bytes * (size_t)copies);
-                lv = end;
-                continue;
-            }
-            int slices = 1;
-            while (slices < L.n_features && level_bytes(lv, (L.n_features + slices - 1) / slices) > small) ++slices;
-            const int per = (L.n_features + slices - 1) / slices;
-            if (level_bytes(lv, per) > small) { planned = false; break; }
-            for (int q0 = 0; q0 < L.n_features; q0 += per) {
-                if (plan.n_groups >= 16) { planned = false; break; }
-                const int g = plan.n_groups++;
-                plan.lv0[g] = lv; plan.lv1[g] = lv + 1; plan.q0[g] = q0; plan.q1[g] = std::min(L.n_features, q0 + per);
-                plan.replicas[g] = 1;
-                plan_bytes = std::max(plan_bytes, level_bytes(lv, plan.q1[g] - plan.q0[g]));
-            }
-            ++lv;
-        }
-        if (planned && plan.n_groups > 0) {
-            // equal work per block: chunk[g] x (levels x features of g) about the same for every group, ~ 448 blocks in all (two per CU)
-            double total = 0.0;
-            for (int g = 0; g < plan.n_groups; ++g) total += (double)(plan.lv1[g] - plan.lv0[g]) * (plan.q1[g] - plan.q0[g]);
-            const double per_block = total * (double)n / 448.0;
-            int blocks = 0;
-            for (int g = 0; g < plan.n_groups; ++g) {
-                const double w = (double)(plan.lv1[g] - plan.lv0[g]) * (plan.q1[g] - plan.q0[g]);
-                long long chunk_g = (long long)(per_block / w);
-                chunk_g = std::max<long long>(1024, (chunk_g + 63) / 64 * 64);
-                chunk_g = std::min<long long>(chunk_g, ((long long)n + 63) / 64 * 64);
-                plan.chunk[g] = (int32_t)chunk_g;
-                plan.first_block[g] = blocks;
-                blocks += (int)(((long long)n + chunk_g - 1) / chunk_g);
-            }
-            plan.first_block[plan.n_groups] = blocks;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_grad_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small);
-            const size_t ld_point = half ? (size_t)L.n_features : (size_t)L.enc, ld_level = half ? (size_t)n * L.n_features : (size_t)L.n_features;
-            hipLaunchKernelGGL(grid_grad_plan_kernel, dim3((unsigned)blocks), dim3(kGridGradBlock), plan_bytes, stream, L, xy_dev, h->d_denc, ld_point, ld_level, n,
-                               plan, h->grad);
-            ++h->n_launches;
-        }
-        int lv = planned && plan.n_groups > 0 ? L.n_levels : 0;
-        // three inputs: every level in one launch through spatial boxes (WOST_GRID_GRAD_BINS=0: the launches per level group below)
-        if (L.dims == 3 && !(std::getenv("WOST_GRID_GRAD_BINS") && std::atoi(std::getenv("WOST_GRID_GRAD_BINS")) == 0) && h->d_bin_order &&
-            (size_t)n <= h->cap_points) {
-            GridBin3Plan bp{};
-            const size_t lds_cap = 152 * 1024;
-            for (int bins : {8, 16}) {
-                int total = 0;
-                for (int l = 0; l < L.n_levels; ++l) {
-                    bp.ext[l] = (int)std::floor(L.scale[l] / (float)bins) + 3;
-                    bp.acc_off[l] = total;
-                    total += bp.ext[l] * bp.ext[l] * bp.ext[l];
-                }
-                bp.acc_off[L.n_levels] = bp.n_acc = total;
-                bp.bins = (size_t)total * L.n_features * sizeof(fx_t) <= lds_cap ? bins : 0;
-                if (bp.bins) break;
-            }
-            if (bp.bins) {
-                const int nb = bp.bins * bp.bins * bp.bins;
-                bp.chunk = 2048;
-                if (const char *w = std::getenv("WOST_GRID_GRAD_BIN_CHUNK")) bp.chunk = std::max(64, std::atoi(w));
-                if (!h->d_bin_tab) NET_TRY(hipMalloc((void **)&h->d_bin_tab, (2 * 4096 + 1 + 2 * 4097) * sizeof(uint32_t)));
-                NET_TRY(hipMemsetAsync(h->d_bin_tab, 0, (2 * (size_t)nb + 1) * sizeof(uint32_t), stream));
-                const unsigned gc = (unsigned)((n + kBin3CountPoints - 1) / kBin3CountPoints);
-                hipLaunchKernelGGL(grid_bin3_count_kernel, dim3(gc), dim3(1024), (size_t)std::max(nb, 2048) * sizeof(uint32_t), stream, xy_dev, n, bp.bins,
-                                   bp.chunk, h->d_bin_tab);
-                hipLaunchKernelGGL(grid_bin3_scatter_kernel, dim3(gc), dim3(1024), 2 * (size_t)nb * sizeof(uint32_t), stream, xy_dev, n, bp.bins, h->d_bin_tab,
-                                   h->d_bin_order);
-                const size_t acc_bytes = (size_t)bp.n_acc * L.n_features * sizeof(fx_t);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_bin3_accumulate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
-                const size_t ld_point = half ? (size_t)L.n_features : (size_t)L.enc, ld_level = half ? (size_t)n * L.n_features : (size_t)L.n_features;
-                hipLaunchKernelGGL(grid_bin3_accumulate_kernel, dim3((unsigned)(n / bp.chunk + nb + 1)), dim3(kGridGradBlock), acc_bytes, stream, L, xy_dev, h->d_denc,
-                                   ld_point, ld_level, bp, h->d_bin_tab, h->d_bin_order, h->grad);
-                h->n_launches += 4;
-                lv = L.n_levels;
-            }
-        }
-        while (lv < L.n_levels) {
-            int end = lv;
-            size_t bytes = 0;
-            while (end < L.n_levels && bytes + level_bytes(end, L.n_features) <= small) bytes += level_bytes(end++, L.n_features);
-            if (end > lv) {
-                launch(lv, end, 0, L.n_features, bytes, 1);
-                lv = end;
-                continue;
-            }
-            // levels of which not even ONE feature fits a block's LDS (three inputs: 32^3 cells and up) add straight to global memory: all
-            // of them and all their features in ONE launch -- a launch per level and feature slice (round 4: sixteen of a step's twenty-odd
-            // launches) walks all n points again each time for the same atomics
-            if (level_bytes(lv, 1) > big) {
-                int end_g = lv;
-                while (end_g < L.n_levels && level_bytes(end_g, 1) > big) ++end_g;
-                launch(lv, end_g, 0, L.n_features, 0, 0);
-                lv = end_g;
-                continue;
-            }
-            // this level alone exceeds the group budget: whole if it fits one block per CU, else feature slices
-            int slices = 1;
-            while (slices < L.n_features && level_bytes(lv, (L.n_features + slices - 1) / slices) > big) ++slices;
-            const int per = (L.n_features + slices - 1) / slices;
-            for (int q0 = 0; q0 < L.n_features; q0 += per) {
-                const int q1 = std::min(L.n_features, q0 + per);
-                const size_t sb = level_bytes(lv, q1 - q0);
-                launch(lv, lv + 1, q0, q1, sb <= big ? sb : 0, sb <= big ? 1 : 0);
-            }
-            ++lv;
-        }
-        NET_TRY(hipGetLastError());
-    }
-    const int astride = L.enc + L.n_hidden * L.n_neurons, dstride = L.n_out_padded + L.n_hidden * L.n_neurons;
-    const int chunk = 1024;
-    const unsigned gridc = (unsigned)((n + chunk - 1) / chunk);
-    const size_t lds_w = 2 * 32 * 64 * sizeof(float);
-    for (int layer = 0; layer <= L.n_hidden && !(h->use_mfma && fused) && !half; ++layer) {
-        const int n_i = layer == 0 ? L.enc : L.n_neurons, n_o = layer == L.n_hidden ? L.n_out_padded : L.n_neurons;
-        const int doff = layer == L.n_hidden ? 0 : L.n_out_padded + layer * L.n_neurons;   // delta of this layer's output
-        const int ioff = layer == 0 ? 0 : L.enc + (layer - 1) * L.n_neurons;               // this layer's input
-        fx_t *gW = h->grad + L.w_off[layer];
-        ++h->n_launches;
-        if (h->use_mfma) {
-#define WG(NO, NI) hipLaunchKernelGGL((weight_grad_mfma_kernel<NO, NI>), dim3(gridc), dim3(256), 0, stream, h->d_deltas, dstride, \
-                                      doff, h->d_acts, astride, ioff, n, chunk, gW)
-            if (layer == 0) WG(64, 32);
-            else if (layer == L.n_hidden) WG(48, 64);
-            else WG(64, 64);
-#undef WG
-        } else {
-            hipLaunchKernelGGL(weight_grad_kernel, dim3(gridc), dim3(256), lds_w, stream, h->d_deltas, dstride, doff, h->d_acts,
-                               astride, ioff, n_o, n_i, n, chunk, gW);
-        }
-    }
-    NET_TRY(hipGetLastError());
-    if (apply_update) return net_apply_update_dev(h, loss_scale, stream);
     return WOST_OK;
 }
 
@@ -2162,6 +1887,134 @@ int net_apply_update_dev(wost_net *h, float loss_scale, hipStream_t stream)
     ++h->n_launches;
     NET_TRY(hipGetLastError());
     return WOST_OK;
+}
+
+// ---- the steps of net_backward_update_dev.  dL/d(encoding) in h->d_denc: point-major rows of enc floats (fp32 kernels), or one n x n_features block per level (half precision)
+struct GradStrides { size_t ld_point, ld_level; };
+static GradStrides grad_strides(const wost_net *h, int n)
+{
+    const size_t nf = (size_t)h->L.n_features;
+    return h->train_precision == 16 ? GradStrides{nf, (size_t)n * nf} : GradStrides{(size_t)h->L.enc, nf};
+}
+
+// dL/dout in h->d_dl -> dL/d(encoding) in h->d_denc; the half-precision and the fused kernels add the weight gradients as well
+static void backward_pass(wost_net *h, const float *xy_dev, int n, hipStream_t stream)
+{
+    const NetLayout &L = h->L;
+    if (h->train_precision == 16) {
+        // recompute the hidden layers from the stored encoding, backward pass, all weight gradients in registers
+        const size_t lds = (size_t)L.n_mlp / 4 * sizeof(uint2) * 2;
+        const unsigned gridb = (unsigned)std::min(((n + 15) / 16 + kHalfThreads / 64 - 1) / (kHalfThreads / 64), 256);      // of 16-point units
+        int k = 0;
+        while (k < 10 && (n >> (k + 10)) > 0) ++k;          // 2^k ~ n / 512, between 1 and 1024
+        hipLaunchKernelGGL(net_train_h_kernel, dim3(gridb), dim3(kHalfThreads), lds, stream, L, h->params_h, h->params_hb,
+                           reinterpret_cast<const uint2 *>(h->d_acts), h->d_dl, n, (float)(1 << k), h->d_denc, h->train_partial);
+        if (check3_on()) check3_train(h, n, gridb, lds, k, stream);
+        hipLaunchKernelGGL(net_train_h_reduce_kernel, dim3((L.n_mlp + 255) / 256, (gridb + 15) / 16), dim3(256), 0, stream, L, h->train_partial, (int)gridb,
+                           h->grad);
+        ++h->n_launches;
+    } else if (h->use_mfma && h->fused_backward) {
+        // backward pass and weight gradients of a 1024-point chunk in one block (deltas stay on chip)
+        const size_t lds = ((size_t)L.n_mlp + 4 * 64 * kTileStride + 3 * 64 * 64) * sizeof(float);
+        auto kfn = net_backward_wgrad_kernel<32, 64, 3, 48>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)((n + 1023) / 1024)), dim3(256), lds, stream, L, h->params_fb, h->d_dl, h->d_mask, n,
+                           h->d_acts, h->d_denc, h->grad);
+    } else if (h->use_mfma) {
+        const size_t lds = (size_t)L.n_mlp * sizeof(float);
+        const int n_tiles = (n + 63) / 64 * 4 / kMfmaSub;
+        const unsigned gridb = (unsigned)std::min((n_tiles + kBwdThreads / 64 - 1) / (kBwdThreads / 64), 256);
+        hipLaunchKernelGGL((net_backward_mfma_kernel<32, 64, 3, 48, kBwdThreads>), dim3(gridb), dim3(kBwdThreads), lds, stream, L,
+                           h->params_fb, h->d_dl, h->d_mask, n, h->d_deltas, h->d_denc);
+    } else {
+        const size_t lds = 2 * 64 * kNetBlock * sizeof(float);
+        hipLaunchKernelGGL(net_backward_kernel, dim3((unsigned)((n + kNetBlock - 1) / kNetBlock)), dim3(kNetBlock), lds, stream, L, h->params, xy_dev, h->d_dl,
+                           h->d_acts, n, h->d_deltas, h->d_denc);
+    }
+    ++h->n_launches;      // (the half-precision branch has counted its second kernel)
+}
+
+// dL/d(encoding) -> the gradient of the grid, by the strategy the plan holds for this network
+static int grid_gradient(wost_net *h, const float *xy_dev, int n, hipStream_t stream)
+{
+    const NetLayout &L = h->L;
+    const TrainPlan &P = h->plan;
+    const GradStrides ld = grad_strides(h, n);
+    if (P.groups.n_groups > 0) {
+        GridGradPlan plan = P.groups;
+        const int blocks = grid_grad_chunks(plan, n);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_grad_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGroupSmall);
+        hipLaunchKernelGGL(grid_grad_plan_kernel, dim3((unsigned)blocks), dim3(kGridGradBlock), P.plan_bytes, stream, L, xy_dev, h->d_denc, ld.ld_point,
+                           ld.ld_level, n, plan, h->grad);
+        ++h->n_launches;
+    } else if (P.bin3.bins && h->d_bin_order && (size_t)n <= h->cap_points) {
+        const GridBin3Plan &bp = P.bin3;
+        const int nb = bp.bins * bp.bins * bp.bins;
+        NET_TRY(hipMemsetAsync(h->d_bin_tab, 0, (2 * (size_t)nb + 1) * sizeof(uint32_t), stream));
+        const unsigned gc = (unsigned)((n + kBin3CountPoints - 1) / kBin3CountPoints);
+        hipLaunchKernelGGL(grid_bin3_count_kernel, dim3(gc), dim3(1024), (size_t)std::max(nb, 2048) * sizeof(uint32_t), stream, xy_dev, n, bp.bins,
+                           bp.chunk, h->d_bin_tab);
+        hipLaunchKernelGGL(grid_bin3_scatter_kernel, dim3(gc), dim3(1024), 2 * (size_t)nb * sizeof(uint32_t), stream, xy_dev, n, bp.bins, h->d_bin_tab,
+                           h->d_bin_order);
+        const size_t acc_bytes = (size_t)bp.n_acc * L.n_features * sizeof(fx_t);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_bin3_accumulate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBin3LdsCap);
+        hipLaunchKernelGGL(grid_bin3_accumulate_kernel, dim3((unsigned)(n / bp.chunk + nb + 1)), dim3(kGridGradBlock), acc_bytes, stream, L, xy_dev, h->d_denc,
+                           ld.ld_point, ld.ld_level, bp, h->d_bin_tab, h->d_bin_order, h->grad);
+        h->n_launches += 4;
+    } else {
+        for (const GridGradStep &s : P.fallback) {
+            const int gchunk = s.bytes > kGroupSmall ? 4096 : 2048;
+            if (s.bytes > 48 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(grid_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGroupBig);
+            hipLaunchKernelGGL(grid_grad_kernel, dim3((unsigned)((n + gchunk - 1) / gchunk)), dim3(kGridGradBlock), s.bytes, stream, L, xy_dev, h->d_denc,
+                               ld.ld_point, ld.ld_level, n, gchunk, s.lv0, s.lv1, s.q0, s.q1, s.use_lds, h->grad);
+            ++h->n_launches;
+        }
+    }
+    NET_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+// the gradients of the MLP matrices, one launch per layer (the half-precision and the fused backward kernels have added them already)
+static void weight_gradients(wost_net *h, int n, hipStream_t stream)
+{
+    const NetLayout &L = h->L;
+    if (h->train_precision == 16 || (h->use_mfma && h->fused_backward)) return;
+    const int astride = L.enc + L.n_hidden * L.n_neurons, dstride = L.n_out_padded + L.n_hidden * L.n_neurons, chunk = 1024;
+    const unsigned gridc = (unsigned)((n + chunk - 1) / chunk);
+    const size_t lds_w = 2 * 32 * 64 * sizeof(float);
+    for (int layer = 0; layer <= L.n_hidden; ++layer) {
+        const int n_i = layer == 0 ? L.enc : L.n_neurons, n_o = layer == L.n_hidden ? L.n_out_padded : L.n_neurons;
+        const int doff = layer == L.n_hidden ? 0 : L.n_out_padded + layer * L.n_neurons;   // delta of this layer's output
+        const int ioff = layer == 0 ? 0 : L.enc + (layer - 1) * L.n_neurons;               // this layer's input
+        fx_t *gW = h->grad + L.w_off[layer];
+        ++h->n_launches;
+        if (h->use_mfma) {
+#define WG(NO, NI) hipLaunchKernelGGL((weight_grad_mfma_kernel<NO, NI>), dim3(gridc), dim3(256), 0, stream, h->d_deltas, dstride, \
+                                      doff, h->d_acts, astride, ioff, n, chunk, gW)
+            if (layer == 0) WG(64, 32);
+            else if (layer == L.n_hidden) WG(48, 64);
+            else WG(64, 64);
+#undef WG
+        } else {
+            hipLaunchKernelGGL(weight_grad_kernel, dim3(gridc), dim3(256), lds_w, stream, h->d_deltas, dstride, doff, h->d_acts,
+                               astride, ioff, n_o, n_i, n, chunk, gW);
+        }
+    }
+}
+
+// backward pass of the step whose forward pass net_forward_train_dev ran, dL/dout in place: the sums in h->grad, then (apply_update) Adam
+int net_backward_update_dev(wost_net *h, const float *xy_dev, int n, float loss_scale, int apply_update, hipStream_t stream)
+{
+    NET_TRY(hipMemsetAsync(h->grad, 0, (size_t)h->n_params * sizeof(fx_t), stream));
+    ++h->n_launches;
+    backward_pass(h, xy_dev, n, stream);
+    NET_TRY(hipGetLastError());
+    const int rc = grid_gradient(h, xy_dev, n, stream);
+    if (rc != WOST_OK) return rc;
+    weight_gradients(h, n, stream);
+    NET_TRY(hipGetLastError());
+    return apply_update ? net_apply_update_dev(h, loss_scale, stream) : WOST_OK;
 }
 
 void *net_gradient_buffer(wost_net *h, uint64_t *count)
@@ -2284,15 +2137,10 @@ static int net_create_dims(int device, const wost_net_config *cfg, uint64_t seed
     }
     h->L = make_layout(*cfg, dims);
     h->n_params = h->L.n_mlp + h->L.n_grid;
-    {
-        // the MFMA forward kernel is instantiated for the reference's network shape
-        const char *unfused = getenv("WOST_NET_FUSED");
-        h->fused_backward = !(unfused && atoi(unfused) == 0);
-        const char *scalar = getenv("WOST_NET_SCALAR");
-        // (three inputs -- GuidedIntegrator<3> -- only with the reference's four features per level: f32_encode_level3)
-        h->use_mfma = (dims == 2 || (dims == 3 && h->L.n_features == 4)) && h->L.enc == 32 && h->L.n_neurons == 64 && h->L.n_hidden == 3 &&
-                      h->L.n_out_padded == 48 && h->L.n_features <= 8 && !(scalar && atoi(scalar) != 0);
-    }
+    // the knobs are read here, once; the MFMA kernels take three inputs only with the reference's four features per level (f32_encode_level3)
+    h->fused_backward = env_int("WOST_NET_FUSED", 1) != 0;
+    h->use_mfma = (dims == 2 || h->L.n_features == 4) && reference_shape(h->L, false) && env_int("WOST_NET_SCALAR", 0) == 0;
+    h->plan = make_train_plan(h->L);
     // initialisation (tiny-cuda-nn defaults): MLP xavier uniform, grid uniform(-1e-4, 1e-4)
     std::vector<float> init(h->n_params);
     uint64_t state = 0, inc = (54u << 1u) | 1u;
@@ -2412,44 +2260,11 @@ int wost_net_set_option(wost_net_handle h, const char *key, double value)
 {
     if (!h || !key) return set_error(WOST_ERR_INVALID, "null argument");
     const std::string k(key);
-    if (k == "precision") {
-        if (value != 16 && value != 32) return set_error(WOST_ERR_INVALID, "precision must be 32 (fp32, default) or 16 (half-precision inference)");
-        if (value == 16) {
-            const NetLayout &L = h->L;
-            if (!(L.enc == 32 && L.n_neurons == 64 && L.n_hidden == 3 && L.n_out_padded == 48 && L.n_features == 4 && L.n_levels == 8))
-                return set_error(WOST_ERR_UNSUPPORTED, "half-precision inference is built for the reference's network shape only (8 levels x 4 features, 3 x 64, two or three inputs)");
-            NET_TRY(hipSetDevice(h->device));
-            if (L.dims == 2 && half_image_entries(L) * sizeof(uint2) > 158 * 1024)
-                return set_error(WOST_ERR_UNSUPPORTED, "half-precision network: weights and grid must fit into 158 KB of LDS");
-            if (!h->inference_h) NET_TRY(hipMalloc((void **)&h->inference_h, half_image_entries(L) * sizeof(uint2)));
-            h->precision = 16;
-            refresh_half(h, nullptr);
-            NET_TRY(hipGetLastError());
-            NET_TRY(hipDeviceSynchronize());
-        } else {
-            h->precision = 32;
-        }
-        return WOST_OK;
-    }
-    if (k == "train_precision") {
-        if (value != 16 && value != 32) return set_error(WOST_ERR_INVALID, "train_precision must be 32 (fp32, default) or 16 (half-precision training passes)");
-        if (value == 16) {
-            const NetLayout &L = h->L;
-            if (!(L.enc == 32 && L.n_neurons == 64 && L.n_hidden == 3 && L.n_out_padded == 48 && L.n_features == 4 && L.n_levels == 8))
-                return set_error(WOST_ERR_UNSUPPORTED, "half-precision training is built for the reference's network shape only (8 levels x 4 features, 3 x 64, two or three inputs)");
-            NET_TRY(hipSetDevice(h->device));
-            if (L.dims == 2 && half_image_entries(L) * sizeof(uint2) > 158 * 1024)
-                return set_error(WOST_ERR_UNSUPPORTED, "half-precision network: weights and grid must fit into 158 KB of LDS");
-            if (!h->params_h) NET_TRY(hipMalloc((void **)&h->params_h, half_image_entries(L) * sizeof(uint2)));
-            if (!h->params_hb) NET_TRY(hipMalloc((void **)&h->params_hb, (size_t)L.n_mlp / 4 * sizeof(uint2)));
-            if (!h->train_partial) NET_TRY(hipMalloc((void **)&h->train_partial, (size_t)256 * L.n_mlp * sizeof(float)));
-            h->train_precision = 16;
-            refresh_half(h, nullptr);
-            NET_TRY(hipGetLastError());
-            NET_TRY(hipDeviceSynchronize());
-        } else {
-            h->train_precision = 32;
-        }
+    const bool training = k == "train_precision";
+    if (k == "precision" || training) {
+        if (value != 16 && value != 32) return set_error(WOST_ERR_INVALID, k + " must be 32 (fp32, default) or 16 (half-precision " + (training ? "training passes)" : "inference)"));
+        if (value == 16) return enable_half(h, training);
+        (training ? h->train_precision : h->precision) = 32;
         return WOST_OK;
     }
     return set_error(WOST_ERR_INVALID, "unknown option: " + k);

@@ -161,6 +161,48 @@ def test_gpu_net3_inference_and_training_match_oracle(orc, n_levels, scale, monk
     net.close()
 
 
+@pytest.fixture(scope="module")
+def regimes3_reference(orc):
+    """three Adam steps of the oracle on the reference's network shape with 100, 20 000 and 3 000 points (the scratch of a handle
+    grows, then is used in part): per step the batch, the gradient, the weights and the EMA weights.  Shared by the cases below."""
+    cfg = default_net_config3()
+    p = _rand_params3(orc, cfg, seed=13)
+    state = orc.net_optimizer_state(cfg)
+    for k in state:
+        state[k] = np.zeros(len(p), state[k].dtype)
+    rng = np.random.default_rng(6)
+    po, steps = p.copy(), []
+    for step, n in enumerate((100, 20000, 3000), 1):
+        x = rng.uniform(-0.05, 1.05, (n, 3)).astype(np.float32)
+        dl48 = np.zeros((n, 48), np.float32)
+        dl48[:, :41] = rng.normal(size=(n, 41)).astype(np.float32)
+        g = orc.net3_backward(cfg, po, x, dl48)
+        inf = orc.net3_optimizer_step(cfg, po, state, g, step, 128.0)
+        steps.append((x, dl48[:, :41].copy(), g, po.copy(), inf))
+    return cfg, p, steps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bins", [None, "0"])
+def test_gpu_net3_one_network_trains_across_batch_sizes(regimes3_reference, monkeypatch, bins):
+    """One handle, three Adam steps with batch sizes far apart: the box tables of grid_bin3_* (default) are cleared for every step,
+    and nothing the network plans once depends on a step's size; WOST_GRID_GRAD_BINS=0: the launches per level group.  Gradients,
+    weights and EMA weights against the oracle bit for bit after every step."""
+    from elaina_amd.guided import GuidingNetwork
+    if bins is not None:
+        monkeypatch.setenv("WOST_GRID_GRAD_BINS", bins)
+    cfg, p, steps = regimes3_reference
+    net = GuidingNetwork(_hip_cfg(cfg), seed=3, dims=3)
+    try:
+        net.set_params(p)
+        for step, (x, dl, g, po, inf) in enumerate(steps, 1):
+            net.train_step(x, dl, 128.0, apply_update=True)
+            assert np.array_equal(net.gradients(), g), (step, len(x))
+            assert np.array_equal(net.params(), po) and np.array_equal(net.inference_params(), inf), (step, len(x))
+    finally:
+        net.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_features,n_levels", [(2, 8), (8, 3)])
 def test_gpu_net3_grid_gradient_with_other_feature_counts(orc, n_features, n_levels):

@@ -279,6 +279,107 @@ def test_gpu_scalar_kernels_match_oracle(orc, monkeypatch):
         net.close()
 
 
+def _batch(n, seed):
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0, 1, (n, 2)).astype(np.float32)
+    dl = (rng.normal(size=(n, 33)) * 128 / n).astype(np.float32)
+    dl48 = np.zeros((n, 48), dtype=np.float32)
+    dl48[:, :33] = dl
+    return xy, dl, dl48
+
+
+@pytest.fixture(scope="module")
+def knob_reference(orc):
+    """parameters, two batches (n = 5: below one 64-point span, the chunk of every group is clamped; n = 4096 + 3: several chunks,
+    the last one ragged) and the oracle's gradients: the same for every setting of the grid-gradient knobs"""
+    cfg = default_net_config()
+    p = _rand_params(orc, cfg, seed=29, gscale=0.1)
+    batches = [_batch(n, 300 + n) for n in (5, 4096 + 3)]
+    return p, [(xy, dl, orc.net_backward(cfg, p, xy, dl48)) for xy, dl, dl48 in batches]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knob,value", [("WOST_GRID_GRAD_PLAN", "0"), ("WOST_GRID_GRAD_COPIES", "1"), ("WOST_GRID_GRAD_COPIES", "8")])
+def test_gpu_grid_gradient_knobs_give_the_oracle_gradient(knob_reference, monkeypatch, knob, value):
+    """WOST_GRID_GRAD_PLAN=0: the grid gradient through one launch per level group (the finest level in two feature slices) instead
+    of the one planned launch; WOST_GRID_GRAD_COPIES: 1 or 8 copies of the coarse levels' accumulators instead of 4.  The knobs are
+    read when a network is created, so each case makes its own.  Fixed-point sums: the oracle's gradient bit for bit."""
+    from elaina_amd.guided import GuidingNetwork
+    monkeypatch.setenv(knob, value)
+    p, batches = knob_reference
+    net = GuidingNetwork(seed=7)
+    try:
+        net.set_params(p)
+        for xy, dl, want in batches:
+            net.train_step(xy, dl, apply_update=False)
+            got = net.gradients()
+            assert np.array_equal(got, want), (len(xy), float(np.abs(got - want).max()))
+    finally:
+        net.close()
+
+
+REGIMES = (5, 20000, 64, 4099)      # below one span, many blocks per group, exactly one span, ragged chunks: one after another
+
+
+@pytest.mark.gpu
+def test_gpu_one_network_trains_across_batch_size_regimes(orc):
+    """One handle, Adam steps with batch sizes from different regimes in turn: what the network plans once (level groups, knobs)
+    must not carry anything of an earlier step's size into the next.  Gradients, weights and EMA weights against the oracle bit
+    for bit after every step."""
+    from elaina_amd.guided import GuidingNetwork
+    cfg = default_net_config()
+    p = _rand_params(orc, cfg, seed=37, gscale=0.1)
+    st = orc.net_optimizer_state(cfg)
+    po = p.copy()
+    net = GuidingNetwork(seed=7)
+    try:
+        net.set_params(p)
+        for step, n in enumerate(REGIMES, 1):
+            xy, dl, dl48 = _batch(n, 700 + n)
+            net.train_step(xy, dl, loss_scale=128.0)
+            g = orc.net_backward(cfg, po, xy, dl48)
+            assert np.array_equal(net.gradients(), g), (step, n)
+            inf = orc.net_optimizer_step(cfg, po, st, g, step=step, loss_scale=128.0)
+            assert np.array_equal(net.params(), po), (step, n)
+            assert np.array_equal(net.inference_params(), inf), (step, n)
+    finally:
+        net.close()
+
+
+@pytest.mark.gpu
+def test_gpu_one_network_trains_across_batch_size_regimes_in_half_precision(orc):
+    """The same sequence with train_precision 16, where the oracle has no forward or backward pass to compare with: before every
+    Adam step of the one handle, a network created for the purpose takes that step alone from the same weights -- equal gradients
+    bit for bit (the kernels are deterministic).  The optimizer is the fp32 one in this mode too, so the oracle's Adam / EMA step
+    on that gradient gives the weights and the EMA weights the handle must hold afterwards."""
+    from elaina_amd.guided import GuidingNetwork
+    cfg = default_net_config()
+    net = GuidingNetwork(seed=7)
+    n_mlp = net.n_mlp_params
+    try:
+        net.set_option("train_precision", 16)
+        po = net.params().copy()
+        st = orc.net_optimizer_state(cfg)
+        for step, n in enumerate(REGIMES, 1):
+            xy, dl, _ = _batch(n, 900 + n)
+            fresh = GuidingNetwork(seed=1)
+            try:
+                fresh.set_params(po)
+                fresh.set_option("train_precision", 16)
+                fresh.train_step(xy, dl, loss_scale=128.0, apply_update=False)
+                want = fresh.gradients().copy()
+            finally:
+                fresh.close()
+            assert np.any(want[:n_mlp] != 0) and np.any(want[n_mlp:] != 0)      # matrices and grid
+            net.train_step(xy, dl, loss_scale=128.0)
+            assert np.array_equal(net.gradients(), want), (step, n)
+            inf = orc.net_optimizer_step(cfg, po, st, want, step=step, loss_scale=128.0)
+            assert np.array_equal(net.params(), po), (step, n)
+            assert np.array_equal(net.inference_params(), inf), (step, n)
+    finally:
+        net.close()
+
+
 @pytest.mark.gpu
 def test_gpu_network_learns_a_field(net):
     """End-to-end sanity: L2 regression of a smooth 33-channel field drives the loss down and the
