@@ -70,6 +70,10 @@ constexpr int kStatCopies = 64;
 struct alignas(256) StatsDev {
     unsigned long long steps, started, absorbed, truncated, nhits, inner_visits, leaf_visits, trav_trips, step_trips, max_stack;
     unsigned long long sp_ge6, sp_ge10, sp_ge14;     // WOST_TRACK developer builds: visits that left at least that many stack entries
+    // WOST_DRAIN developer builds, the persistent launch: wall_clock64() at the moment a wave stops on the dry queue (earliest,
+    // latest, sum and number of waves; the earliest as the maximum of the complement: the counters start at zero) and the latest
+    // moment a wave reached the end of the kernel
+    unsigned long long stop_min, stop_max, stop_sum, stop_waves, end_max;
 };
 __device__ __forceinline__ StatsDev *my_stats(StatsDev *s) { return s + (blockIdx.x & (kStatCopies - 1)); }
 
@@ -93,7 +97,11 @@ struct RoundParams {
     const uint32_t *order; // the k-th walker of the launch is input slot order[k] (wost_order.h); nullptr = slot k
     int32_t reserve;       // REFILL launches: input slots a wave reserves per atomic on the cursor; 0 = exactly those it needs
     int32_t leave_dry;     // REFILL launches: 1 = a wave that finds the input queue dry finishes the steps in flight and hands its
-                           //   walkers to the output queue (the host repacks them: rounds); 0 = it stays until its last pixel is done
+                           //   walkers to the output queue (the host repacks them: rounds); 0 = it stays until its last pixel is done;
+                           //   2 (PERSIST) = as 1, and a wave also looks at the cursor every few step trips: once the queue is dry
+                           //   every wave stops at its next look, not only one that needs a refill
+    int32_t dry_cadence;   //   ... walk steps of a wave's busiest lane between two looks once the queue is nearly dry (a power of
+    int32_t dry_shift;     //   two), and while R slots are unread: max(dry_cadence, R >> dry_shift) steps (launch_ordinary)
     uint32_t *count_long;  // ... and counts the pixels it hands over that are expected to need long_steps walk steps or more
     float long_steps;
     // walk_quad_kernel, the launch of the long remainders: the first thin_count walkers sit four to a wave (sixteen to a workgroup)
@@ -456,7 +464,10 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
     const bool has_d = P.dm.n_segs > 0;
     int mode = alive ? MODE_WAIT : MODE_DONE;
     bool fresh = true;   // first trip: no finished step yet, only start the query
-    int budget = P.steps_per_round;
+    // (PERSIST with leave_dry 2: no round ends such a launch, and the budget counts the steps to the wave's next look at the
+    // cursor instead, above kLookBase -- see the end of the step phase; no register beside the 80 the instantiation lives on)
+    constexpr int kLookBase = 1 << 30;
+    int budget = (PERSIST && P.leave_dry == 2) ? kLookBase + P.dry_cadence : P.steps_per_round;
     Trav T = trav_begin(Closest{WOST_INF, -1});
     uint32_t trav_trips = 0, step_trips = 0;   // wave-uniform: scheduler diagnostics
 #ifdef WOST_TRACK
@@ -467,6 +478,15 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
 #else
 #define WOST_TRACK_VISIT_PRE() do {} while (0)
 #define WOST_TRACK_VISIT_POST() do {} while (0)
+#endif
+#ifdef WOST_DRAIN
+    // (no lane has left the loop's wave-uniform control flow at either place: the first active lane speaks for the wave; a
+    // wave's budgets are all positive until it stops and none is afterwards)
+#define WOST_DRAIN_STOP() do { if (PERSIST && budget > 0 && (threadIdx.x & 63) == 0) { \
+        const unsigned long long t_ = wall_clock64(); StatsDev *sd_ = my_stats(P.stats); \
+        atomicMax(&sd_->stop_min, ~t_); atomicMax(&sd_->stop_max, t_); atomicAdd(&sd_->stop_sum, t_); atomicAdd(&sd_->stop_waves, 1ull); } } while (0)
+#else
+#define WOST_DRAIN_STOP() do {} while (0)
 #endif
     const LdsColumn stk{stack, (uint32_t)P.stack_stride};
     for (;;) {
@@ -505,7 +525,10 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                 }
                 // the queue is dry: with leave_dry the wave stops here -- no new step starts (budget 0), queries in flight finish
                 // their step, pixels still open go to the output queue at the end of the kernel like the survivors of a round
-                if (P.leave_dry && __ballot(mode == MODE_REFILL && s2 >= n_in)) budget = 0;
+                if (P.leave_dry && __ballot(mode == MODE_REFILL && s2 >= n_in)) {
+                    WOST_DRAIN_STOP();
+                    budget = 0;
+                }
                 if (mode == MODE_REFILL) {
                     if (open) {       // (a walker that left for the slack launch is not resolved here: `open` is false)
                         float *f = P.field + 3 * (size_t)((int32_t)pix - P.field_base);
@@ -672,6 +695,22 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                     hb &= hb - 1;
                 }
             }
+            if (PERSIST && P.leave_dry == 2 && __ballot((uint32_t)(budget - 1) < (uint32_t)kLookBase)) {
+                // the global look (leave_dry 2): a wave that needs no refill learns here that the queue is dry, and stops like one
+                // that does -- without it a wave walks on until one of ITS lanes completes a pixel, half a millisecond on average,
+                // and the launch lasts until the last of six thousand waves has (9 - 12 ms in config 2, EXPERIMENTS 32), while
+                // what the others handed over waits behind it.  The cursor only grows and claims beyond n_in keep it there, so
+                // cursor >= n_in is exactly "no unread slot"; an atomic load of agent scope sees the other waves' atomics (a plain
+                // load may be served from a stale line).  Such a load is answered beyond the L2 of the wave's XCD and the wave waits
+                // for it: a look on every fourth trip of the whole launch cost 13 % of it.  So the wave looks rarely while the
+                // queue is far from dry -- R unread slots last at least R >> dry_shift steps -- and every dry_cadence steps at the
+                // end.  The steps are counted where they are counted already: every lane gets the number of steps to the next look
+                // as its budget above kLookBase, and the first lane to use them up (a budget in 1 .. kLookBase; a wave that has
+                // stopped has none above 0) makes the wave look.
+                const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(P.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (cur >= n_in) WOST_DRAIN_STOP();
+                budget = cur >= n_in ? 0 : kLookBase + (int)max((uint32_t)P.dry_cadence, (n_in - cur) >> P.dry_shift);
+            }
         }
     }
     // ---- resolve finished pixels (reference integrator.cu:616-620) -------------------------
@@ -722,6 +761,9 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
         atomicAdd(&st->trav_trips, (unsigned long long)trav_trips);
         atomicAdd(&st->step_trips, (unsigned long long)step_trips);
     }
+#ifdef WOST_DRAIN
+    if (PERSIST && lane == 0) atomicMax(&my_stats(P.stats)->end_max, (unsigned long long)wall_clock64());
+#endif
 #ifdef WOST_TRACK
     {
         uint32_t w[4] = {trk_leaf, trk_ge6, trk_ge10, trk_ge14};
@@ -1225,6 +1267,9 @@ struct wost_context {
                            //   longest expected chain first, until none is left; the rest of the solve runs in rounds): -1 = automatic, 0, 1
     int persist_order = 1; // ... in the order of wost_order.h (0: queue order; comparison runs)
     int few_order = 1;     // the one-launch path of few samples per pixel in that order too (config 2's frame at 1 / 2 / 4 spp: 2.64 -> 2.48, 4.09 -> 3.55, 6.79 -> 5.68 ms)
+    int dry_stop = 1;      // the persistent launch: once its input queue is dry every wave stops at its next look at the cursor (1), or only a
+                           //   wave that needs a refill does (0: the rule until this option existed; comparison runs)
+    int dry_cadence = 4;   // ... a wave looks again after dry_cadence walk steps of its busiest lane (a power of two), less often while the queue is far from dry
     int resident_blocks = 0;  // blocks of a one-launch / persistent launch; 0 = as many as the chip holds (tests: a few blocks drain a small frame)
     // what a persistent launch hands over (run_solve): the pixels expected to need `long_steps` walk steps or more run to their end at
     // once, four lanes to a walker, on a stream of higher priority beside the rounds of the others (0 = none do); the first round
@@ -1564,6 +1609,13 @@ int wost_set_option(wost_handle h, const char *key, double value)
         h->long_thin = (int)value;
     } else if (k == "tail_sort") {
         h->tail_sort = value != 0;
+    } else if (k == "dry_stop") {
+        if (value != 0 && value != 1) return fail(WOST_ERR_INVALID, "dry_stop must be 0 or 1");
+        h->dry_stop = (int)value;
+    } else if (k == "dry_cadence") {
+        const int v = (int)value;
+        if (value != v || v < 1 || v > 1024 || (v & (v - 1))) return fail(WOST_ERR_INVALID, "dry_cadence must be a power of two in 1..1024");
+        h->dry_cadence = v;
     } else if (k == "resident_blocks") {
         if (value < 0 || value > 65535) return fail(WOST_ERR_INVALID, "resident_blocks must be in 0..65535 (0 = what the chip holds)");
         h->resident_blocks = (int)value;
@@ -1835,7 +1887,13 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
         rp.cursor = c->cursor;
         rp.steps_per_round = 0x7fffffff;
         rp.reserve = persist ? 0 : 64;
-        rp.leave_dry = persist ? 1 : 0;
+        rp.leave_dry = persist ? (c->dry_stop ? 2 : 1) : 0;
+        rp.dry_cadence = c->dry_cadence;
+        // How long R unread slots last at least: a pixel takes spp walk steps or more, so the resident lanes claim at most
+        // lanes / spp slots per walk step of a lane.  R >> dry_shift steps with 2^dry_shift >= lanes / spp end before the queue is
+        // dry, and the bound is pessimistic (config 2: 1 536 slots per trip possible, 220 taken).
+        rp.dry_shift = 0;
+        while (rp.dry_shift < 31 && ((uint64_t)std::max(c->settings.spp, 1) << rp.dry_shift) < (uint64_t)p.grid * (unsigned)bs) ++rp.dry_shift;
         if (persist) set_schedule(c, g.ntree, true, rp);
         if (persist ? c->persist_order : c->few_order) {
             if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
@@ -1961,6 +2019,21 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
         sd.max_stack = std::max(sd.max_stack, k.max_stack);
         sd.sp_ge6 += k.sp_ge6; sd.sp_ge10 += k.sp_ge10; sd.sp_ge14 += k.sp_ge14;
     }
+#ifdef WOST_DRAIN
+    {
+        // the drain of the persistent launch, on the 100 MHz clock of wall_clock64(): when the waves stopped on the dry queue,
+        // counted from the first that did, and when the last wave reached the end of the kernel
+        unsigned long long t0 = ~0ull, t1 = 0, n = 0, t_end = 0;
+        for (const StatsDev &k : copies) {
+            if (k.stop_waves) t0 = std::min(t0, ~k.stop_min);
+            t1 = std::max(t1, k.stop_max); n += k.stop_waves; t_end = std::max(t_end, k.end_max);
+        }
+        double sum = 0.0;
+        for (const StatsDev &k : copies) sum += (double)(k.stop_sum - k.stop_waves * t0);
+        if (n) fprintf(stderr, "WOST_DRAIN: %llu waves stopped on the dry queue; after the first: mean %.3f ms, last %.3f ms, end of the kernel %.3f ms\n", n,
+                       sum / (double)n * 1e-5, (double)(t1 - t0) * 1e-5, (double)(t_end - t0) * 1e-5);
+    }
+#endif
 #ifdef WOST_TRACK
     fprintf(stderr, "WOST_TRACK: visits %llu leaf %llu max_stack %llu visits leaving >=6 / >=10 / >=14 entries: %llu / %llu / %llu\n", sd.inner_visits,
             sd.leaf_visits, sd.max_stack, sd.sp_ge6, sd.sp_ge10, sd.sp_ge14);

@@ -379,7 +379,9 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
  * end beside the rounds of the others, the first "long_thin" (2048) of them four to a wave, at most "long_cap" (32768);
  * "tail_sort" (1): the first round after it takes its walkers in the order of their expected remainders; "few_order" (1): the
  * one-launch path of few samples per pixel takes the pixels longest-first too; "resident_blocks": workgroups of those launches
- * (0 = what the chip holds).
+ * (0 = what the chip holds); "dry_stop" (1): once the input queue of the persistent launch is dry every wave stops at its next
+ * look at the queue's cursor and hands its pixels over (0: only a wave that needs a refill does), "dry_cadence" (a power of two
+ * in 1..1024, default 4): near the end of the queue a wave looks again after that many walk steps of its busiest lane.
  * "spp" changes samplesPerPixel of an existing handle (a pixel's first k samples do not depend on
  * the total, so solving with spp = k reproduces the state of a longer solve after k samples: the
  * host mirror uses this for saveSppMetrics frames). */

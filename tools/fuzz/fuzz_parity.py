@@ -92,7 +92,9 @@ def main():
             # the hand-over with long remainders beside the rounds (every pixel long, none, a capped number, all thin or none), sorted or not
             popts = {"persist": 1, "resident_blocks": int(rng.choice([1, 2, 3, 7])), "persist_order": int(rng.choice([0, 1, 1])),
                      "long_steps": int(rng.choice([0, 8, 24, 64, 1024])), "long_cap": int(rng.choice([5, 64, 32768])), "long_thin": int(rng.choice([0, 3, 2048])),
-                     "tail_sort": int(rng.choice([0, 1]))}
+                     "tail_sort": int(rng.choice([0, 1])),
+                     # ... and how a wave learns that the queue is dry: from its own refill only, or from a look at the cursor every few step trips
+                     "dry_stop": int(rng.choice([0, 1, 1])), "dry_cadence": int(rng.choice([1, 2, 4, 16, 1024]))}
             feat.append(str(popts))
             for k, v in popts.items():
                 it.set_option(k, v)
