@@ -825,226 +825,286 @@ static void g3_free(wost3_guided *g)
     delete g;
 }
 
-static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats)
+// ---- the solve driver, in the shape of wost_guided.hip's.  First everything that is fixed for one solve.  g3_plan() fills it once per solve and is the only
+// place that reads the driver's environment switches -- at solve time, not at handle creation: they may change between two solves on one handle.
+struct G3Plan {
+    bool emissive, ntree, source;     // the scene's flags = the template arguments of the walk kernels
+    int stack_words;                  // a lane's traversal stack ...
+    size_t lds, lds_fused;            // ... and the LDS of a 256-lane block: stack columns and task pools; with the fused kernel's exchange area on top
+    // the tree queries of a wave's walkers through its task pools, as in walk3_kernel (WOST3_WAVE=0: one descent per thread; WOST3_POOL_CAP)
+    int pool_cap, pool_offset;
+    int lane_shift; uint64_t resident;      // one walker per 2^lane_shift lanes of the walk kernels (WOST3_G_SHIFT); lanes of all the blocks the chip holds at once
+    unsigned grid_px, grid_pix;       // blocks of the walk kernels; of begin / train-set / resolve (one thread per pixel)
+    uint32_t train_offset; int n_train_pixels, n_train_blocks;      // trainPixelOffset of this solve
+    bool fused;                       // a whole sample in one launch (WOST3_G_FUSED=0 / 1: never / always)
+    G3Net F;                          // the network's fp32 image for it
+};
+
+// prepareSolve (integrator.cu:126): the integrator's host sampler (pcg32, seed of the handle, increment 1)
+static uint32_t g3_host_pcg_next(wost3_guided *g)
 {
-    const auto t_start = std::chrono::high_resolution_clock::now();
-    W3_TRY(hipSetDevice(g->device));
-    wost3_context *c = g->scene;
+    const uint64_t old = g->host_rng;
+    g->host_rng = old * 0x5851f42d4c957f2dULL + 1u;
+    const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
+    return (xs >> rot) | (xs << ((~rot + 1u) & 31));
+}
+
+// The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource).  These are all the walk instantiations there are:
+//   G3_FUSED  g3_fused_kernel<E, T, S>   G3_SEPARATE  g3_separate_kernel<E, T, S>   G3_TAIL  g3_tail_kernel<E, T, S>   G3_SAMPLE  g3_sample_kernel<T>
+enum G3Kernel { G3_FUSED, G3_SEPARATE, G3_TAIL, G3_SAMPLE };
+template <bool E, bool T, bool S>
+static const void *g3_kernel_of(G3Kernel kind)
+{
+    if (kind == G3_FUSED) return reinterpret_cast<const void *>(g3_fused_kernel<E, T, S>);
+    if (kind == G3_SEPARATE) return reinterpret_cast<const void *>(g3_separate_kernel<E, T, S>);
+    return kind == G3_TAIL ? reinterpret_cast<const void *>(g3_tail_kernel<E, T, S>) : reinterpret_cast<const void *>(g3_sample_kernel<T>);
+}
+static const void *g3_kernel(G3Kernel k, const G3Plan &pl)
+{
+    if (pl.emissive && pl.ntree) return pl.source ? g3_kernel_of<true, true, true>(k) : g3_kernel_of<true, true, false>(k);
+    if (pl.emissive) return pl.source ? g3_kernel_of<true, false, true>(k) : g3_kernel_of<true, false, false>(k);
+    if (pl.ntree) return pl.source ? g3_kernel_of<false, true, true>(k) : g3_kernel_of<false, true, false>(k);
+    return pl.source ? g3_kernel_of<false, false, true>(k) : g3_kernel_of<false, false, false>(k);
+}
+
+static G3Plan g3_plan(wost3_guided *g)
+{
+    const wost3_context *c = g->scene;
     const wost3_guided_settings &s = g->s;
     const int N = s.width * s.height;
-    hipStream_t stream = c->stream;
+    G3Plan pl{};
     const int d_levels = c->dm.view.n_tris > 0 ? c->dm.view.levels : 1, n_levels = c->nm.view.n_tris > 0 ? c->nm.view.levels : 1;
-    const int stack_words = 3 * std::max(d_levels, n_levels) + 4;
-    size_t lds = (size_t)stack_words * 256 * sizeof(uint32_t);
-    const bool ntree = c->nm.view.n_tris > WOST_FLAT_MAX, emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive;
-    G3Params P{};
-    // the tree queries of a wave's walkers through its task pools, as in walk3_kernel (WOST3_WAVE=0: one descent per thread)
-    P.pool_cap = (d_levels <= 11 && n_levels <= 11) ? 512 : 0;
-    if (const char *w = std::getenv("WOST3_WAVE")) P.pool_cap = std::atoi(w) != 0 ? P.pool_cap : 0;
-    if (const char *w = std::getenv("WOST3_POOL_CAP")) P.pool_cap = P.pool_cap ? std::min(4096, std::max(96, std::atoi(w))) : 0;
-    P.pool_offset = stack_words * 256;
-    if (P.pool_cap && lds + (size_t)4 * (2 * (size_t)P.pool_cap + kPool3OwnerWords) * sizeof(uint32_t) + 8 > 64 * 1024) P.pool_cap = 0;
-    if (P.pool_cap) lds += (size_t)4 * (2 * (size_t)P.pool_cap + kPool3OwnerWords) * sizeof(uint32_t) + 8;
-    P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.box = g->box; P.src = c->src;
-    const bool has_src = c->src.rgb != nullptr;
-    P.n_pixels = N; P.shard_index = shard_index; P.shard_count = shard_count;
-    P.rng = g->rng; P.sol = g->sol; P.cur_depth = g->cur_depth; P.rec = g->rec; P.state = g->state; P.wx = g->wx; P.wn = g->wn;
-    P.wthp = g->wthp; P.wrb = g->wrb; P.won = g->won; P.whint = g->whint; P.hint0 = g->hint0;
-    // (counters: [1] the queue, [0] and [2] the live lists written at even / odd depths)
-    P.q_pid = g->q_pid; P.q_count = g->q_count + 1; P.net_in = g->net_in; P.net_out = g->net_out; P.stats = g->stats;
-    P.max_train_depth = s.max_train_depth; P.stack_stride = 256;
-    uint32_t train_offset = 0;
-    if (s.train_pixel_stride > 1) {
-        if (s.train_pixel_offset >= 0) train_offset = (uint32_t)s.train_pixel_offset;
-        else {
-            // prepareSolve (integrator.cu:126): one draw of the integrator's host sampler per solve (pcg32, seed of the handle)
-            const uint64_t old = g->host_rng;
-            g->host_rng = old * 0x5851f42d4c957f2dULL + 1u;
-            const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
-            union { uint32_t u; float f; } x;
-            x.u = (((xs >> rot) | (xs << ((~rot + 1u) & 31))) >> 9) | 0x3f800000u;
-            train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
-        }
+    pl.emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive; pl.ntree = c->nm.view.n_tris > WOST3_FLAT_MAX; pl.source = c->src.rgb != nullptr;
+    pl.stack_words = 3 * std::max(d_levels, n_levels) + 4;
+    pl.lds = (size_t)pl.stack_words * 256 * sizeof(uint32_t);
+    pl.pool_cap = (d_levels <= 11 && n_levels <= 11) ? 512 : 0;
+    if (env3_int("WOST3_WAVE", 1, -INT_MAX, INT_MAX) == 0) pl.pool_cap = 0;
+    if (pl.pool_cap) pl.pool_cap = env3_int("WOST3_POOL_CAP", pl.pool_cap, 96, 4096);
+    pl.pool_offset = pl.stack_words * 256;
+    const size_t lds_pools = pool3_lds_bytes(4, pl.pool_cap) + 8;      // (+ 8: g3_pools() starts them at an 8-byte boundary)
+    if (pl.pool_cap && pl.lds + lds_pools > 64 * 1024) pl.pool_cap = 0;
+    if (pl.pool_cap) pl.lds += lds_pools;
+    // prepareSolve (integrator.cu:126): trainPixelOffset = stride <= 1 ? 0 : sampler.get1D() * stride, one draw per solve; a caller-fixed offset (>= 0) overrides the draw
+    if (s.train_pixel_stride > 1 && s.train_pixel_offset >= 0) pl.train_offset = (uint32_t)s.train_pixel_offset;
+    else if (s.train_pixel_stride > 1) {
+        union { uint32_t u; float f; } x;
+        x.u = (g3_host_pcg_next(g) >> 9) | 0x3f800000u;
+        pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
-    P.train_offset = (int32_t)train_offset; P.train_stride = s.train_pixel_stride;
-    const int n_train_pixels = (int)(((size_t)N - train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride);
-    const int n_train_blocks = (n_train_pixels + 255) / 256;
-    W3_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
+    pl.n_train_pixels = (int)(((size_t)N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride); pl.n_train_blocks = (pl.n_train_pixels + 255) / 256;
     // walkers per lane of the walk kernels: spread out while all blocks of the frame are still resident at once (two blocks per CU: the
     // stack columns and the task pools take 46 to 64 KB of LDS).  Round 4 spread as far as 1.5 x three blocks per CU: a frame of 256^2
     // then ran its blocks in two rounds, each as long as its longest walk (the shell scene, 16 samples: 118 -> 89 ms with one round)
-    uint64_t resident = 0;
-    {
-        int n_cus = 256;
-        (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, g->device);
-        resident = (uint64_t)n_cus * 2 * 256;
-        P.lane_shift = 0;
-        while (P.pool_cap > 0 && P.lane_shift < 3 && ((uint64_t)N << (P.lane_shift + 1)) <= resident) ++P.lane_shift;
-        if (const char *w = std::getenv("WOST3_G_SHIFT")) P.lane_shift = std::min(4, std::max(0, std::atoi(w)));
-    }
-    const unsigned grid_px = (unsigned)((((uint64_t)N << P.lane_shift) + 255) / 256);      // walk kernels (begin / train-set / resolve: one thread per pixel)
-    const unsigned grid_pix = (unsigned)((N + 255) / 256);
-    uint32_t launches = 0;
-    uint64_t train_samples = 0;
-    double train_ms = 0.0;
-    const int opt_before = net_optimizer_steps(g->net);
-    const uint64_t net_launches_before = net_launch_count(g->net);
-    bool training = true;
-    float uniform_fraction = s.uniform_fraction_training;
-    int max_guided_depth = s.max_guided_depth_training;
+    int n_cus = 256;
+    (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, g->device);
+    pl.resident = (uint64_t)n_cus * 2 * 256;
+    while (pl.pool_cap > 0 && pl.lane_shift < 3 && ((uint64_t)N << (pl.lane_shift + 1)) <= pl.resident) ++pl.lane_shift;
+    pl.lane_shift = env3_int("WOST3_G_SHIFT", pl.lane_shift, 0, 4);
+    pl.grid_px = (unsigned)((((uint64_t)N << pl.lane_shift) + 255) / 256); pl.grid_pix = (unsigned)((N + 255) / 256);
     // One launch per sample (g3_fused_kernel) when the network offers its fp32 MFMA fragments and the frame has at most 1.5 walkers per
     // resident lane (196 608 on MI355X): such a solve is bound by its launches -- 30 per sample, each as long as its slowest wave.  A
     // larger frame is bound by throughput, and there the launches per depth win: all their kernels run on compacted lists of the walkers
     // that are left, the fused kernel's waves keep their dead lanes.  8 samples, 4 trained, fused / per depth in ms
     // (tools/probes/g3_forms_by_frame.py): icosphere 256^2 25 / 35, 362^2 30 / 44, 512^2 53 / 58, 724^2 120 / 91, 1024^2 212 / 158; shell
-    // 44 / 52, 70 / 82, 132 / 105, 223 / 174, 457 / 301.  WOST3_G_FUSED=0 / 1: never / always.
-    G3Net Fn{};
-    bool fused = false;
-    {
-        F32NetView fv{};
-        const char *env = std::getenv("WOST3_G_FUSED");
-        const bool want = env ? env[0] != '0' : 2 * (uint64_t)N <= 3 * resident;
-        if (want && net_f32_view3(g->net, &fv) == WOST_OK && fv.L.n_levels == 8 && fv.L.n_features == 4 && fv.L.n_out == 41) {
-            Fn.frag = fv.frag; Fn.grid = fv.grid;
-            for (int l = 0; l < 4; ++l) Fn.w_off[l] = fv.L.w_off[l];
-            for (int l = 0; l < 8; ++l) { Fn.scale[l] = fv.L.scale[l]; Fn.res[l] = (uint32_t)fv.L.res[l]; }
-            for (int l = 0; l <= 8; ++l) Fn.off[l] = fv.L.level_off[l];
-            Fn.xch_offset = (int32_t)((lds + 3) / 4);
-            fused = true;
-        }
+    // 44 / 52, 70 / 82, 132 / 105, 223 / 174, 457 / 301.
+    F32NetView fv{};
+    const char *env = std::getenv("WOST3_G_FUSED");
+    const bool want = env ? env[0] != '0' : 2 * (uint64_t)N <= 3 * pl.resident;
+    if (want && net_f32_view3(g->net, &fv) == WOST_OK && fv.L.n_levels == 8 && fv.L.n_features == 4 && fv.L.n_out == 41) {
+        pl.F.frag = fv.frag; pl.F.grid = fv.grid;
+        for (int l = 0; l < 4; ++l) pl.F.w_off[l] = fv.L.w_off[l];
+        for (int l = 0; l < 8; ++l) { pl.F.scale[l] = fv.L.scale[l]; pl.F.res[l] = (uint32_t)fv.L.res[l]; }
+        for (int l = 0; l <= 8; ++l) pl.F.off[l] = fv.L.level_off[l];
+        pl.F.xch_offset = (int32_t)((pl.lds + 3) / 4);
+        pl.fused = true;
     }
-    const size_t lds_fused = ((size_t)Fn.xch_offset + 4 * (size_t)kG3XchWords) * sizeof(uint32_t);
-    if (fused && lds_fused > 48 * 1024) {
-        // the stack columns and pools were sized against 64 KB, the exchange area comes on top (up to 76 KB): ask once, before the
-        // sample loop, and take the launches per depth -- which need no more than `lds` -- when the device refuses
-        hipError_t e = hipSuccess;
-#define G3_ATTR(E, T) (has_src ? hipFuncSetAttribute(reinterpret_cast<const void *>(g3_fused_kernel<E, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused) \
-                               : hipFuncSetAttribute(reinterpret_cast<const void *>(g3_fused_kernel<E, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused))
-        if (ntree) e = emissive ? G3_ATTR(true, true) : G3_ATTR(false, true);
-        else e = emissive ? G3_ATTR(true, false) : G3_ATTR(false, false);
-#undef G3_ATTR
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            fused = false;
-        }
+    pl.lds_fused = ((size_t)pl.F.xch_offset + 4 * (size_t)kG3XchWords) * sizeof(uint32_t);
+    // the stack columns and pools were sized against 64 KB, the exchange area comes on top (up to 76 KB): ask once per solve, for the one
+    // instantiation it launches, and take the launches per depth -- which need no more than `lds` -- when the device refuses
+    if (pl.fused && pl.lds_fused > 48 * 1024 &&
+        hipFuncSetAttribute(g3_kernel(G3_FUSED, pl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_fused) != hipSuccess) {
+        (void)hipGetLastError();
+        pl.fused = false;
     }
-    for (int sample = 0; sample < s.spp; ++sample) {
-        if (sample == s.train_spp_count) {      // :991-996
-            training = false;
-            uniform_fraction = s.uniform_fraction_guiding;
-            max_guided_depth = s.max_guided_depth_guiding;
+    return pl;
+}
+
+// the guiding state of a sample (ctor state integrator.cu:1158-1160, prepareSolve :125-126, the switch :991-996)
+struct GuidePhase { bool training; float uniform_fraction; int max_guided_depth; };
+static GuidePhase phase_at(const wost3_guided_settings &s, int sample)
+{
+    if (sample < s.train_spp_count) return {true, s.uniform_fraction_training, s.max_guided_depth_training};
+    return {false, s.uniform_fraction_guiding, s.max_guided_depth_guiding};
+}
+
+// what the steps of a solve count and hand to each other
+struct G3Run {
+    std::chrono::high_resolution_clock::time_point t_start;
+    uint64_t net_launches_before; int opt_before;      // the network's counters when the solve began
+    uint32_t launches = 0;                  // of this file; the network counts its own
+    double train_ms = 0.0; uint64_t train_samples = 0;
+};
+
+// one launch of a walk kernel, counted (the kernels per depth take P alone; `grid` blocks: the frame's, or the queue's for G3_SAMPLE)
+static void launch_g3(G3Kernel kind, const G3Plan &pl, G3Run &run, unsigned grid, hipStream_t st, G3Params P)
+{
+    void *args[] = {&P, const_cast<G3Net *>(&pl.F)};
+    ++run.launches;
+    (void)hipLaunchKernel(g3_kernel(kind, pl), dim3(grid), dim3(256), args, kind == G3_FUSED ? pl.lds_fused : pl.lds, st);
+}
+
+// The G3Params fields that every launch of a solve shares.  A sample adds its phase (begin_sample), a launch per depth its lists and depth.
+static G3Params g3_base_params(const wost3_guided *g, const G3Plan &pl, int shard_index, int shard_count)
+{
+    const wost3_context *c = g->scene;
+    G3Params P{};
+    P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.box = g->box; P.src = c->src;
+    P.n_pixels = g->s.width * g->s.height; P.shard_index = shard_index; P.shard_count = shard_count;
+    P.rng = g->rng; P.sol = g->sol; P.cur_depth = g->cur_depth; P.rec = g->rec; P.state = g->state; P.wx = g->wx; P.wn = g->wn;
+    P.wthp = g->wthp; P.wrb = g->wrb; P.won = g->won; P.whint = g->whint; P.hint0 = g->hint0;
+    // (counters: [1] the queue, [0] and [2] the live lists written at even / odd depths)
+    P.q_pid = g->q_pid; P.q_count = g->q_count + 1; P.net_in = g->net_in; P.net_out = g->net_out; P.stats = g->stats;
+    P.max_train_depth = g->s.max_train_depth; P.stack_stride = 256;
+    P.train_offset = (int32_t)pl.train_offset; P.train_stride = g->s.train_pixel_stride;
+    P.pool_cap = pl.pool_cap; P.pool_offset = pl.pool_offset; P.lane_shift = pl.lane_shift;
+    return P;
+}
+
+// start of a sample: its phase into P, then the evaluation points (counted)
+static void begin_sample(const G3Plan &pl, G3Run &run, G3Params &P, const GuidePhase &ph, int sample, hipStream_t stream)
+{
+    P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.first_sample = sample == 0 ? 1 : 0;
+    hipLaunchKernelGGL(g3_begin_kernel, dim3(pl.grid_pix), dim3(256), 0, stream, P);
+    ++run.launches;
+}
+
+// one sample in one launch
+static int walk_fused(const G3Plan &pl, G3Run &run, G3Params P, const GuidePhase &ph, int sample, hipStream_t stream)
+{
+    begin_sample(pl, run, P, ph, sample, stream);
+    P.max_guided_depth = ph.max_guided_depth;
+    launch_g3(G3_FUSED, pl, run, pl.grid_px, stream, P);
+    W3_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+// One sample on the one-launch-per-depth path: begin, then per depth separate / network / sample, and the tail once nothing needs
+// the network any more.  No host round trip inside a sample: the launches of a depth are sized for the frame (their kernels read the
+// true length of the queue on the device; a block beyond it ends at once), and from the first depth that needs no network on, ONE
+// launch takes every walker that is left to its end (g3_tail_kernel).  A round trip per depth -- later one every fourth depth -- and the
+// launch pairs of the late depths, whose few walkers cost a launch what its slowest tree query costs, were most of the solve's wall
+// time (about 2000 launches per 16-sample solve).
+static int walk_per_depth(wost3_guided *g, const G3Plan &pl, G3Run &run, G3Params P, const GuidePhase &ph, int sample, hipStream_t stream)
+{
+    const size_t N = (size_t)P.n_pixels;
+    begin_sample(pl, run, P, ph, sample, stream);
+    const uint32_t n_upper = (uint32_t)N;
+    for (int depth = 0; depth < g->s.max_depth; ++depth) {
+        P.depth = depth; P.guiding = depth < ph.max_guided_depth ? 1 : 0;
+        // the walkers that reached this depth: the list the previous depth's sample kernel wrote (depth 0: every pixel)
+        P.l_pid = depth > 0 ? g->l_pid + (size_t)((depth - 1) & 1) * N : nullptr;
+        P.l_count = depth > 0 ? g->q_count + 2 * ((depth - 1) & 1) : nullptr;
+        if (!P.guiding) {
+            // (the tail starts on the compacted list of the walkers that are left and keeps them to their end: launches of a few depths
+            // with the survivors compacted in between were measured and lose -- EXPERIMENTS 23 -- the tail waits for its steps, not for lanes)
+            launch_g3(G3_TAIL, pl, run, pl.grid_px, stream, P);
+            break;
         }
-        P.training = training ? 1 : 0; P.uniform_fraction = uniform_fraction; P.first_sample = sample == 0 ? 1 : 0;
-        hipLaunchKernelGGL(g3_begin_kernel, dim3(grid_pix), dim3(256), 0, stream, P);
-        ++launches;
-        // No host round trip inside a sample: the launches of a depth are sized for the frame (their kernels read the true length of
-        // the queue on the device; a block beyond it ends at once), and from the first depth that needs no network on, ONE launch
-        // takes every walker that is left to its end (g3_tail_kernel).  A round trip per depth -- later one every fourth depth --
-        // and the launch pairs of the late depths, whose few walkers cost a launch what its slowest tree query costs, were most
-        // of the solve's wall time (about 2000 launches per 16-sample solve).
-        const uint32_t n_upper = (uint32_t)N;
-        if (fused) {
-            P.max_guided_depth = max_guided_depth;
-#define G3_FUSED(E, T)                                                                                                                      \
-    do {                                                                                                                                    \
-        auto kfn = has_src ? g3_fused_kernel<E, T, true> : g3_fused_kernel<E, T, false>;                                                      \
-        hipLaunchKernelGGL(kfn, dim3(grid_px), dim3(256), lds_fused, stream, P, Fn);                                                         \
-    } while (0)
-            if (ntree) { if (emissive) G3_FUSED(true, true); else G3_FUSED(false, true); }
-            else       { if (emissive) G3_FUSED(true, false); else G3_FUSED(false, false); }
-#undef G3_FUSED
-            ++launches;
-        }
-        for (int depth = 0; depth < s.max_depth && !fused; ++depth) {
-            P.depth = depth; P.guiding = depth < max_guided_depth ? 1 : 0;
-            // the walkers that reached this depth: the list the previous depth's sample kernel wrote (depth 0: every pixel)
-            P.l_pid = depth > 0 ? g->l_pid + (size_t)((depth - 1) & 1) * N : nullptr;
-            P.l_count = depth > 0 ? g->q_count + 2 * ((depth - 1) & 1) : nullptr;
-            if (!P.guiding) {
-#define G3_LAUNCH(K, E, T)                                                                                              \
-    do {                                                                                                                \
-        if (has_src) hipLaunchKernelGGL((K<E, T, true>), dim3(grid_px), dim3(256), lds, stream, P);                       \
-        else hipLaunchKernelGGL((K<E, T, false>), dim3(grid_px), dim3(256), lds, stream, P);                              \
-    } while (0)
-                // (the tail starts on the compacted list of the walkers that are left and keeps them to their end: launches of a few depths
-                // with the survivors compacted in between were measured and lose -- EXPERIMENTS 23 -- the tail waits for its steps, not for lanes)
-                if (ntree) { if (emissive) G3_LAUNCH(g3_tail_kernel, true, true); else G3_LAUNCH(g3_tail_kernel, false, true); }
-                else       { if (emissive) G3_LAUNCH(g3_tail_kernel, true, false); else G3_LAUNCH(g3_tail_kernel, false, false); }
-                ++launches;
-                break;
-            }
-            // the queue's counter and that of the live list this depth's sample kernel writes: two adjacent words
-            W3_TRY(hipMemsetAsync(g->q_count + (depth & 1), 0, 2 * sizeof(uint32_t), stream));
-            P.l_next_pid = g->l_pid + (size_t)(depth & 1) * N; P.l_next_count = g->q_count + 2 * (depth & 1);
-            if (ntree) { if (emissive) G3_LAUNCH(g3_separate_kernel, true, true); else G3_LAUNCH(g3_separate_kernel, false, true); }
-            else       { if (emissive) G3_LAUNCH(g3_separate_kernel, true, false); else G3_LAUNCH(g3_separate_kernel, false, false); }
-            ++launches;
-            {
-                const int rc = net_inference_dev(g->net, g->net_in, P.q_count, (int)n_upper, g->net_out, true, stream, 0);
-                if (rc != WOST_OK) return rc;
-            }
-            const unsigned grid_q = (unsigned)((((uint64_t)n_upper << P.lane_shift) + 255u) / 256u);
-            if (ntree) hipLaunchKernelGGL((g3_sample_kernel<true>), dim3(grid_q), dim3(256), lds, stream, P);
-            else hipLaunchKernelGGL((g3_sample_kernel<false>), dim3(grid_q), dim3(256), lds, stream, P);
-            ++launches;
-        }
-        W3_TRY(hipGetLastError());
-        if (training) {
-            const auto t0 = std::chrono::high_resolution_clock::now();
-            T3Params T{};
-            T.G = P; T.block_sums = g->block_sums; T.n_train_pixels = n_train_pixels;
-            T.t_x = g->t_x; T.t_dir = g->t_dir; T.t_sol = g->t_sol; T.t_li = g->t_li; T.t_pdf = g->t_pdf; T.t_nrm = g->t_nrm; T.t_onn = g->t_onn;
-            hipLaunchKernelGGL((g3_train_set_kernel<false>), dim3(n_train_blocks), dim3(256), 0, stream, T);
-            hipLaunchKernelGGL(g3_scan_kernel, dim3(1), dim3(1024), 0, stream, g->block_sums, n_train_blocks);
-            hipLaunchKernelGGL((g3_train_set_kernel<true>), dim3(n_train_blocks), dim3(256), 0, stream, T);
-            launches += 3;
-            W3_TRY(hipMemcpyAsync(g->host_word, g->block_sums + n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            W3_TRY(hipStreamSynchronize(stream));
-            const size_t n = g->host_word[0];
-            g->last_train_n = (uint32_t)n;
-            train_samples += n;
-            const size_t bs = (size_t)s.batch_size;
-            size_t n_batches = std::min(n / bs + 1, (size_t)s.batches_per_spp);
-            for (size_t it = 0; it < n_batches; ++it) {
-                if (it * bs > n) break;
-                size_t local = std::min(n - it * bs, bs);
-                local -= local % 128;
-                if (local < (size_t)s.min_batch_size) break;
-                const size_t o = it * bs;
-                float *out = nullptr, *dl = nullptr;
-                int rc = net_forward_train_dev(g->net, g->t_x + 3 * o, (int)local, stream, &out, &dl);
-                if (rc != WOST_OK) return rc;
-                launch_vmm3_loss_gradients(stream, out, g->t_dir + 3 * o, g->t_li + o, g->t_pdf + o, g->t_onn + o, g->t_nrm + 3 * o, (int)local, s.loss_scale,
-                                           dl, (float *)nullptr);
-                ++launches;
-                rc = net_backward_update_dev(g->net, g->t_x + 3 * o, (int)local, s.loss_scale, 1, stream);
-                if (rc != WOST_OK) return rc;
-            }
-            W3_TRY(hipStreamSynchronize(stream));
-            train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-        }
+        // the queue's counter and that of the live list this depth's sample kernel writes: two adjacent words
+        W3_TRY(hipMemsetAsync(g->q_count + (depth & 1), 0, 2 * sizeof(uint32_t), stream));
+        P.l_next_pid = g->l_pid + (size_t)(depth & 1) * N; P.l_next_count = g->q_count + 2 * (depth & 1);
+        launch_g3(G3_SEPARATE, pl, run, pl.grid_px, stream, P);
+        const int rc = net_inference_dev(g->net, g->net_in, P.q_count, (int)n_upper, g->net_out, true, stream, 0);
+        if (rc != WOST_OK) return rc;      // (counted by the network)
+        launch_g3(G3_SAMPLE, pl, run, (unsigned)((((uint64_t)n_upper << pl.lane_shift) + 255u) / 256u), stream, P);
     }
-    hipLaunchKernelGGL(g3_resolve_kernel, dim3((unsigned)((3 * N + 255) / 256)), dim3(256), 0, stream, g->sol, g->state, N, (float)s.spp, g->field);
+    W3_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+// entries of batch `it` of a training set of n: what is left of the set, rounded down to 128; false = no further batch
+static bool batch_len(size_t n, size_t it, const wost3_guided_settings &s, size_t &local)
+{
+    const size_t bs = (size_t)s.batch_size;
+    if (it * bs > n) return false;
+    local = std::min(n - it * bs, bs) / 128 * 128;
+    return local >= (size_t)s.min_batch_size;
+}
+
+// trainStep (:618-668) after a trained sample: the ordered training set (count, scan, scatter), its size read back, then up to
+// batches_per_spp Adam steps.  Two synchronisations; train_ms is host time and includes both.
+static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, const G3Params &P, hipStream_t stream)
+{
+    const wost3_guided_settings &s = g->s;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    T3Params T{};
+    T.G = P; T.block_sums = g->block_sums; T.n_train_pixels = pl.n_train_pixels;
+    T.t_x = g->t_x; T.t_dir = g->t_dir; T.t_sol = g->t_sol; T.t_li = g->t_li; T.t_pdf = g->t_pdf; T.t_nrm = g->t_nrm; T.t_onn = g->t_onn;
+    hipLaunchKernelGGL((g3_train_set_kernel<false>), dim3(pl.n_train_blocks), dim3(256), 0, stream, T);
+    hipLaunchKernelGGL(g3_scan_kernel, dim3(1), dim3(1024), 0, stream, g->block_sums, pl.n_train_blocks);
+    hipLaunchKernelGGL((g3_train_set_kernel<true>), dim3(pl.n_train_blocks), dim3(256), 0, stream, T);
+    run.launches += 3;
+    W3_TRY(hipMemcpyAsync(g->host_word, g->block_sums + pl.n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    W3_TRY(hipStreamSynchronize(stream));
+    const size_t n = g->host_word[0], bs = (size_t)s.batch_size;
+    g->last_train_n = (uint32_t)n; run.train_samples += n;
+    const size_t n_batches = std::min(n / bs + 1, (size_t)s.batches_per_spp);
+    for (size_t it = 0, local = 0; it < n_batches && batch_len(n, it, s, local); ++it) {
+        const size_t o = it * bs;
+        float *out = nullptr, *dl = nullptr;
+        int rc = net_forward_train_dev(g->net, g->t_x + 3 * o, (int)local, stream, &out, &dl);
+        if (rc != WOST_OK) return rc;
+        launch_vmm3_loss_gradients(stream, out, g->t_dir + 3 * o, g->t_li + o, g->t_pdf + o, g->t_onn + o, g->t_nrm + 3 * o, (int)local, s.loss_scale, dl, (float *)nullptr);
+        ++run.launches;      // the loss-gradient kernel; the network's own launches are counted by the network
+        rc = net_backward_update_dev(g->net, g->t_x + 3 * o, (int)local, s.loss_scale, 1, stream);
+        if (rc != WOST_OK) return rc;
+    }
+    W3_TRY(hipStreamSynchronize(stream));
+    run.train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    return WOST_OK;
+}
+
+// resolve (not counted), the copies of the field, the counters folded and the stats
+static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
+{
+    const int N = g->s.width * g->s.height;
+    hipLaunchKernelGGL(g3_resolve_kernel, dim3((unsigned)((3 * N + 255) / 256)), dim3(256), 0, stream, g->sol, g->state, N, (float)g->s.spp, g->field);
     W3_TRY(hipGetLastError());
     if (field_host) W3_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) W3_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     std::vector<GStats3Dev> copies(kStat3Copies);
     W3_TRY(hipMemcpyAsync(copies.data(), g->stats, kStat3Copies * sizeof(GStats3Dev), hipMemcpyDeviceToHost, stream));
     W3_TRY(hipStreamSynchronize(stream));
-    if (stats) {
-        *stats = wost_guided_stats{};
-        for (const GStats3Dev &k : copies) {
-            stats->walk_steps += k.steps; stats->walks_started += k.started; stats->walks_absorbed += k.absorbed;
-            stats->walks_truncated += k.truncated; stats->neumann_hits += k.nhits; stats->guided_steps += k.guided; stats->net_points += k.net_points;
-        }
-        stats->train_samples = train_samples;
-        stats->optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - opt_before);
-        stats->train_ms = train_ms;
-        stats->kernel_launches = launches + (uint32_t)(net_launch_count(g->net) - net_launches_before);
-        stats->reserved = train_offset;
-        stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t_start).count();
+    wost_guided_stats out{};
+    for (const GStats3Dev &k : copies) {
+        out.walk_steps += k.steps; out.walks_started += k.started; out.walks_absorbed += k.absorbed; out.walks_truncated += k.truncated;
+        out.neumann_hits += k.nhits; out.guided_steps += k.guided; out.net_points += k.net_points;
     }
+    out.train_samples = run.train_samples; out.train_ms = run.train_ms;
+    out.optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - run.opt_before); out.reserved = pl.train_offset;
+    out.kernel_launches = run.launches + (uint32_t)(net_launch_count(g->net) - run.net_launches_before);
+    out.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
+    if (stats) *stats = out;
     return WOST_OK;
+}
+
+// the shared driver: field_host (n_pixels*3, may be null) and/or field_dev (device, n_pixels*3)
+static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats)
+{
+    G3Run run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
+    W3_TRY(hipSetDevice(g->device));
+    hipStream_t stream = g->scene->stream;
+    const G3Plan pl = g3_plan(g);      // (the draw of the training-pixel offset: before any launch)
+    W3_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
+    const G3Params P = g3_base_params(g, pl, shard_index, shard_count);
+    for (int sample = 0; sample < g->s.spp; ++sample) {
+        const GuidePhase ph = phase_at(g->s, sample);
+        // both paths give the same results
+        int rc = pl.fused ? walk_fused(pl, run, P, ph, sample, stream) : walk_per_depth(g, pl, run, P, ph, sample, stream);
+        if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, P, stream);
+        if (rc != WOST_OK) return rc;
+    }
+    return finish_guided3(g, pl, run, stream, field_host, field_dev, stats);
 }
 
 extern "C" {

@@ -718,75 +718,82 @@ static void destroy3(wost3_context *c)
     delete c;
 }
 
+// ---- the solve driver.  Everything that is fixed for one solve of n pixels: walk3_plan() fills it once per solve and is the only place that reads the
+// driver's environment switches -- at solve time, not at handle creation: they may change between two solves on one handle.
+struct Walk3Plan {
+    bool emissive, source, ntree, wave;      // walk3_kernel's template arguments; wave: the closest-point queries by the wave as well (WOST3_WAVE=0: the lane machine)
+    // Neumann mesh on the tree: its silhouette and ray queries are answered by the wave as a whole, through task pools in LDS behind the stack
+    // columns.  coop 2: the rays of the source and boundary samples through the pools as well (1: by the lane, 0: the per-lane queries)
+    int coop, pool_cap, ray_slot_trigger, cp_slot_trigger;      // WOST3_COOP / POOL_CAP / RAY_TRIGGER / CP_TRIGGER
+    int wait_weight, trav_burst;             // WOST3_WAIT_WEIGHT / TRAV_BURST
+    int stack_words; size_t lds;             // the stack columns of a block, in words; its LDS, the pools included
+    unsigned grid;                           // persistent blocks (WOST3_BLOCKS_PER_CU, WOST3_MAX_BLOCKS)
+};
+
+static Walk3Plan walk3_plan(const wost3_context *c, int n)
+{
+    const int bs = kWalk3Threads, big = INT_MAX;
+    const int lv = std::max(c->dm.view.n_tris > 0 ? c->dm.view.levels : 1, c->nm.view.n_tris > 0 ? c->nm.view.levels : 1);
+    Walk3Plan pl{};
+    pl.emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive; pl.source = c->src.rgb != nullptr; pl.ntree = c->nm.view.n_tris > WOST3_FLAT_MAX;
+    // a step that answers its Neumann queries on the tree is long and divergent: it waits until eight ninths of the
+    // busy walkers of the wave stand at it (tools/probes/bench3d_shell.py: 1.8x over the Dirichlet-only setting on a 1280-triangle shell)
+    pl.wait_weight = env3_int("WOST3_WAIT_WEIGHT", pl.ntree ? 1 : c->wait_weight, 1, big);
+    pl.trav_burst = env3_int("WOST3_TRAV_BURST", c->trav_burst, 1, big);
+    pl.cp_slot_trigger = env3_int("WOST3_CP_TRIGGER", 64, 1, 64);
+    pl.ray_slot_trigger = env3_int("WOST3_RAY_TRIGGER", 32, 1, 64);
+    pl.pool_cap = env3_int("WOST3_POOL_CAP", 512, 96, 4096);      // (64 roots must fit)
+    pl.coop = pl.ntree ? env3_int("WOST3_COOP", 2, 0, 2) : 0;
+    if (c->nm.view.levels > 11) pl.coop = 0;      // (node and slot indices of a task: 26 bits, 4^(levels + 1) slots)
+    pl.wave = c->dm.view.n_tris > 0 && c->dm.view.levels <= 11 && env3_int("WOST3_WAVE", 1, -big, big) != 0;
+    pl.stack_words = (3 * lv + 1) * bs;
+    pl.lds = (size_t)pl.stack_words * sizeof(uint32_t);
+    const size_t lds_pools = pool3_lds_bytes(bs / 64, pl.pool_cap);
+    if (pl.lds + lds_pools > 64 * 1024) { pl.wave = false; pl.coop = 0; }      // (trees of millions of triangles: the stack columns alone fill the block's LDS)
+    if (pl.wave || pl.coop) pl.lds += lds_pools;
+    // persistent blocks: as many as the chip holds (LDS stacks and registers allow about four per CU), or fewer for small frames
+    int n_cus = 256;
+    (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+    pl.grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * env3_int("WOST3_BLOCKS_PER_CU", 4, 1, big));
+    // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
+    if (const int cap = env3_int("WOST3_MAX_BLOCKS", 0, 0, big)) pl.grid = std::min(pl.grid, (unsigned)cap);
+    return pl;
+}
+
+// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are
+template <bool E, bool S>
+static const void *walk3_kernel_of(bool ntree, bool wave)
+{
+    if (ntree) return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, true, true>) : reinterpret_cast<const void *>(walk3_kernel<E, S, true, false>);
+    return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, false, true>) : reinterpret_cast<const void *>(walk3_kernel<E, S, false, false>);
+}
+static const void *walk3_kernel_of(const Walk3Plan &pl)
+{
+    if (pl.emissive) return pl.source ? walk3_kernel_of<true, true>(pl.ntree, pl.wave) : walk3_kernel_of<true, false>(pl.ntree, pl.wave);
+    return pl.source ? walk3_kernel_of<false, true>(pl.ntree, pl.wave) : walk3_kernel_of<false, false>(pl.ntree, pl.wave);
+}
+
 static int run_solve3(wost3_context *c, int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, float *field_dev,
                       int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
     const auto t0 = std::chrono::high_resolution_clock::now();
     W3_TRY(hipSetDevice(c->device));
     W3_TRY(hipMemsetAsync(c->stats, 0, kStat3Copies * sizeof(Stats3Dev), stream));
-    Walk3Params P{};
-    P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.src = c->src;
-    P.field = field_dev; P.field_base = field_base; P.pixel_begin = pixel_begin; P.pixel_end = pixel_end;
-    P.shard_index = shard_index; P.shard_count = shard_count; P.stats = c->stats;
-    P.cursor = c->cursor;
-    P.tiled = (pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
-    P.wait_weight = c->wait_weight; P.trav_burst = c->trav_burst;
-    // a step that answers its Neumann queries on the tree is long and divergent: it waits until eight ninths of the
-    // busy walkers of the wave stand at it (tools/probes/bench3d_shell.py: 1.8x over the Dirichlet-only setting on a 1280-triangle shell)
-    if (c->nm.view.n_tris > WOST3_FLAT_MAX) P.wait_weight = 1;
-    if (const char *w = std::getenv("WOST3_WAIT_WEIGHT")) P.wait_weight = std::max(1, std::atoi(w));
-    if (const char *w = std::getenv("WOST3_TRAV_BURST")) P.trav_burst = std::max(1, std::atoi(w));
     W3_TRY(hipMemsetAsync(c->cursor, 0, sizeof(uint32_t), stream));
-    const int bs = kWalk3Threads, n = pixel_end - pixel_begin;
-    const int lv = std::max(c->dm.view.n_tris > 0 ? c->dm.view.levels : 1, c->nm.view.n_tris > 0 ? c->nm.view.levels : 1);
-    size_t lds = (size_t)(3 * lv + 1) * bs * sizeof(uint32_t);
+    const int n = pixel_end - pixel_begin;
     float ms = 0.0f;
     if (n > 0) {
+        const Walk3Plan pl = walk3_plan(c, n);
+        Walk3Params P{};
+        P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.src = c->src;
+        P.field = field_dev; P.field_base = field_base; P.pixel_begin = pixel_begin; P.pixel_end = pixel_end;
+        P.shard_index = shard_index; P.shard_count = shard_count; P.stats = c->stats; P.cursor = c->cursor;
+        P.tiled = (pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
+        P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
+        P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
+        void *args[] = {&P};
         W3_TRY(hipEventRecord(c->ev0, stream));
-        const bool emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive;
-        const bool ntree = c->nm.view.n_tris > WOST3_FLAT_MAX;
-        // Neumann mesh on the tree: its silhouette and ray queries are answered by the wave as a whole, through task pools in LDS
-        // behind the stack columns (developer knobs: WOST3_COOP=0 for the per-lane queries, WOST3_POOL_CAP, WOST3_RAY_TRIGGER)
-        P.coop = ntree ? 2 : 0;          // 2: the rays of the source and boundary samples through the pools as well (1: by the lane)
-        P.pool_cap = 512;
-        P.ray_slot_trigger = 32;
-        P.cp_slot_trigger = 64;
-        if (const char *w = std::getenv("WOST3_CP_TRIGGER")) P.cp_slot_trigger = std::min(64, std::max(1, std::atoi(w)));
-        if (const char *w = std::getenv("WOST3_COOP")) P.coop = ntree ? std::max(0, std::min(2, std::atoi(w))) : 0;
-        if (const char *w = std::getenv("WOST3_POOL_CAP")) P.pool_cap = std::min(4096, std::max(96, std::atoi(w)));     // (64 roots must fit)
-        if (const char *w = std::getenv("WOST3_RAY_TRIGGER")) P.ray_slot_trigger = std::min(64, std::max(1, std::atoi(w)));
-        if (c->nm.view.levels > 11) P.coop = 0;      // (node and slot indices of a task: 26 bits, 4^(levels + 1) slots)
-        P.stack_words = (3 * lv + 1) * bs;
-        // the closest-point queries by the wave as well (WOST3_WAVE=0: the lane machine)
-        bool wave = c->dm.view.n_tris > 0 && c->dm.view.levels <= 11;
-        if (const char *w = std::getenv("WOST3_WAVE")) wave = wave && std::atoi(w) != 0;
-        const size_t lds_pools = (size_t)(bs / 64) * (2 * (size_t)P.pool_cap + kPool3OwnerWords) * sizeof(uint32_t);
-        if (lds + lds_pools > 64 * 1024) {      // (trees of millions of triangles: the stack columns alone fill the block's LDS)
-            wave = false;
-            P.coop = 0;
-        }
-        if (wave || P.coop) lds += lds_pools;
-        auto kfn = ntree ? (c->src.rgb ? (emissive ? walk3_kernel<true, true, true> : walk3_kernel<false, true, true>)
-                                       : (emissive ? walk3_kernel<true, false, true> : walk3_kernel<false, false, true>))
-                         : (c->src.rgb ? (emissive ? walk3_kernel<true, true, false> : walk3_kernel<false, true, false>)
-                                       : (emissive ? walk3_kernel<true, false, false> : walk3_kernel<false, false, false>));
-        if (wave)
-            kfn = ntree ? (c->src.rgb ? (emissive ? walk3_kernel<true, true, true, true> : walk3_kernel<false, true, true, true>)
-                                      : (emissive ? walk3_kernel<true, false, true, true> : walk3_kernel<false, false, true, true>))
-                        : (c->src.rgb ? (emissive ? walk3_kernel<true, true, false, true> : walk3_kernel<false, true, false, true>)
-                                      : (emissive ? walk3_kernel<true, false, false, true> : walk3_kernel<false, false, false, true>));
-        // persistent blocks: as many as the chip holds (LDS stacks and registers allow about four per CU), or fewer for small frames
-        int n_cus = 256;
-        (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        int per_cu = 4;
-        if (const char *w = std::getenv("WOST3_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(w));
-        unsigned grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * per_cu);
-        // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
-        if (const char *w = std::getenv("WOST3_MAX_BLOCKS")) {
-            const int cap = std::atoi(w);
-            if (cap >= 1) grid = std::min(grid, (unsigned)cap);
-        }
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(bs), lds, stream, P);
+        (void)hipLaunchKernel(walk3_kernel_of(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
         W3_TRY(hipGetLastError());
         W3_TRY(hipEventRecord(c->ev1, stream));
     }

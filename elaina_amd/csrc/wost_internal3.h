@@ -3,6 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -41,6 +44,15 @@ static hipError_t upload3(std::vector<void *> &allocs, const T *src, size_t coun
     allocs.push_back(p);
     *dst = reinterpret_cast<const T *>(p);
     return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// LDS bytes of the task pools (WavePool3) of a block of `waves` waves: per wave two pools of pool_cap tasks and the owners' words
+inline size_t pool3_lds_bytes(int waves, int pool_cap) { return (size_t)waves * (2 * (size_t)pool_cap + kPool3OwnerWords) * sizeof(uint32_t); }
+// an environment switch of the 3-D drivers as an integer clamped to lo..hi; `fallback` when it is not set
+inline int env3_int(const char *name, int fallback, int lo, int hi)
+{
+    const char *w = std::getenv(name);
+    return w ? std::min(hi, std::max(lo, std::atoi(w))) : fallback;
 }
 
 }  // namespace wost

@@ -339,6 +339,10 @@ FUSED_MODES = [({}, "one launch per sample, walkers spread over the lanes (a sma
                ({"WOST3_G_SHIFT": "0", "WOST3_G_FUSED": "1"}, "one launch per sample, 64 walkers per wave: four units of the matrices at once"),
                ({"WOST3_G_FUSED": "0"}, "the launches per depth"),
                ({"WOST3_G_FUSED": "0", "WOST3_G_SHIFT": "0"}, "the launches per depth, 64 walkers per wave")]
+# the walk kernels' tree queries without the waves' task pools (the path of trees deeper than 11 levels), and with the smallest pools
+POOL_MODES = [({"WOST3_WAVE": "0"}, "one launch per sample, one descent per lane"),
+              ({"WOST3_WAVE": "0", "WOST3_G_FUSED": "0"}, "the launches per depth, one descent per lane"),
+              ({"WOST3_POOL_CAP": "96"}, "one launch per sample, task pools of 96 entries")]
 
 
 @pytest.mark.gpu
@@ -346,12 +350,13 @@ def test_gpu_guided3_reference_network_fused_and_per_depth(orc):
     """the reference's eight-level network (the shape the MFMA kernels and g3_fused_kernel cover; the tests above use four levels
     = the scalar kernels and the launches per depth): a frozen random network and a trained solve with an emissive Neumann face,
     each through the fused kernel (spread walkers: one unit; 64 walkers per wave: four units) and through the launches per
-    depth -- all equal to the oracle bit for bit, and the fused solves take a few launches per sample"""
+    depth -- all equal to the oracle bit for bit, and the fused solves take a few launches per sample; the frozen network also
+    with one tree descent per lane in place of the waves' task pools (WOST3_WAVE=0) and with the smallest pools"""
     cfg = default_net_config3()
     sd = mixed_cube()
     p = _rand_params3(orc, cfg, seed=3, wscale=0.3, gscale=1.0)
     ref = None
-    for env, what in FUSED_MODES:
+    for env, what in FUSED_MODES + POOL_MODES:
         gi, ref = _with_env(env, lambda: _gpu_and_oracle3(orc, sd, 40, 32, 3, 48, 0, params=p, cfg=cfg, ref=ref))
         assert np.array_equal(gi.solution, ref["field"]), (what, float(np.abs(gi.solution - ref["field"]).max()))
         for k in COUNTERS:
@@ -370,6 +375,47 @@ def test_gpu_guided3_reference_network_fused_and_per_depth(orc):
         assert np.array_equal(gi.solution, ref["field"]), what
         assert np.array_equal(gi.network.params(), ref["params"]), what
         gi.close()
+
+
+def _host_sampler_offsets3(seed, stride, n):
+    """the handle's host sampler restated: pcg32 from state 0x853c49e6748fea9b ^ seed with increment 1, one get1D() * stride per solve"""
+    mask, state, out = (1 << 64) - 1, 0x853c49e6748fea9b ^ seed, []
+    for _ in range(n):
+        old, state = state, (state * 0x5851f42d4c957f2d + 1) & mask
+        xs, rot = (((old >> 18) ^ old) >> 27) & 0xffffffff, old >> 59
+        r = ((xs >> rot) | (xs << ((-rot) & 31))) & 0xffffffff
+        f = np.array([(r >> 9) | 0x3f800000], np.uint32).view(np.float32)[0] - np.float32(1.0)
+        out.append(int(f * np.float32(stride)))
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_train_pixel_offset_is_drawn_per_solve_3d(orc):
+    """trainPixelStride > 1 with the offset left at -1: prepareSolve draws trainPixelOffset = get1D() * stride from the handle's host
+    sampler (integrator.cu:126), one draw per solve -- the two draws of this handle differ (0, then 1), so one draw per handle would
+    show.  stats.reserved reports the offset, and each solve equals the oracle's with that offset fixed, bit for bit."""
+    from elaina_amd.guided import GuidedIntegratorSettings
+    from elaina_amd.integrator3d import GuidedIntegrator3, Problem3
+    sd, cfg = mixed_cube(), _cfg()
+    w, h, spp, depth, stride = 36, 28, 4, 48, 3
+    expect = _host_sampler_offsets3(7, stride, 2)
+    assert expect == [0, 1]
+    st = GuidedIntegratorSettings(frameSize=(w, h), samplesPerPixel=spp, trainSppCount=2, maxWalkingDepth=depth, epsilonShell=EPS,
+                                  batchSize=512, minBatchSize=128, trainPixelStride=stride)          # trainPixelOffset = -1: drawn
+    gi = GuidedIntegrator3(Problem3.from_dict(sd), st, AABB3, network_config=_hip_cfg(cfg), seed=7)
+    p0 = gi.network.params()
+    for k in range(2):
+        gi.network.set_params(p0)                    # same starting network, the next draw of the host sampler
+        gi.solve()
+        assert gi.last_stats["reserved"] == expect[k]
+        gs = guided_settings3(w, h, spp, depth, EPS, AABB3[0], AABB3[1], train_spp_count=2, batch_size=512, min_batch_size=128,
+                              train_pixel_stride=stride, train_pixel_offset=expect[k])
+        trained = p0.copy()
+        ref = orc.solve_guided3(sd, gs, cfg, trained, threads=16)
+        assert gi.last_stats["train_samples"] == ref["train_samples"] and gi.last_stats["optimizer_steps"] == ref["optimizer_steps"] > 0
+        assert np.array_equal(gi.solution, ref["field"]), float(np.abs(gi.solution - ref["field"]).max())
+        assert np.array_equal(gi.network.params(), trained)
+    gi.close()
 
 
 @pytest.mark.gpu
