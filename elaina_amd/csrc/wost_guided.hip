@@ -36,14 +36,14 @@
 #include "../../include/wost.h"
 #include "wost_internal.h"
 #include "wost_order.h"
+#include "wost_train.h"
 #include "wost_net_device.h"
 #include "wost_vmm_device.h"
 #include "wost_walk.h"
 
 namespace wost {
 
-constexpr int kMaxTrainDepth = 4;     // reference parameters.h:7 (record slots per pixel)
-constexpr int kRecFields = 12;        // sol rgb, pos xy, dir xy, pdf, thp, normal xy, onNeumann
+using Rec2 = Rec<2>;                  // the fields of a training record (wost_train.h)
 constexpr uint32_t kDead = 0xffffffffu;
 constexpr uint32_t kOnNeumann = 0x80000000u;
 
@@ -218,7 +218,7 @@ __device__ __forceinline__ bool is_training_pixel(const GParams &P, uint32_t pid
 // `rp` = record column of the pixel: pid + (record set of the sample) * n_pixels
 __device__ __forceinline__ float &rec_at(const GParams &P, int slot, int field, uint32_t rp)
 {
-    return P.rec[((size_t)slot * kRecFields + field) * P.rec_ld + rp];
+    return P.rec[((size_t)slot * Rec2::kFields + field) * P.rec_ld + rp];
 }
 
 // recordSolution / recordSourceContribution (reference guided.h:48-68): add to every record
@@ -367,13 +367,13 @@ __device__ __forceinline__ void record_vertex(const GParams &P, uint32_t rp, flo
 {
     const uint32_t d = P.cur_depth[rp];
     if (d >= (uint32_t)kMaxTrainDepth) return;
-    rec_at(P, d, 0, rp) = 0.0f; rec_at(P, d, 1, rp) = 0.0f; rec_at(P, d, 2, rp) = 0.0f;
-    rec_at(P, d, 3, rp) = x; rec_at(P, d, 4, rp) = y;
-    rec_at(P, d, 5, rp) = dirx; rec_at(P, d, 6, rp) = diry;
-    rec_at(P, d, 7, rp) = pdf;
-    rec_at(P, d, 8, rp) = thp;
-    rec_at(P, d, 9, rp) = nx; rec_at(P, d, 10, rp) = ny;
-    rec_at(P, d, 11, rp) = on_n ? 1.0f : 0.0f;
+    rec_at(P, d, Rec2::kSol, rp) = 0.0f; rec_at(P, d, Rec2::kSol + 1, rp) = 0.0f; rec_at(P, d, Rec2::kSol + 2, rp) = 0.0f;
+    rec_at(P, d, Rec2::kPos, rp) = x; rec_at(P, d, Rec2::kPos + 1, rp) = y;
+    rec_at(P, d, Rec2::kDir, rp) = dirx; rec_at(P, d, Rec2::kDir + 1, rp) = diry;
+    rec_at(P, d, Rec2::kPdf, rp) = pdf;
+    rec_at(P, d, Rec2::kThp, rp) = thp;
+    rec_at(P, d, Rec2::kNrm, rp) = nx; rec_at(P, d, Rec2::kNrm + 1, rp) = ny;
+    rec_at(P, d, Rec2::kOnN, rp) = on_n ? 1.0f : 0.0f;
     P.cur_depth[rp] = d + 1;
 }
 
@@ -1021,123 +1021,6 @@ __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GPar
     }
 }
 
-// ---- training set: generate_training_data (reference train.h:423-471), ordered ----------------
-struct TrainSet {
-    float *xy, *dir, *sol, *li, *pdf, *nrm;
-    uint8_t *onn;
-};
-
-struct TParams {
-    GAabb box;
-    const uint32_t *cur_depth;
-    const float *rec;          // column 0 of the record set to gather
-    size_t rec_ld;
-    int32_t n_pixels;
-    uint32_t train_offset, train_stride;
-    int32_t n_train_pixels;
-    uint32_t *block_sums;     // [n_blocks + 1]
-    TrainSet ts;
-};
-
-__device__ __forceinline__ bool record_valid(const TParams &T, int slot, uint32_t pid, float out[kRecFields])
-{
-    for (int f = 0; f < kRecFields; ++f) out[f] = T.rec[((size_t)slot * kRecFields + f) * T.rec_ld + pid];
-    if (!aabb_contains(T.box, out[3], out[4])) return false;
-    // |solution / thp| per channel, 0 where the throughput vanished
-    for (int c = 0; c < 3; ++c) {
-        float v = 0.0f;
-        if (fabsf(out[8]) > 1e-5f) v = out[c] / out[8];
-        out[c] = fabsf(v);
-    }
-    float ix, iy;
-    normalize_coord(T.box, out[3], out[4], ix, iy);
-    const bool bad = isnan(ix) || isnan(iy) || isnan(out[5]) || isnan(out[6]) || isnan(out[7]) || out[7] == 0 ||
-                     isnan(out[0]) || isnan(out[1]) || isnan(out[2]);
-    out[3] = ix;
-    out[4] = iy;
-    return !bad;
-}
-
-// pass 1: samples per training pixel -> per-block sums; pass 3: scatter at the scanned offsets
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void train_set_kernel(TParams T)
-{
-    __shared__ uint32_t sh[256];
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    uint32_t cnt = 0;
-    uint32_t pid = 0, depth = 0;
-    if (t < T.n_train_pixels) {
-        pid = T.train_offset + (uint32_t)t * T.train_stride;
-        depth = min(T.cur_depth[pid], (uint32_t)kMaxTrainDepth);
-    }
-    float r[kMaxTrainDepth][kRecFields];
-    bool ok[kMaxTrainDepth];
-#pragma unroll
-    for (int k = 0; k < kMaxTrainDepth; ++k) {
-        ok[k] = (uint32_t)k < depth && record_valid(T, k, pid, r[k]);
-        cnt += ok[k] ? 1u : 0u;
-    }
-    // block-level exclusive scan of cnt
-    sh[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        uint32_t v = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if (!SCATTER) {
-        if (threadIdx.x == 255) T.block_sums[blockIdx.x] = sh[255];
-        return;
-    }
-    uint32_t o = T.block_sums[blockIdx.x] + sh[threadIdx.x] - cnt;
-#pragma unroll
-    for (int k = 0; k < kMaxTrainDepth; ++k) {
-        if (!ok[k]) continue;
-        const float *q = r[k];
-        T.ts.xy[2 * (size_t)o] = q[3]; T.ts.xy[2 * (size_t)o + 1] = q[4];
-        T.ts.dir[2 * (size_t)o] = q[5]; T.ts.dir[2 * (size_t)o + 1] = q[6];
-        T.ts.sol[3 * (size_t)o] = q[0]; T.ts.sol[3 * (size_t)o + 1] = q[1]; T.ts.sol[3 * (size_t)o + 2] = q[2];
-        T.ts.li[o] = (q[0] + q[1] + q[2]) / 3.0f;      // Color::mean() (train.h:519)
-        T.ts.pdf[o] = q[7];
-        T.ts.nrm[2 * (size_t)o] = q[9]; T.ts.nrm[2 * (size_t)o + 1] = q[10];
-        T.ts.onn[o] = q[11] != 0.0f ? 1 : 0;
-        ++o;
-    }
-}
-
-// pass 2: exclusive scan of the block sums by one block; block_sums[n_blocks] = total
-__global__ __launch_bounds__(256) void train_scan_kernel(uint32_t *block_sums, int n_blocks)
-{
-    __shared__ uint32_t sh[256];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n_blocks; base += 256) {
-        const int i = base + threadIdx.x;
-        const uint32_t v = i < n_blocks ? block_sums[i] : 0u;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            uint32_t a = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0u;
-            __syncthreads();
-            sh[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (i < n_blocks) block_sums[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[n_blocks] = carry;
-}
-
-__global__ void resolve_kernel(const float *sol, int n, float spp, float *field)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 3 * n) field[i] = sol[i] / spp;
-}
-
 }  // namespace wost
 
 using namespace wost;
@@ -1196,33 +1079,13 @@ struct wost_guided {
     EventRing train_events;               // device time of the training passes in that mode
 };
 
-static uint32_t host_pcg_next(wost_guided *g)
-{
-    const uint64_t old = g->host_rng_state;
-    g->host_rng_state = old * WOST_PCG32_MULT + g->host_rng_inc;
-    const uint32_t xorshifted = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
-    return (xorshifted >> rot) | (xorshifted << ((~rot + 1u) & 31));
-}
-
 #define G_TRY(expr)                                                                                      \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
         if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-template <class T>
-static hipError_t galloc(wost_guided *g, T **p, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) {
-        g->allocs.push_back(v);
-        *p = reinterpret_cast<T *>(v);
-    }
-    return e;
-}
-
-// release one buffer of galloc before the handle goes (a buffer that is replaced by a larger one)
+// release one buffer of device_alloc before the handle goes (a buffer that is replaced by a larger one)
 static void gfree_one(wost_guided *g, void *p)
 {
     if (!p) return;
@@ -1299,13 +1162,13 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
         b.ex = hix - lox; b.ey = hiy - loy;
     }
     hipError_t e = hipSuccess;
-#define GA(ptr, count) if (e == hipSuccess) e = galloc(g, &(ptr), (count))
+#define GA(ptr, count) if (e == hipSuccess) e = device_alloc(g->allocs, &(ptr), (count))
     for (int k = 0; k < 2; ++k) {
         GA(g->q[k].pid, N); GA(g->q[k].x, N); GA(g->q[k].y, N); GA(g->q[k].thp, N); GA(g->q[k].nx, N); GA(g->q[k].ny, N);
         GA(g->q[k].rb, N); GA(g->q[k].hint, N);
     }
     GA(g->counts, 2); GA(g->rng, N); GA(g->sol, 3 * N); GA(g->field, 3 * N);
-    GA(g->rec, (size_t)kMaxTrainDepth * kRecFields * N);
+    GA(g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * N);
     GA(g->net_in, 2 * N); GA(g->net_out, 33 * N); GA(g->cur_depth, N); GA(g->hint0, N); GA(g->stats, kStatCopies);
     GA(g->dbg, 4); GA(g->d0_d2, N); GA(g->cursor, 1); GA(g->pstate, N);
     // sized for offset 0 (the largest set); the offset of a solve may be drawn per solve (run_guided)
@@ -1315,14 +1178,12 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
     // (reference integrator/guided/integrator.cu:1134, core/sampler.h:20-27, core/config.h:7)
     g->host_rng_inc = (1ull << 1u) | 1ull;
     g->host_rng_state = 0;
-    (void)host_pcg_next(g);
+    (void)host_pcg_next(g->host_rng_state, g->host_rng_inc);
     g->host_rng_state += 42ull;
-    (void)host_pcg_next(g);
+    (void)host_pcg_next(g->host_rng_state, g->host_rng_inc);
     GA(g->block_sums, (size_t)g->n_train_blocks + 1);
-    const size_t M = (size_t)g->n_train_pixels * kMaxTrainDepth;
-    GA(g->ts.xy, 2 * M); GA(g->ts.dir, 2 * M); GA(g->ts.sol, 3 * M); GA(g->ts.li, M); GA(g->ts.pdf, M); GA(g->ts.nrm, 2 * M);
-    GA(g->ts.onn, M);
 #undef GA
+    if (e == hipSuccess) e = alloc_train_set(g->allocs, g->ts, 2, (size_t)g->n_train_pixels * kMaxTrainDepth);
     if (e == hipSuccess) e = hipHostMalloc((void **)&g->host_counts, 32 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipHostMalloc((void **)&g->depth_counts, (size_t)std::max(1, s->max_depth) * sizeof(uint32_t));
     for (int d = 0; e == hipSuccess && d < s->max_depth; ++d) {
@@ -1414,15 +1275,7 @@ int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, fl
     if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
     G_TRY(hipSetDevice(h->device));
     *n = (int32_t)h->last_train_n;
-    const size_t m = std::min<size_t>(h->last_train_n, (size_t)capacity);
-    if (m == 0) return WOST_OK;
-    if (xy) G_TRY(hipMemcpy(xy, h->ts.xy, m * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir) G_TRY(hipMemcpy(dir, h->ts.dir, m * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (solution) G_TRY(hipMemcpy(solution, h->ts.sol, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir_pdf) G_TRY(hipMemcpy(dir_pdf, h->ts.pdf, m * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal) G_TRY(hipMemcpy(normal, h->ts.nrm, m * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (on_neumann) G_TRY(hipMemcpy(on_neumann, h->ts.onn, m, hipMemcpyDeviceToHost));
-    return WOST_OK;
+    return copy_train_set(h->ts, 2, std::min<size_t>(h->last_train_n, (size_t)capacity), xy, dir, solution, dir_pdf, normal, on_neumann);
 }
 
 }  // extern "C"
@@ -1450,14 +1303,6 @@ struct GuidedPlan {
     int n_trained, group;
     bool reordered;
 };
-
-// the guiding state of a sample (ctor state integrator.cu:1158-1160, prepareSolve :125-126, the switch :991-996)
-struct GuidePhase { bool training; float uniform_fraction; int max_guided_depth; };
-static GuidePhase phase_at(const wost_guided_settings &s, int sample)
-{
-    if (sample < s.train_spp_count) return {true, s.uniform_fraction_training, s.max_guided_depth_training};
-    return {false, s.uniform_fraction_guiding, s.max_guided_depth_guiding};
-}
 
 // what the steps of a solve count and hand to each other
 struct GuidedRun {
@@ -1530,7 +1375,7 @@ static GuidedPlan guided_plan(wost_guided *g)
     if (s.train_pixel_stride > 1 && s.train_pixel_offset >= 0) pl.train_offset = (uint32_t)s.train_pixel_offset;
     else if (s.train_pixel_stride > 1) {
         union { uint32_t u; float f; } x;
-        x.u = (host_pcg_next(g) >> 9) | 0x3f800000u;
+        x.u = (host_pcg_next(g->host_rng_state, g->host_rng_inc) >> 9) | 0x3f800000u;
         pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
     g->last_train_offset = pl.train_offset;
@@ -1664,62 +1509,19 @@ static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GP
 static int enqueue_train_set(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, hipStream_t st, int j, const TrainSet &ts)
 {
     const size_t N = g->n_pixels;
-    TParams T{};
-    T.box = g->box; T.cur_depth = g->cur_depth + (size_t)j * N; T.rec = g->rec + (size_t)j * N; T.rec_ld = N * (size_t)g->rec_sets; T.n_pixels = (int)N;
+    const GAabb &b = g->box;
+    TrainSetParams<2> T{{b.minx, b.miny}, {b.maxx, b.maxy}, {b.cx, b.cy}, {b.ex, b.ey}};
+    T.rec = g->rec + (size_t)j * N; T.rec_ld = N * (size_t)g->rec_sets; T.cur_depth = g->cur_depth + (size_t)j * N;
     T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->gs.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
-    hipLaunchKernelGGL((train_set_kernel<false>), dim3(pl.n_train_blocks), dim3(256), 0, st, T);
-    hipLaunchKernelGGL(train_scan_kernel, dim3(1), dim3(256), 0, st, g->block_sums, pl.n_train_blocks);
-    hipLaunchKernelGGL((train_set_kernel<true>), dim3(pl.n_train_blocks), dim3(256), 0, st, T);
     run.launches += 3;
-    G_TRY(hipGetLastError());
-    G_TRY(hipMemcpyAsync(g->host_counts + 1 + j, g->block_sums + pl.n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    return WOST_OK;
-}
-
-// entries of batch `it` of a training set of n: what is left of the set, rounded down to 128; 0 = no further batch
-static size_t batch_len(size_t n, size_t it, const wost_guided_settings &s)
-{
-    const size_t bs = (size_t)s.batch_size;
-    if (it * bs > n) return 0;
-    const size_t local = std::min(n - it * bs, bs) / 128 * 128;
-    return local < (size_t)s.min_batch_size ? 0 : local;
+    return wost::enqueue_train_set(T, pl.n_train_blocks, st, g->host_counts + 1 + j);
 }
 
 // trainStep (:618-668): up to batches_per_spp Adam steps on the n entries of the training set `ts`
 static int train_passes(wost_guided *g, GuidedRun &run, size_t n, hipStream_t st, const TrainSet &ts)
 {
-    const wost_guided_settings &s = g->gs;
     g->last_train_n = (uint32_t)n; run.train_samples += n;
-    const size_t bs = (size_t)s.batch_size;
-    size_t n_batches = std::min<size_t>(n / bs + 1, (size_t)s.batches_per_spp);
-    if (g->sync) {
-        // shared network: every rank must take the same number of steps -- the smallest number of full batches any rank has
-        int64_t vmin = 0;
-        while ((size_t)vmin < n_batches && batch_len(n, (size_t)vmin, s)) ++vmin;
-        if (g->sync(g->sync_user, WOST_SYNC_MIN_I64_HOST, &vmin, 1) != 0) return set_error(WOST_ERR_DEVICE, "sync callback failed (batch count)");
-        n_batches = (size_t)std::max<int64_t>(vmin, 0);
-    }
-    for (size_t it = 0; it < n_batches; ++it) {
-        const size_t local = batch_len(n, it, s), o = it * bs;
-        if (!local) break;
-        float *raw = nullptr, *dl = nullptr;
-        int rc = net_forward_train_dev(g->net, ts.xy + 2 * o, (int)local, st, &raw, &dl);
-        if (rc != WOST_OK) return rc;
-        launch_vmm_loss_gradients(st, raw, ts.dir + 2 * o, ts.li + o, ts.pdf + o, ts.onn + o, ts.nrm + 2 * o, (int)local, s.loss_scale, dl, nullptr);
-        ++run.launches;      // the loss-gradient kernel; the network's own launches are counted by the network
-        rc = net_backward_update_dev(g->net, ts.xy + 2 * o, (int)local, s.loss_scale, g->sync ? 0 : 1, st);
-        if (rc != WOST_OK) return rc;
-        if (!g->sync) continue;
-        // sum the fixed-point gradients of all ranks (integer sums: the same network everywhere, bit for bit), then step
-        G_TRY(hipStreamSynchronize(st));
-        uint64_t count = 0;
-        void *gbuf = net_gradient_buffer(g->net, &count);
-        if (g->sync(g->sync_user, WOST_SYNC_SUM_I64_DEVICE, gbuf, count) != 0)
-            return set_error(WOST_ERR_DEVICE, "sync callback failed (gradient all-reduce)");
-        rc = net_apply_update_dev(g->net, s.loss_scale, st);
-        if (rc != WOST_OK) return rc;
-    }
-    return WOST_OK;
+    return wost::train_passes<2>(g->net, ts, n, train_schedule(g->gs), TrainSync{g->sync, g->sync_user}, st, run.launches);
 }
 
 // one record set per sample of a training launch (201 MB each at 1024^2: sized for 288 GB of HBM)
@@ -1731,8 +1533,8 @@ static int grow_record_sets(wost_guided *g, int sets, hipStream_t stream)
     G_TRY(hipStreamSynchronize(stream));
     gfree_one(g, g->rec); gfree_one(g, g->cur_depth);
     g->rec = nullptr; g->cur_depth = nullptr; g->rec_sets = 0;
-    G_TRY(galloc(g, &g->rec, (size_t)kMaxTrainDepth * kRecFields * g->n_pixels * sets));
-    G_TRY(galloc(g, &g->cur_depth, g->n_pixels * sets));
+    G_TRY(device_alloc(g->allocs, &g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * g->n_pixels * sets));
+    G_TRY(device_alloc(g->allocs, &g->cur_depth, g->n_pixels * sets));
     g->rec_sets = sets;
     return WOST_OK;
 }
@@ -1758,14 +1560,12 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
         G_TRY(hipEventCreateWithFlags(&g->ev_ts, hipEventDisableTiming));
         for (hipEvent_t &e : g->ev_train) G_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         G_TRY(g->train_events.init(64));
-        for (uint8_t *&p : g->snap) G_TRY(galloc(g, &p, snap_bytes));
+        for (uint8_t *&p : g->snap) G_TRY(device_alloc(g->allocs, &p, snap_bytes));
     }
     // the passes of a group read their training sets while the next group walks over the record sets: one array set per sample
     while ((int)g->ts_more.size() + 1 < pl.group) {
         TrainSet t{};
-        const size_t M = (size_t)g->n_train_pixels * kMaxTrainDepth;
-        G_TRY(galloc(g, &t.xy, 2 * M)); G_TRY(galloc(g, &t.dir, 2 * M)); G_TRY(galloc(g, &t.sol, 3 * M)); G_TRY(galloc(g, &t.li, M));
-        G_TRY(galloc(g, &t.pdf, M)); G_TRY(galloc(g, &t.nrm, 2 * M)); G_TRY(galloc(g, &t.onn, M));
+        G_TRY(alloc_train_set(g->allocs, t, 2, (size_t)g->n_train_pixels * kMaxTrainDepth));
         g->ts_more.push_back(t);
     }
     hipStream_t B = g->train_stream;
@@ -1839,7 +1639,7 @@ static int emit_frame(wost_guided *g, const GuidedRun &run, hipStream_t stream, 
 {
     const int N = (int)g->n_pixels, due = frame_due(g, sample);
     if (!due) return WOST_OK;
-    hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)(sample + 1), g->field);
+    launch_resolve(g->sol, N, (float)(sample + 1), g->field, stream);
     std::vector<float> frame((size_t)N * 3);
     G_TRY(hipMemcpyAsync(frame.data(), g->field, frame.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
     G_TRY(hipStreamSynchronize(stream));
@@ -1932,7 +1732,7 @@ static int train_after_walk(wost_guided *g, const GuidedPlan &pl, GuidedRun &run
 static int finish_guided(wost_guided *g, const GuidedRun &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
 {
     const int N = (int)g->n_pixels;
-    hipLaunchKernelGGL(resolve_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, g->sol, N, (float)g->gs.spp, g->field);
+    launch_resolve(g->sol, N, (float)g->gs.spp, g->field, stream);
     G_TRY(hipGetLastError());
     if (field_host) G_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) G_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));

@@ -14,6 +14,7 @@
 #include "../../include/wost.h"
 #include "wost_internal3.h"
 #include "wost_net_device.h"
+#include "wost_train.h"
 #include "wost_vmm3_device.h"
 
 // =====================================================================================================================
@@ -33,8 +34,7 @@
 // depth that needs no network on, g3_tail_kernel takes every walker that is left to its end in one launch.
 namespace wost {
 
-constexpr int kRec3Fields = 15;      // sol rgb, pos xyz, dir xyz, pdf, thp, normal xyz, onNeumann
-constexpr int kMaxTrainDepth3 = 4;   // parameters.h:7
+using Rec3 = Rec<3>;                 // the fields of a training record (wost_train.h)
 
 struct alignas(256) GStats3Dev {
     unsigned long long steps, started, absorbed, truncated, nhits, guided, net_points;
@@ -114,13 +114,13 @@ __device__ __forceinline__ bool g3_training_pixel(const G3Params &P, uint32_t pi
 
 __device__ __forceinline__ float &rec3_at(const G3Params &P, int slot, int field, uint32_t pid)
 {
-    return P.rec[((size_t)slot * kRec3Fields + field) * (size_t)P.n_pixels + pid];
+    return P.rec[((size_t)slot * Rec3::kFields + field) * (size_t)P.n_pixels + pid];
 }
 
 // recordSolution / recordSourceContribution (guided.h:48-68): add to every record this walk has created
 __device__ __forceinline__ void g3_record_solution(const G3Params &P, uint32_t pid, const float (&c)[3])
 {
-    const uint32_t n = min(P.cur_depth[pid], (uint32_t)kMaxTrainDepth3);
+    const uint32_t n = min(P.cur_depth[pid], (uint32_t)kMaxTrainDepth);
     for (uint32_t i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) rec3_at(P, i, k, pid) = rec3_at(P, i, k, pid) + c[k];
 }
@@ -480,14 +480,14 @@ __device__ __forceinline__ bool g3_sample_body(const G3Params &P, int depth, boo
             }
             if (record) {       // incrementDepth (guided.h:21-46): the vertex BEFORE the step
                 const uint32_t d = P.cur_depth[p];
-                if (d < (uint32_t)kMaxTrainDepth3) {
-                    rec3_at(P, d, 0, pid) = 0.0f; rec3_at(P, d, 1, pid) = 0.0f; rec3_at(P, d, 2, pid) = 0.0f;
-                    rec3_at(P, d, 3, pid) = x.x; rec3_at(P, d, 4, pid) = x.y; rec3_at(P, d, 5, pid) = x.z;
-                    rec3_at(P, d, 6, pid) = dir.x; rec3_at(P, d, 7, pid) = dir.y; rec3_at(P, d, 8, pid) = dir.z;
-                    rec3_at(P, d, 9, pid) = pdf;
-                    rec3_at(P, d, 10, pid) = thp;
-                    rec3_at(P, d, 11, pid) = nn.x; rec3_at(P, d, 12, pid) = nn.y; rec3_at(P, d, 13, pid) = nn.z;
-                    rec3_at(P, d, 14, pid) = on_n ? 1.0f : 0.0f;
+                if (d < (uint32_t)kMaxTrainDepth) {
+                    rec3_at(P, d, Rec3::kSol, pid) = 0.0f; rec3_at(P, d, Rec3::kSol + 1, pid) = 0.0f; rec3_at(P, d, Rec3::kSol + 2, pid) = 0.0f;
+                    rec3_at(P, d, Rec3::kPos, pid) = x.x; rec3_at(P, d, Rec3::kPos + 1, pid) = x.y; rec3_at(P, d, Rec3::kPos + 2, pid) = x.z;
+                    rec3_at(P, d, Rec3::kDir, pid) = dir.x; rec3_at(P, d, Rec3::kDir + 1, pid) = dir.y; rec3_at(P, d, Rec3::kDir + 2, pid) = dir.z;
+                    rec3_at(P, d, Rec3::kPdf, pid) = pdf;
+                    rec3_at(P, d, Rec3::kThp, pid) = thp;
+                    rec3_at(P, d, Rec3::kNrm, pid) = nn.x; rec3_at(P, d, Rec3::kNrm + 1, pid) = nn.y; rec3_at(P, d, Rec3::kNrm + 2, pid) = nn.z;
+                    rec3_at(P, d, Rec3::kOnN, pid) = on_n ? 1.0f : 0.0f;
                     P.cur_depth[p] = d + 1;
                 }
             }
@@ -668,119 +668,6 @@ __global__ __launch_bounds__(256, 2) void g3_fused_kernel(G3Params P, G3Net F)
     }
 }
 
-
-// ---- the training set of a pass, in (pixel, record) order (train.h:423-471) ------------------------------------------------
-struct T3Params {
-    G3Params G;
-    uint32_t *block_sums;      // records per block of 256 training pixels; after the scan: first output index of the block
-    int32_t n_train_pixels;
-    float *t_x, *t_dir, *t_sol, *t_li, *t_pdf, *t_nrm;
-    uint8_t *t_onn;
-};
-
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void g3_train_set_kernel(T3Params T)
-{
-    __shared__ uint32_t s_scan[256];
-    const G3Params &P = T.G;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    uint32_t n_valid = 0;
-    uint32_t valid_mask = 0;
-    uint32_t pid = 0;
-    if (t < T.n_train_pixels) {
-        pid = (uint32_t)P.train_offset + (uint32_t)t * (uint32_t)P.train_stride;
-        const uint32_t depth = P.cur_depth[pid];
-        for (uint32_t k = 0; k < depth; ++k) {
-            const V3 rp = v3(rec3_at(P, k, 3, pid), rec3_at(P, k, 4, pid), rec3_at(P, k, 5, pid));
-            if (!g3_box_contains(P.box, rp)) continue;
-            const float thp = rec3_at(P, k, 10, pid), pdf = rec3_at(P, k, 9, pid);
-            float s3[3];
-            bool bad = false;
-            for (int ch = 0; ch < 3; ++ch) {
-                float v = 0.0f;
-                if (fabsf(thp) > 1e-5f) v = rec3_at(P, k, ch, pid) / thp;
-                s3[ch] = fabsf(v);
-                bad = bad || isnan(s3[ch]);
-            }
-            float in3[3];
-            g3_normalize(P.box, rp, in3);
-            bad = bad || isnan(in3[0]) || isnan(in3[1]) || isnan(in3[2]) || isnan(rec3_at(P, k, 6, pid)) || isnan(rec3_at(P, k, 7, pid)) ||
-                  isnan(rec3_at(P, k, 8, pid)) || isnan(pdf) || pdf == 0;
-            if (bad) continue;
-            valid_mask |= 1u << k;
-            ++n_valid;
-        }
-    }
-    // exclusive prefix of n_valid over the block
-    s_scan[threadIdx.x] = n_valid;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const uint32_t v = threadIdx.x >= (unsigned)off ? s_scan[threadIdx.x - off] : 0u;
-        __syncthreads();
-        s_scan[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if (!SCATTER) {
-        if (threadIdx.x == 255) T.block_sums[blockIdx.x] = s_scan[255];
-        return;
-    }
-    size_t o = (size_t)T.block_sums[blockIdx.x] + (s_scan[threadIdx.x] - n_valid);
-    for (uint32_t k = 0; k < (uint32_t)kMaxTrainDepth3; ++k) {
-        if (!(valid_mask & (1u << k))) continue;
-        const V3 rp = v3(rec3_at(P, k, 3, pid), rec3_at(P, k, 4, pid), rec3_at(P, k, 5, pid));
-        const float thp = rec3_at(P, k, 10, pid);
-        float s3[3], in3[3];
-        for (int ch = 0; ch < 3; ++ch) {
-            float v = 0.0f;
-            if (fabsf(thp) > 1e-5f) v = rec3_at(P, k, ch, pid) / thp;
-            s3[ch] = fabsf(v);
-        }
-        g3_normalize(P.box, rp, in3);
-        for (int c = 0; c < 3; ++c) {
-            T.t_x[3 * o + c] = in3[c];
-            T.t_dir[3 * o + c] = rec3_at(P, k, 6 + c, pid);
-            T.t_sol[3 * o + c] = s3[c];
-            T.t_nrm[3 * o + c] = rec3_at(P, k, 11 + c, pid);
-        }
-        T.t_li[o] = (s3[0] + s3[1] + s3[2]) / 3.0f;
-        T.t_pdf[o] = rec3_at(P, k, 9, pid);
-        T.t_onn[o] = rec3_at(P, k, 14, pid) != 0.0f ? 1 : 0;
-        ++o;
-    }
-}
-
-// exclusive scan of the block sums in place (one block; the total goes to sums[n])
-__global__ __launch_bounds__(1024) void g3_scan_kernel(uint32_t *sums, int n)
-{
-    __shared__ uint32_t s[1024];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + threadIdx.x;
-        const uint32_t v = i < n ? sums[i] : 0u;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const uint32_t a = threadIdx.x >= (unsigned)off ? s[threadIdx.x - off] : 0u;
-            __syncthreads();
-            s[threadIdx.x] += a;
-            __syncthreads();
-        }
-        if (i < n) sums[i] = carry + s[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += s[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[n] = carry;
-}
-
-__global__ void g3_resolve_kernel(const float *sol, const int32_t *owned_state, int n, float spp, float *field)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 3 * n) field[i] = sol[i] / spp;
-}
-
 }  // namespace wost
 
 using namespace wost;
@@ -796,23 +683,13 @@ struct wost3_guided {
     float *sol = nullptr, *rec = nullptr, *wx = nullptr, *wn = nullptr, *wthp = nullptr, *wrb = nullptr, *net_in = nullptr, *net_out = nullptr, *field = nullptr;
     uint32_t *cur_depth = nullptr, *q_pid = nullptr, *q_count = nullptr, *block_sums = nullptr, *l_pid = nullptr;
     int32_t *state = nullptr, *whint = nullptr, *hint0 = nullptr;
-    uint8_t *won = nullptr, *t_onn = nullptr;
-    float *t_x = nullptr, *t_dir = nullptr, *t_sol = nullptr, *t_li = nullptr, *t_pdf = nullptr, *t_nrm = nullptr;
+    uint8_t *won = nullptr;
+    TrainSet ts{};
     GStats3Dev *stats = nullptr;
     uint32_t *host_word = nullptr;      // pinned
     uint32_t last_train_n = 0;
     uint64_t host_rng = 0;
 };
-
-template <class T>
-static hipError_t g3_alloc(wost3_guided *g, T **p, size_t count)
-{
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) g->allocs.push_back(q);
-    *p = reinterpret_cast<T *>(q);
-    return e;
-}
 
 static void g3_free(wost3_guided *g)
 {
@@ -839,15 +716,6 @@ struct G3Plan {
     bool fused;                       // a whole sample in one launch (WOST3_G_FUSED=0 / 1: never / always)
     G3Net F;                          // the network's fp32 image for it
 };
-
-// prepareSolve (integrator.cu:126): the integrator's host sampler (pcg32, seed of the handle, increment 1)
-static uint32_t g3_host_pcg_next(wost3_guided *g)
-{
-    const uint64_t old = g->host_rng;
-    g->host_rng = old * 0x5851f42d4c957f2dULL + 1u;
-    const uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u), rot = (uint32_t)(old >> 59u);
-    return (xs >> rot) | (xs << ((~rot + 1u) & 31));
-}
 
 // The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource).  These are all the walk instantiations there are:
 //   G3_FUSED  g3_fused_kernel<E, T, S>   G3_SEPARATE  g3_separate_kernel<E, T, S>   G3_TAIL  g3_tail_kernel<E, T, S>   G3_SAMPLE  g3_sample_kernel<T>
@@ -888,7 +756,7 @@ static G3Plan g3_plan(wost3_guided *g)
     if (s.train_pixel_stride > 1 && s.train_pixel_offset >= 0) pl.train_offset = (uint32_t)s.train_pixel_offset;
     else if (s.train_pixel_stride > 1) {
         union { uint32_t u; float f; } x;
-        x.u = (g3_host_pcg_next(g) >> 9) | 0x3f800000u;
+        x.u = (host_pcg_next(g->host_rng, 1u) >> 9) | 0x3f800000u;      // the integrator's host sampler: seed of the handle, increment 1
         pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
     pl.n_train_pixels = (int)(((size_t)N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride); pl.n_train_blocks = (pl.n_train_pixels + 255) / 256;
@@ -927,14 +795,6 @@ static G3Plan g3_plan(wost3_guided *g)
         pl.fused = false;
     }
     return pl;
-}
-
-// the guiding state of a sample (ctor state integrator.cu:1158-1160, prepareSolve :125-126, the switch :991-996)
-struct GuidePhase { bool training; float uniform_fraction; int max_guided_depth; };
-static GuidePhase phase_at(const wost3_guided_settings &s, int sample)
-{
-    if (sample < s.train_spp_count) return {true, s.uniform_fraction_training, s.max_guided_depth_training};
-    return {false, s.uniform_fraction_guiding, s.max_guided_depth_guiding};
 }
 
 // what the steps of a solve count and hand to each other
@@ -1022,43 +882,23 @@ static int walk_per_depth(wost3_guided *g, const G3Plan &pl, G3Run &run, G3Param
     return WOST_OK;
 }
 
-// entries of batch `it` of a training set of n: what is left of the set, rounded down to 128; false = no further batch
-static bool batch_len(size_t n, size_t it, const wost3_guided_settings &s, size_t &local)
-{
-    const size_t bs = (size_t)s.batch_size;
-    if (it * bs > n) return false;
-    local = std::min(n - it * bs, bs) / 128 * 128;
-    return local >= (size_t)s.min_batch_size;
-}
-
 // trainStep (:618-668) after a trained sample: the ordered training set (count, scan, scatter), its size read back, then up to
 // batches_per_spp Adam steps.  Two synchronisations; train_ms is host time and includes both.
-static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, const G3Params &P, hipStream_t stream)
+static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, hipStream_t stream)
 {
-    const wost3_guided_settings &s = g->s;
     const auto t0 = std::chrono::high_resolution_clock::now();
-    T3Params T{};
-    T.G = P; T.block_sums = g->block_sums; T.n_train_pixels = pl.n_train_pixels;
-    T.t_x = g->t_x; T.t_dir = g->t_dir; T.t_sol = g->t_sol; T.t_li = g->t_li; T.t_pdf = g->t_pdf; T.t_nrm = g->t_nrm; T.t_onn = g->t_onn;
-    hipLaunchKernelGGL((g3_train_set_kernel<false>), dim3(pl.n_train_blocks), dim3(256), 0, stream, T);
-    hipLaunchKernelGGL(g3_scan_kernel, dim3(1), dim3(1024), 0, stream, g->block_sums, pl.n_train_blocks);
-    hipLaunchKernelGGL((g3_train_set_kernel<true>), dim3(pl.n_train_blocks), dim3(256), 0, stream, T);
+    TrainSetParams<3> T{};
+    for (int a = 0; a < 3; ++a) { T.min[a] = g->box.min[a]; T.max[a] = g->box.max[a]; T.c[a] = g->box.c[a]; T.e[a] = g->box.e[a]; }
+    T.rec = g->rec; T.rec_ld = (size_t)g->s.width * g->s.height; T.cur_depth = g->cur_depth;
+    T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->s.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = g->ts;
     run.launches += 3;
-    W3_TRY(hipMemcpyAsync(g->host_word, g->block_sums + pl.n_train_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    int rc = enqueue_train_set(T, pl.n_train_blocks, stream, g->host_word);
+    if (rc != WOST_OK) return rc;
     W3_TRY(hipStreamSynchronize(stream));
-    const size_t n = g->host_word[0], bs = (size_t)s.batch_size;
+    const size_t n = g->host_word[0];
     g->last_train_n = (uint32_t)n; run.train_samples += n;
-    const size_t n_batches = std::min(n / bs + 1, (size_t)s.batches_per_spp);
-    for (size_t it = 0, local = 0; it < n_batches && batch_len(n, it, s, local); ++it) {
-        const size_t o = it * bs;
-        float *out = nullptr, *dl = nullptr;
-        int rc = net_forward_train_dev(g->net, g->t_x + 3 * o, (int)local, stream, &out, &dl);
-        if (rc != WOST_OK) return rc;
-        launch_vmm3_loss_gradients(stream, out, g->t_dir + 3 * o, g->t_li + o, g->t_pdf + o, g->t_onn + o, g->t_nrm + 3 * o, (int)local, s.loss_scale, dl, (float *)nullptr);
-        ++run.launches;      // the loss-gradient kernel; the network's own launches are counted by the network
-        rc = net_backward_update_dev(g->net, g->t_x + 3 * o, (int)local, s.loss_scale, 1, stream);
-        if (rc != WOST_OK) return rc;
-    }
+    rc = train_passes<3>(g->net, g->ts, n, train_schedule(g->s), TrainSync{nullptr, nullptr}, stream, run.launches);
+    if (rc != WOST_OK) return rc;
     W3_TRY(hipStreamSynchronize(stream));
     run.train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return WOST_OK;
@@ -1068,7 +908,7 @@ static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, const
 static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
 {
     const int N = g->s.width * g->s.height;
-    hipLaunchKernelGGL(g3_resolve_kernel, dim3((unsigned)((3 * N + 255) / 256)), dim3(256), 0, stream, g->sol, g->state, N, (float)g->s.spp, g->field);
+    launch_resolve(g->sol, N, (float)g->s.spp, g->field, stream);
     W3_TRY(hipGetLastError());
     if (field_host) W3_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) W3_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -1101,7 +941,7 @@ static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float 
         const GuidePhase ph = phase_at(g->s, sample);
         // both paths give the same results
         int rc = pl.fused ? walk_fused(pl, run, P, ph, sample, stream) : walk_per_depth(g, pl, run, P, ph, sample, stream);
-        if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, P, stream);
+        if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, stream);
         if (rc != WOST_OK) return rc;
     }
     return finish_guided3(g, pl, run, stream, field_host, field_dev, stats);
@@ -1114,7 +954,7 @@ int wost3_guided_create(const wost3_scene_desc *scene, const wost3_guided_settin
 {
     if (!scene || !s || !net || !out) return set_error(WOST_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (s->max_train_depth < 0 || s->max_train_depth > kMaxTrainDepth3 || s->train_pixel_stride < 1 || s->batch_size < 128 ||
+    if (s->max_train_depth < 0 || s->max_train_depth > kMaxTrainDepth || s->train_pixel_stride < 1 || s->batch_size < 128 ||
         s->batches_per_spp < 0 || s->train_spp_count < 0)
         return set_error(WOST_ERR_INVALID, "bad guided settings");
     if (net->n_output != 41) return set_error(WOST_ERR_INVALID, "the 3-D guiding network has 41 outputs (8 x (lambda, kappa, mean vector) + selection logit)");
@@ -1138,14 +978,14 @@ int wost3_guided_create(const wost3_scene_desc *scene, const wost3_guided_settin
             g->box.c[a] = (lo + hi) / 2.0f; g->box.e[a] = hi - lo;
         }
     }
-    const size_t N = (size_t)s->width * s->height, cap = N * kMaxTrainDepth3;
+    const size_t N = (size_t)s->width * s->height;
     hipError_t e = hipSuccess;
-#define G3A(p, n) if (e == hipSuccess) e = g3_alloc(g, &g->p, (n))
-    G3A(rng, N); G3A(sol, 3 * N); G3A(cur_depth, N); G3A(rec, (size_t)kMaxTrainDepth3 * kRec3Fields * N); G3A(state, N); G3A(wx, 3 * N); G3A(wn, 3 * N);
+#define G3A(p, n) if (e == hipSuccess) e = device_alloc(g->allocs, &g->p, (n))
+    G3A(rng, N); G3A(sol, 3 * N); G3A(cur_depth, N); G3A(rec, (size_t)kMaxTrainDepth * Rec3::kFields * N); G3A(state, N); G3A(wx, 3 * N); G3A(wn, 3 * N);
     G3A(wthp, N); G3A(wrb, N); G3A(won, N); G3A(whint, N); G3A(hint0, N); G3A(q_pid, N); G3A(l_pid, 2 * N); G3A(q_count, 4); G3A(net_in, 3 * N); G3A(net_out, 41 * N);
     G3A(field, 3 * N); G3A(stats, kStat3Copies); G3A(block_sums, N / 256 + 4);
-    G3A(t_x, 3 * cap); G3A(t_dir, 3 * cap); G3A(t_sol, 3 * cap); G3A(t_li, cap); G3A(t_pdf, cap); G3A(t_nrm, 3 * cap); G3A(t_onn, cap);
 #undef G3A
+    if (e == hipSuccess) e = alloc_train_set(g->allocs, g->ts, 3, N * kMaxTrainDepth);
     if (e == hipSuccess) e = hipHostMalloc((void **)&g->host_word, 4 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(g->cur_depth, 0, N * sizeof(uint32_t));
     if (e != hipSuccess) {
@@ -1207,15 +1047,7 @@ int wost3_guided_train_set(wost3_guided_handle h, int32_t capacity, int32_t *n, 
     if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
     W3_TRY(hipSetDevice(h->device));
     *n = (int32_t)h->last_train_n;
-    const size_t m = std::min((size_t)capacity, (size_t)h->last_train_n);
-    if (m == 0) return WOST_OK;
-    if (xyz) W3_TRY(hipMemcpy(xyz, h->t_x, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir) W3_TRY(hipMemcpy(dir, h->t_dir, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (solution) W3_TRY(hipMemcpy(solution, h->t_sol, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir_pdf) W3_TRY(hipMemcpy(dir_pdf, h->t_pdf, m * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal) W3_TRY(hipMemcpy(normal, h->t_nrm, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (on_neumann) W3_TRY(hipMemcpy(on_neumann, h->t_onn, m, hipMemcpyDeviceToHost));
-    return WOST_OK;
+    return copy_train_set(h->ts, 3, std::min((size_t)capacity, (size_t)h->last_train_n), xyz, dir, solution, dir_pdf, normal, on_neumann);
 }
 
 }  // extern "C"

@@ -241,7 +241,7 @@ def test_gpu_net3_grid_gradient_with_other_feature_counts(orc, n_features, n_lev
 
 
 def _gpu_and_oracle3(orc, sd, w, h, spp, depth, train_spp, uf=(0.5, 0.5), mgd=(10, 10), batch=1024, min_batch=256, params=None,
-                     stride=1, offset=0, dump=True, cfg=None, ref=None):
+                     stride=1, offset=0, dump=True, cfg=None, ref=None, aabb=AABB3):
     from elaina_amd.guided import GuidedIntegratorSettings
     from elaina_amd.integrator3d import GuidedIntegrator3, Problem3
     cfg = cfg or _cfg()
@@ -249,14 +249,14 @@ def _gpu_and_oracle3(orc, sd, w, h, spp, depth, train_spp, uf=(0.5, 0.5), mgd=(1
                                   uniformFractionInTrainingPhase=uf[0], uniformFractionInGuidingPhase=uf[1],
                                   maxGuidedDepthInTrainingPhase=mgd[0], maxGuidedDepthInGuidingPhase=mgd[1], batchSize=batch,
                                   minBatchSize=min_batch, trainPixelStride=stride, trainPixelOffset=offset)
-    gi = GuidedIntegrator3(Problem3.from_dict(sd), st, AABB3, network_config=_hip_cfg(cfg), seed=7)
+    gi = GuidedIntegrator3(Problem3.from_dict(sd), st, aabb, network_config=_hip_cfg(cfg), seed=7)
     if params is not None:
         gi.network.set_params(params)
     p0 = gi.network.params()
     gi.solve()
     if ref is not None:      # (the oracle's half of this solve has been computed already)
         return gi, ref
-    gs = guided_settings3(w, h, spp, depth, EPS, AABB3[0], AABB3[1], train_spp_count=train_spp, uniform_fraction=uf, max_guided_depth=mgd,
+    gs = guided_settings3(w, h, spp, depth, EPS, aabb[0], aabb[1], train_spp_count=train_spp, uniform_fraction=uf, max_guided_depth=mgd,
                           batch_size=batch, min_batch_size=min_batch, train_pixel_stride=stride, train_pixel_offset=offset)
     dump_spp = min(train_spp, spp) - 1 if (dump and train_spp > 0) else -1
     trained = p0.copy()
@@ -294,6 +294,23 @@ def test_gpu_first_pass_records_match_oracle_3d(orc):
     ts, to = gi.train_set(), ref["train_set"]
     assert gi.last_stats["optimizer_steps"] == 0
     assert gi.last_stats["train_samples"] == len(ts["xyz"]) == len(to["xyz"]) == ref["train_samples"] > 1000
+    assert np.array_equal(gi.solution, ref["field"])
+    for k in ("xyz", "dir", "solution", "dir_pdf", "normal", "on_neumann"):
+        assert np.array_equal(ts[k], to[k]), k
+    for k in COUNTERS:
+        assert gi.last_stats[k] == ref[k], k
+    gi.close()
+
+
+@pytest.mark.gpu
+def test_gpu_first_pass_records_rejected_by_the_box_3d(orc):
+    """a guiding box inside the cube: records outside it are written by the walk and left out of the training set, so a pixel's
+    count and its depth differ -- the ordered training set bit for bit"""
+    sd = cube_scene3(n=3, d_faces=(4, 5), n_faces=(0, 1, 2, 3), value=lambda x, y, z: z, flux=lambda x, y, z, f: 0.3 * (f - 1.5))
+    gi, ref = _gpu_and_oracle3(orc, sd, 40, 40, 1, 48, 1, min_batch=10 ** 9, aabb=((0.25, 0.2, 0.3), (0.8, 0.7, 0.75)))
+    ts, to = gi.train_set(), ref["train_set"]
+    assert gi.last_stats["optimizer_steps"] == 0
+    assert gi.last_stats["train_samples"] == len(ts["xyz"]) == len(to["xyz"]) == ref["train_samples"] > 0
     assert np.array_equal(gi.solution, ref["field"])
     for k in ("xyz", "dir", "solution", "dir_pdf", "normal", "on_neumann"):
         assert np.array_equal(ts[k], to[k]), k

@@ -179,6 +179,45 @@ def test_gpu_first_pass_records_match_oracle(oracle):
     gi.close()
 
 
+def _check_first_pass(gi, ref):
+    """the assertions of test_gpu_first_pass_records_match_oracle; returns the size of the training set"""
+    ts, to = gi.train_set(), ref["train_set"]
+    assert gi.last_stats["optimizer_steps"] == 0
+    assert gi.last_stats["train_samples"] == len(ts["xy"]) == len(to["xy"]) == ref["train_samples"]
+    assert np.array_equal(gi.solution, ref["field"])
+    for k in ("xy", "dir", "solution", "dir_pdf", "normal", "on_neumann"):
+        assert np.array_equal(ts[k], to[k]), k
+    for k in ("walk_steps", "walks_absorbed", "walks_truncated", "neumann_hits", "guided_steps"):
+        assert gi.last_stats[k] == ref[k], k
+    return len(ts["xy"])
+
+
+@pytest.mark.gpu
+def test_gpu_first_pass_records_past_one_scan_chunk(oracle):
+    """258 blocks of 256 training pixels: the scan of the block sums (256 threads) takes a second trip with the carry of the
+    first -- records and the ordered training set bit for bit"""
+    prob = laplace_box()
+    w, h = 258, 256
+    assert (w * h + 255) // 256 > 256
+    gi, ref = _gpu_and_oracle(oracle, prob, w, h, 1, 8, 1, min_batch=10 ** 9)
+    _check_first_pass(gi, ref)
+    gi.close()
+
+
+@pytest.mark.gpu
+def test_gpu_first_pass_records_rejected_by_the_box(oracle):
+    """a guiding box inside the domain: records outside it are written by the walk and left out of the training set, so a
+    pixel's count and its depth differ -- bit for bit; fewer entries than with the box around the domain"""
+    prob = laplace_box()
+    aabb = ((0.25, 0.2), (0.8, 0.7))
+    gi, ref = _gpu_and_oracle(oracle, prob, 48, 48, 1, 32, 1, min_batch=10 ** 9, aabb=aabb)
+    n = _check_first_pass(gi, ref)
+    gs = guided_settings(48, 48, 1, 32, EPS, AABB[0], AABB[1], train_spp_count=1, min_batch_size=10 ** 9)
+    usual = oracle.solve_guided(prob.as_dict(), gs, default_net_config(), gi.network.params(), threads=16)["train_samples"]
+    assert 0 < n < usual
+    gi.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("spp,uf", [(8, (0.5, 0.5)), (3, (0.0, 0.0)), (3, (0.9, 0.25))])
 def test_gpu_frozen_network_matches_oracle(oracle, spp, uf):
