@@ -183,6 +183,80 @@ __global__ __launch_bounds__(256) void init_kernel(InitParams P)
 }
 
 // ------------------------------------------------------------------------------------------
+// init of a point solve (wost_solve_points): the caller's points instead of the frame's
+// ------------------------------------------------------------------------------------------
+struct InitPointsParams {
+    DevMesh dm;
+    DevSettings st;
+    WalkQueue out;
+    uint32_t *count_out;
+    const float *points;     // the call's points (x, y); this launch takes points [first, first + n)
+    float *field;            // the call's field: a walker's pix is its point's index in the call
+    int32_t first, n;
+    int32_t seed_base, seed_width;
+    int32_t stack_stride;
+};
+
+// Thread t takes point i = first + t of the call: the stream of pixel seed_base + i in a
+// frame seed_width wide, pix = i, the rest as init_kernel writes it.  A point with a non-finite coordinate is never queued -- no walker may carry a NaN into a persistent launch -- and
+// its field entry is NaN.  A caller's point can lie thousands of extents from the mesh, where the descent opens every box
+// (closest_point_wave): beyond dm.huge2 the depth-0 query is that scan, through the ballot loop of the SLACK walk kernels --
+// the same candidates and the same tie rule as the descent, hence the same bits.
+__global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
+{
+    extern __shared__ uint32_t lds_stack[];
+    uint32_t *stack = lds_stack + threadIdx.x;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool owned = t < P.n;
+    const int pid = P.first + (owned ? t : 0);
+    float x0 = 0, y0 = 0;
+    if (owned) {
+        x0 = P.points[2 * (size_t)pid];
+        y0 = P.points[2 * (size_t)pid + 1];
+    }
+    const bool finite = isfinite(x0) && isfinite(y0);
+    const bool active = owned && finite && P.st.spp > 0;
+    if (owned && !active) {
+        float *f = P.field + 3 * (size_t)pid;
+        const float z = finite ? 0.0f / (float)P.st.spp : __int_as_float(0x7fc00000);
+        f[0] = z; f[1] = z; f[2] = z;
+    }
+    Pcg rng{0, 1};
+    Closest c0{WOST_INF, -1};
+    bool huge = false;
+    if (active) {
+        pcg_seed_pixel(rng, P.seed_base + pid, P.seed_width);
+        if (P.dm.n_segs > 0) {
+            c0 = slot_candidate(P.dm, 0, x0, y0);
+            huge = c0.d2 > P.dm.huge2;
+            if (!huge) c0 = closest_point(P.dm, x0, y0, c0, stack, P.stack_stride);
+        }
+    }
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_point_wave(P.dm, __shfl(x0, src), __shfl(y0, src));
+        if ((int)(threadIdx.x & 63) == src) c0 = r;
+        hb &= hb - 1;
+    }
+    const uint32_t s = block_push(active, P.count_out);
+    if (active) {
+        WalkQueue &q = P.out;
+        q.pix[s] = pid;
+        q.x0[s] = x0; q.y0[s] = y0;
+        q.px[s] = x0; q.py[s] = y0;
+        q.rng[s] = rng.state;
+        q.meta[s] = META_PACK(0, 0, 0);
+        q.nx[s] = 0.0f; q.ny[s] = 0.0f;
+        q.hint[s] = c0.slot;
+        q.thp[s] = 1.0f;
+        q.sr[s] = 0.0f; q.sg[s] = 0.0f; q.sb[s] = 0.0f;
+        q.d0_d2[s] = c0.d2;
+        q.d0_slot[s] = c0.slot;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // the walk round
 // ------------------------------------------------------------------------------------------
 struct Lane {
@@ -1298,6 +1372,7 @@ struct wost_context {
     int n_cus = 256;
     StatsDev *host_stats = nullptr;            // pinned: the counters as they stood after each launch (last_launches)
     std::vector<wost_launch_info> last_launches;
+    uint64_t steps_before = 0;                 // a point solve in chunks: the walk steps of its earlier chunks (wost_launch_info::walk_steps_done)
 };
 
 namespace wost {
@@ -1937,15 +2012,28 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     kernel_ms += ms;
     wost_launch_info li{p.kind, p.n_round, p.n_active - p.n_round + p.far + p.beside_far, p.n_round > 0 ? p.grid : 0u, ms, 0};
+    li.walk_steps_done = c->steps_before;
     for (int k = 0; k < kStatCopies; ++k) li.walk_steps_done += c->host_stats[k].steps;
     c->last_launches.push_back(li);
     if (getenv("WOST_TRACE_LAUNCHES")) fprintf(stderr, "launch %d: walkers %u of %u (+ %u strayed) grid %u %.3f ms -> %u left, %u strayed%s\n", launches, p.n_round, p.n_active, p.far, p.grid, ms, c->host_count[0], c->host_count[2], persist ? " (persistent)" : "");
     return WOST_OK;
 }
 
+// The first step of a solve, the one that fills queue 0: the frame init on a pixel range and a shard, or (points != nullptr) the
+// point init on points [first, first + n) of a call -- one chunk of a point solve, at most n_pixels points.
+struct FirstStep {
+    int32_t pixel_begin, pixel_end, shard_index, shard_count;
+    const float *points;
+    int32_t first, n, seed_base, seed_width;
+};
+static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count)
+{
+    return FirstStep{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0, 0, 0};
+}
+
 // the shared solve driver: field_dev indexed by (pix - field_base)
-static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count,
-                     float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
+// (a later chunk of a point solve, fs.first > 0, appends to last_launches, its walk_steps_done counted on from c->steps_before)
+static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
     const auto t_start = std::chrono::high_resolution_clock::now();
     HIP_TRY(hipSetDevice(c->device));
@@ -1953,12 +2041,17 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
     HIP_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
 
-    const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
-    const InitParams ip{c->dm.view, c->dst, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
-                        pixel_begin, pixel_end, shard_index, shard_count, tiles_x, tiles_y, g.bs};
-    const long long n_threads = (long long)tiles_x * tiles_y * 64;
-    const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
-    hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
+    if (fs.points) {
+        const InitPointsParams ip{c->dm.view, c->dst, c->queue[0], c->counts + 0, fs.points, field_dev, fs.first, fs.n, fs.seed_base, fs.seed_width, g.bs};
+        hipLaunchKernelGGL(init_points_kernel, dim3((unsigned)(((long long)fs.n + g.bs - 1) / g.bs)), dim3(g.bs), g.lds, stream, ip);
+    } else {
+        const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
+        const InitParams ip{c->dm.view, c->dst, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
+                            fs.pixel_begin, fs.pixel_end, fs.shard_index, fs.shard_count, tiles_x, tiles_y, g.bs};
+        const long long n_threads = (long long)tiles_x * tiles_y * 64;
+        const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
+        hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->host_count, c->counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1967,7 +2060,11 @@ static int run_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, in
     double kernel_ms = 0.0;
     uint32_t launches = 0;
     int cur = 0;
-    c->last_launches.clear();
+    const bool later_chunk = fs.points && fs.first > 0;
+    if (!later_chunk) {
+        c->last_launches.clear();
+        c->steps_before = 0;
+    }
     const RoundParams base = base_params(c, g, field_dev, field_base);
     SideStreamGuard long_guard, far_guard;   // armed: a launch of the long remainders / of strayed walkers was queued
     uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (launch_strayed)
@@ -2097,7 +2194,7 @@ int wost_solve(wost_handle h, int32_t pixel_begin, int32_t pixel_end, float *fie
     }
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
-    int rc = run_solve(h, pixel_begin, pixel_end, 0, 1, h->field, pixel_begin, h->stream, stats);
+    int rc = run_solve(h, frame_step(pixel_begin, pixel_end, 0, 1), h->field, pixel_begin, h->stream, stats);
     if (rc != WOST_OK) return rc;
     HIP_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2115,7 +2212,67 @@ int wost_solve_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, 
         return fail(WOST_ERR_INVALID, "bad shard");
     // NULL is the legacy default stream, which is also torch's default stream
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return run_solve(h, 0, (int32_t)h->n_pixels, shard_index, shard_count, field_rgb_dev, 0, s, stats);
+    return run_solve(h, frame_step(0, (int32_t)h->n_pixels, shard_index, shard_count), field_rgb_dev, 0, s, stats);
+}
+
+// The point solve on device arrays: chunks of at most n_pixels points -- what the handle's queues, order buffers and out_capacity
+// hold -- each a pass of the driver; a walker's pix is its point's index in the call, so every chunk writes the call's field.
+static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_dev,
+                            hipStream_t stream, wost_stats *stats)
+{
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    wost_stats total{};
+    const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
+    for (int32_t first = 0; first < n; first += cap) {
+        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width};
+        wost_stats st{};
+        const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
+        if (rc != WOST_OK) return rc;
+        total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
+        total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
+        total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
+        total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
+        c->steps_before = total.walk_steps;
+    }
+    total.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    if (stats) *stats = total;
+    return WOST_OK;
+}
+
+int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
+                          void *stream, wost_stats *stats)
+{
+    const int rc = check_point_solve(h, pts_xy_dev, field_rgb_dev, n, seed_base, seed_width);
+    if (rc != WOST_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return WOST_OK;
+    return solve_points_dev(h, pts_xy_dev, n, seed_base, seed_width, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb, wost_stats *stats)
+{
+    int rc = check_point_solve(h, pts_xy, field_rgb, n, seed_base, seed_width);
+    if (rc == WOST_OK) rc = check_points_finite(pts_xy, n, 2);
+    if (rc != WOST_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return WOST_OK;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    HIP_TRY(hipSetDevice(h->device));
+    Scratch s;
+    float *d_pts, *d_field;
+    HIP_TRY(s.alloc(&d_pts, (size_t)n * 2));
+    HIP_TRY(s.alloc(&d_field, (size_t)n * 3));
+    HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
+    rc = solve_points_dev(h, d_pts, n, seed_base, seed_width, d_field, h->stream, stats);
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(field_rgb, d_field, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    return WOST_OK;
 }
 
 int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, int32_t *count)

@@ -54,6 +54,11 @@ struct Walk3Params {
     // NTREE kernels: the Neumann-side tree queries of a step answered by the wave as a whole (closest_silhouette3_wave,
     // ray_closest3_wave); pool_cap tasks per pool and wave, behind the stack columns of the block in LDS
     int32_t coop, pool_cap, stack_words, ray_slot_trigger, cp_slot_trigger;
+    // a point solve (wost3_solve_points, the POINTS instantiations): slot s is point pixel_begin + s of `points` (x, y, z) on the
+    // stream of pixel seed_base + that index in a frame seed_width wide -- no tiles, no shards, no mask; nullptr = the pixels of the frame
+    // (at the end: the frame instantiations read every other field where they always did)
+    const float *points;
+    int32_t seed_base, seed_width;
 };
 
 // One lane = one pixel, all its samples one after the other on the pixel's PCG stream (the reference's per-pixel
@@ -380,7 +385,9 @@ __device__ __forceinline__ Closest closest_triangle_wave(const DevMesh3 &m, V3 q
 
 // WAVE = true: the closest-point queries are answered by the wave as a whole as well (closest_triangle_pool) -- every trip of
 // the loop is then "all queries of the wave, then one step for every walker": no lane waits for another's descent.
-template <bool EMISSIVE, bool SOURCE, bool NTREE, bool WAVE = false>
+// POINTS = true: the launch of a point solve (wost3_solve_points) -- a refill takes a caller's point instead of a pixel of the frame.
+// A template flag, not a test of P.points: with the test every frame instantiation held two more registers (EXPERIMENTS).
+template <bool EMISSIVE, bool SOURCE, bool NTREE, bool WAVE = false, bool POINTS = false>
 #ifndef WOST3_WAVES
 #define WOST3_WAVES 1       // waves per SIMD walk3_kernel is compiled for (tuning builds override it)
 #endif
@@ -456,6 +463,27 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
             if (mode == MODE_REFILL) {
                 if (s2 >= n_slots) {
                     mode = MODE_DONE;
+                } else if (POINTS) {
+                    // a caller's point.  One with a non-finite coordinate is never walked -- no NaN walker in a persistent
+                    // launch -- and its field entry is NaN; the lane asks again on the next trip
+                    const int pid = P.pixel_begin + (int)s2;
+                    const V3 q = v3(P.points[3 * (size_t)pid], P.points[3 * (size_t)pid + 1], P.points[3 * (size_t)pid + 2]);
+                    const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+                    if (!finite || P.st.spp <= 0) {
+                        float *f = P.field + 3 * (size_t)(pid - P.field_base);
+                        const float z = finite ? 0.0f / (float)P.st.spp : __int_as_float(0x7fc00000);
+                        f[0] = z; f[1] = z; f[2] = z;
+                    } else {
+                        t_steps += L.c_steps; t_started += L.c_started; t_absorbed += L.c_absorbed; t_truncated += L.c_truncated; t_nhits += L.c_nhits;
+                        L = Lane3{};
+                        L.pid = pid;
+                        L.rng = Pcg{0, 1};
+                        pcg_seed_pixel(L.rng, P.seed_base + pid, P.seed_width);
+                        L.p_eval = q;
+                        L.hint = L.hint0 = -1;
+                        L.sample = 0;
+                        begin_sample();
+                    }
                 } else {
                     // slots walk the frame in 8x8 tiles when the range is the whole tiled frame (neighbouring walkers in a wave)
                     int pid = P.pixel_begin + (int)s2;
@@ -760,22 +788,31 @@ static Walk3Plan walk3_plan(const wost3_context *c, int n)
     return pl;
 }
 
-// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are
-template <bool E, bool S>
+// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are, and the sixteen of a point solve beside them
+template <bool E, bool S, bool PTS>
 static const void *walk3_kernel_of(bool ntree, bool wave)
 {
-    if (ntree) return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, true, true>) : reinterpret_cast<const void *>(walk3_kernel<E, S, true, false>);
-    return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, false, true>) : reinterpret_cast<const void *>(walk3_kernel<E, S, false, false>);
+    if (ntree) return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, true, true, PTS>) : reinterpret_cast<const void *>(walk3_kernel<E, S, true, false, PTS>);
+    return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, false, true, PTS>) : reinterpret_cast<const void *>(walk3_kernel<E, S, false, false, PTS>);
 }
+template <bool PTS>
 static const void *walk3_kernel_of(const Walk3Plan &pl)
 {
-    if (pl.emissive) return pl.source ? walk3_kernel_of<true, true>(pl.ntree, pl.wave) : walk3_kernel_of<true, false>(pl.ntree, pl.wave);
-    return pl.source ? walk3_kernel_of<false, true>(pl.ntree, pl.wave) : walk3_kernel_of<false, false>(pl.ntree, pl.wave);
+    if (pl.emissive) return pl.source ? walk3_kernel_of<true, true, PTS>(pl.ntree, pl.wave) : walk3_kernel_of<true, false, PTS>(pl.ntree, pl.wave);
+    return pl.source ? walk3_kernel_of<false, true, PTS>(pl.ntree, pl.wave) : walk3_kernel_of<false, false, PTS>(pl.ntree, pl.wave);
 }
 
-static int run_solve3(wost3_context *c, int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, float *field_dev,
-                      int32_t field_base, hipStream_t stream, wost_stats *stats)
+// The first step of a solve, what a lane's refill reads: the pixels [pixel_begin, pixel_end) of the frame and a shard of its tiles, or
+// (points != nullptr) the points [pixel_begin, pixel_end) of a caller's list with their seeds.
+struct FirstStep3 {
+    int32_t pixel_begin, pixel_end, shard_index, shard_count;
+    const float *points;
+    int32_t seed_base, seed_width;
+};
+
+static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
+    const int32_t pixel_begin = fs.pixel_begin, pixel_end = fs.pixel_end, shard_index = fs.shard_index, shard_count = fs.shard_count;
     const auto t0 = std::chrono::high_resolution_clock::now();
     W3_TRY(hipSetDevice(c->device));
     W3_TRY(hipMemsetAsync(c->stats, 0, kStat3Copies * sizeof(Stats3Dev), stream));
@@ -788,12 +825,13 @@ static int run_solve3(wost3_context *c, int32_t pixel_begin, int32_t pixel_end, 
         P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.src = c->src;
         P.field = field_dev; P.field_base = field_base; P.pixel_begin = pixel_begin; P.pixel_end = pixel_end;
         P.shard_index = shard_index; P.shard_count = shard_count; P.stats = c->stats; P.cursor = c->cursor;
-        P.tiled = (pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
+        P.tiled = (!fs.points && pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
+        P.points = fs.points; P.seed_base = fs.seed_base; P.seed_width = fs.seed_width;
         P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
         P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
         void *args[] = {&P};
         W3_TRY(hipEventRecord(c->ev0, stream));
-        (void)hipLaunchKernel(walk3_kernel_of(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
+        (void)hipLaunchKernel(fs.points ? walk3_kernel_of<true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
         W3_TRY(hipGetLastError());
         W3_TRY(hipEventRecord(c->ev1, stream));
     }
@@ -904,7 +942,7 @@ int wost3_solve(wost3_handle h, int32_t pixel_begin, int32_t pixel_end, float *f
     }
     W3_TRY(hipSetDevice(h->device));
     W3_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
-    const int rc = run_solve3(h, pixel_begin, pixel_end, 0, 1, h->field, pixel_begin, h->stream, stats);
+    const int rc = run_solve3(h, FirstStep3{pixel_begin, pixel_end, 0, 1, nullptr, 0, 0}, h->field, pixel_begin, h->stream, stats);
     if (rc != WOST_OK) return rc;
     W3_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     W3_TRY(hipStreamSynchronize(h->stream));
@@ -915,7 +953,41 @@ int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count
 {
     if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
     if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
-    return run_solve3(h, 0, (int32_t)h->n_pixels, shard_index, shard_count, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+    return run_solve3(h, FirstStep3{0, (int32_t)h->n_pixels, shard_index, shard_count, nullptr, 0, 0}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
+                           void *stream, wost_stats *stats)
+{
+    const int rc = check_point_solve(h, pts_xyz_dev, field_rgb_dev, n, seed_base, seed_width);
+    if (rc != WOST_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return WOST_OK;
+    return run_solve3(h, FirstStep3{0, n, 0, 1, pts_xyz_dev, seed_base, seed_width}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb, wost_stats *stats)
+{
+    int rc = check_point_solve(h, pts_xyz, field_rgb, n, seed_base, seed_width);
+    if (rc == WOST_OK) rc = check_points_finite(pts_xyz, n, 3);
+    if (rc != WOST_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return WOST_OK;
+    W3_TRY(hipSetDevice(h->device));
+    Scratch3 s;
+    float *d_pts, *d_field;
+    W3_TRY(s.alloc(&d_pts, (size_t)n * 3));
+    W3_TRY(s.alloc(&d_field, (size_t)n * 3));
+    W3_TRY(hipMemcpyAsync(d_pts, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W3_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
+    rc = run_solve3(h, FirstStep3{0, n, 0, 1, d_pts, seed_base, seed_width}, d_field, 0, h->stream, stats);
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    W3_TRY(hipMemcpyAsync(field_rgb, d_field, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    W3_TRY(hipStreamSynchronize(h->stream));
+    return WOST_OK;
 }
 
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist, float *out_uv,

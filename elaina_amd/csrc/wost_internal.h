@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -14,6 +15,25 @@ namespace wost {
 
 // records the message returned by wost_last_error() on this thread; returns `code`
 int set_error(int code, const std::string &msg);
+
+// The argument rules of the point solves (wost_solve_points & co., include/wost.h), checked before any device work:
+// WOST_OK, or WOST_ERR_INVALID with its message recorded
+inline int check_point_solve(const void *h, const void *pts, const void *field, int32_t n, int32_t seed_base, int32_t seed_width)
+{
+    if (!h || !pts || !field) return set_error(WOST_ERR_INVALID, "null argument");
+    if (n < 0) return set_error(WOST_ERR_INVALID, "negative number of points");
+    if (seed_width <= 0) return set_error(WOST_ERR_INVALID, "seed_width must be positive");
+    if (seed_base < 0 || (int64_t)seed_base + n > ((int64_t)1 << 28))
+        return set_error(WOST_ERR_INVALID, "seed_base must be >= 0 and seed_base + n at most 2^28");
+    return WOST_OK;
+}
+// ... and of their host variants: every one of the n * dim coordinates is finite
+inline int check_points_finite(const float *pts, int32_t n, int dim)
+{
+    for (int64_t i = 0; i < (int64_t)n * dim; ++i)
+        if (!std::isfinite(pts[i])) return set_error(WOST_ERR_INVALID, "point " + std::to_string(i / dim) + " has a non-finite coordinate");
+    return WOST_OK;
+}
 
 // What the guided integrator needs from a wost_context (wost_hip.hip): the uploaded scene.
 struct SceneView {

@@ -103,6 +103,28 @@ class UniformIntegrator:
         self.last_stats = st.as_dict()
         return self.last_stats
 
+    def solve_points(self, points, seed_base=0, seed_width=None):
+        """the solve at the caller's evaluation points ([n, 2] floats) instead of the frame's pixels (wost_solve_points):
+        point i runs on the random stream of pixel seed_base + i in a frame seed_width wide (default: the frame's width);
+        returns the (n, 3) float32 field"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        field = np.zeros((len(p), 3), dtype=np.float32)
+        st = Stats()
+        width = self.settings.frameSize[0] if seed_width is None else seed_width
+        _check(self.lib.wost_solve_points(self._handle, _fp(p), len(p), int(seed_base), int(width), _fp(field), C.byref(st)),
+               "wost_solve_points")
+        self.last_stats = st.as_dict()
+        return field
+
+    def solve_points_dev(self, points_ptr, n, field_ptr, stream_ptr=None, seed_base=0, seed_width=None):
+        """the same on device pointers (ints): n * 2 floats of points, n * 3 floats of field, on the caller's stream"""
+        st = Stats()
+        width = self.settings.frameSize[0] if seed_width is None else seed_width
+        _check(self.lib.wost_solve_points_dev(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), int(width), C.c_void_p(field_ptr),
+                                               C.c_void_p(stream_ptr or 0), C.byref(st)), "wost_solve_points_dev")
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
     def renderDirichletSDF(self):
         out = np.zeros(self.n_pixels, dtype=np.float32)
         _check(self.lib.wost_render_sdf(self._handle, capi.MESH_DIRICHLET, _fp(out)), "wost_render_sdf")

@@ -124,6 +124,26 @@ int wost_solve(wost_handle h, int32_t pixel_begin, int32_t pixel_end, float *fie
 int wost_solve_sharded(wost_handle h, int32_t shard_index, int32_t shard_count,
                        float *field_rgb_dev, void *stream, wost_stats *stats);
 
+/* The solve at n evaluation points of the caller (pts_xy: n * 2 floats) instead of the pixels of the frame.  The reference has
+ * no counterpart: its EvaluationGrid is the only probe (core/evaluation_grid.h).  Point i is solved with the handle's settings
+ * and meshes exactly as a pixel is; its samples share one PCG32 stream seeded as the reference seeds pixel seed_base + i of a
+ * frame seed_width wide (integrator/uniform/integrator.cu:71-77), and field_rgb[3 i ..] receives solution / spp.  So
+ *   - the frame's own evaluation points in row-major order with seed_base = 0 and seed_width = width reproduce wost_solve
+ *     bit for bit, and
+ *   - the result of a point does not depend on how a list is cut into calls, as long as seed_base moves with the cut.
+ * The frame's mask does not apply (it is a property of the frame); spp = 0 behaves as in the frame.  seed_base >= 0,
+ * seed_width > 0 and seed_base + n <= 2^28 (the frame cap of wost_create; the seed is the reference's int product).  A list
+ * longer than the frame runs in chunks of width * height points on the handle's queues; wost_stats sums the chunks and
+ * wost_last_launches lists their launches in order.  n == 0: WOST_OK and zeroed stats.
+ * wost_solve_points: host arrays; a non-finite coordinate is refused (WOST_ERR_INVALID names the first bad index, nothing is
+ * launched).  wost_solve_points_dev: DEVICE arrays and the caller's stream as in wost_solve_sharded (NULL = default stream);
+ * the call returns after the stream work has completed; a point with a non-finite coordinate is never walked, its field
+ * entry is NaN. */
+int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width,
+                      float *field_rgb, wost_stats *stats);
+int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                          float *field_rgb_dev, void *stream, wost_stats *stats);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -350,7 +370,7 @@ int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, fl
 int wost_guided_set_option(wost_guided_handle h, const char *key, double value);
 int wost_guided_destroy(wost_guided_handle h);
 
-/* The launches of the last wost_solve / wost_solve_sharded of this handle, in order (bench.py prices the dominant one against
+/* The launches of the last wost_solve / wost_solve_sharded / wost_solve_points[_dev] of this handle, in order (bench.py prices the dominant one against
  * the roofline; the reference has no counterpart: its solveImpl issues 2 + 5 * depth full-frame launches per sample,
  * integrator/uniform/integrator.cu:529-623).  Writes min(*count, capacity) records. */
 typedef struct wost_launch_info {
@@ -429,6 +449,15 @@ int wost3_solve(wost3_handle h, int32_t pixel_begin, int32_t pixel_end, float *f
 /* the 8x8 pixel tiles t % shard_count == shard_index into a zero-filled full-frame DEVICE buffer (as wost_solve_sharded) */
 int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, void *stream,
                         wost_stats *stats);
+/* The solve at n evaluation points of the caller (pts_xyz: n * 3 floats), which need not lie on one slice: wost_solve_points in
+ * 3-D, with the same rules (stream of pixel seed_base + i in a frame seed_width wide, integrator/uniform/integrator.cu:71-77;
+ * no mask; seed_base + n <= 2^28; non-finite coordinates refused by the host variant and answered with NaN, unwalked, by the
+ * device variant).  The reference has no counterpart: its EvaluationGrid is the only probe (core/evaluation_grid.h).  Lanes
+ * hold the walkers, so a list of any length is one launch. */
+int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb,
+                       wost_stats *stats);
+int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                           float *field_rgb_dev, void *stream, wost_stats *stats);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
