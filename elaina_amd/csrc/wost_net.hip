@@ -2114,6 +2114,15 @@ static int net_create_dims(int device, const wost_net_config *cfg, uint64_t seed
         cfg->n_hidden_layers >= kNetMaxLevels || cfg->n_output < 1 || cfg->n_output > 64 || cfg->base_resolution < 1 ||
         !(cfg->per_level_scale >= 1.0f))
         return set_error(WOST_ERR_UNSUPPORTED, "network shape outside this build (widths <= 64, multiples of 8)");
+    {
+        // (offsets are 32-bit: a grid of three inputs has res^3 entries per level; an infinite per_level_scale gives no number at all)
+        double entries = 0.0;
+        for (int i = 0; i < cfg->n_levels; ++i) {
+            const double r = std::ceil(std::exp2((double)i * std::log2((double)cfg->per_level_scale)) * cfg->base_resolution - 1.0) + 1.0;
+            entries += dims == 3 ? r * r * r : r * r;
+        }
+        if (!(entries * cfg->n_features_per_level <= 1.0e9)) return set_error(WOST_ERR_UNSUPPORTED, "grid encoding too large");
+    }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
@@ -2123,18 +2132,6 @@ static int net_create_dims(int device, const wost_net_config *cfg, uint64_t seed
     if (!h) return set_error(WOST_ERR_NOMEM, "out of host memory");
     h->device = device;
     h->cfg = *cfg;
-    {
-        // (offsets are 32-bit: a grid of three inputs has res^3 entries per level)
-        double entries = 0.0;
-        for (int i = 0; i < cfg->n_levels; ++i) {
-            const double r = std::ceil(std::exp2((double)i * std::log2((double)cfg->per_level_scale)) * cfg->base_resolution - 1.0) + 1.0;
-            entries += dims == 3 ? r * r * r : r * r;
-        }
-        if (entries * cfg->n_features_per_level > 1.0e9) {
-            delete h;
-            return set_error(WOST_ERR_UNSUPPORTED, "grid encoding too large");
-        }
-    }
     h->L = make_layout(*cfg, dims);
     h->n_params = h->L.n_mlp + h->L.n_grid;
     // the knobs are read here, once; the MFMA kernels take three inputs only with the reference's four features per level (f32_encode_level3)

@@ -220,7 +220,9 @@ typedef struct wost_net *wost_net_handle;
 
 /* integrator/guided/integrator.cu:1095-1131 (network + optimizer + trainer construction):
  * allocates parameters on `device` and initialises them from `seed` (util/network.h:113-136;
- * MLP xavier-uniform, grid uniform(-1e-4, 1e-4)). */
+ * MLP xavier-uniform, grid uniform(-1e-4, 1e-4)).  Shapes: 1-16 levels x 1-8 features with an encoded width <= 64 that is a multiple
+ * of 8, 8-64 neurons (a multiple of 8), 1-15 hidden layers, 1-64 outputs, base_resolution >= 1, a finite per_level_scale >= 1, at most
+ * 1e9 grid floats; anything else is WOST_ERR_UNSUPPORTED, decided before a device is looked for. */
 int wost_net_create(int device, const wost_net_config *cfg, uint64_t seed, wost_net_handle *out);
 int wost_net_destroy(wost_net_handle h);
 int wost_net_n_params(wost_net_handle h, uint64_t *n_total, uint64_t *n_mlp);
@@ -235,7 +237,11 @@ int wost_net_set_gradient_buffer(wost_net_handle h, void *dev_int64);
 /* sets training and inference parameters, resets the optimizer state */
 int wost_net_set_params(wost_net_handle h, const float *host);
 /* network->inference (integrator/guided/integrator.cu:560,597; util/network.h:39-47): xy[n*2] in [0,1]^2 -> out[n*n_output];
- * use_inference_params = 1 evaluates the EMA weights (what rendering uses), 0 the training ones. */
+ * use_inference_params = 1 evaluates the EMA weights (what rendering uses), 0 the training ones.
+ * A point outside [0,1]^2 (a walker outside the guiding box) is evaluated too: its cell index floor(scale * x + 0.5) is negative or past
+ * the level, and the entry it reads is (cx + cy * res) mod 2^32, then mod the level's padded entry count -- tiny-cuda-nn's 32-bit dense
+ * grid_index.  The value is well defined and equal to the CPU restatement's, not an extrapolation of the field (three inputs: the same
+ * sum in 64 bits). */
 int wost_net_inference(wost_net_handle h, const float *xy, int32_t n, float *out, int use_inference_params);
 /* "precision": 32 (default) = fp32 everywhere, bit-exact against the CPU restatement; 16 = the reference's own
  * network precision for inference (tiny-cuda-nn FullyFusedMLP + grid in half, util/network.h:21-196,

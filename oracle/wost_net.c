@@ -90,10 +90,13 @@ static void encode(const wo_net_config *c, int dims, const wn_layout *l, const f
         for (int k = 0; k < nc; ++k) {
             const uint32_t cx = pi[0] + (k & 1), cy = pi[1] + ((k >> 1) & 1), cz = pi[2] + ((k >> 2) & 1);
             float w = ((k & 1) ? pf[0] : 1.0f - pf[0]) * ((k & 2) ? pf[1] : 1.0f - pf[1]);
-            size_t lin = (size_t)cx + (size_t)cy * (size_t)res;
+            /* Two inputs: index and stride in uint32_t, as tiny-cuda-nn's grid_index keeps them (and as every HIP kernel does): the sum
+             * wraps modulo 2^32 before % n_level.  Inside the unit square nothing wraps; outside it (a walker outside the guiding box)
+             * floorf() is negative, and this rule decides which entry the point reads.  Three inputs: 64-bit. */
+            size_t lin = (size_t)(uint32_t)(cx + cy * (uint32_t)res);
             if (dims == 3) {
                 w = w * ((k & 4) ? pf[2] : 1.0f - pf[2]);
-                lin += (size_t)cz * (size_t)res * (size_t)res;
+                lin = (size_t)cx + (size_t)cy * (size_t)res + (size_t)cz * (size_t)res * (size_t)res;
             }
             const size_t idx = lin % n_level;                                       /* dense grid_index */
             const float *g = grid + (l->level_off[lv] + idx) * c->n_features;

@@ -124,16 +124,22 @@ def test_oracle_guided_phase_switch_and_quirks(oracle):
 
 # ---- HIP integrator against the oracle ---------------------------------------------------------
 def _gpu_and_oracle(oracle, prob, w, h, spp, depth, train_spp, uf=(0.5, 0.5), mgd=(10, 10), batch=2048, min_batch=512,
-                    params=None, seed=7, dump=True, stride=1, offset=0, aabb=None):
+                    params=None, seed=7, dump=True, stride=1, offset=0, aabb=None, cfg=None):
+    """cfg: the oracle's NetConfig of another network shape (default: the reference's); ref["params"]: the oracle's weights after the solve"""
     from elaina_amd.guided import GuidedIntegrator, GuidedIntegratorSettings
-    cfg = default_net_config()
+    network_config = None
+    if cfg is not None:
+        from elaina_amd import capi
+        network_config = capi.NetConfig(cfg.n_levels, cfg.n_features, cfg.base_resolution, cfg.per_level_scale, cfg.n_neurons, cfg.n_hidden_layers,
+                                        cfg.n_output, cfg.learning_rate, cfg.beta1, cfg.beta2, cfg.epsilon, cfg.l2_reg, cfg.ema_decay)
+    cfg = cfg or default_net_config()
     aabb = aabb or AABB
     st = GuidedIntegratorSettings(frameSize=(w, h), samplesPerPixel=spp, trainSppCount=train_spp, maxWalkingDepth=depth,
                                   epsilonShell=EPS, uniformFractionInTrainingPhase=uf[0],
                                   uniformFractionInGuidingPhase=uf[1], maxGuidedDepthInTrainingPhase=mgd[0],
                                   maxGuidedDepthInGuidingPhase=mgd[1], batchSize=batch, minBatchSize=min_batch,
                                   trainPixelStride=stride, trainPixelOffset=offset)
-    gi = GuidedIntegrator(prob, st, aabb, seed=seed)
+    gi = GuidedIntegrator(prob, st, aabb, network_config=network_config, seed=seed)
     if params is not None:
         gi.network.set_params(params)
     p0 = gi.network.params()
@@ -142,7 +148,9 @@ def _gpu_and_oracle(oracle, prob, w, h, spp, depth, train_spp, uf=(0.5, 0.5), mg
                          max_guided_depth=mgd, batch_size=batch, min_batch_size=min_batch, train_pixel_stride=stride,
                          train_pixel_offset=offset)
     dump_spp = min(train_spp, spp) - 1 if (dump and train_spp > 0) else -1
-    ref = oracle.solve_guided(prob.as_dict(), gs, cfg, p0.copy(), threads=16, dump_spp=dump_spp)
+    trained = p0.copy()
+    ref = oracle.solve_guided(prob.as_dict(), gs, cfg, trained, threads=16, dump_spp=dump_spp)
+    ref["params"] = trained
     return gi, ref
 
 

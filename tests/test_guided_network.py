@@ -15,11 +15,12 @@ def orc():
     return Oracle()
 
 
-def _rand_params(orc, cfg, seed=5, wscale=0.25, gscale=0.5):
-    n = orc.net_n_params(cfg)
+def _rand_params(orc, cfg, seed=5, wscale=0.25, gscale=0.5, dims=2):
+    n = orc.net3_n_params(cfg) if dims == 3 else orc.net_n_params(cfg)
     rng = np.random.default_rng(seed)
     p = rng.uniform(-wscale, wscale, n).astype(np.float32)
-    n_mlp = 64 * 32 + 2 * 64 * 64 + 48 * 64
+    # the matrices of any network shape (64 * 32 + 2 * 64 * 64 + 48 * 64 for the reference's)
+    n_mlp = cfg.n_neurons * (cfg.n_levels * cfg.n_features + (cfg.n_hidden_layers - 1) * cfg.n_neurons + cfg.n_output_padded)
     p[n_mlp:] = rng.uniform(-gscale, gscale, n - n_mlp).astype(np.float32)
     return p
 
