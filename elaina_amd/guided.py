@@ -32,13 +32,17 @@ def vonmises_sample(kappa, seed, per_point=1, device=0):
     return th.reshape(len(k), per_point)
 
 
-def vmm_pdf_sample(raw, wi, seed, device=0):
+def vmm_pdf_sample(raw, wi, seed, device=0, sample=True):
+    """sample=False: the density alone (a null sample_dir; no stream is seeded, no direction drawn) -> (pdf, None)"""
     lib = capi.load()
     r = np.ascontiguousarray(raw, dtype=np.float32)
     w = np.ascontiguousarray(wi, dtype=np.float32)
-    s = np.ascontiguousarray(seed, dtype=np.uint64)
     n = len(w)
     pdf = np.zeros(n, dtype=np.float32)
+    if not sample:
+        _check(lib.wost_vmm_pdf_sample(device, _fp(r), _fp(w), None, n, _fp(pdf), None), "wost_vmm_pdf_sample")
+        return pdf, None
+    s = np.ascontiguousarray(seed, dtype=np.uint64)
     d = np.zeros((n, 2), dtype=np.float32)
     _check(lib.wost_vmm_pdf_sample(device, _fp(r), _fp(w), _u64(s), n, _fp(pdf), _fp(d)), "wost_vmm_pdf_sample")
     return pdf, d

@@ -227,13 +227,18 @@ def vmf_sample(kappa, mu, seed, per_point=1, device=0):
     return out
 
 
-def vmm3_pdf_sample(raw, wi, seed, device=0):
-    """VMM<3,8>::pdf(wi) and ::sample (reference distribution.h:279-345) from 40 raw outputs per point"""
+def vmm3_pdf_sample(raw, wi, seed, device=0, sample=True):
+    """VMM<3,8>::pdf(wi) and ::sample (reference distribution.h:279-345) from 40 raw outputs per point; sample=False: the density
+    alone (a null sample_dir; no stream is seeded, no direction drawn) -> (pdf, None)"""
     lib = capi.load()
     r = np.ascontiguousarray(raw, dtype=np.float32)
     w = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
-    s = np.ascontiguousarray(seed, dtype=np.uint64)
     n = len(w)
+    if not sample:
+        pdf = np.zeros(n, np.float32)
+        _check(lib.wost3_vmm_pdf_sample(device, _fp(r), _fp(w), None, n, _fp(pdf), None), "wost3_vmm_pdf_sample")
+        return pdf, None
+    s = np.ascontiguousarray(seed, dtype=np.uint64)
     pdf, d = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
     _check(lib.wost3_vmm_pdf_sample(device, _fp(r), _fp(w), s.ctypes.data_as(C.POINTER(C.c_uint64)), n, _fp(pdf), _fp(d)), "wost3_vmm_pdf_sample")
     return pdf, d

@@ -483,12 +483,15 @@ class Oracle:
         self.lib.wo3_vmf_sample_batch(_fp(k), _fp(m), s.ctypes.data_as(C.POINTER(C.c_uint64)), len(k), per_point, _fp(out))
         return out
 
-    def vmm3_pdf_sample(self, raw, wi, seed):
+    def vmm3_pdf_sample(self, raw, wi, seed, sample=True):
         r = np.ascontiguousarray(raw, dtype=np.float32)
         w = np.ascontiguousarray(wi, dtype=np.float32)
-        s = np.ascontiguousarray(seed, dtype=np.uint64)
         n = len(w)
         pdf = np.zeros(n, dtype=np.float32)
+        if not sample:      # the density alone: a null dir
+            self.lib.wo3_vmm_pdf_sample(_fp(r), _fp(w), None, n, _fp(pdf), None)
+            return pdf, None
+        s = np.ascontiguousarray(seed, dtype=np.uint64)
         d = np.zeros((n, 3), dtype=np.float32)
         self.lib.wo3_vmm_pdf_sample(_fp(r), _fp(w), s.ctypes.data_as(C.POINTER(C.c_uint64)), n, _fp(pdf), _fp(d))
         return pdf, d
@@ -717,12 +720,15 @@ class Oracle:
                                        C.c_float(loss_scale), _fp(g), _fp(lk))
         return g, lk
 
-    def vmm_pdf_sample(self, raw, wi, seed):
+    def vmm_pdf_sample(self, raw, wi, seed, sample=True):
         r = np.ascontiguousarray(raw, dtype=np.float32)
         w = np.ascontiguousarray(wi, dtype=np.float32)
-        s = np.ascontiguousarray(seed, dtype=np.uint64)
         n = len(w)
         pdf = np.zeros(n, dtype=np.float32)
+        if not sample:      # the density alone: a null dir
+            self.lib.wo_vmm_pdf_sample(_fp(r), _fp(w), None, n, _fp(pdf), None)
+            return pdf, None
+        s = np.ascontiguousarray(seed, dtype=np.uint64)
         d = np.zeros((n, 2), dtype=np.float32)
         self.lib.wo_vmm_pdf_sample(_fp(r), _fp(w), s.ctypes.data_as(C.POINTER(C.c_uint64)), n, _fp(pdf), _fp(d))
         return pdf, d

@@ -4,15 +4,17 @@
  * Best-Fisher rejection sampling in double precision, and the 8-lobe mixture VMM<2,8> built
  * from raw network outputs.  TEST INFRASTRUCTURE ONLY.
  *
- * Restates (paths relative to /root/reference):
+ * Restates (paths relative to the reference's source tree):
  *   util/vonmises.h:17-93 (coefficients, evalPoly, logModifiedBesselFn), :95-118
  *   (rejectionSample), :121-209 (VonMises), integrator/guided/distribution.h:19-45,136-198
  *   (VMFKernel<2>, VMM<2,N>), integrator/guided/train.h:50-79 (output activations),
  *   util/transformation.h:47-50 (frameFromTangent), core/sampler.h:74-85 (nextDouble).
  * Pinned by the reference's own known-answer constants (test/vonmises_test.cu:5-22,57-59,
  * 124-148, commented out there but numerically valid -- SURVEY.md section 4).
- * Transcendentals are libm here and ocml on the GPU: parity is within the 1e-5 relative
- * tolerance the reference's tests use, not bit-exact.
+ * Transcendentals are the deterministic kernels of wost_detmath.h on both sides (fp32 exp / log /
+ * sin / cos, fp64 cospi / log / acos for the rejection sampler): the batch entry points of the
+ * device equal these functions bit for bit, saturated and non-finite raw outputs included
+ * (tests/test_guided_distribution.py, tests/test_guided_saturated.py).
  */
 #include <math.h>
 #include <stddef.h>

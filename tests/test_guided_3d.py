@@ -272,9 +272,10 @@ COUNTERS = ("walk_steps", "walks_started", "walks_absorbed", "walks_truncated", 
 @pytest.mark.parametrize("spp,uf,mgd", [(4, (0.5, 0.5), (10, 10)), (2, (0.0, 0.0), (10, 10)), (2, (0.9, 0.25), (3, 3)), (3, (0.5, 0.5), (0, 0)),
                                         (2, (1.0, 1.0), (10, 10))])
 def test_gpu_frozen_network_walks_match_oracle(orc, spp, uf, mgd):
-    """training off, a random network with pronounced lobes: routing, vMF mixture sampling, MIS pdf, reflection about the
-    Neumann normals of the cube's side faces, throughput -- bit-exact; also with no guided depth (plain steps, R_B without
-    the 0.99 factor) and with uniform fraction 1 (walks routed to the mixture end, :1031)"""
+    """training off, a random network with mild lobes (MLP weights in +-0.3: raw outputs within +-0.83 and log kappa <= 0.65, so kappa <= 1.9
+    and no end of the clamp is touched; test_guided_saturated.py asserts these figures and holds the saturated networks): routing, vMF mixture sampling, MIS pdf,
+    reflection about the Neumann normals of the cube's side faces, throughput -- bit-exact; also with no guided depth (plain
+    steps, R_B without the 0.99 factor) and with uniform fraction 1 (walks routed to the mixture end, :1031)"""
     sd = mixed_cube()
     p = _rand_params3(orc, _cfg(), seed=3, wscale=0.3, gscale=1.0)
     gi, ref = _gpu_and_oracle3(orc, sd, 40, 32, spp, 48, 0, uf=uf, mgd=mgd, params=p)

@@ -29,7 +29,7 @@ KNOBS = ("WOST_GUIDED_MAX_BLOCKS", "WOST_GUIDED_FUSED", "WOST_GUIDED_TAIL_CHUNK"
 
 
 def _lobed_params(oracle, seed=3):
-    # a random network with pronounced lobes (test_gpu_frozen_network_matches_oracle)
+    # the random network of test_gpu_frozen_network_matches_oracle (raw outputs in [-2.70, 2.20], kappa <= 6.2: mild lobes)
     rng = np.random.default_rng(seed)
     n = oracle.net_n_params(default_net_config())
     p = rng.uniform(-0.3, 0.3, n).astype(np.float32)
@@ -63,7 +63,9 @@ def _settings(sc):
     from elaina_amd.guided import GuidedIntegratorSettings
     return GuidedIntegratorSettings(frameSize=(sc["w"], sc["h"]), samplesPerPixel=sc["spp"], trainSppCount=sc["train"],
                                     maxWalkingDepth=sc["depth"], epsilonShell=sc["eps"], batchSize=sc["batch"], minBatchSize=sc["min_batch"],
-                                    trainPixelStride=sc.get("stride", 1), trainPixelOffset=sc.get("offset", 0))
+                                    trainPixelStride=sc.get("stride", 1), trainPixelOffset=sc.get("offset", 0),
+                                    uniformFractionInTrainingPhase=sc.get("uf", (0.5, 0.5))[0],
+                                    uniformFractionInGuidingPhase=sc.get("uf", (0.5, 0.5))[1])
 
 
 def _fused_blocks(capfd):
@@ -116,7 +118,7 @@ def _oracle(oracle, sc, params):
     """the oracle's field and counters, and the network it trained from `params`"""
     gs = guided_settings(sc["w"], sc["h"], sc["spp"], sc["depth"], sc["eps"], sc["aabb"][0], sc["aabb"][1], train_spp_count=sc["train"],
                          batch_size=sc["batch"], min_batch_size=sc["min_batch"], train_pixel_stride=sc.get("stride", 1),
-                         train_pixel_offset=sc.get("offset", 0))
+                         train_pixel_offset=sc.get("offset", 0), uniform_fraction=sc.get("uf", (0.5, 0.5)))
     sd = sc["prob"].as_dict()
     if sc.get("mask") is not None:
         sd["mask"] = sc["mask"]
