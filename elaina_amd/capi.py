@@ -176,10 +176,10 @@ EXPORTS = [
     "wost_vonmises_eval", "wost_vonmises_sample", "wost_vmm_pdf_sample", "wost_vmm_loss_gradients",
     "wost_net_create", "wost_net_destroy", "wost_net_n_params", "wost_net_get_params",
     "wost_net_set_params", "wost_net_set_gradient_buffer", "wost_net_inference", "wost_net_train_step", "wost_net_set_option",
-    "wost_guided_create", "wost_guided_set_sync", "wost_guided_set_frame_callback", "wost_guided_network", "wost_guided_scene", "wost_guided_query_network", "wost_guided_solve", "wost_guided_solve_sharded", "wost_guided_train_set", "wost_guided_set_option", "wost_guided_destroy",
+    "wost_guided_create", "wost_guided_set_sync", "wost_guided_set_frame_callback", "wost_guided_network", "wost_guided_scene", "wost_guided_query_network", "wost_guided_solve", "wost_guided_solve_sharded", "wost_guided_solve_points", "wost_guided_solve_points_dev", "wost_guided_train_set", "wost_guided_set_option", "wost_guided_destroy",
     "wost3_create", "wost3_solve", "wost3_solve_sharded", "wost3_solve_points", "wost3_solve_points_dev", "wost3_closest_point", "wost3_closest_silhouette", "wost3_ray_intersect", "wost3_mesh_build_check",
     "wost3_render_sdf", "wost3_render_source", "wost3_destroy", "wost3_vmf_eval", "wost3_vmf_sample", "wost3_vmm_pdf_sample", "wost3_vmm_loss_gradients",
-    "wost3_net_create", "wost3_guided_create", "wost3_guided_destroy", "wost3_guided_network", "wost3_guided_solve", "wost3_guided_solve_sharded",
+    "wost3_net_create", "wost3_guided_create", "wost3_guided_destroy", "wost3_guided_network", "wost3_guided_solve", "wost3_guided_solve_sharded", "wost3_guided_solve_points", "wost3_guided_solve_points_dev",
     "wost3_guided_query_network", "wost3_guided_train_set", "wost3_guided_scene",
     "wost_last_error", "wost_version", "wost_mesh_build_check",
 ]
@@ -245,6 +245,8 @@ def load():
     L.wost_guided_query_network.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     L.wost_guided_solve.argtypes = [C.c_void_p, fp, C.POINTER(GuidedStats)]
     L.wost_guided_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
+    L.wost_guided_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(GuidedStats)]
+    L.wost_guided_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
     L.wost_guided_train_set.argtypes = [C.c_void_p, C.c_int32, ip, fp, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
     L.wost_guided_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
     L.wost_guided_destroy.argtypes = [C.c_void_p]
@@ -274,6 +276,8 @@ def load():
     L.wost3_guided_scene.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.wost3_guided_solve.argtypes = [C.c_void_p, fp, C.POINTER(GuidedStats)]
     L.wost3_guided_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
+    L.wost3_guided_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(GuidedStats)]
+    L.wost3_guided_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
     L.wost3_guided_query_network.argtypes = [C.c_void_p, fp, C.c_int32, fp]
     L.wost3_guided_train_set.argtypes = [C.c_void_p, C.c_int32, ip, fp, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
     L.wost_last_error.restype = C.c_char_p

@@ -175,7 +175,33 @@ struct GParams {
     int32_t d0_valid;         // d0_d2 holds the query of every evaluation point (after the first fused launch of a solve)
     const uint32_t *order;    // item k of a launch belongs to pixel order[k % n_pixels] (longest expected walk first, wost_order.h); nullptr: tile order
     unsigned long long *dbg;  // WOST_GUIDED_DEBUG: [0] first start, [1] first wave out of pixels, [2] last wave out of pixels, [3] end (100 MHz ticks)
+    // a point solve (wost_guided_solve_points): "pixel" p is point p of `points` (x, y) on the random stream of pixel seed_base + p
+    // of a frame seed_width wide, and n_pixels is the length of the list; nullptr: the frame
+    const float *points;
+    int32_t seed_base, seed_width;
 };
+
+// the random stream of pixel p at the start of a solve
+__device__ __forceinline__ void seed_pixel(const GParams &P, bool points, Pcg &rng, int p)
+{
+    if (points) pcg_seed_pixel(rng, P.seed_base + p, P.seed_width);
+    else pcg_seed_pixel(rng, p, P.st.width);
+}
+
+// whether pixel p is walked by this solve, and its evaluation point.  Frame: the pixels of the solve's shard that the mask leaves.
+// Point solve: no tile, shard or mask -- every point with finite coordinates.
+__device__ __forceinline__ bool start_pixel(const GParams &P, bool points, int p, float &x, float &y)
+{
+    if (points) {
+        x = P.points[2 * (size_t)p]; y = P.points[2 * (size_t)p + 1];
+        return isfinite(x) && isfinite(y);
+    }
+    const int px = p % P.st.width, py = p / P.st.width;
+    const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
+    const bool active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
+    if (active) eval_point(P.probe, px, py, P.st.width, P.st.height, x, y);
+    return active;
+}
 
 // the network as the fused kernel needs it: half precision (image) or fp32 (frag32 / grid32)
 struct FusedNet {
@@ -261,8 +287,10 @@ __global__ __launch_bounds__(256) void begin_sample_kernel(GParams P)
     // queue order = 8x8 pixel tiles (a wave starts with 64 walkers that are neighbours in BOTH
     // directions and visit the same nodes of the tree), row-major when the frame is not made of
     // whole tiles.  The order of the queue has no influence on any result.
+    // A point solve queues its points in the order of the list.
+    const bool points = P.points != nullptr;
     int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (((P.st.width | P.st.height) & 7) == 0 && p < P.n_pixels) {
+    if (!points && ((P.st.width | P.st.height) & 7) == 0 && p < P.n_pixels) {
         const int tiles_x = P.st.width >> 3, tile = p >> 6, in_tile = p & 63;
         p = ((tile / tiles_x) * 8 + (in_tile >> 3)) * P.st.width + (tile % tiles_x) * 8 + (in_tile & 7);
     }
@@ -272,16 +300,13 @@ __global__ __launch_bounds__(256) void begin_sample_kernel(GParams P)
     if (in_frame) {
         if (P.first_sample) {
             Pcg rng;
-            pcg_seed_pixel(rng, p, P.st.width);
+            seed_pixel(P, points, rng, p);
             P.rng[p] = rng.state;
             P.sol[3 * (size_t)p] = 0.0f; P.sol[3 * (size_t)p + 1] = 0.0f; P.sol[3 * (size_t)p + 2] = 0.0f;
             P.hint0[p] = 0;
         }
         P.cur_depth[p] = 0;
-        const int px = p % P.st.width, py = p / P.st.width;
-        const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
-        active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
-        if (active) eval_point(P.probe, p % P.st.width, p / P.st.width, P.st.width, P.st.height, x, y);
+        active = start_pixel(P, points, p, x, y);
     }
     const uint32_t s = block_push(active, P.count_out);
     wave_count(active, &my_stats(P.stats)->started);
@@ -628,7 +653,7 @@ __global__ __launch_bounds__(256) void guided_init_kernel(GParams P)
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P.n_pixels) return;
     Pcg r0;
-    pcg_seed_pixel(r0, p, P.st.width);
+    seed_pixel(P, P.points != nullptr, r0, p);
     P.rng[p] = r0.state;
     P.sol[3 * (size_t)p] = 0.0f; P.sol[3 * (size_t)p + 1] = 0.0f; P.sol[3 * (size_t)p + 2] = 0.0f;
     P.hint0[p] = 0;
@@ -663,7 +688,9 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-template <bool EMISSIVE, bool TREE, bool SOURCE, bool HALF>
+// POINTS = true: the launch of a point solve (wost_guided_solve_points) -- a refill takes a caller's point instead of a pixel of
+// the frame.  A template flag, as in walk3_kernel, so that the frame instantiations stay what they were (EXPERIMENTS 36).
+template <bool EMISSIVE, bool TREE, bool SOURCE, bool HALF, bool POINTS>
 __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GParams P, FusedNet F)
 {
     constexpr int kFusedThreads = fused_threads(HALF), kXchWords = fused_xch_words(HALF);
@@ -720,14 +747,18 @@ __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GPar
     // walks while the chip ran empty.  Which lane walks a sample has no influence on any result.
     const bool handed = P.n_samples > 1;
     const uint32_t n_items = n_slots * (uint32_t)P.n_samples;
-    const bool tiled = ((P.st.width | P.st.height) & 7) == 0;
+    const bool tiled = !POINTS && ((P.st.width | P.st.height) & 7) == 0;      // (a point solve takes its points in the order of the list)
     bool dbg_out = false;
     if (P.dbg && lane == 0) atomicMin(P.dbg + 0, wall_clock64());
 
     // start sample `sidx` of pixel `pid` in this lane (begin_sample_kernel for one pixel)
     auto begin_walk = [&]() {
-        const int px = (int)pid % P.st.width, py = (int)pid / P.st.width;
-        eval_point(P.probe, px, py, P.st.width, P.st.height, x, y);
+        if (POINTS) {
+            x = P.points[2 * (size_t)pid]; y = P.points[2 * (size_t)pid + 1];
+        } else {
+            const int px = (int)pid % P.st.width, py = (int)pid / P.st.width;
+            eval_point(P.probe, px, py, P.st.width, P.st.height, x, y);
+        }
         on_n = false; thp = 1.0f; nx = 0.0f; ny = 0.0f; depth = 0;
         hint = ld_px(P.hint0 + pid);
         rng.state = ld_px(P.rng + pid);
@@ -791,16 +822,21 @@ __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GPar
                         // (a launch of several samples per pixel has these set before it starts: its items of a pixel may arrive in any order)
                         if (P.first_sample) {
                             Pcg r0;
-                            pcg_seed_pixel(r0, p, P.st.width);
+                            seed_pixel(P, POINTS, r0, p);
                             st_px(P.rng + p, r0.state);
                             st_px(P.sol + 3 * (size_t)p, 0.0f); st_px(P.sol + 3 * (size_t)p + 1, 0.0f); st_px(P.sol + 3 * (size_t)p + 2, 0.0f);
                             st_px(P.hint0 + p, (int32_t)0);
                         }
                         P.cur_depth[p] = 0;
                     }
-                    const int px = p % P.st.width, py = p / P.st.width;
-                    const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
-                    const bool active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
+                    bool active;
+                    if (POINTS) {
+                        active = isfinite(P.points[2 * (size_t)p]) && isfinite(P.points[2 * (size_t)p + 1]);
+                    } else {
+                        const int px = p % P.st.width, py = p / P.st.width;
+                        const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
+                        active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
+                    }
                     if (active) {
                         bool start = true;
                         sidx = 0;
@@ -814,7 +850,7 @@ __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GPar
                             begin_walk();
                         }
                     }
-                    // inactive pixel (mask, other shard) or a credit left with the pixel's walker: the lane asks again on the next trip
+                    // inactive pixel (mask, other shard, a point that is not finite) or a credit left with the pixel's walker: the lane asks again on the next trip
                 }
             }
         }
@@ -1077,6 +1113,8 @@ struct wost_guided {
     hipEvent_t ev_ts = nullptr;           // the training set of a sample is complete (walk stream)
     hipEvent_t ev_train[2] = {nullptr, nullptr};   // training pass k is complete and its weights are in snap[k % 2] (training stream)
     EventRing train_events;               // device time of the training passes in that mode
+    float *pts_buf = nullptr;             // wost_guided_solve_points: the caller's host list on the device (grown on demand)
+    size_t pts_cap = 0;                   // points it holds
 };
 
 #define G_TRY(expr)                                                                                      \
@@ -1302,7 +1340,20 @@ struct GuidedPlan {
     // that the network a sample sees is a few training passes older.  Both need the fused kernel; a solve with intermediate frames keeps the reference's order.
     int n_trained, group;
     bool reordered;
+    // what a point solve changes (wost_guided_solve_points; job.pts == nullptr: the frame): the walkers are the n points of the
+    // caller's list -- the plan is built for them, not for the frame -- and the call may override trainSppCount
+    PointJob job;
+    int n;                            // walkers of the solve: the pixels of the frame, or the points of the list
+    int train_spp_count;
 };
+
+// the guiding state of sample `sample` of this solve
+static GuidePhase phase_of(const wost_guided *g, const GuidedPlan &pl, int sample)
+{
+    wost_guided_settings s = g->gs;
+    s.train_spp_count = pl.train_spp_count;
+    return phase_at(s, sample);
+}
 
 // what the steps of a solve count and hand to each other
 struct GuidedRun {
@@ -1317,22 +1368,23 @@ struct GuidedRun {
 
 // The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource), the network's precision
 // H(alf).  These are all the walk instantiations there are:
-//   G_FUSED  guided_sample_kernel<E, T, S, H>   G_SEPARATE  separate_kernel<E, T, S>   G_TAIL  tail_kernel<E, T, S>   G_SAMPLE  sample_kernel<T>
+//   G_FUSED  guided_sample_kernel<E, T, S, H, P(oints)>   G_SEPARATE  separate_kernel<E, T, S>   G_TAIL  tail_kernel<E, T, S>   G_SAMPLE  sample_kernel<T>
 enum GKernel { G_FUSED, G_SEPARATE, G_TAIL, G_SAMPLE };
 template <bool E, bool T, bool S>
-static const void *guided_kernel_of(GKernel kind, bool half)
+static const void *guided_kernel_of(GKernel kind, bool half, bool points)
 {
-    if (kind == G_FUSED) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false>);
+    if (kind == G_FUSED && points) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, true>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, true>);
+    if (kind == G_FUSED) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, false>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, false>);
     if (kind == G_SEPARATE) return reinterpret_cast<const void *>(separate_kernel<E, T, S>);
     return kind == G_TAIL ? reinterpret_cast<const void *>(tail_kernel<E, T, S>) : reinterpret_cast<const void *>(sample_kernel<T>);
 }
 static const void *guided_kernel(GKernel k, const GuidedPlan &pl)
 {
-    const bool h = pl.fused_half;
-    if (pl.emissive && pl.tree) return pl.source ? guided_kernel_of<true, true, true>(k, h) : guided_kernel_of<true, true, false>(k, h);
-    if (pl.emissive) return pl.source ? guided_kernel_of<true, false, true>(k, h) : guided_kernel_of<true, false, false>(k, h);
-    if (pl.tree) return pl.source ? guided_kernel_of<false, true, true>(k, h) : guided_kernel_of<false, true, false>(k, h);
-    return pl.source ? guided_kernel_of<false, false, true>(k, h) : guided_kernel_of<false, false, false>(k, h);
+    const bool h = pl.fused_half, p = pl.job.pts != nullptr;
+    if (pl.emissive && pl.tree) return pl.source ? guided_kernel_of<true, true, true>(k, h, p) : guided_kernel_of<true, true, false>(k, h, p);
+    if (pl.emissive) return pl.source ? guided_kernel_of<true, false, true>(k, h, p) : guided_kernel_of<true, false, false>(k, h, p);
+    if (pl.tree) return pl.source ? guided_kernel_of<false, true, true>(k, h, p) : guided_kernel_of<false, true, false>(k, h, p);
+    return pl.source ? guided_kernel_of<false, false, true>(k, h, p) : guided_kernel_of<false, false, false>(k, h, p);
 }
 // one launch of a walk kernel, counted; Fn: the network image of a G_FUSED launch (the kernels per depth take P alone)
 static void launch_guided(GKernel kind, const GuidedPlan &pl, GuidedRun &run, unsigned grid, hipStream_t st, GParams P, FusedNet Fn = FusedNet{})
@@ -1355,18 +1407,23 @@ static bool fused_shape(const NetLayout *L, FusedNet &Fn)
     return true;
 }
 
+// intermediate frames belong to the frame solve
+static bool wants_frames(const wost_guided *g, const GuidedPlan &pl) { return g->frame_fn && !pl.job.pts; }
+
 static int env_int(const char *name, int fallback, int at_least)
 {
     const char *w = std::getenv(name);
     return w ? std::max(at_least, std::atoi(w)) : fallback;
 }
 
-static GuidedPlan guided_plan(wost_guided *g)
+static GuidedPlan guided_plan(wost_guided *g, const PointJob &job)
 {
     const wost_guided_settings &s = g->gs;
     const SceneView &v = g->view;
-    const size_t N = g->n_pixels;
+    const size_t N = job.pts ? (size_t)job.n : g->n_pixels;
     GuidedPlan pl{};
+    pl.job = job; pl.n = (int)N;
+    pl.train_spp_count = job.pts && job.train_spp_count >= 0 ? job.train_spp_count : s.train_spp_count;
     pl.emissive = v.nm.n_segs > 0 && v.nm.emissive; pl.tree = v.nm.n_segs > WOST_FLAT_MAX; pl.source = v.src.rgb != nullptr;
     pl.stack_words = 3 * std::max(v.dm.n_segs > 0 ? v.dm.levels : 1, v.nm.n_segs > 0 ? v.nm.levels : 1) + 1;
     pl.lds = (size_t)pl.stack_words * 256 * sizeof(uint32_t);
@@ -1379,8 +1436,9 @@ static GuidedPlan guided_plan(wost_guided *g)
         pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
     g->last_train_offset = pl.train_offset;
-    pl.n_train_pixels = (int)((N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride);
-    pl.n_train_blocks = (pl.n_train_pixels + 255) / 256;
+    // (a list may be shorter than the offset: no training pixel, and one block that finds none)
+    pl.n_train_pixels = N > pl.train_offset ? (int)((N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride) : 0;
+    pl.n_train_blocks = std::max(1, (pl.n_train_pixels + 255) / 256);
     const char *env = std::getenv("WOST_GUIDED_FUSED");
     const bool wanted = !(env && env[0] == '0');
     HalfNetView hv{}; F32NetView fv{};
@@ -1412,8 +1470,8 @@ static GuidedPlan guided_plan(wost_guided *g)
         pl.fused = fits && hipFuncSetAttribute(guided_kernel(G_FUSED, pl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_fused) == hipSuccess;
         if (fits && !pl.fused) (void)hipGetLastError();
     }
-    pl.n_trained = std::min(s.spp, s.train_spp_count);
-    pl.reordered = pl.fused && pl.n_trained > 0 && !g->frame_fn && !pl.dbg && (g->pipeline || g->train_group > 1);
+    pl.n_trained = std::min(s.spp, pl.train_spp_count);
+    pl.reordered = pl.fused && pl.n_trained > 0 && !wants_frames(g, pl) && !pl.dbg && (g->pipeline || g->train_group > 1);
     pl.group = pl.reordered ? std::min(std::max(g->train_group, 1), pl.n_trained) : 1;
     return pl;
 }
@@ -1435,7 +1493,9 @@ static GParams base_params(const wost_guided *g, const GuidedPlan &pl, int shard
     GParams P{};
     P.dm = v.dm; P.nm = v.nm; P.st = v.st; P.probe = v.probe; P.src = v.src; P.box = g->box; P.mask = v.mask;
     P.rng = g->rng; P.sol = g->sol; P.cur_depth = g->cur_depth; P.rec = g->rec; P.hint0 = g->hint0;
-    P.rec_ld = N * (size_t)g->rec_sets; P.net_in = g->net_in; P.net_out = g->net_out; P.net_ld = N; P.stats = g->stats; P.n_pixels = (int32_t)N; P.stack_stride = 256;
+    // (rec_ld and net_ld are the arrays' allocated leading dimensions; n_pixels counts the walkers of this solve: record set j starts at column j * n_pixels)
+    P.rec_ld = N * (size_t)g->rec_sets; P.net_in = g->net_in; P.net_out = g->net_out; P.net_ld = N; P.stats = g->stats; P.n_pixels = (int32_t)pl.n; P.stack_stride = 256;
+    P.points = pl.job.pts; P.seed_base = pl.job.seed_base; P.seed_width = pl.job.seed_width;
     P.max_train_depth = g->gs.max_train_depth; P.train_offset = pl.train_offset; P.train_stride = (uint32_t)g->gs.train_pixel_stride; P.shard_index = shard_index; P.shard_count = shard_count;
     P.d0_d2 = g->d0_d2; P.cursor = g->cursor; P.pstate = g->pstate; P.stack_words = pl.fused_stack_words;
     P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.tail_chunk = pl.tail_chunk; P.tail_margin_pct = pl.tail_margin_pct;
@@ -1466,7 +1526,7 @@ struct DivisorGuard { wost_net_handle net; ~DivisorGuard() { net_set_gradient_di
 static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GParams P, const FusedNet &Fn, hipStream_t st,
                         const GuidePhase &ph, int sample, int n_samples)
 {
-    const int N = (int)g->n_pixels;
+    const int N = pl.n;
     if (pl.dbg) {
         const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
         G_TRY(hipMemcpyAsync(g->dbg, init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -1508,10 +1568,10 @@ static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GP
 // the training set of record set j of the launch that has just walked, in (pixel, record) order, into `ts`; its size arrives in host_counts[1 + j]
 static int enqueue_train_set(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, hipStream_t st, int j, const TrainSet &ts)
 {
-    const size_t N = g->n_pixels;
+    const size_t n = (size_t)pl.n;      // record set j: the columns from j * (walkers of the solve) on, as the walk kernels count them
     const GAabb &b = g->box;
     TrainSetParams<2> T{{b.minx, b.miny}, {b.maxx, b.maxy}, {b.cx, b.cy}, {b.ex, b.ey}};
-    T.rec = g->rec + (size_t)j * N; T.rec_ld = N * (size_t)g->rec_sets; T.cur_depth = g->cur_depth + (size_t)j * N;
+    T.rec = g->rec + (size_t)j * n; T.rec_ld = g->n_pixels * (size_t)g->rec_sets; T.cur_depth = g->cur_depth + (size_t)j * n;
     T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->gs.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
     run.launches += 3;
     return wost::enqueue_train_set(T, pl.n_train_blocks, st, g->host_counts + 1 + j);
@@ -1584,7 +1644,7 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
     std::vector<int> first(1, 0);      // group k: the samples first[k] .. first[k + 1] - 1
     while (first.back() < pl.n_trained) first.push_back(first.back() + group_at(pl, first.back()));
     const int n_groups = (int)first.size() - 1;
-    const GuidePhase ph = phase_at(g->gs, 0);
+    const GuidePhase ph = phase_of(g, pl, 0);
     // (the training stream starts behind whatever the walk stream has been given so far)
     G_TRY(hipEventRecord(g->ev_ts, stream));
     G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
@@ -1626,18 +1686,18 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
 }
 
 // intermediate frames (reference integrator.cu:1049-1081): bit 0 = the spp schedule asks for one after sample j, bit 1 = the time schedule
-static int frame_due(const wost_guided *g, int j)
+static int frame_due(const wost_guided *g, const GuidedPlan &pl, int j)
 {
-    if (!g->frame_fn) return 0;
+    if (!wants_frames(g, pl)) return 0;
     const bool by_spp = g->frame_spp_every > 0 && j % g->frame_spp_every == 0 && j < g->frame_spp_until;
     const bool by_time = g->frame_time_every > 0 && j % g->frame_time_every == 0;
     return (by_spp ? 1 : 0) | (by_time ? 2 : 0);
 }
 
 // ... and the frame after `sample`, if one is due
-static int emit_frame(wost_guided *g, const GuidedRun &run, hipStream_t stream, int sample)
+static int emit_frame(wost_guided *g, const GuidedPlan &pl, const GuidedRun &run, hipStream_t stream, int sample)
 {
-    const int N = (int)g->n_pixels, due = frame_due(g, sample);
+    const int N = (int)g->n_pixels, due = frame_due(g, pl, sample);
     if (!due) return WOST_OK;
     launch_resolve(g->sol, N, (float)(sample + 1), g->field, stream);
     std::vector<float> frame((size_t)N * 3);
@@ -1657,11 +1717,11 @@ static int samples_this_launch(const wost_guided *g, const GuidedPlan &pl, const
     if (!ph.training) {
         // nothing is trained between the remaining samples: one launch runs them all, up to the next intermediate frame the caller asked for
         int last = sample;
-        while (last < g->gs.spp - 1 && !frame_due(g, last)) ++last;
+        while (last < g->gs.spp - 1 && !frame_due(g, pl, last)) ++last;
         n_run = std::min(last - sample + 1, pl.samples_per_launch);
     }
     n_run = std::min(n_run, 0xffff);      // a pixel's state word counts the samples of a launch in 16 bits (arrived << 16 | complete)
-    return (int)std::min<uint64_t>((uint64_t)n_run, std::max<uint64_t>(1, 0xffffffffull / std::max<uint64_t>(g->n_pixels, 1)));      // (items of a launch are counted in 32 bits)
+    return (int)std::min<uint64_t>((uint64_t)n_run, std::max<uint64_t>(1, 0xffffffffull / std::max<uint64_t>((uint64_t)pl.n, 1)));      // (items of a launch are counted in 32 bits)
 }
 
 // One sample on the one-launch-per-depth path: begin, then per depth separate / network / sample, and the tail once nothing
@@ -1669,7 +1729,7 @@ static int samples_this_launch(const wost_guided *g, const GuidedPlan &pl, const
 static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GParams P, const GuidePhase &ph, int sample, hipStream_t stream)
 {
     const wost_guided_settings &s = g->gs;
-    const int N = (int)g->n_pixels;
+    const int N = pl.n;
     P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.first_sample = sample == 0;
     int cur = 0;     // queue holding the evaluation points of this depth
     G_TRY(hipMemsetAsync(g->counts + cur, 0, sizeof(uint32_t), stream));
@@ -1700,7 +1760,7 @@ static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, 
         if (polled == depth && n_cur == 0) break;      // known to be empty
         const uint32_t n_out = n_cur;                  // an upper bound
         const size_t ev = g->net_events.begin(stream);
-        const int rc = net_inference_dev(g->net, g->net_in, g->counts + nxt, (int)n_out, g->net_out, true, stream, (size_t)N);
+        const int rc = net_inference_dev(g->net, g->net_in, g->counts + nxt, (int)n_out, g->net_out, true, stream, P.net_ld);
         g->net_events.end(ev, stream);
         if (rc != WOST_OK) return rc;      // (counted by the network)
         P.in = g->q[nxt]; P.count_in = g->counts + nxt;
@@ -1729,10 +1789,11 @@ static int train_after_walk(wost_guided *g, const GuidedPlan &pl, GuidedRun &run
 }
 
 // resolve, the copies of the field, the counters folded and the stats
-static int finish_guided(wost_guided *g, const GuidedRun &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
+static int finish_guided(wost_guided *g, const GuidedPlan &pl, const GuidedRun &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
 {
-    const int N = (int)g->n_pixels;
-    launch_resolve(g->sol, N, (float)g->gs.spp, g->field, stream);
+    const int N = pl.n;
+    if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 2, N, (float)g->gs.spp, g->field, stream);
+    else launch_resolve(g->sol, N, (float)g->gs.spp, g->field, stream);
     G_TRY(hipGetLastError());
     if (field_host) G_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) G_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -1752,8 +1813,10 @@ static int finish_guided(wost_guided *g, const GuidedRun &run, hipStream_t strea
     return WOST_OK;
 }
 
-// the shared driver: field_host (n_pixels*3, may be null) and/or field_dev (device, n_pixels*3)
-static int run_guided(wost_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats)
+// the shared driver: field_host (n*3 floats for the n walkers of the solve, may be null) and/or field_dev (device, n*3); `job`: the
+// caller's points instead of the frame's pixels (no shards then)
+static int run_guided(wost_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats,
+                      const PointJob &job = PointJob{})
 {
     GuidedRun run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
     DivisorGuard divisor{g->net};
@@ -1762,7 +1825,7 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
     G_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
     int rc = sync_rank_count(g);      // (before the plan: a solve that ends here has drawn nothing from the host sampler)
     if (rc != WOST_OK) return rc;
-    const GuidedPlan pl = guided_plan(g);
+    const GuidedPlan pl = guided_plan(g, job);
     rc = grow_record_sets(g, pl.group, stream);
     if (rc != WOST_OK) return rc;
     const GParams P = base_params(g, pl, shard_index, shard_count);
@@ -1773,16 +1836,16 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
         sample = pl.n_trained;
     }
     for (; sample < g->gs.spp; ++sample) {
-        const GuidePhase ph = phase_at(g->gs, sample);
+        const GuidePhase ph = phase_of(g, pl, sample);
         // both paths give the same results; the fused one is used whenever it exists
         const int n_run = pl.fused ? samples_this_launch(g, pl, ph, sample) : 1;      // samples this iteration covers
         rc = pl.fused ? launch_fused(g, pl, run, P, pl.F, stream, ph, sample, n_run) : walk_per_depth(g, pl, run, P, ph, sample, stream);
         if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, stream, n_run);
         sample += n_run - 1;     // the index of the last sample this iteration has run
-        if (rc == WOST_OK) rc = emit_frame(g, run, stream, sample);
+        if (rc == WOST_OK) rc = emit_frame(g, pl, run, stream, sample);
         if (rc != WOST_OK) return rc;
     }
-    return finish_guided(g, run, stream, field_host, field_dev, stats);
+    return finish_guided(g, pl, run, stream, field_host, field_dev, stats);
 }
 
 extern "C" {
@@ -1799,6 +1862,52 @@ int wost_guided_solve_sharded(wost_guided_handle g, int32_t shard_index, int32_t
     if (!g || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
     if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
     return run_guided(g, shard_index, shard_count, nullptr, field_rgb_dev, stats);
+}
+
+// the check of a point solve that needs the handle: the per-pixel state, the record sets and the queues are sized by the frame
+static int check_point_capacity(const wost_guided *g, int32_t n)
+{
+    if ((size_t)n > g->n_pixels)
+        return set_error(WOST_ERR_INVALID, "a guided point solve takes at most width * height = " + std::to_string(g->n_pixels) + " points per call (the handle's capacity); got " + std::to_string(n));
+    return WOST_OK;
+}
+
+int wost_guided_solve_points_dev(wost_guided_handle g, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                                 int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats)
+{
+    int rc = check_guided_point_solve(g, pts_xy_dev, field_rgb_dev, n, seed_base, seed_width, train_spp_count);
+    if (rc != WOST_OK) return rc;
+    if (n == 0) {
+        if (stats) *stats = wost_guided_stats{};
+        return WOST_OK;
+    }
+    rc = check_point_capacity(g, n);
+    if (rc != WOST_OK) return rc;
+    return run_guided(g, 0, 1, nullptr, field_rgb_dev, stats, PointJob{pts_xy_dev, n, seed_base, seed_width, train_spp_count});
+}
+
+int wost_guided_solve_points(wost_guided_handle g, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width,
+                             int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats)
+{
+    int rc = check_guided_point_solve(g, pts_xy, field_rgb, n, seed_base, seed_width, train_spp_count);
+    if (rc == WOST_OK) rc = check_points_finite(pts_xy, n, 2);
+    if (rc != WOST_OK) return rc;
+    if (n == 0) {
+        if (stats) *stats = wost_guided_stats{};
+        return WOST_OK;
+    }
+    rc = check_point_capacity(g, n);
+    if (rc != WOST_OK) return rc;
+    G_TRY(hipSetDevice(g->device));
+    if (g->pts_cap < (size_t)n) {
+        // (nothing on the device reads the list between two solves)
+        gfree_one(g, g->pts_buf);
+        g->pts_buf = nullptr; g->pts_cap = 0;
+        G_TRY(device_alloc(g->allocs, &g->pts_buf, (size_t)n * 2));
+        g->pts_cap = (size_t)n;
+    }
+    G_TRY(hipMemcpyAsync(g->pts_buf, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, g->view.stream));
+    return run_guided(g, 0, 1, field_rgb, nullptr, stats, PointJob{g->pts_buf, n, seed_base, seed_width, train_spp_count});
 }
 
 }  // extern "C"

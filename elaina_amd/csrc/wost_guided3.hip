@@ -82,6 +82,10 @@ struct G3Params {
     // one walker per lane, and a wave's 64 queries through its pools take as long as they take; spread over more waves the same
     // queries run on more CUs at once (the lanes without a walker work on the other lanes' tree nodes)
     int32_t lane_shift;
+    // a point solve (wost3_guided_solve_points): "pixel" p is point p of `points` (x, y, z) on the random stream of pixel seed_base + p
+    // of a frame seed_width wide, and n_pixels is the length of the list; nullptr: the frame
+    const float *points;
+    int32_t seed_base, seed_width;
 };
 
 // the walker (pixel or queue entry) of this thread, or -1
@@ -145,18 +149,26 @@ __global__ __launch_bounds__(256) void g3_begin_kernel(G3Params P)
     if (p < P.n_pixels) {
         if (P.first_sample) {
             Pcg rng;
-            pcg_seed_pixel(rng, p, P.st.width);
+            if (P.points) pcg_seed_pixel(rng, P.seed_base + p, P.seed_width);
+            else pcg_seed_pixel(rng, p, P.st.width);
             P.rng[p] = rng.state;
             P.sol[3 * (size_t)p] = 0.0f; P.sol[3 * (size_t)p + 1] = 0.0f; P.sol[3 * (size_t)p + 2] = 0.0f;
             P.hint0[p] = -1;
         }
         P.cur_depth[p] = 0;
-        const int px = p % P.st.width, py = p / P.st.width;
-        const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
-        active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
+        V3 x = v3(0.0f, 0.0f, 0.0f);
+        if (P.points) {
+            // no tile, shard or mask: every point with finite coordinates is walked
+            x = v3(P.points[3 * (size_t)p], P.points[3 * (size_t)p + 1], P.points[3 * (size_t)p + 2]);
+            active = isfinite(x.x) && isfinite(x.y) && isfinite(x.z);
+        } else {
+            const int px = p % P.st.width, py = p / P.st.width;
+            const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
+            active = (tile % P.shard_count) == P.shard_index && (P.mask == nullptr || P.mask[p] != 0);
+            if (active) x = eval_point3(P.probe, px, py, P.st.width, P.st.height);
+        }
         P.state[p] = active ? 1 : 0;
         if (active) {
-            const V3 x = eval_point3(P.probe, px, py, P.st.width, P.st.height);
             P.wx[3 * (size_t)p] = x.x; P.wx[3 * (size_t)p + 1] = x.y; P.wx[3 * (size_t)p + 2] = x.z;
             P.wn[3 * (size_t)p] = 0.0f; P.wn[3 * (size_t)p + 1] = 0.0f; P.wn[3 * (size_t)p + 2] = 0.0f;
             P.wthp[p] = 1.0f;
@@ -689,6 +701,8 @@ struct wost3_guided {
     uint32_t *host_word = nullptr;      // pinned
     uint32_t last_train_n = 0;
     uint64_t host_rng = 0;
+    float *pts_buf = nullptr;           // wost3_guided_solve_points: the caller's host list on the device (grown on demand)
+    size_t pts_cap = 0;                 // points it holds
 };
 
 static void g3_free(wost3_guided *g)
@@ -715,7 +729,20 @@ struct G3Plan {
     uint32_t train_offset; int n_train_pixels, n_train_blocks;      // trainPixelOffset of this solve
     bool fused;                       // a whole sample in one launch (WOST3_G_FUSED=0 / 1: never / always)
     G3Net F;                          // the network's fp32 image for it
+    // what a point solve changes (wost3_guided_solve_points; job.pts == nullptr: the frame): the walkers are the n points of the caller's
+    // list -- the plan is built for them, not for the frame -- and the call may override trainSppCount
+    PointJob job;
+    int n;                            // walkers of the solve: the pixels of the frame, or the points of the list
+    int train_spp_count;
 };
+
+// the guiding state of sample `sample` of this solve
+static GuidePhase phase_of(const wost3_guided *g, const G3Plan &pl, int sample)
+{
+    wost3_guided_settings s = g->s;
+    s.train_spp_count = pl.train_spp_count;
+    return phase_at(s, sample);
+}
 
 // The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource).  These are all the walk instantiations there are:
 //   G3_FUSED  g3_fused_kernel<E, T, S>   G3_SEPARATE  g3_separate_kernel<E, T, S>   G3_TAIL  g3_tail_kernel<E, T, S>   G3_SAMPLE  g3_sample_kernel<T>
@@ -735,12 +762,14 @@ static const void *g3_kernel(G3Kernel k, const G3Plan &pl)
     return pl.source ? g3_kernel_of<false, false, true>(k) : g3_kernel_of<false, false, false>(k);
 }
 
-static G3Plan g3_plan(wost3_guided *g)
+static G3Plan g3_plan(wost3_guided *g, const PointJob &job)
 {
     const wost3_context *c = g->scene;
     const wost3_guided_settings &s = g->s;
-    const int N = s.width * s.height;
+    const int N = job.pts ? job.n : s.width * s.height;
     G3Plan pl{};
+    pl.job = job; pl.n = N;
+    pl.train_spp_count = job.pts && job.train_spp_count >= 0 ? job.train_spp_count : s.train_spp_count;
     const int d_levels = c->dm.view.n_tris > 0 ? c->dm.view.levels : 1, n_levels = c->nm.view.n_tris > 0 ? c->nm.view.levels : 1;
     pl.emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive; pl.ntree = c->nm.view.n_tris > WOST3_FLAT_MAX; pl.source = c->src.rgb != nullptr;
     pl.stack_words = 3 * std::max(d_levels, n_levels) + 4;
@@ -759,7 +788,9 @@ static G3Plan g3_plan(wost3_guided *g)
         x.u = (host_pcg_next(g->host_rng, 1u) >> 9) | 0x3f800000u;      // the integrator's host sampler: seed of the handle, increment 1
         pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
-    pl.n_train_pixels = (int)(((size_t)N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride); pl.n_train_blocks = (pl.n_train_pixels + 255) / 256;
+    // (a list may be shorter than the offset: no training pixel, and one block that finds none)
+    pl.n_train_pixels = (size_t)N > pl.train_offset ? (int)(((size_t)N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride) : 0;
+    pl.n_train_blocks = std::max(1, (pl.n_train_pixels + 255) / 256);
     // walkers per lane of the walk kernels: spread out while all blocks of the frame are still resident at once (two blocks per CU: the
     // stack columns and the task pools take 46 to 64 KB of LDS).  Round 4 spread as far as 1.5 x three blocks per CU: a frame of 256^2
     // then ran its blocks in two rounds, each as long as its longest walk (the shell scene, 16 samples: 118 -> 89 ms with one round)
@@ -819,7 +850,8 @@ static G3Params g3_base_params(const wost3_guided *g, const G3Plan &pl, int shar
     const wost3_context *c = g->scene;
     G3Params P{};
     P.dm = c->dm.view; P.nm = c->nm.view; P.st = c->dst; P.probe = c->probe; P.mask = c->mask; P.box = g->box; P.src = c->src;
-    P.n_pixels = g->s.width * g->s.height; P.shard_index = shard_index; P.shard_count = shard_count;
+    P.n_pixels = pl.n; P.shard_index = shard_index; P.shard_count = shard_count;      // (the walkers of this solve; also the leading dimension of its records)
+    P.points = pl.job.pts; P.seed_base = pl.job.seed_base; P.seed_width = pl.job.seed_width;
     P.rng = g->rng; P.sol = g->sol; P.cur_depth = g->cur_depth; P.rec = g->rec; P.state = g->state; P.wx = g->wx; P.wn = g->wn;
     P.wthp = g->wthp; P.wrb = g->wrb; P.won = g->won; P.whint = g->whint; P.hint0 = g->hint0;
     // (counters: [1] the queue, [0] and [2] the live lists written at even / odd depths)
@@ -889,7 +921,7 @@ static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, hipSt
     const auto t0 = std::chrono::high_resolution_clock::now();
     TrainSetParams<3> T{};
     for (int a = 0; a < 3; ++a) { T.min[a] = g->box.min[a]; T.max[a] = g->box.max[a]; T.c[a] = g->box.c[a]; T.e[a] = g->box.e[a]; }
-    T.rec = g->rec; T.rec_ld = (size_t)g->s.width * g->s.height; T.cur_depth = g->cur_depth;
+    T.rec = g->rec; T.rec_ld = (size_t)pl.n; T.cur_depth = g->cur_depth;      // (rec3_at: the records' leading dimension is the walkers of the solve)
     T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->s.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = g->ts;
     run.launches += 3;
     int rc = enqueue_train_set(T, pl.n_train_blocks, stream, g->host_word);
@@ -907,8 +939,9 @@ static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, hipSt
 // resolve (not counted), the copies of the field, the counters folded and the stats
 static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
 {
-    const int N = g->s.width * g->s.height;
-    launch_resolve(g->sol, N, (float)g->s.spp, g->field, stream);
+    const int N = pl.n;
+    if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 3, N, (float)g->s.spp, g->field, stream);
+    else launch_resolve(g->sol, N, (float)g->s.spp, g->field, stream);
     W3_TRY(hipGetLastError());
     if (field_host) W3_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
     if (field_dev) W3_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -928,17 +961,19 @@ static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, h
     return WOST_OK;
 }
 
-// the shared driver: field_host (n_pixels*3, may be null) and/or field_dev (device, n_pixels*3)
-static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats)
+// the shared driver: field_host (n*3 floats for the n walkers of the solve, may be null) and/or field_dev (device, n*3); `job`: the
+// caller's points instead of the frame's pixels (no shards then)
+static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats,
+                       const PointJob &job = PointJob{})
 {
     G3Run run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
     W3_TRY(hipSetDevice(g->device));
     hipStream_t stream = g->scene->stream;
-    const G3Plan pl = g3_plan(g);      // (the draw of the training-pixel offset: before any launch)
+    const G3Plan pl = g3_plan(g, job);      // (the draw of the training-pixel offset: before any launch)
     W3_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
     const G3Params P = g3_base_params(g, pl, shard_index, shard_count);
     for (int sample = 0; sample < g->s.spp; ++sample) {
-        const GuidePhase ph = phase_at(g->s, sample);
+        const GuidePhase ph = phase_of(g, pl, sample);
         // both paths give the same results
         int rc = pl.fused ? walk_fused(pl, run, P, ph, sample, stream) : walk_per_depth(g, pl, run, P, ph, sample, stream);
         if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, stream);
@@ -1027,6 +1062,56 @@ int wost3_guided_solve_sharded(wost3_guided_handle h, int32_t shard_index, int32
     if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
     if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
     return run_guided3(h, shard_index, shard_count, nullptr, field_rgb_dev, stats);
+}
+
+// the check of a point solve that needs the handle: the per-pixel state, the records and the queues are sized by the frame
+static int check_point_capacity3(const wost3_guided *g, int32_t n)
+{
+    const size_t cap = (size_t)g->s.width * g->s.height;
+    if ((size_t)n > cap)
+        return set_error(WOST_ERR_INVALID, "a guided point solve takes at most width * height = " + std::to_string(cap) + " points per call (the handle's capacity); got " + std::to_string(n));
+    return WOST_OK;
+}
+
+int wost3_guided_solve_points_dev(wost3_guided_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                                  int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats)
+{
+    int rc = check_guided_point_solve(h, pts_xyz_dev, field_rgb_dev, n, seed_base, seed_width, train_spp_count);
+    if (rc != WOST_OK) return rc;
+    if (n == 0) {
+        if (stats) *stats = wost_guided_stats{};
+        return WOST_OK;
+    }
+    rc = check_point_capacity3(h, n);
+    if (rc != WOST_OK) return rc;
+    return run_guided3(h, 0, 1, nullptr, field_rgb_dev, stats, PointJob{pts_xyz_dev, n, seed_base, seed_width, train_spp_count});
+}
+
+int wost3_guided_solve_points(wost3_guided_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width,
+                              int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats)
+{
+    int rc = check_guided_point_solve(h, pts_xyz, field_rgb, n, seed_base, seed_width, train_spp_count);
+    if (rc == WOST_OK) rc = check_points_finite(pts_xyz, n, 3);
+    if (rc != WOST_OK) return rc;
+    if (n == 0) {
+        if (stats) *stats = wost_guided_stats{};
+        return WOST_OK;
+    }
+    rc = check_point_capacity3(h, n);
+    if (rc != WOST_OK) return rc;
+    W3_TRY(hipSetDevice(h->device));
+    if (h->pts_cap < (size_t)n) {
+        // (nothing on the device reads the list between two solves)
+        if (h->pts_buf) {
+            h->allocs.erase(std::find(h->allocs.begin(), h->allocs.end(), (void *)h->pts_buf));
+            (void)hipFree(h->pts_buf);
+        }
+        h->pts_buf = nullptr; h->pts_cap = 0;
+        W3_TRY(device_alloc(h->allocs, &h->pts_buf, (size_t)n * 3));
+        h->pts_cap = (size_t)n;
+    }
+    W3_TRY(hipMemcpyAsync(h->pts_buf, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->scene->stream));
+    return run_guided3(h, 0, 1, field_rgb, nullptr, stats, PointJob{h->pts_buf, n, seed_base, seed_width, train_spp_count});
 }
 
 // queryNetwork(Vector3f) (exec.cu:175-186, guided/integrator.cu:566-615): the raw mixture parameters (41 per point) of the

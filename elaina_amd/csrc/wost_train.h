@@ -81,6 +81,26 @@ int train_passes(wost_net_handle net, const TrainSet &ts, size_t n, const TrainS
 
 // field = sol / spp for n pixels (rgb)
 void launch_resolve(const float *sol, int n, float spp, float *field, hipStream_t st);
+// ... for the n points of a point solve (`dim` coordinates each): a point with a non-finite coordinate was never walked, its entry is NaN
+void launch_resolve_points(const float *sol, const float *points, int dim, int n, float spp, float *field, hipStream_t st);
+
+// A guided solve at the caller's points instead of the frame's pixels (wost_guided_solve_points & co., include/wost.h): walker i
+// is point i of `pts` (device, dim floats each) on the random stream of pixel seed_base + i of a frame seed_width wide.
+// pts == nullptr: the frame solve.
+struct PointJob {
+    const float *pts;
+    int32_t n, seed_base, seed_width;
+    int32_t train_spp_count;      // -1: the handle's setting; >= 0: the first min(spp, train_spp_count) samples train
+};
+// the argument rules of the guided point solves: those of check_point_solve, then the training override
+inline int check_guided_point_solve(const void *h, const void *pts, const void *field, int32_t n, int32_t seed_base, int32_t seed_width,
+                                    int32_t train_spp_count)
+{
+    const int rc = check_point_solve(h, pts, field, n, seed_base, seed_width);
+    if (rc != WOST_OK) return rc;
+    if (train_spp_count < -1) return set_error(WOST_ERR_INVALID, "train_spp_count must be -1 (the handle's setting) or >= 0");
+    return WOST_OK;
+}
 
 // `count` elements on the current device, owned by the allocation list of a handle
 template <class T>

@@ -126,7 +126,16 @@ __global__ void resolve_kernel(const float *sol, int n, float spp, float *field)
     if (i < 3 * n) field[i] = sol[i] / spp;
 }
 
-#define TRAIN_TRY(expr)                                                                                  \
+__global__ void resolve_points_kernel(const float *sol, const float *points, int dim, int n, float spp, float *field)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool finite = true;
+    for (int a = 0; a < dim; ++a) finite = finite && isfinite(points[(size_t)dim * i + a]);
+    for (int k = 0; k < 3; ++k) field[3 * (size_t)i + k] = finite ? sol[3 * (size_t)i + k] / spp : __builtin_nanf("");
+}
+
+#define TRAIN_TRY(expr)                                                                                 \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
         if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
@@ -196,6 +205,11 @@ template int train_passes<3>(wost_net_handle, const TrainSet &, size_t, const Tr
 void launch_resolve(const float *sol, int n, float spp, float *field, hipStream_t st)
 {
     hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)((3 * (size_t)n + 255) / 256)), dim3(256), 0, st, sol, n, spp, field);
+}
+
+void launch_resolve_points(const float *sol, const float *points, int dim, int n, float spp, float *field, hipStream_t st)
+{
+    hipLaunchKernelGGL(resolve_points_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, st, sol, points, dim, n, spp, field);
 }
 
 hipError_t alloc_train_set(std::vector<void *> &allocs, TrainSet &ts, int dim, size_t capacity)

@@ -321,6 +321,32 @@ class GuidedIntegrator3:
         self.last_stats = st.as_dict()
         return self.last_stats
 
+    def solve_points(self, points, seed_base=0, seed_width=None, train_spp=None):
+        """the guided solve at the caller's evaluation points ([n, 3] floats, at most frame width * height of them) instead of the
+        frame's pixels (wost3_guided_solve_points): point i takes the place of pixel i of a solve over n pixels, on the random stream of
+        pixel seed_base + i in a frame seed_width wide (default: the frame's width).  train_spp: None = the settings' trainSppCount,
+        otherwise the number of training samples of this call -- 0 probes with the network as it is and leaves it unchanged.
+        Returns the (n, 3) float32 field; the counters are in last_stats"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        field = np.zeros((len(p), 3), dtype=np.float32)
+        st = capi.GuidedStats()
+        width = self.settings.frameSize[0] if seed_width is None else seed_width
+        _check(self.lib.wost3_guided_solve_points(self._handle, _fp(p), len(p), int(seed_base), int(width), -1 if train_spp is None else int(train_spp),
+               _fp(field), C.byref(st)), "wost3_guided_solve_points")
+        self.last_stats = st.as_dict()
+        return field
+
+    def solve_points_dev(self, points_ptr, n, field_ptr, seed_base=0, seed_width=None, train_spp=None):
+        """the same on device pointers (ints): n * 3 floats of points, complete when the call is made, and n * 3 floats of field; runs
+        on the integrator's own stream and returns the stats when the work is complete.  A point with a non-finite coordinate is
+        not walked: its field entry is NaN"""
+        st = capi.GuidedStats()
+        width = self.settings.frameSize[0] if seed_width is None else seed_width
+        _check(self.lib.wost3_guided_solve_points_dev(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), int(width),
+               -1 if train_spp is None else int(train_spp), C.c_void_p(field_ptr), C.byref(st)), "wost3_guided_solve_points_dev")
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
     def queryNetwork(self, p):
         pts = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
         raw = np.zeros((len(pts), 41), dtype=np.float32)

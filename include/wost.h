@@ -322,6 +322,38 @@ int wost_guided_solve(wost_guided_handle h, float *field_rgb, wost_guided_stats 
  * after the work has completed. */
 int wost_guided_solve_sharded(wost_guided_handle h, int32_t shard_index, int32_t shard_count,
                               float *field_rgb_dev, wost_guided_stats *stats);
+/* The guided solve at n evaluation points of the caller (pts_xy: n * 2 floats) instead of the pixels of the frame: wost_solve_points
+ * for the guided integrator.  The driver and the kernels are those of wost_guided_solve; only where a walker starts differs.
+ *   Point identity.  Point i takes the place of pixel i of a guided solve over n pixels: it is walked with the handle's settings,
+ *     meshes, source term, guiding box and network; all its samples share the PCG32 stream seeded as the reference seeds pixel
+ *     seed_base + i of a frame seed_width wide; field_rgb[3 i ..] receives solution / spp.  It is a training point iff the sample
+ *     is a training sample and (i - trainPixelOffset) % trainPixelStride == 0, with i the index IN THE CALL; trainPixelOffset is
+ *     fixed or drawn from the handle's host sampler exactly as a frame solve draws it: one draw per solve.
+ *   Frame equivalence.  The frame's own evaluation points in row-major order with seed_base = 0, seed_width = width and
+ *     train_spp_count = -1 reproduce wost_guided_solve bit for bit on a frame without a mask: the field, the counters, the training
+ *     sets and the trained weights.
+ *   train_spp_count.  -1: the handle's setting.  >= 0 overrides it for this call: the first min(spp, train_spp_count) samples
+ *     train; 0 = a frozen network, the guiding-phase settings from the first sample on.  < -1: WOST_ERR_INVALID.  The call starts
+ *     from the network's current state and leaves the trained state behind, as wost_guided_solve does -- so a handle can train on
+ *     a frame once (wost_guided_solve) and then be probed anywhere with train_spp_count = 0.  With 0 the result of a point does
+ *     not depend on how a list is cut into calls, as long as seed_base moves with the cut.  With training the list trains ONE
+ *     network: every point sees what all points of the call have taught it, so a cut changes the result.
+ *   Capacity.  n <= width * height of the handle: the per-pixel state, the record sets and the queues are sized by the frame, and a
+ *     guided solve cannot be run in chunks without changing what the network sees.  A longer list is WOST_ERR_INVALID; the message
+ *     names the capacity.
+ *   The frame's mask, the shards and the intermediate-frame callback do not apply.  The options "pipeline" and "train_group" and the
+ *     network's "precision" / "train_precision" are honoured exactly as by the frame solve.  Afterwards wost_guided_train_set returns
+ *     the last training pass of the point solve.
+ *   Arguments, checked in this order before the handle is read or a device is asked for: a null handle, list or field; n < 0;
+ *     seed_width <= 0; seed_base < 0 or seed_base + n > 2^28; train_spp_count < -1.  n == 0: WOST_OK and zeroed stats.
+ * wost_guided_solve_points: host arrays; a non-finite coordinate is refused (WOST_ERR_INVALID names the first bad index, nothing
+ * is launched).  wost_guided_solve_points_dev: DEVICE arrays, complete when the call is made; the work runs on the handle's own
+ * stream and the call returns when it is complete, like wost_guided_solve_sharded; a point with a non-finite coordinate is never
+ * walked and never recorded, its field entry is NaN. */
+int wost_guided_solve_points(wost_guided_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width,
+                             int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats);
+int wost_guided_solve_points_dev(wost_guided_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                                 int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats);
 /* Shared network across shards (optional).  By default every shard trains its own network; with
  * a sync callback the shards train ONE network: before every Adam step the callback must sum the
  * fixed-point gradient buffer over all ranks (WOST_SYNC_SUM_I64_DEVICE: data = device int64[count],
@@ -538,6 +570,13 @@ int wost3_guided_scene(wost3_guided_handle h, wost3_handle *scene);             
 int wost3_guided_solve(wost3_guided_handle h, float *field_rgb, wost_guided_stats *stats);
 int wost3_guided_solve_sharded(wost3_guided_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev,
                                wost_guided_stats *stats);
+/* The guided solve at n evaluation points of the caller (pts_xyz: n * 3 floats), which need not lie on one slice: the contract of
+ * wost_guided_solve_points in every clause (point identity, frame equivalence with wost3_guided_solve, train_spp_count, the capacity
+ * n <= width * height, the argument checks, host and device variants), with wost3_guided_train_set afterwards. */
+int wost3_guided_solve_points(wost3_guided_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width,
+                              int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats);
+int wost3_guided_solve_points_dev(wost3_guided_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+                                  int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats);
 /* queryNetwork(Vector3f) (exec.cu:175-186): raw = n * 41 mixture parameters of the inference weights at pts (n * 3, world) */
 int wost3_guided_query_network(wost3_guided_handle h, const float *pts, int32_t n, float *raw);
 /* the ordered training set of the last training pass (tests): xyz = normalised inputs, dir / normal 3 floats per sample */
