@@ -114,6 +114,12 @@ struct RoundParams {
     // NEUMANN_TREE launches of walk_round_kernel: the Neumann-side tree queries of a step by the wave as a whole (wost_coop.h):
     // pool_cap tasks per pool and wave, pool_offset words into the block's LDS (behind the stack columns); 0 = per lane
     int32_t coop, pool_cap, pool_offset, ray_slot_trigger;
+    // the carried launches (walk_round_carry_kernel, walk_quad_carry_kernel) of a continued solve (wost_solve_more): a pixel that is
+    // resolved leaves its generator state and its three raw sums under its pixel id, and its field entry is sum / carry_total --
+    // the samples of the earlier calls and of this one; st.spp is this call's count.  (At the end: no other entry reads them.)
+    uint64_t *carry_rng;
+    float *carry_sum;
+    int32_t carry_total;
 };
 
 struct InitParams {
@@ -129,6 +135,11 @@ struct InitParams {
     int32_t shard_index, shard_count;
     int32_t tiles_x, tiles_y;
     int32_t stack_stride;
+    // a continued solve (wost_solve_more) with carry_done > 0 samples behind it: a walker starts from its pixel's carried generator
+    // state and raw sums instead of the seed and zero; st.spp is this call's count and the walker counts its samples from 0
+    const uint64_t *carry_rng;
+    const float *carry_sum;
+    int32_t carry_done;
 };
 
 #define META_SAMPLE(m) ((m) & 0xfffffu)
@@ -165,6 +176,12 @@ __global__ __launch_bounds__(256) void init_kernel(InitParams P)
         pcg_seed_pixel(rng, pid, P.st.width);
         if (P.dm.n_segs > 0) c0 = closest_point(P.dm, x0, y0, slot_candidate(P.dm, 0, x0, y0), stack, P.stack_stride);
     }
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f;
+    if (active && P.carry_done > 0) {
+        rng.state = P.carry_rng[pid];
+        const float *cs = P.carry_sum + 3 * (size_t)pid;
+        sr = cs[0]; sg = cs[1]; sb = cs[2];
+    }
     const uint32_t s = block_push(active, P.count_out);
     if (active) {
         WalkQueue &q = P.out;
@@ -176,7 +193,7 @@ __global__ __launch_bounds__(256) void init_kernel(InitParams P)
         q.nx[s] = 0.0f; q.ny[s] = 0.0f;
         q.hint[s] = c0.slot;
         q.thp[s] = 1.0f;
-        q.sr[s] = 0.0f; q.sg[s] = 0.0f; q.sb[s] = 0.0f;
+        q.sr[s] = sr; q.sg[s] = sg; q.sb[s] = sb;
         q.d0_d2[s] = c0.d2;
         q.d0_slot[s] = c0.slot;
     }
@@ -475,6 +492,21 @@ __device__ __forceinline__ void store_lane(const WalkQueue &q, uint32_t s, const
     q.d0_d2[s] = L.d0_d2; q.d0_slot[s] = L.d0_slot;
 }
 
+// A pixel is resolved (reference integrator.cu:616-620): its sums divided by its samples.  CARRY (a continued solve): the
+// generator state and the raw sums stay behind under the pixel id for the next call, and the samples are those of all calls.
+template <bool CARRY>
+__device__ __forceinline__ void resolve_pixel(const RoundParams &P, uint32_t pix, const Lane &L)
+{
+    float *f = P.field + 3 * (size_t)((int32_t)pix - P.field_base);
+    if (CARRY) {
+        P.carry_rng[pix] = L.rng.state;
+        float *cs = P.carry_sum + 3 * (size_t)pix;
+        cs[0] = L.sr; cs[1] = L.sg; cs[2] = L.sb;
+    }
+    const float spp = (float)(CARRY ? P.carry_total : P.st.spp);
+    f[0] = L.sr / spp; f[1] = L.sg / spp; f[2] = L.sb / spp;
+}
+
 // walkers order[0 .. n) of `in` (0 .. n without an order) copied to slots 0 .. n of `out`
 __global__ __launch_bounds__(256) void gather_walkers_kernel(WalkQueue in, const uint32_t *order, uint32_t n, WalkQueue out)
 {
@@ -503,11 +535,10 @@ __global__ __launch_bounds__(256) void gather_walkers_kernel(WalkQueue in, const
 // pixel).  Eight registers fewer -- the instantiation wants 98 where six waves per SIMD allow 80, and what it spilled was not
 // only cold: the PCG state went through scratch at every step (a build with 96 registers and five waves per SIMD was 7 % faster
 // than the spilling one at the same five waves, profiles/r06_o_*).
-template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool REFILL = false, bool SOURCE = false, bool SLACK = false, bool PERSIST = false>
-#ifndef WOST_ROUND_WAVES
-#define WOST_ROUND_WAVES 6      // waves per SIMD the round kernel is compiled for (tuning builds override it)
-#endif
-__global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk_round_kernel(RoundParams P)
+// CARRY: the body of walk_round_carry_kernel, the entry of a continued solve (resolve_pixel).  A flag of the body and a second
+// entry, not a seventh parameter of walk_round_kernel and not a test at run time: the frame kernels keep their names and their code.
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool REFILL, bool SOURCE, bool SLACK, bool PERSIST, bool CARRY>
+__device__ __forceinline__ void walk_round_body(const RoundParams &P)
 {
     extern __shared__ uint32_t lds_stack[];       // the traversal stack columns, one per lane
     uint32_t *stack = lds_stack + threadIdx.x;
@@ -605,9 +636,7 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
                 }
                 if (mode == MODE_REFILL) {
                     if (open) {       // (a walker that left for the slack launch is not resolved here: `open` is false)
-                        float *f = P.field + 3 * (size_t)((int32_t)pix - P.field_base);
-                        const float spp = (float)P.st.spp;
-                        f[0] = L.sr / spp; f[1] = L.sg / spp; f[2] = L.sb / spp;
+                        resolve_pixel<CARRY>(P, pix, L);
                     }
                     open = false;
                     if (PERSIST) {
@@ -789,9 +818,7 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
     }
     // ---- resolve finished pixels (reference integrator.cu:616-620) -------------------------
     if (open && !alive) {
-        float *f = P.field + 3 * (size_t)((int32_t)pix - P.field_base);
-        const float spp = (float)P.st.spp;
-        f[0] = L.sr / spp; f[1] = L.sg / spp; f[2] = L.sb / spp;
+        resolve_pixel<CARRY>(P, pix, L);
     }
     // ---- stream compaction of the survivors: ballot + popcount, one atomic per block ------
     const int lane = threadIdx.x & 63;
@@ -857,6 +884,20 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
 #endif
 }
 
+#ifndef WOST_ROUND_WAVES
+#define WOST_ROUND_WAVES 6      // waves per SIMD the round kernel is compiled for (tuning builds override it)
+#endif
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool REFILL = false, bool SOURCE = false, bool SLACK = false, bool PERSIST = false>
+__global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk_round_kernel(RoundParams P)
+{
+    walk_round_body<NEUMANN_EMISSIVE, NEUMANN_TREE, REFILL, SOURCE, SLACK, PERSIST, false>(P);
+}
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool REFILL = false, bool SOURCE = false, bool SLACK = false, bool PERSIST = false>
+__global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk_round_carry_kernel(RoundParams P)
+{
+    walk_round_body<NEUMANN_EMISSIVE, NEUMANN_TREE, REFILL, SOURCE, SLACK, PERSIST, true>(P);
+}
+
 
 // ------------------------------------------------------------------------------------------
 // the walk round of an under-filled launch: four lanes per walker (wost_quad.h)
@@ -865,8 +906,8 @@ __global__ __launch_bounds__(256, NEUMANN_TREE ? 4 : WOST_ROUND_WAVES) void walk
 // and visiting order -- but a quad of lanes holds ONE walker: the closest-point descent is shared between the four
 // lanes (one child box each), everything else runs replicated.  The host launches it when the walkers left would fill
 // less than a quarter of the resident lanes, where a launch lasts as long as its longest chain of dependent visits.
-template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE, bool SLACK>
-__global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE, bool SLACK, bool CARRY>
+__device__ __forceinline__ void walk_quad_body(const RoundParams &P)
 {
     extern __shared__ uint32_t lds_stack[];
     const int j = threadIdx.x & 3;
@@ -980,9 +1021,7 @@ __global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
     }
     const bool lead = j == 0;       // one lane of the quad speaks for the walker
     if (open && !alive && lead) {
-        float *f = P.field + 3 * (size_t)((int32_t)pix - P.field_base);
-        const float spp = (float)P.st.spp;
-        f[0] = L.sr / spp; f[1] = L.sg / spp; f[2] = L.sb / spp;
+        resolve_pixel<CARRY>(P, pix, L);
     }
     const int lane = threadIdx.x & 63;
     const bool far = !SLACK && mode == MODE_FAR;
@@ -1012,6 +1051,17 @@ __global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
         atomicAdd(&st->trav_trips, (unsigned long long)trav_trips);
         atomicAdd(&st->step_trips, (unsigned long long)step_trips);
     }
+}
+
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE, bool SLACK>
+__global__ __launch_bounds__(256, 4) void walk_quad_kernel(RoundParams P)
+{
+    walk_quad_body<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE, SLACK, false>(P);
+}
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE, bool SLACK>
+__global__ __launch_bounds__(256, 4) void walk_quad_carry_kernel(RoundParams P)
+{
+    walk_quad_body<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE, SLACK, true>(P);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1373,6 +1423,12 @@ struct wost_context {
     StatsDev *host_stats = nullptr;            // pinned: the counters as they stood after each launch (last_launches)
     std::vector<wost_launch_info> last_launches;
     uint64_t steps_before = 0;                 // a point solve in chunks: the walk steps of its earlier chunks (wost_launch_info::walk_steps_done)
+    // the carried frame solve (wost_solve_more): per pixel the PCG32 state after its samples so far and the three raw sums (20
+    // bytes, allocated on first use), the samples done, and the shard they belong to (carry_shard_count 0: none yet)
+    void *carry_mem = nullptr;
+    uint64_t *carry_rng = nullptr;
+    float *carry_sum = nullptr;
+    int32_t carry_done = 0, carry_shard_index = 0, carry_shard_count = 0;
 };
 
 namespace wost {
@@ -1430,6 +1486,7 @@ static void destroy_ctx(wost_context *c)
     if (c->stats) (void)hipFree(c->stats);
     if (c->field) (void)hipFree(c->field);
     if (c->cursor) (void)hipFree(c->cursor);
+    if (c->carry_mem) (void)hipFree(c->carry_mem);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -1803,11 +1860,20 @@ static RoundParams base_params(const wost_context *c, const LaunchGeometry &g, f
 // arguments E(missive), T(ree), S(ource).  These are all the instantiations there are:
 //   ROUND  walk_round_kernel<E, T, 0, S, slack, 0>    ONE         walk_round_kernel<E, T, 1, 0, 0, 0>  (no source term: launch_ordinary)
 //   QUAD   walk_quad_kernel<E, T, S, slack>           PERSISTENT  walk_round_kernel<E, T, 1, S, 0, 1>
+// and beside each its carried entry (walk_round_carry_kernel, walk_quad_carry_kernel), which the launches of a continued solve
+// take (rp.carry_rng != nullptr).
 static void launch_walk(const LaunchGeometry &g, int kind, bool slack, unsigned grid, hipStream_t stream, const RoundParams &rp)
 {
     auto launch = [&](auto E, auto T, auto S) {
         constexpr bool e = decltype(E)::value, t = decltype(T)::value, s = decltype(S)::value;
-        if (kind == WOST_LAUNCH_QUAD && slack) hipLaunchKernelGGL((walk_quad_kernel<e, t, s, true>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
+        if (rp.carry_rng) {
+            if (kind == WOST_LAUNCH_QUAD && slack) hipLaunchKernelGGL((walk_quad_carry_kernel<e, t, s, true>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
+            else if (kind == WOST_LAUNCH_QUAD) hipLaunchKernelGGL((walk_quad_carry_kernel<e, t, s, false>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
+            else if (kind == WOST_LAUNCH_PERSISTENT) hipLaunchKernelGGL((walk_round_carry_kernel<e, t, true, s, false, true>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+            else if (kind == WOST_LAUNCH_ONE) hipLaunchKernelGGL((walk_round_carry_kernel<e, t, true, false, false, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+            else if (slack) hipLaunchKernelGGL((walk_round_carry_kernel<e, t, false, s, true, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+            else hipLaunchKernelGGL((walk_round_carry_kernel<e, t, false, s, false, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
+        } else if (kind == WOST_LAUNCH_QUAD && slack) hipLaunchKernelGGL((walk_quad_kernel<e, t, s, true>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
         else if (kind == WOST_LAUNCH_QUAD) hipLaunchKernelGGL((walk_quad_kernel<e, t, s, false>), dim3(grid), dim3(g.bs), g.lds_quad, stream, rp);
         else if (kind == WOST_LAUNCH_PERSISTENT) hipLaunchKernelGGL((walk_round_kernel<e, t, true, s, false, true>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
         else if (kind == WOST_LAUNCH_ONE) hipLaunchKernelGGL((walk_round_kernel<e, t, true, false, false, false>), dim3(grid), dim3(g.bs), g.lds_round, stream, rp);
@@ -1942,9 +2008,12 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
     // cannot keep the lanes busy (measured on config 2's frame: 1 spp 3.5 -> 3.0 ms, 4 spp 8.3 -> 7.9 ms, 8 spp 13.0 -> 13.5 ms)
     // and the queue is larger than one residency; the 16-bit lane counters bound spp * max_depth.
     // (the one-launch form of few samples has no instantiation with a source term; the persistent launch has)
-    const bool can_persist = (int64_t)c->settings.spp * c->settings.max_depth < 65535 && first;
+    // (the samples of this solve: rp.st.spp -- the handle's setting, or the count of a continued call)
+    const int32_t spp = rp.st.spp;
+    const bool can_persist = (int64_t)spp * c->settings.max_depth < 65535 && first;
     const bool can_refill = can_persist && !g.has_src;
-    const bool few = can_refill && (c->refill == 1 || (c->refill == -1 && c->settings.spp <= 4 && p.grid > g.resident));
+    // (the automatic choice of the one-launch form gives way to a persistent launch the caller asked for: persist 1)
+    const bool few = can_refill && (c->refill == 1 || (c->refill == -1 && c->persist != 1 && spp <= 4 && p.grid > g.resident));
     // PERSISTENT first launch (many samples per pixel, more walkers than resident lanes): the same resident threads, but the
     // lanes take whole pixels -- all of a pixel's samples, the pixels in the order of wost_order.h, longest expected chain first
     // -- until the input queue is dry; then every wave hands what it holds to the output queue and the rest of the solve runs
@@ -1952,7 +2021,7 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
     // 108 of its 252 ms in launches where a third of the lanes had finished their pixel, EXPERIMENTS 25); what the rounds
     // get is the remainder of one pixel per lane.
     const bool persist = can_persist && !few && c->refill != 1 &&
-                         (c->persist == 1 || (c->persist == -1 && c->settings.spp > 4 && p.n_active > g.resident_threads));
+                         (c->persist == 1 || (c->persist == -1 && spp > 4 && p.n_active > g.resident_threads));
     if (few || persist) {
         p.kind = persist ? WOST_LAUNCH_PERSISTENT : WOST_LAUNCH_ONE;
         rp.lane_shift = 0;
@@ -1968,7 +2037,7 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
         // lanes / spp slots per walk step of a lane.  R >> dry_shift steps with 2^dry_shift >= lanes / spp end before the queue is
         // dry, and the bound is pessimistic (config 2: 1 536 slots per trip possible, 220 taken).
         rp.dry_shift = 0;
-        while (rp.dry_shift < 31 && ((uint64_t)std::max(c->settings.spp, 1) << rp.dry_shift) < (uint64_t)p.grid * (unsigned)bs) ++rp.dry_shift;
+        while (rp.dry_shift < 31 && ((uint64_t)std::max(spp, 1) << rp.dry_shift) < (uint64_t)p.grid * (unsigned)bs) ++rp.dry_shift;
         if (persist) set_schedule(c, g.ntree, true, rp);
         if (persist ? c->persist_order : c->few_order) {
             if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
@@ -2021,14 +2090,18 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
 
 // The first step of a solve, the one that fills queue 0: the frame init on a pixel range and a shard, or (points != nullptr) the
 // point init on points [first, first + n) of a call -- one chunk of a point solve, at most n_pixels points.
+// A frame step with carry_more > 0 is a call of a continued solve (wost_solve_more): carry_more samples on top of the carry_done
+// in the handle's carried buffers -- the solve runs with spp = carry_more, whatever the handle's own setting.
 struct FirstStep {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
     int32_t first, n, seed_base, seed_width;
+    int32_t carry_done, carry_more;
 };
-static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count)
+static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, int32_t carry_done = 0,
+                            int32_t carry_more = 0)
 {
-    return FirstStep{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0, 0, 0};
+    return FirstStep{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0, 0, 0, carry_done, carry_more};
 }
 
 // the shared solve driver: field_dev indexed by (pix - field_base)
@@ -2040,14 +2113,19 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     const LaunchGeometry g = launch_geometry(c);
     HIP_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
+    // the plan of the solve takes its sample count from here: the handle's setting, or the count of a continued call
+    const bool carried = !fs.points && fs.carry_more > 0;
+    DevSettings st = c->dst;
+    if (carried) st.spp = fs.carry_more;
 
     if (fs.points) {
         const InitPointsParams ip{c->dm.view, c->dst, c->queue[0], c->counts + 0, fs.points, field_dev, fs.first, fs.n, fs.seed_base, fs.seed_width, g.bs};
         hipLaunchKernelGGL(init_points_kernel, dim3((unsigned)(((long long)fs.n + g.bs - 1) / g.bs)), dim3(g.bs), g.lds, stream, ip);
     } else {
         const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
-        const InitParams ip{c->dm.view, c->dst, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
-                            fs.pixel_begin, fs.pixel_end, fs.shard_index, fs.shard_count, tiles_x, tiles_y, g.bs};
+        const InitParams ip{c->dm.view, st, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
+                            fs.pixel_begin, fs.pixel_end, fs.shard_index, fs.shard_count, tiles_x, tiles_y, g.bs,
+                            c->carry_rng, c->carry_sum, carried ? fs.carry_done : 0};
         const long long n_threads = (long long)tiles_x * tiles_y * 64;
         const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
         hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
@@ -2065,7 +2143,11 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
         c->last_launches.clear();
         c->steps_before = 0;
     }
-    const RoundParams base = base_params(c, g, field_dev, field_base);
+    RoundParams base = base_params(c, g, field_dev, field_base);
+    base.st = st;
+    if (carried) {
+        base.carry_rng = c->carry_rng; base.carry_sum = c->carry_sum; base.carry_total = fs.carry_done + fs.carry_more;
+    }
     SideStreamGuard long_guard, far_guard;   // armed: a launch of the long remainders / of strayed walkers was queued
     uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (launch_strayed)
     bool handed_over = false;     // the previous launch was persistent: queue[cur] holds what it handed over, with estimates
@@ -2224,7 +2306,7 @@ static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, in
     wost_stats total{};
     const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
     for (int32_t first = 0; first < n; first += cap) {
-        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width};
+        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width, 0, 0};
         wost_stats st{};
         const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
         if (rc != WOST_OK) return rc;
@@ -2236,6 +2318,79 @@ static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, in
     }
     total.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     if (stats) *stats = total;
+    return WOST_OK;
+}
+
+// ---- the continued frame solve ----
+// The arguments of a continued call that need no look at the handle, in the order and wording of the other solves.
+static int check_solve_more(const void *h, const void *field, int32_t more_spp)
+{
+    if (!h || !field) return fail(WOST_ERR_INVALID, "null argument");
+    if (more_spp < 1 || more_spp > (1 << 20) - 1) return fail(WOST_ERR_INVALID, "more_spp must be in 1..2^20-1");
+    return WOST_OK;
+}
+
+static int solve_more(wost_context *c, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_dev, hipStream_t stream, wost_stats *stats)
+{
+    if (c->carry_shard_count > 0 && (c->carry_shard_index != shard_index || c->carry_shard_count != shard_count))
+        return fail(WOST_ERR_INVALID, "the carried solve belongs to shard " + std::to_string(c->carry_shard_index) + " of " + std::to_string(c->carry_shard_count) +
+                                          " (wost_solve_restart releases it)");
+    if ((int64_t)c->carry_done + more_spp > (1 << 20) - 1)
+        return fail(WOST_ERR_INVALID, "spp_done + more_spp must be at most 2^20-1 (spp_done is " + std::to_string(c->carry_done) + ")");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->carry_mem) {
+        HIP_TRY(hipMalloc(&c->carry_mem, c->n_pixels * (sizeof(uint64_t) + 3 * sizeof(float))));
+        c->carry_rng = static_cast<uint64_t *>(c->carry_mem);
+        c->carry_sum = reinterpret_cast<float *>(c->carry_rng + c->n_pixels);
+    }
+    const int32_t done = c->carry_done;
+    const int rc = run_solve(c, frame_step(0, (int32_t)c->n_pixels, shard_index, shard_count, done, more_spp), field_dev, 0, stream, stats);
+    if (rc != WOST_OK) {
+        // launches may have written some pixels' carried state and not others': the carried solve is gone
+        (void)hipStreamSynchronize(stream);
+        c->carry_done = 0; c->carry_shard_count = 0;
+        g_last_error += " (the carried solve was dropped: spp_done is 0)";
+        return rc;
+    }
+    c->carry_done = done + more_spp; c->carry_shard_index = shard_index; c->carry_shard_count = shard_count;
+    return WOST_OK;
+}
+
+int wost_solve_more(wost_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
+{
+    int rc = check_solve_more(h, field_rgb, more_spp);
+    if (rc != WOST_OK) return rc;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemsetAsync(h->field, 0, h->n_pixels * 3 * sizeof(float), h->stream));
+    rc = solve_more(h, 0, 1, more_spp, h->field, h->stream, stats);
+    if (rc != WOST_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(field_rgb, h->field, h->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    return WOST_OK;
+}
+
+int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
+                            wost_stats *stats)
+{
+    const int rc = check_solve_more(h, field_rgb_dev, more_spp);
+    if (rc != WOST_OK) return rc;
+    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return fail(WOST_ERR_INVALID, "bad shard");
+    return solve_more(h, shard_index, shard_count, more_spp, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+int wost_solve_restart(wost_handle h)
+{
+    if (!h) return fail(WOST_ERR_INVALID, "null argument");
+    h->carry_done = 0; h->carry_shard_index = 0; h->carry_shard_count = 0;
+    return WOST_OK;
+}
+
+int wost_solve_progress(wost_handle h, int32_t *spp_done)
+{
+    if (!h || !spp_done) return fail(WOST_ERR_INVALID, "null argument");
+    *spp_done = h->carry_done;
     return WOST_OK;
 }
 

@@ -59,6 +59,12 @@ struct Walk3Params {
     // (at the end: the frame instantiations read every other field where they always did)
     const float *points;
     int32_t seed_base, seed_width;
+    // a continued frame solve (wost3_solve_more, the CARRY instantiations): a pixel with carry_done > 0 samples behind it starts
+    // from its carried generator state and raw sums; a resolved pixel leaves both under its pixel id and its field entry is
+    // sum / carry_total; st.spp is this call's count and a lane counts the call's samples from 0.  (At the end, like the points.)
+    uint64_t *carry_rng;
+    float *carry_sum;
+    int32_t carry_done, carry_total;
 };
 
 // One lane = one pixel, all its samples one after the other on the pixel's PCG stream (the reference's per-pixel
@@ -387,7 +393,8 @@ __device__ __forceinline__ Closest closest_triangle_wave(const DevMesh3 &m, V3 q
 // the loop is then "all queries of the wave, then one step for every walker": no lane waits for another's descent.
 // POINTS = true: the launch of a point solve (wost3_solve_points) -- a refill takes a caller's point instead of a pixel of the frame.
 // A template flag, not a test of P.points: with the test every frame instantiation held two more registers (EXPERIMENTS).
-template <bool EMISSIVE, bool SOURCE, bool NTREE, bool WAVE = false, bool POINTS = false>
+// CARRY = true (frame forms only): the launch of a continued solve (wost3_solve_more, Walk3Params::carry_rng).
+template <bool EMISSIVE, bool SOURCE, bool NTREE, bool WAVE = false, bool POINTS = false, bool CARRY = false>
 #ifndef WOST3_WAVES
 #define WOST3_WAVES 1       // waves per SIMD walk3_kernel is compiled for (tuning builds override it)
 #endif
@@ -506,6 +513,11 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                             L.pid = pid;
                             L.rng = Pcg{0, 1};
                             pcg_seed_pixel(L.rng, pid, P.st.width);
+                            if (CARRY && P.carry_done > 0) {
+                                L.rng.state = P.carry_rng[pid];
+                                const float *cs = P.carry_sum + 3 * (size_t)pid;
+                                L.sol[0] = cs[0]; L.sol[1] = cs[1]; L.sol[2] = cs[2];
+                            }
                             L.p_eval = eval_point3(P.probe, px, py, P.st.width, P.st.height);
                             L.hint = L.hint0 = -1;
                             L.sample = 0;
@@ -616,7 +628,12 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                     begin_sample();
                 } else {
                     float *f = P.field + 3 * (size_t)(L.pid - P.field_base);
-                    const float spp = (float)P.st.spp;
+                    if (CARRY) {
+                        P.carry_rng[L.pid] = L.rng.state;
+                        float *cs = P.carry_sum + 3 * (size_t)L.pid;
+                        cs[0] = L.sol[0]; cs[1] = L.sol[1]; cs[2] = L.sol[2];
+                    }
+                    const float spp = (float)(CARRY ? P.carry_total : P.st.spp);
                     f[0] = L.sol[0] / spp; f[1] = L.sol[1] / spp; f[2] = L.sol[2] / spp;
                     mode = MODE_REFILL;
                 }
@@ -740,6 +757,7 @@ static void destroy3(wost3_context *c)
     if (c->field) (void)hipFree(c->field);
     if (c->stats) (void)hipFree(c->stats);
     if (c->cursor) (void)hipFree(c->cursor);
+    if (c->carry_mem) (void)hipFree(c->carry_mem);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -788,26 +806,30 @@ static Walk3Plan walk3_plan(const wost3_context *c, int n)
     return pl;
 }
 
-// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are, and the sixteen of a point solve beside them
-template <bool E, bool S, bool PTS>
+// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are, the sixteen of a point solve and the
+// sixteen of a continued frame solve beside them
+template <bool E, bool S, bool PTS, bool CARRY>
 static const void *walk3_kernel_of(bool ntree, bool wave)
 {
-    if (ntree) return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, true, true, PTS>) : reinterpret_cast<const void *>(walk3_kernel<E, S, true, false, PTS>);
-    return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, false, true, PTS>) : reinterpret_cast<const void *>(walk3_kernel<E, S, false, false, PTS>);
+    if (ntree) return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, true, true, PTS, CARRY>) : reinterpret_cast<const void *>(walk3_kernel<E, S, true, false, PTS, CARRY>);
+    return wave ? reinterpret_cast<const void *>(walk3_kernel<E, S, false, true, PTS, CARRY>) : reinterpret_cast<const void *>(walk3_kernel<E, S, false, false, PTS, CARRY>);
 }
-template <bool PTS>
+template <bool PTS, bool CARRY = false>
 static const void *walk3_kernel_of(const Walk3Plan &pl)
 {
-    if (pl.emissive) return pl.source ? walk3_kernel_of<true, true, PTS>(pl.ntree, pl.wave) : walk3_kernel_of<true, false, PTS>(pl.ntree, pl.wave);
-    return pl.source ? walk3_kernel_of<false, true, PTS>(pl.ntree, pl.wave) : walk3_kernel_of<false, false, PTS>(pl.ntree, pl.wave);
+    if (pl.emissive) return pl.source ? walk3_kernel_of<true, true, PTS, CARRY>(pl.ntree, pl.wave) : walk3_kernel_of<true, false, PTS, CARRY>(pl.ntree, pl.wave);
+    return pl.source ? walk3_kernel_of<false, true, PTS, CARRY>(pl.ntree, pl.wave) : walk3_kernel_of<false, false, PTS, CARRY>(pl.ntree, pl.wave);
 }
 
 // The first step of a solve, what a lane's refill reads: the pixels [pixel_begin, pixel_end) of the frame and a shard of its tiles, or
 // (points != nullptr) the points [pixel_begin, pixel_end) of a caller's list with their seeds.
+// A frame step with carry_more > 0 is a call of a continued solve (wost3_solve_more): carry_more samples on top of the carry_done in
+// the handle's carried buffers -- the launch runs with spp = carry_more, whatever the handle's own setting.
 struct FirstStep3 {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
     int32_t seed_base, seed_width;
+    int32_t carry_done = 0, carry_more = 0;
 };
 
 static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
@@ -827,11 +849,16 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
         P.shard_index = shard_index; P.shard_count = shard_count; P.stats = c->stats; P.cursor = c->cursor;
         P.tiled = (!fs.points && pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
         P.points = fs.points; P.seed_base = fs.seed_base; P.seed_width = fs.seed_width;
+        const bool carried = !fs.points && fs.carry_more > 0;
+        if (carried) {
+            P.st.spp = fs.carry_more;
+            P.carry_rng = c->carry_rng; P.carry_sum = c->carry_sum; P.carry_done = fs.carry_done; P.carry_total = fs.carry_done + fs.carry_more;
+        }
         P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
         P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
         void *args[] = {&P};
         W3_TRY(hipEventRecord(c->ev0, stream));
-        (void)hipLaunchKernel(fs.points ? walk3_kernel_of<true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
+        (void)hipLaunchKernel(fs.points ? walk3_kernel_of<true>(pl) : carried ? walk3_kernel_of<false, true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
         W3_TRY(hipGetLastError());
         W3_TRY(hipEventRecord(c->ev1, stream));
     }
@@ -954,6 +981,78 @@ int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count
     if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
     if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
     return run_solve3(h, FirstStep3{0, (int32_t)h->n_pixels, shard_index, shard_count, nullptr, 0, 0}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+// ---- the continued frame solve (wost_solve_more in 3-D: the same checks, in the same order and words) ----
+static int check_solve_more3(const void *h, const void *field, int32_t more_spp)
+{
+    if (!h || !field) return set_error(WOST_ERR_INVALID, "null argument");
+    if (more_spp < 1 || more_spp > (1 << 20) - 1) return set_error(WOST_ERR_INVALID, "more_spp must be in 1..2^20-1");
+    return WOST_OK;
+}
+
+static int solve_more3(wost3_context *c, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_dev, hipStream_t stream, wost_stats *stats)
+{
+    if (c->carry_shard_count > 0 && (c->carry_shard_index != shard_index || c->carry_shard_count != shard_count))
+        return set_error(WOST_ERR_INVALID, "the carried solve belongs to shard " + std::to_string(c->carry_shard_index) + " of " +
+                                               std::to_string(c->carry_shard_count) + " (wost3_solve_restart releases it)");
+    if ((int64_t)c->carry_done + more_spp > (1 << 20) - 1)
+        return set_error(WOST_ERR_INVALID, "spp_done + more_spp must be at most 2^20-1 (spp_done is " + std::to_string(c->carry_done) + ")");
+    W3_TRY(hipSetDevice(c->device));
+    if (!c->carry_mem) {
+        W3_TRY(hipMalloc(&c->carry_mem, c->n_pixels * (sizeof(uint64_t) + 3 * sizeof(float))));
+        c->carry_rng = static_cast<uint64_t *>(c->carry_mem);
+        c->carry_sum = reinterpret_cast<float *>(c->carry_rng + c->n_pixels);
+    }
+    const int32_t done = c->carry_done;
+    FirstStep3 fs{0, (int32_t)c->n_pixels, shard_index, shard_count, nullptr, 0, 0};
+    fs.carry_done = done; fs.carry_more = more_spp;
+    const int rc = run_solve3(c, fs, field_dev, 0, stream, stats);
+    if (rc != WOST_OK) {
+        // the launch may have written some pixels' carried state and not others': the carried solve is gone
+        const std::string msg = wost_last_error();
+        (void)hipStreamSynchronize(stream);
+        c->carry_done = 0; c->carry_shard_count = 0;
+        return set_error(rc, msg + " (the carried solve was dropped: spp_done is 0)");
+    }
+    c->carry_done = done + more_spp; c->carry_shard_index = shard_index; c->carry_shard_count = shard_count;
+    return WOST_OK;
+}
+
+int wost3_solve_more(wost3_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
+{
+    int rc = check_solve_more3(h, field_rgb, more_spp);
+    if (rc != WOST_OK) return rc;
+    W3_TRY(hipSetDevice(h->device));
+    W3_TRY(hipMemsetAsync(h->field, 0, h->n_pixels * 3 * sizeof(float), h->stream));
+    rc = solve_more3(h, 0, 1, more_spp, h->field, h->stream, stats);
+    if (rc != WOST_OK) return rc;
+    W3_TRY(hipMemcpyAsync(field_rgb, h->field, h->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    W3_TRY(hipStreamSynchronize(h->stream));
+    return WOST_OK;
+}
+
+int wost3_solve_more_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
+                             wost_stats *stats)
+{
+    const int rc = check_solve_more3(h, field_rgb_dev, more_spp);
+    if (rc != WOST_OK) return rc;
+    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
+    return solve_more3(h, shard_index, shard_count, more_spp, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+}
+
+int wost3_solve_restart(wost3_handle h)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    h->carry_done = 0; h->carry_shard_index = 0; h->carry_shard_count = 0;
+    return WOST_OK;
+}
+
+int wost3_solve_progress(wost3_handle h, int32_t *spp_done)
+{
+    if (!h || !spp_done) return set_error(WOST_ERR_INVALID, "null argument");
+    *spp_done = h->carry_done;
+    return WOST_OK;
 }
 
 int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,

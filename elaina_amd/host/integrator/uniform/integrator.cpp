@@ -38,40 +38,69 @@ UniformIntegrator<2>::~UniformIntegrator()
     if (handle) wost_destroy(handle);
 }
 
+// saveSppMetrics* / saveTimeMetrics* (reference integrator.cu:578-609): frames/<sampleId>.exr|png and
+// frames_time/<elapsed ms>.exr|png = solution / (sampleId + 1) after sample sampleId, written while the samples accumulate.
+// The pixels of these integrators do not advance in lock step, but a solve can be taken up again (wost_solve_more): frame k
+// comes after the continued call that brings the carried solve to k + 1 samples, the last call brings it to samplesPerPixel
+// and is the solution -- samplesPerPixel samples of work in all, and the time frames are keyed by the milliseconds since the
+// start of solve(), as in the reference.  more(count, field, stats) runs `count` further samples; `total` receives the
+// counters and times of all calls, which are those of the single solve.
+template <class More>
+static void solve_with_metric_frames(const UniformIntegratorSettings &s, const fs::path &basePath,
+                                     std::chrono::high_resolution_clock::time_point start, std::vector<float> &f, wost_stats &total, More &&more)
+{
+    if (s.saveSppMetricsDuration > 0) fs::create_directories(basePath / "frames");
+    if (s.saveTimeMetricsDuration > 0) fs::create_directories(basePath / "frames_time");
+    total = wost_stats{};
+    int done = 0;
+    auto advance = [&](int to) {
+        if (to <= done) return;
+        wost_stats st{};
+        more(to - done, f.data(), &st);
+        total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
+        total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
+        total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
+        total.solve_ms += st.solve_ms; total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches;
+        total.reserved = std::max(total.reserved, st.reserved);
+        done = to;
+    };
+    for (int sampleId = 0; sampleId < s.samplesPerPixel; ++sampleId) {
+        const bool by_spp = s.saveSppMetricsDuration > 0 && sampleId % s.saveSppMetricsDuration == 0 && sampleId < s.saveSppMetricsUntil;
+        const bool by_time = s.saveTimeMetricsDuration > 0 && sampleId % s.saveTimeMetricsDuration == 0;
+        if (!by_spp && !by_time) continue;
+        advance(sampleId + 1);
+        if (by_spp) {
+            write_exr(basePath / "frames" / (std::to_string(sampleId) + ".exr"), s.frameSize.x, s.frameSize.y, f);
+            write_png(basePath / "frames" / (std::to_string(sampleId) + ".png"), s.frameSize.x, s.frameSize.y, f);
+        }
+        if (by_time) {
+            const auto elapsed = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
+            write_exr(basePath / "frames_time" / (std::to_string(elapsed) + ".exr"), s.frameSize.x, s.frameSize.y, f);
+            write_png(basePath / "frames_time" / (std::to_string(elapsed) + ".png"), s.frameSize.x, s.frameSize.y, f);
+        }
+    }
+    advance(s.samplesPerPixel);
+}
+
+static bool wants_metric_frames(const UniformIntegratorSettings &s)
+{
+    return (s.saveSppMetricsDuration > 0 || s.saveTimeMetricsDuration > 0) && s.samplesPerPixel > 0;
+}
+
 uint64_t UniformIntegrator<2>::solve()
 {
     const auto start = std::chrono::high_resolution_clock::now();
     const int n = integratorSettings.frameSize.x * integratorSettings.frameSize.y;
     std::vector<float> &f = channels[(size_t)ExportImageChannel::SOLUTION];
     f.assign((size_t)n * 3, 0.0f);
-    // saveSppMetrics* / saveTimeMetrics* (reference integrator.cu:578-609): frames/<sampleId>.exr|png and
-    // frames_time/<elapsed ms>.exr|png = solution / (sampleId + 1) after sample sampleId.  The pixels of this
-    // integrator do not advance in lock step, but a pixel's first k samples do not depend on the total: each
-    // frame is a solve with spp = k (extra work, a debug feature); the time frames are keyed by the milliseconds
-    // since the start of solve(), as in the reference.
-    const IntegratorSettings &s = integratorSettings;
-    if (s.saveSppMetricsDuration > 0 || s.saveTimeMetricsDuration > 0) {
-        if (s.saveSppMetricsDuration > 0) fs::create_directories(basePath / "frames");
-        if (s.saveTimeMetricsDuration > 0) fs::create_directories(basePath / "frames_time");
-        for (int sampleId = 0; sampleId < s.samplesPerPixel; ++sampleId) {
-            const bool by_spp = s.saveSppMetricsDuration > 0 && sampleId % s.saveSppMetricsDuration == 0 && sampleId < s.saveSppMetricsUntil;
-            const bool by_time = s.saveTimeMetricsDuration > 0 && sampleId % s.saveTimeMetricsDuration == 0;
-            if (!by_spp && !by_time) continue;
-            check_wost(wost_set_option(handle, "spp", sampleId + 1), "wost_set_option(spp)");
-            check_wost(wost_solve(handle, 0, n, f.data(), &last_stats), "wost_solve");
-            if (by_spp) {
-                write_exr(basePath / "frames" / (std::to_string(sampleId) + ".exr"), s.frameSize.x, s.frameSize.y, f);
-                write_png(basePath / "frames" / (std::to_string(sampleId) + ".png"), s.frameSize.x, s.frameSize.y, f);
-            }
-            if (by_time) {
-                const auto elapsed = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
-                write_exr(basePath / "frames_time" / (std::to_string(elapsed) + ".exr"), s.frameSize.x, s.frameSize.y, f);
-                write_png(basePath / "frames_time" / (std::to_string(elapsed) + ".png"), s.frameSize.x, s.frameSize.y, f);
-            }
-        }
-        check_wost(wost_set_option(handle, "spp", s.samplesPerPixel), "wost_set_option(spp)");
+    if (wants_metric_frames(integratorSettings)) {
+        check_wost(wost_solve_restart(handle), "wost_solve_restart");
+        solve_with_metric_frames(integratorSettings, basePath, start, f, last_stats, [&](int more, float *field, wost_stats *st) {
+            check_wost(wost_solve_more(handle, more, field, st), "wost_solve_more");
+        });
+    } else {
+        check_wost(wost_solve(handle, 0, n, f.data(), &last_stats), "wost_solve");
     }
-    check_wost(wost_solve(handle, 0, n, f.data(), &last_stats), "wost_solve");
     const auto end = std::chrono::high_resolution_clock::now();
     return (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(end - start).count();
 }
@@ -128,7 +157,14 @@ uint64_t UniformIntegrator<3>::solve()
     const int n = integratorSettings.frameSize.x * integratorSettings.frameSize.y;
     std::vector<float> &f = channels[(size_t)ExportImageChannel::SOLUTION];
     f.assign((size_t)n * 3, 0.0f);
-    check_wost(wost3_solve(handle, 0, n, f.data(), &last_stats), "wost3_solve");
+    if (wants_metric_frames(integratorSettings)) {
+        check_wost(wost3_solve_restart(handle), "wost3_solve_restart");
+        solve_with_metric_frames(integratorSettings, basePath, start, f, last_stats, [&](int more, float *field, wost_stats *st) {
+            check_wost(wost3_solve_more(handle, more, field, st), "wost3_solve_more");
+        });
+    } else {
+        check_wost(wost3_solve(handle, 0, n, f.data(), &last_stats), "wost3_solve");
+    }
     return (uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::high_resolution_clock::now() - start).count();
 }
 

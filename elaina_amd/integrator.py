@@ -125,6 +125,36 @@ class UniformIntegrator:
         self.last_stats = st.as_dict()
         return self.last_stats
 
+    # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
+    def solve_more(self, more_spp):
+        """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- wost_solve's at
+        spp = spp_done, bit for bit -- is in self.solution; returns wall milliseconds"""
+        field = np.zeros((self.n_pixels, 3), dtype=np.float32)
+        st = Stats()
+        _check(self.lib.wost_solve_more(self._handle, int(more_spp), _fp(field), C.byref(st)), "wost_solve_more")
+        self.solution = field
+        self.last_stats = st.as_dict()
+        return int(st.solve_ms)
+
+    def solve_more_sharded(self, shard_index, shard_count, more_spp, field_dev_ptr, stream_ptr=None):
+        """the same for one shard (as solve_sharded): the carried solve belongs to the shard of its first call"""
+        st = Stats()
+        _check(self.lib.wost_solve_more_sharded(self._handle, shard_index, shard_count, int(more_spp), C.c_void_p(field_dev_ptr),
+                                                C.c_void_p(stream_ptr or 0), C.byref(st)), "wost_solve_more_sharded")
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
+    def restart(self):
+        """forget the carried solve: spp_done = 0, no shard"""
+        _check(self.lib.wost_solve_restart(self._handle), "wost_solve_restart")
+
+    @property
+    def spp_done(self):
+        """samples per pixel of the carried solve so far"""
+        n = C.c_int32(0)
+        _check(self.lib.wost_solve_progress(self._handle, C.byref(n)), "wost_solve_progress")
+        return n.value
+
     def renderDirichletSDF(self):
         out = np.zeros(self.n_pixels, dtype=np.float32)
         _check(self.lib.wost_render_sdf(self._handle, capi.MESH_DIRICHLET, _fp(out)), "wost_render_sdf")

@@ -144,6 +144,31 @@ int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t see
 int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
                           float *field_rgb_dev, void *stream, wost_stats *stats);
 
+/* The continued frame solve: a handle can carry ONE frame solve -- for every pixel the PCG32 state after its samples so far
+ * and its three raw fp32 sums (20 bytes per pixel, allocated on the first call), the number of samples done and the shard they
+ * belong to.  wost_solve_more runs the samples [done, done + more_spp) of every unmasked pixel on top of that state, stores it
+ * back, and field_rgb (width * height * 3 host floats) receives sum / (done + more_spp); done grows by more_spp.  A pixel's
+ * samples share one PCG32 stream and are added to fp32 sums in order, so after any sequence of calls the field is that of
+ * wost_solve over the full frame with spp = done, bit for bit.  Masked pixels are 0 and carry nothing.  The reference writes
+ * such frames while its samples accumulate (integrator/uniform/integrator.cu:578-609).
+ *   - more_spp >= 1 and done + more_spp <= 2^20 - 1 (the cap of the "spp" option); anything else is refused with the bound named
+ *     and the carried solve untouched.  The handle's own spp setting is neither read nor changed.
+ *   - wost_stats and wost_last_launches describe this call alone; over the calls walk_steps, walks_started, walks_absorbed,
+ *     walks_truncated and neumann_hits sum to those of the single solve.
+ *   - wost_solve, wost_solve_sharded, the point solves and wost_set_option leave the carried solve alone; launch options may
+ *     change between two calls (the bits do not depend on them).
+ *   - wost_solve_more_sharded follows wost_solve_sharded: a zero-filled DEVICE field, only owned pixels written, the caller's
+ *     stream.  The first call of a carried solve binds it to (shard_index, shard_count) -- wost_solve_more binds (0, 1) -- and
+ *     a later call with another shard is refused with WOST_ERR_INVALID and a message that names the carried shard.
+ *   - wost_solve_restart forgets the carried solve (done = 0, no shard); wost_solve_progress reports done.
+ *   - a call that fails after device work has begun drops the carried solve (done = 0) and says so in wost_last_error.
+ * Not carried: the guided integrators, point lists; a carried solve cannot be saved. */
+int wost_solve_more(wost_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats);
+int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp,
+                            float *field_rgb_dev, void *stream, wost_stats *stats);
+int wost_solve_restart(wost_handle h);
+int wost_solve_progress(wost_handle h, int32_t *spp_done);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -496,6 +521,13 @@ int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t 
                        wost_stats *stats);
 int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width,
                            float *field_rgb_dev, void *stream, wost_stats *stats);
+/* The continued frame solve in 3-D: wost_solve_more & co. with the same rules (one carried solve per handle, bound to its shard;
+ * the field after any sequence of calls is wost3_solve's at spp = done, bit for bit). */
+int wost3_solve_more(wost3_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats);
+int wost3_solve_more_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev,
+                             void *stream, wost_stats *stats);
+int wost3_solve_restart(wost3_handle h);
+int wost3_solve_progress(wost3_handle h, int32_t *spp_done);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
