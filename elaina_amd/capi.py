@@ -78,6 +78,11 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Adaptive(C.Structure):
+    """wost_adaptive (include/wost.h)"""
+    _fields_ = [("batch_spp", C.c_int32), ("min_batches", C.c_int32), ("max_spp", C.c_int32), ("abs_tol", C.c_float), ("rel_tol", C.c_float)]
+
+
 class Mesh3Desc(C.Structure):
     """wost3_mesh_desc (include/wost.h)"""
     _fields_ = [("n_verts", C.c_int32), ("n_tris", C.c_int32), ("verts", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_int32)),
@@ -172,14 +177,16 @@ FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_double, C.PO
 
 EXPORTS = [
     "wost_create", "wost_solve", "wost_solve_sharded", "wost_solve_points", "wost_solve_points_dev",
-    "wost_solve_more", "wost_solve_more_sharded", "wost_solve_restart", "wost_solve_progress", "wost_render_sdf", "wost_render_source", "wost_closest_point",
+    "wost_solve_more", "wost_solve_more_sharded", "wost_solve_restart", "wost_solve_progress",
+    "wost_solve_more_where", "wost_solve_more_where_sharded", "wost_solve_carried", "wost_solve_adaptive", "wost_solve_adaptive_sharded", "wost_render_sdf", "wost_render_source", "wost_closest_point",
     "wost_closest_silhouette", "wost_ray_intersect", "wost_set_option", "wost_last_launches", "wost_destroy",
     "wost_vonmises_eval", "wost_vonmises_sample", "wost_vmm_pdf_sample", "wost_vmm_loss_gradients",
     "wost_net_create", "wost_net_destroy", "wost_net_n_params", "wost_net_get_params",
     "wost_net_set_params", "wost_net_set_gradient_buffer", "wost_net_inference", "wost_net_train_step", "wost_net_set_option",
     "wost_guided_create", "wost_guided_set_sync", "wost_guided_set_frame_callback", "wost_guided_network", "wost_guided_scene", "wost_guided_query_network", "wost_guided_solve", "wost_guided_solve_sharded", "wost_guided_solve_points", "wost_guided_solve_points_dev", "wost_guided_train_set", "wost_guided_set_option", "wost_guided_destroy",
     "wost3_create", "wost3_solve", "wost3_solve_sharded", "wost3_solve_points", "wost3_solve_points_dev",
-    "wost3_solve_more", "wost3_solve_more_sharded", "wost3_solve_restart", "wost3_solve_progress", "wost3_closest_point", "wost3_closest_silhouette", "wost3_ray_intersect", "wost3_mesh_build_check",
+    "wost3_solve_more", "wost3_solve_more_sharded", "wost3_solve_restart", "wost3_solve_progress",
+    "wost3_solve_more_where", "wost3_solve_more_where_sharded", "wost3_solve_carried", "wost3_solve_adaptive", "wost3_solve_adaptive_sharded", "wost3_closest_point", "wost3_closest_silhouette", "wost3_ray_intersect", "wost3_mesh_build_check",
     "wost3_render_sdf", "wost3_render_source", "wost3_destroy", "wost3_vmf_eval", "wost3_vmf_sample", "wost3_vmm_pdf_sample", "wost3_vmm_loss_gradients",
     "wost3_net_create", "wost3_guided_create", "wost3_guided_destroy", "wost3_guided_network", "wost3_guided_solve", "wost3_guided_solve_sharded", "wost3_guided_solve_points", "wost3_guided_solve_points_dev",
     "wost3_guided_query_network", "wost3_guided_train_set", "wost3_guided_scene",
@@ -222,6 +229,11 @@ def load():
         getattr(L, pre + "solve_more_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         getattr(L, pre + "solve_restart").argtypes = [C.c_void_p]
         getattr(L, pre + "solve_progress").argtypes = [C.c_void_p, ip]
+        getattr(L, pre + "solve_more_where").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), fp, C.POINTER(Stats)]
+        getattr(L, pre + "solve_more_where_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        getattr(L, pre + "solve_carried").argtypes = [C.c_void_p, ip, ip, fp, fp]
+        getattr(L, pre + "solve_adaptive").argtypes = [C.c_void_p, C.POINTER(Adaptive), fp, fp, ip, C.POINTER(Stats)]
+        getattr(L, pre + "solve_adaptive_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.wost_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
     L.wost_render_source.argtypes = [C.c_void_p, fp]
     L.wost_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]

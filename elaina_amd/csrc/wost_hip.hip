@@ -37,6 +37,7 @@
 #include "wost_order.h"
 #include "wost_device.h"
 #include "wost_internal.h"
+#include "wost_carry.h"
 #include "wost_walk.h"
 #include "wost_quad.h"
 #include "wost_coop.h"
@@ -135,11 +136,13 @@ struct InitParams {
     int32_t shard_index, shard_count;
     int32_t tiles_x, tiles_y;
     int32_t stack_stride;
-    // a continued solve (wost_solve_more) with carry_done > 0 samples behind it: a walker starts from its pixel's carried generator
-    // state and raw sums instead of the seed and zero; st.spp is this call's count and the walker counts its samples from 0
+    // a call of a continued solve (wost_solve_more & co., carry_n != nullptr): a walker of a pixel with carry_n[pid] > 0 samples
+    // behind it starts from the pixel's carried generator state and raw sums instead of the seed and zero; st.spp is this call's
+    // count and the walker counts its samples from 0.  select (nullptr: every pixel): a pixel whose byte is 0 is not queued.
     const uint64_t *carry_rng;
     const float *carry_sum;
-    int32_t carry_done;
+    const uint32_t *carry_n;
+    const uint8_t *select;
 };
 
 #define META_SAMPLE(m) ((m) & 0xfffffu)
@@ -162,8 +165,10 @@ __global__ __launch_bounds__(256) void init_kernel(InitParams P)
     int pid = y * P.st.width + x;
     owned = owned && pid >= P.pixel_begin && pid < P.pixel_end && (tile % P.shard_count) == P.shard_index;
     bool active = owned && (P.mask == nullptr || P.mask[pid] != 0) && P.st.spp > 0;
+    active = active && (P.select == nullptr || P.select[pid] != 0);
     if (owned && !active) {
-        // masked pixel: solution stays 0 (reference integrator.cu:92-95, :616-620)
+        // masked pixel: solution stays 0 (reference integrator.cu:92-95, :616-620); a pixel that a continued call leaves out
+        // gets its entry from the kernel that closes the call (wost_carry.hip)
         float *f = P.field + 3 * (size_t)(pid - P.field_base);
         float z = 0.0f / (float)P.st.spp;
         f[0] = z; f[1] = z; f[2] = z;
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256) void init_kernel(InitParams P)
         if (P.dm.n_segs > 0) c0 = closest_point(P.dm, x0, y0, slot_candidate(P.dm, 0, x0, y0), stack, P.stack_stride);
     }
     float sr = 0.0f, sg = 0.0f, sb = 0.0f;
-    if (active && P.carry_done > 0) {
+    if (active && P.carry_n != nullptr && P.carry_n[pid] > 0u) {
         rng.state = P.carry_rng[pid];
         const float *cs = P.carry_sum + 3 * (size_t)pid;
         sr = cs[0]; sg = cs[1]; sb = cs[2];
@@ -1423,12 +1428,8 @@ struct wost_context {
     StatsDev *host_stats = nullptr;            // pinned: the counters as they stood after each launch (last_launches)
     std::vector<wost_launch_info> last_launches;
     uint64_t steps_before = 0;                 // a point solve in chunks: the walk steps of its earlier chunks (wost_launch_info::walk_steps_done)
-    // the carried frame solve (wost_solve_more): per pixel the PCG32 state after its samples so far and the three raw sums (20
-    // bytes, allocated on first use), the samples done, and the shard they belong to (carry_shard_count 0: none yet)
-    void *carry_mem = nullptr;
-    uint64_t *carry_rng = nullptr;
-    float *carry_sum = nullptr;
-    int32_t carry_done = 0, carry_shard_index = 0, carry_shard_count = 0;
+    // the carried frame solve (wost_solve_more & co., wost_carry.h)
+    wost::CarryState carry;
 };
 
 namespace wost {
@@ -1486,7 +1487,7 @@ static void destroy_ctx(wost_context *c)
     if (c->stats) (void)hipFree(c->stats);
     if (c->field) (void)hipFree(c->field);
     if (c->cursor) (void)hipFree(c->cursor);
-    if (c->carry_mem) (void)hipFree(c->carry_mem);
+    carry_free(c->carry);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -2090,18 +2091,21 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
 
 // The first step of a solve, the one that fills queue 0: the frame init on a pixel range and a shard, or (points != nullptr) the
 // point init on points [first, first + n) of a call -- one chunk of a point solve, at most n_pixels points.
-// A frame step with carry_more > 0 is a call of a continued solve (wost_solve_more): carry_more samples on top of the carry_done
-// in the handle's carried buffers -- the solve runs with spp = carry_more, whatever the handle's own setting.
+// A frame step with carry_more > 0 is a call of a continued solve (wost_solve_more & co.): carry_more samples on top of those in
+// the handle's carried buffers -- the solve runs with spp = carry_more, whatever the handle's own setting -- on the pixels of the
+// device map carry_select (nullptr: every pixel).  carry_append: not the first walk of its call, it appends to last_launches.
 struct FirstStep {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
     int32_t first, n, seed_base, seed_width;
     int32_t carry_done, carry_more;
+    const uint8_t *carry_select;
+    bool carry_append;
 };
 static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, int32_t carry_done = 0,
-                            int32_t carry_more = 0)
+                            int32_t carry_more = 0, const uint8_t *carry_select = nullptr, bool carry_append = false)
 {
-    return FirstStep{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0, 0, 0, carry_done, carry_more};
+    return FirstStep{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0, 0, 0, carry_done, carry_more, carry_select, carry_append};
 }
 
 // the shared solve driver: field_dev indexed by (pix - field_base)
@@ -2125,7 +2129,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
         const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
         const InitParams ip{c->dm.view, st, c->probe, c->queue[0], c->counts + 0, c->mask, field_dev, field_base,
                             fs.pixel_begin, fs.pixel_end, fs.shard_index, fs.shard_count, tiles_x, tiles_y, g.bs,
-                            c->carry_rng, c->carry_sum, carried ? fs.carry_done : 0};
+                            c->carry.rng, c->carry.sum, carried ? c->carry.n : nullptr, carried ? fs.carry_select : nullptr};
         const long long n_threads = (long long)tiles_x * tiles_y * 64;
         const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
         hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
@@ -2138,7 +2142,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     double kernel_ms = 0.0;
     uint32_t launches = 0;
     int cur = 0;
-    const bool later_chunk = fs.points && fs.first > 0;
+    const bool later_chunk = (fs.points && fs.first > 0) || (carried && fs.carry_append);
     if (!later_chunk) {
         c->last_launches.clear();
         c->steps_before = 0;
@@ -2146,7 +2150,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     RoundParams base = base_params(c, g, field_dev, field_base);
     base.st = st;
     if (carried) {
-        base.carry_rng = c->carry_rng; base.carry_sum = c->carry_sum; base.carry_total = fs.carry_done + fs.carry_more;
+        base.carry_rng = c->carry.rng; base.carry_sum = c->carry.sum; base.carry_total = fs.carry_done + fs.carry_more;
     }
     SideStreamGuard long_guard, far_guard;   // armed: a launch of the long remainders / of strayed walkers was queued
     uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (launch_strayed)
@@ -2306,7 +2310,7 @@ static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, in
     wost_stats total{};
     const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
     for (int32_t first = 0; first < n; first += cap) {
-        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width, 0, 0};
+        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width, 0, 0, nullptr, false};
         wost_stats st{};
         const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
         if (rc != WOST_OK) return rc;
@@ -2321,76 +2325,116 @@ static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, in
     return WOST_OK;
 }
 
-// ---- the continued frame solve ----
-// The arguments of a continued call that need no look at the handle, in the order and wording of the other solves.
-static int check_solve_more(const void *h, const void *field, int32_t more_spp)
+// ---- the continued frame solve (the drivers: wost_carry.hip) ----
+static CarryFrame carry_frame(const wost_context *c) { return CarryFrame{c->device, c->settings.width, c->settings.height, c->mask}; }
+
+// a walk of the carried solve: a pass of the solve driver on the selected pixels (the 2-D walkers are queued by init_kernel from
+// the map; the id list is the 3-D lanes')
+static CarryWalk carry_walk(wost_context *c, int32_t shard_index, int32_t shard_count)
 {
-    if (!h || !field) return fail(WOST_ERR_INVALID, "null argument");
-    if (more_spp < 1 || more_spp > (1 << 20) - 1) return fail(WOST_ERR_INVALID, "more_spp must be in 1..2^20-1");
+    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *, uint32_t, float *field_dev, hipStream_t stream,
+                                         wost_stats *stats) {
+        const bool append = c->carry.walks > 0;
+        if (!append) c->steps_before = 0;
+        const int rc = run_solve(c, frame_step(0, (int32_t)c->n_pixels, shard_index, shard_count, c->carry.done, more_spp, sel, append), field_dev, 0,
+                                 stream, stats);
+        if (rc == WOST_OK && stats) c->steps_before += stats->walk_steps;
+        return rc;
+    };
+}
+
+// the field of a host call: the handle's device field, zero-filled; after the call it travels to the caller
+static int host_field_begin(wost_context *c)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemsetAsync(c->field, 0, c->n_pixels * 3 * sizeof(float), c->stream));
+    return WOST_OK;
+}
+static int host_field_end(wost_context *c, float *field_rgb, wost_stats *stats, std::chrono::high_resolution_clock::time_point t0)
+{
+    HIP_TRY(hipMemcpyAsync(field_rgb, c->field, c->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return WOST_OK;
 }
 
-static int solve_more(wost_context *c, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_dev, hipStream_t stream, wost_stats *stats)
+int wost_solve_more_where(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
 {
-    if (c->carry_shard_count > 0 && (c->carry_shard_index != shard_index || c->carry_shard_count != shard_count))
-        return fail(WOST_ERR_INVALID, "the carried solve belongs to shard " + std::to_string(c->carry_shard_index) + " of " + std::to_string(c->carry_shard_count) +
-                                          " (wost_solve_restart releases it)");
-    if ((int64_t)c->carry_done + more_spp > (1 << 20) - 1)
-        return fail(WOST_ERR_INVALID, "spp_done + more_spp must be at most 2^20-1 (spp_done is " + std::to_string(c->carry_done) + ")");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->carry_mem) {
-        HIP_TRY(hipMalloc(&c->carry_mem, c->n_pixels * (sizeof(uint64_t) + 3 * sizeof(float))));
-        c->carry_rng = static_cast<uint64_t *>(c->carry_mem);
-        c->carry_sum = reinterpret_cast<float *>(c->carry_rng + c->n_pixels);
-    }
-    const int32_t done = c->carry_done;
-    const int rc = run_solve(c, frame_step(0, (int32_t)c->n_pixels, shard_index, shard_count, done, more_spp), field_dev, 0, stream, stats);
-    if (rc != WOST_OK) {
-        // launches may have written some pixels' carried state and not others': the carried solve is gone
-        (void)hipStreamSynchronize(stream);
-        c->carry_done = 0; c->carry_shard_count = 0;
-        g_last_error += " (the carried solve was dropped: spp_done is 0)";
-        return rc;
-    }
-    c->carry_done = done + more_spp; c->carry_shard_index = shard_index; c->carry_shard_count = shard_count;
-    return WOST_OK;
+    int rc = carry_check_more(h, field_rgb, more_spp);
+    if (rc != WOST_OK) return rc;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if ((rc = host_field_begin(h)) != WOST_OK) return rc;
+    rc = carry_more_where(h->carry, carry_frame(h), 0, 1, more_spp, select, true, h->field, h->stream, stats, carry_walk(h, 0, 1), "wost_");
+    if (rc != WOST_OK) return rc;
+    if (h->carry.walks == 0) h->last_launches.clear();
+    return host_field_end(h, field_rgb, stats, t0);
 }
 
 int wost_solve_more(wost_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
 {
-    int rc = check_solve_more(h, field_rgb, more_spp);
+    return wost_solve_more_where(h, more_spp, nullptr, field_rgb, stats);
+}
+
+int wost_solve_more_where_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, const uint8_t *select_dev,
+                                  float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    int rc = carry_check_more(h, field_rgb_dev, more_spp);
+    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
     if (rc != WOST_OK) return rc;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->field, 0, h->n_pixels * 3 * sizeof(float), h->stream));
-    rc = solve_more(h, 0, 1, more_spp, h->field, h->stream, stats);
-    if (rc != WOST_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(field_rgb, h->field, h->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    return WOST_OK;
+    rc = carry_more_where(h->carry, carry_frame(h), shard_index, shard_count, more_spp, select_dev, false, field_rgb_dev,
+                          reinterpret_cast<hipStream_t>(stream), stats, carry_walk(h, shard_index, shard_count), "wost_");
+    if (rc == WOST_OK && h->carry.walks == 0) h->last_launches.clear();
+    return rc;
 }
 
 int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
                             wost_stats *stats)
 {
-    const int rc = check_solve_more(h, field_rgb_dev, more_spp);
+    return wost_solve_more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
+}
+
+int wost_solve_adaptive_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a, float *field_rgb_dev, void *stream,
+                                wost_stats *stats)
+{
+    int rc = carry_check_adaptive(h, a, field_rgb_dev);
+    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
     if (rc != WOST_OK) return rc;
-    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return fail(WOST_ERR_INVALID, "bad shard");
-    return solve_more(h, shard_index, shard_count, more_spp, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+    rc = carry_adaptive(h->carry, carry_frame(h), shard_index, shard_count, *a, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats,
+                        carry_walk(h, shard_index, shard_count), "wost_");
+    if (rc == WOST_OK && h->carry.walks == 0) h->last_launches.clear();
+    return rc;
+}
+
+int wost_solve_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
+{
+    int rc = carry_check_adaptive(h, a, field_rgb);
+    if (rc != WOST_OK) return rc;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if ((rc = host_field_begin(h)) != WOST_OK) return rc;
+    rc = carry_adaptive(h->carry, carry_frame(h), 0, 1, *a, h->field, h->stream, stats, carry_walk(h, 0, 1), "wost_");
+    if (rc != WOST_OK) return rc;
+    if (h->carry.walks == 0) h->last_launches.clear();
+    if ((stderr_rgb || spp_map) && (rc = carry_read(h->carry, carry_frame(h), spp_map, nullptr, nullptr, stderr_rgb, h->stream)) != WOST_OK) return rc;
+    return host_field_end(h, field_rgb, stats, t0);
+}
+
+int wost_solve_carried(wost_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
+{
+    if (!h) return fail(WOST_ERR_INVALID, "null argument");
+    return carry_read(h->carry, carry_frame(h), spp, batches, sum_rgb, stderr_rgb, h->stream);
 }
 
 int wost_solve_restart(wost_handle h)
 {
     if (!h) return fail(WOST_ERR_INVALID, "null argument");
-    h->carry_done = 0; h->carry_shard_index = 0; h->carry_shard_count = 0;
+    carry_restart(h->carry);
     return WOST_OK;
 }
 
 int wost_solve_progress(wost_handle h, int32_t *spp_done)
 {
     if (!h || !spp_done) return fail(WOST_ERR_INVALID, "null argument");
-    *spp_done = h->carry_done;
+    *spp_done = h->carry.done;
     return WOST_OK;
 }
 

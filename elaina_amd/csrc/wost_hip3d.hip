@@ -59,12 +59,17 @@ struct Walk3Params {
     // (at the end: the frame instantiations read every other field where they always did)
     const float *points;
     int32_t seed_base, seed_width;
-    // a continued frame solve (wost3_solve_more, the CARRY instantiations): a pixel with carry_done > 0 samples behind it starts
-    // from its carried generator state and raw sums; a resolved pixel leaves both under its pixel id and its field entry is
-    // sum / carry_total; st.spp is this call's count and a lane counts the call's samples from 0.  (At the end, like the points.)
+    // a continued frame solve (wost3_solve_more & co., the CARRY instantiations): a pixel with carry_n[pid] > 0 samples behind it
+    // starts from its carried generator state and raw sums; a resolved pixel leaves both under its pixel id and its field entry is
+    // sum / carry_total (the kernel that closes the call writes the pixel's own: wost_carry.hip); st.spp is this call's count and a
+    // lane counts the call's samples from 0.  ids != nullptr: the call walks a selection -- slot s is pixel ids[s] of n_ids, every
+    // one owned and unmasked.  (At the end, like the points.)
     uint64_t *carry_rng;
     float *carry_sum;
     int32_t carry_done, carry_total;
+    const uint32_t *carry_n;
+    const int32_t *ids;
+    int32_t n_ids;
 };
 
 // One lane = one pixel, all its samples one after the other on the pixel's PCG stream (the reference's per-pixel
@@ -417,7 +422,7 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
     Trav T = trav_begin(Closest{WOST_INF, -1});
     uint32_t pool_next = 0, pool_end = 0;
     uint32_t t_steps = 0, t_started = 0, t_absorbed = 0, t_truncated = 0, t_nhits = 0;
-    const uint32_t n_slots = (uint32_t)(P.pixel_end - P.pixel_begin);
+    const uint32_t n_slots = CARRY && P.ids ? (uint32_t)P.n_ids : (uint32_t)(P.pixel_end - P.pixel_begin);
 
     // start the query of a step (or serve it from the cache of the evaluation point)
     auto begin_step = [&]() {
@@ -493,15 +498,16 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                     }
                 } else {
                     // slots walk the frame in 8x8 tiles when the range is the whole tiled frame (neighbouring walkers in a wave)
-                    int pid = P.pixel_begin + (int)s2;
-                    if (P.tiled) {
+                    const bool listed = CARRY && P.ids != nullptr;
+                    int pid = listed ? P.ids[s2] : P.pixel_begin + (int)s2;
+                    if (!listed && P.tiled) {
                         const int tiles_x = P.st.width >> 3, tile = pid >> 6, in_tile = pid & 63;
                         pid = ((tile / tiles_x) * 8 + (in_tile >> 3)) * P.st.width + (tile % tiles_x) * 8 + (in_tile & 7);
                     }
                     const int px = pid % P.st.width, py = pid / P.st.width;
                     const int tile = (py >> 3) * ((P.st.width + 7) >> 3) + (px >> 3);
-                    if ((tile % P.shard_count) == P.shard_index) {
-                        const bool masked = P.mask != nullptr && P.mask[pid] == 0;
+                    if (listed || (tile % P.shard_count) == P.shard_index) {
+                        const bool masked = !listed && P.mask != nullptr && P.mask[pid] == 0;
                         if (masked || P.st.spp <= 0) {
                             float *f = P.field + 3 * (size_t)(pid - P.field_base);
                             const float spp = (float)P.st.spp;
@@ -513,7 +519,7 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                             L.pid = pid;
                             L.rng = Pcg{0, 1};
                             pcg_seed_pixel(L.rng, pid, P.st.width);
-                            if (CARRY && P.carry_done > 0) {
+                            if (CARRY && P.carry_n[pid] > 0u) {
                                 L.rng.state = P.carry_rng[pid];
                                 const float *cs = P.carry_sum + 3 * (size_t)pid;
                                 L.sol[0] = cs[0]; L.sol[1] = cs[1]; L.sol[2] = cs[2];
@@ -757,7 +763,7 @@ static void destroy3(wost3_context *c)
     if (c->field) (void)hipFree(c->field);
     if (c->stats) (void)hipFree(c->stats);
     if (c->cursor) (void)hipFree(c->cursor);
-    if (c->carry_mem) (void)hipFree(c->carry_mem);
+    carry_free(c->carry);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -823,13 +829,16 @@ static const void *walk3_kernel_of(const Walk3Plan &pl)
 
 // The first step of a solve, what a lane's refill reads: the pixels [pixel_begin, pixel_end) of the frame and a shard of its tiles, or
 // (points != nullptr) the points [pixel_begin, pixel_end) of a caller's list with their seeds.
-// A frame step with carry_more > 0 is a call of a continued solve (wost3_solve_more): carry_more samples on top of the carry_done in
-// the handle's carried buffers -- the launch runs with spp = carry_more, whatever the handle's own setting.
+// A frame step with carry_more > 0 is a call of a continued solve (wost3_solve_more & co.): carry_more samples on top of those in
+// the handle's carried buffers -- the launch runs with spp = carry_more, whatever the handle's own setting -- on the carry_n_ids
+// pixels of the device list carry_ids (nullptr: every pixel of the shard).
 struct FirstStep3 {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
     int32_t seed_base, seed_width;
     int32_t carry_done = 0, carry_more = 0;
+    const int32_t *carry_ids = nullptr;
+    int32_t carry_n_ids = 0;
 };
 
 static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
@@ -839,7 +848,8 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
     W3_TRY(hipSetDevice(c->device));
     W3_TRY(hipMemsetAsync(c->stats, 0, kStat3Copies * sizeof(Stats3Dev), stream));
     W3_TRY(hipMemsetAsync(c->cursor, 0, sizeof(uint32_t), stream));
-    const int n = pixel_end - pixel_begin;
+    // (the lanes a launch needs: those of the selection where a continued call has one)
+    const int n = fs.carry_more > 0 && fs.carry_ids ? fs.carry_n_ids : pixel_end - pixel_begin;
     float ms = 0.0f;
     if (n > 0) {
         const Walk3Plan pl = walk3_plan(c, n);
@@ -852,7 +862,8 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
         const bool carried = !fs.points && fs.carry_more > 0;
         if (carried) {
             P.st.spp = fs.carry_more;
-            P.carry_rng = c->carry_rng; P.carry_sum = c->carry_sum; P.carry_done = fs.carry_done; P.carry_total = fs.carry_done + fs.carry_more;
+            P.carry_rng = c->carry.rng; P.carry_sum = c->carry.sum; P.carry_done = fs.carry_done; P.carry_total = fs.carry_done + fs.carry_more;
+            P.carry_n = c->carry.n; P.ids = fs.carry_ids; P.n_ids = fs.carry_n_ids;
         }
         P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
         P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
@@ -983,75 +994,106 @@ int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count
     return run_solve3(h, FirstStep3{0, (int32_t)h->n_pixels, shard_index, shard_count, nullptr, 0, 0}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
 }
 
-// ---- the continued frame solve (wost_solve_more in 3-D: the same checks, in the same order and words) ----
-static int check_solve_more3(const void *h, const void *field, int32_t more_spp)
+// ---- the continued frame solve (wost_solve_more & co. in 3-D: the same drivers, wost_carry.hip) ----
+static CarryFrame carry_frame3(const wost3_context *c) { return CarryFrame{c->device, c->settings.width, c->settings.height, c->mask}; }
+
+// a walk of the carried solve: one launch, its lanes on the pixels of the id list where the call has a selection
+static CarryWalk carry_walk3(wost3_context *c, int32_t shard_index, int32_t shard_count)
 {
-    if (!h || !field) return set_error(WOST_ERR_INVALID, "null argument");
-    if (more_spp < 1 || more_spp > (1 << 20) - 1) return set_error(WOST_ERR_INVALID, "more_spp must be in 1..2^20-1");
+    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *ids, uint32_t n_sel, float *field_dev, hipStream_t stream,
+                                         wost_stats *stats) {
+        FirstStep3 fs{0, (int32_t)c->n_pixels, shard_index, shard_count, nullptr, 0, 0};
+        fs.carry_done = c->carry.done; fs.carry_more = more_spp;
+        if (sel) { fs.carry_ids = ids; fs.carry_n_ids = (int32_t)n_sel; }
+        return run_solve3(c, fs, field_dev, 0, stream, stats);
+    };
+}
+
+static int host_field_begin3(wost3_context *c)
+{
+    W3_TRY(hipSetDevice(c->device));
+    W3_TRY(hipMemsetAsync(c->field, 0, c->n_pixels * 3 * sizeof(float), c->stream));
+    return WOST_OK;
+}
+static int host_field_end3(wost3_context *c, float *field_rgb, wost_stats *stats, std::chrono::high_resolution_clock::time_point t0)
+{
+    W3_TRY(hipMemcpyAsync(field_rgb, c->field, c->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    W3_TRY(hipStreamSynchronize(c->stream));
+    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return WOST_OK;
 }
 
-static int solve_more3(wost3_context *c, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_dev, hipStream_t stream, wost_stats *stats)
+int wost3_solve_more_where(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
 {
-    if (c->carry_shard_count > 0 && (c->carry_shard_index != shard_index || c->carry_shard_count != shard_count))
-        return set_error(WOST_ERR_INVALID, "the carried solve belongs to shard " + std::to_string(c->carry_shard_index) + " of " +
-                                               std::to_string(c->carry_shard_count) + " (wost3_solve_restart releases it)");
-    if ((int64_t)c->carry_done + more_spp > (1 << 20) - 1)
-        return set_error(WOST_ERR_INVALID, "spp_done + more_spp must be at most 2^20-1 (spp_done is " + std::to_string(c->carry_done) + ")");
-    W3_TRY(hipSetDevice(c->device));
-    if (!c->carry_mem) {
-        W3_TRY(hipMalloc(&c->carry_mem, c->n_pixels * (sizeof(uint64_t) + 3 * sizeof(float))));
-        c->carry_rng = static_cast<uint64_t *>(c->carry_mem);
-        c->carry_sum = reinterpret_cast<float *>(c->carry_rng + c->n_pixels);
-    }
-    const int32_t done = c->carry_done;
-    FirstStep3 fs{0, (int32_t)c->n_pixels, shard_index, shard_count, nullptr, 0, 0};
-    fs.carry_done = done; fs.carry_more = more_spp;
-    const int rc = run_solve3(c, fs, field_dev, 0, stream, stats);
-    if (rc != WOST_OK) {
-        // the launch may have written some pixels' carried state and not others': the carried solve is gone
-        const std::string msg = wost_last_error();
-        (void)hipStreamSynchronize(stream);
-        c->carry_done = 0; c->carry_shard_count = 0;
-        return set_error(rc, msg + " (the carried solve was dropped: spp_done is 0)");
-    }
-    c->carry_done = done + more_spp; c->carry_shard_index = shard_index; c->carry_shard_count = shard_count;
-    return WOST_OK;
+    int rc = carry_check_more(h, field_rgb, more_spp);
+    if (rc != WOST_OK) return rc;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if ((rc = host_field_begin3(h)) != WOST_OK) return rc;
+    rc = carry_more_where(h->carry, carry_frame3(h), 0, 1, more_spp, select, true, h->field, h->stream, stats, carry_walk3(h, 0, 1), "wost3_");
+    if (rc != WOST_OK) return rc;
+    return host_field_end3(h, field_rgb, stats, t0);
 }
 
 int wost3_solve_more(wost3_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
 {
-    int rc = check_solve_more3(h, field_rgb, more_spp);
+    return wost3_solve_more_where(h, more_spp, nullptr, field_rgb, stats);
+}
+
+int wost3_solve_more_where_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, const uint8_t *select_dev,
+                                   float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    int rc = carry_check_more(h, field_rgb_dev, more_spp);
+    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
     if (rc != WOST_OK) return rc;
-    W3_TRY(hipSetDevice(h->device));
-    W3_TRY(hipMemsetAsync(h->field, 0, h->n_pixels * 3 * sizeof(float), h->stream));
-    rc = solve_more3(h, 0, 1, more_spp, h->field, h->stream, stats);
-    if (rc != WOST_OK) return rc;
-    W3_TRY(hipMemcpyAsync(field_rgb, h->field, h->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    return carry_more_where(h->carry, carry_frame3(h), shard_index, shard_count, more_spp, select_dev, false, field_rgb_dev,
+                            reinterpret_cast<hipStream_t>(stream), stats, carry_walk3(h, shard_index, shard_count), "wost3_");
 }
 
 int wost3_solve_more_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
                              wost_stats *stats)
 {
-    const int rc = check_solve_more3(h, field_rgb_dev, more_spp);
+    return wost3_solve_more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
+}
+
+int wost3_solve_adaptive_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a, float *field_rgb_dev, void *stream,
+                                 wost_stats *stats)
+{
+    int rc = carry_check_adaptive(h, a, field_rgb_dev);
+    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
     if (rc != WOST_OK) return rc;
-    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
-    return solve_more3(h, shard_index, shard_count, more_spp, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+    return carry_adaptive(h->carry, carry_frame3(h), shard_index, shard_count, *a, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats,
+                          carry_walk3(h, shard_index, shard_count), "wost3_");
+}
+
+int wost3_solve_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
+{
+    int rc = carry_check_adaptive(h, a, field_rgb);
+    if (rc != WOST_OK) return rc;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if ((rc = host_field_begin3(h)) != WOST_OK) return rc;
+    rc = carry_adaptive(h->carry, carry_frame3(h), 0, 1, *a, h->field, h->stream, stats, carry_walk3(h, 0, 1), "wost3_");
+    if (rc != WOST_OK) return rc;
+    if ((stderr_rgb || spp_map) && (rc = carry_read(h->carry, carry_frame3(h), spp_map, nullptr, nullptr, stderr_rgb, h->stream)) != WOST_OK) return rc;
+    return host_field_end3(h, field_rgb, stats, t0);
+}
+
+int wost3_solve_carried(wost3_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    return carry_read(h->carry, carry_frame3(h), spp, batches, sum_rgb, stderr_rgb, h->stream);
 }
 
 int wost3_solve_restart(wost3_handle h)
 {
     if (!h) return set_error(WOST_ERR_INVALID, "null argument");
-    h->carry_done = 0; h->carry_shard_index = 0; h->carry_shard_count = 0;
+    carry_restart(h->carry);
     return WOST_OK;
 }
 
 int wost3_solve_progress(wost3_handle h, int32_t *spp_done)
 {
     if (!h || !spp_done) return set_error(WOST_ERR_INVALID, "null argument");
-    *spp_done = h->carry_done;
+    *spp_done = h->carry.done;
     return WOST_OK;
 }
 

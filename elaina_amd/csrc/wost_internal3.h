@@ -12,6 +12,7 @@
 #include "../../include/wost.h"
 #include "wost_device3.h"
 #include "wost_internal.h"
+#include "wost_carry.h"
 
 namespace wost {
 
@@ -73,12 +74,8 @@ struct wost3_context {
     int wait_weight = 32, trav_burst = 3;   // a sweep over both constants: a leaf visit (four exact triangle distances) is dear, steps are served early
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the carried frame solve (wost3_solve_more): per pixel the PCG32 state after its samples so far and the three raw sums (20
-    // bytes, allocated on first use), the samples done, and the shard they belong to (carry_shard_count 0: none yet)
-    void *carry_mem = nullptr;
-    uint64_t *carry_rng = nullptr;
-    float *carry_sum = nullptr;
-    int32_t carry_done = 0, carry_shard_index = 0, carry_shard_count = 0;
+    // the carried frame solve (wost3_solve_more & co., wost_carry.h)
+    wost::CarryState carry;
 };
 
 #define W3_TRY(expr)                                                                                   \

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .carried import CarriedSolves
 from .capi import MeshDesc, SceneDesc, Settings, Stats, _check, _fp, _ip
 
 
@@ -66,7 +67,8 @@ def scene_desc(keep, problem, w, h):
     return sc
 
 
-class UniformIntegrator:
+class UniformIntegrator(CarriedSolves):
+    _prefix = "wost_"      # (CarriedSolves: solve_more_where, carried, solve_adaptive)
     VectorType = tuple
 
     def __init__(self, problem, settings, device=0):

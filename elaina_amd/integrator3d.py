@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .carried import CarriedSolves
 from .capi import Mesh3Desc, Scene3Desc, Settings, Stats, _check, _fp, _ip
 
 
@@ -80,7 +81,8 @@ def scene3_desc(keep, problem, w, h):
     return sc
 
 
-class UniformIntegrator3:
+class UniformIntegrator3(CarriedSolves):
+    _prefix = "wost3_"      # (CarriedSolves: solve_more_where, carried, solve_adaptive)
     VectorType = tuple
 
     def __init__(self, problem, settings, device=0):

@@ -144,9 +144,9 @@ int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t see
 int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
                           float *field_rgb_dev, void *stream, wost_stats *stats);
 
-/* The continued frame solve: a handle can carry ONE frame solve -- for every pixel the PCG32 state after its samples so far
- * and its three raw fp32 sums (20 bytes per pixel, allocated on the first call), the number of samples done and the shard they
- * belong to.  wost_solve_more runs the samples [done, done + more_spp) of every unmasked pixel on top of that state, stores it
+/* The continued frame solve: a handle can carry ONE frame solve -- for every pixel the PCG32 state after its samples so far,
+ * its three raw fp32 sums, its own sample and batch counts and the batch statistics of the error estimate below (52 bytes per
+ * pixel, allocated and zeroed on the first call), the samples asked for so far and the shard they belong to.  wost_solve_more runs the samples [done, done + more_spp) of every unmasked pixel on top of that state, stores it
  * back, and field_rgb (width * height * 3 host floats) receives sum / (done + more_spp); done grows by more_spp.  A pixel's
  * samples share one PCG32 stream and are added to fp32 sums in order, so after any sequence of calls the field is that of
  * wost_solve over the full frame with spp = done, bit for bit.  Masked pixels are 0 and carry nothing.  The reference writes
@@ -168,6 +168,45 @@ int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_co
                             float *field_rgb_dev, void *stream, wost_stats *stats);
 int wost_solve_restart(wost_handle h);
 int wost_solve_progress(wost_handle h, int32_t *spp_done);
+
+/* Continuing a SELECTION of pixels, the per-pixel state, and solves that stop by a per-pixel error estimate.
+ * Every pixel of a carried solve has its own sample count n and batch count K: a batch is one continued call that walked the
+ * pixel.  A pixel taken up at any count continues its own PCG32 stream and fp32 sums, so its field entry, sum / n, is that of
+ * wost_solve at spp = n, bit for bit, whatever the other pixels did.
+ *   - wost_solve_more_where: wost_solve_more on the pixels whose byte in select (width * height host bytes) is nonzero; NULL
+ *     means every pixel and is wost_solve_more.  Masked pixels stay 0 and carry nothing even when selected; the pixels of
+ *     another shard are not this handle's.  field_rgb receives every pixel's sum / n (0 where n is 0); wost_stats counts the
+ *     walks of the selected pixels alone.  An empty selection returns WOST_OK with zeroed stats and the field of the carried
+ *     state, and launches no walk.  wost_solve_more_where_sharded takes the selection from DEVICE bytes (select_dev) and is
+ *     bound to its shard like wost_solve_more_sharded.
+ *   - wost_solve_progress keeps its meaning: the sum of more_spp over the calls since the restart -- the count of a pixel that
+ *     every call selected -- and the bound 2^20 - 1 applies to it.  The per-pixel counts come from wost_solve_carried.
+ *   - the error estimate (batch means): with b_k the sum a pixel gained in its batch k of m_k samples, q = sum_k b_k^2 / m_k,
+ *     N = n, S = sum: v = max(q - S * S / N, 0), se = sqrt(v / ((K - 1) * N)) per channel, in fp32 in this order; +inf while
+ *     K < 2.  It is the standard error of the pixel's mean S / N when the batches are independent and equally distributed.
+ *   - wost_solve_carried copies the state to host arrays of width * height (spp, batches) and width * height * 3 (sum_rgb,
+ *     stderr_rgb) entries; any of them may be NULL.  A pixel that is unowned, masked or never walked has 0, 0, 0 sums and +inf.
+ *   - wost_solve_adaptive is this loop on the carried solve, as it stands when the call begins: select the pixels that are
+ *     owned, unmasked, NOT converged and have n + batch_spp <= max_spp; while any is selected, run batch_spp samples on them
+ *     (a wost_solve_more_where on the device selection) and select again.  Converged: K >= min_batches and in every channel
+ *     se <= max(abs_tol, rel_tol * |S / N|); a NaN is never converged.  Per round the host reads back one count.  A second
+ *     call with tighter tolerances or a larger max_spp resumes.  wost_stats sums the rounds (solve_ms: the whole call) and
+ *     wost_last_launches lists all rounds' launches in order.  stderr_rgb and spp_map (host, may be NULL) receive se and n.
+ *     Refused before the handle is read: batch_spp < 1, min_batches < 2, max_spp < batch_spp, a tolerance that is negative or
+ *     not finite.  Stopping by the estimate biases the result (pixels whose early batches agree by chance stop early), and
+ *     batch means under-estimates the error of a pixel with rare bright contributions: see DESIGN 4.3d. */
+typedef struct wost_adaptive {
+    int32_t batch_spp, min_batches, max_spp;
+    float abs_tol, rel_tol;
+} wost_adaptive;
+int wost_solve_more_where(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats);
+int wost_solve_more_where_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp,
+                                  const uint8_t *select_dev, float *field_rgb_dev, void *stream, wost_stats *stats);
+int wost_solve_carried(wost_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb);
+int wost_solve_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map,
+                        wost_stats *stats);
+int wost_solve_adaptive_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a,
+                                float *field_rgb_dev, void *stream, wost_stats *stats);
 
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
@@ -528,6 +567,15 @@ int wost3_solve_more_sharded(wost3_handle h, int32_t shard_index, int32_t shard_
                              void *stream, wost_stats *stats);
 int wost3_solve_restart(wost3_handle h);
 int wost3_solve_progress(wost3_handle h, int32_t *spp_done);
+/* ... and its selections, per-pixel state and adaptive solves (wost_solve_more_where & co., the same rules) */
+int wost3_solve_more_where(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats);
+int wost3_solve_more_where_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp,
+                                   const uint8_t *select_dev, float *field_rgb_dev, void *stream, wost_stats *stats);
+int wost3_solve_carried(wost3_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb);
+int wost3_solve_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map,
+                         wost_stats *stats);
+int wost3_solve_adaptive_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a,
+                                 float *field_rgb_dev, void *stream, wost_stats *stats);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
