@@ -582,12 +582,6 @@ struct B2Buffer {
 
 }  // namespace
 
-#define B2_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string("mesh build: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static inline dim3 b2_grid(long long count) { return dim3((unsigned)std::max<long long>(1, (count + 255) / 256)); }
 
 int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
@@ -623,10 +617,10 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
                  o_flatCol = out.take((size_t)n * 48), o_sil = out.take((size_t)nv * sizeof(DevSilVertex)), o_silN = out.take((size_t)nv * 16),
                  o_scanBox = out.take(n_scan_pad * 16), o_scanHl = out.take(n_scan_pad * 4), o_scanId = out.take(n_scan_pad * 8);
     size_t sort_a = 0, sort_b = 0, scan_c = 0, scan_d = 0;
-    B2_TRY(rocprim::radix_sort_pairs(nullptr, sort_a, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, 32u));
-    B2_TRY(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, (unsigned)(32 + rid_bits)));
-    B2_TRY(rocprim::inclusive_scan_by_key(nullptr, scan_c, (uint32_t *)nullptr, (float4 *)nullptr, (float4 *)nullptr, (size_t)n, B2BoxOp()));
-    B2_TRY(rocprim::exclusive_scan(nullptr, scan_d, (int32_t *)nullptr, (int32_t *)nullptr, 0, n_slots, rocprim::plus<int32_t>()));
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(nullptr, sort_a, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, 32u));
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, (unsigned)(32 + rid_bits)));
+    WOST_BUILD_TRY(rocprim::inclusive_scan_by_key(nullptr, scan_c, (uint32_t *)nullptr, (float4 *)nullptr, (float4 *)nullptr, (size_t)n, B2BoxOp()));
+    WOST_BUILD_TRY(rocprim::exclusive_scan(nullptr, scan_d, (int32_t *)nullptr, (int32_t *)nullptr, 0, n_slots, rocprim::plus<int32_t>()));
     const size_t max_ranges = (size_t)2 * S.cap;
     const size_t t_meta = tmp.take(sizeof(B2Meta)), t_verts = tmp.take((size_t)nv * 8), t_segs = tmp.take((size_t)n * 8), t_colors = tmp.take(d.colors ? (size_t)nv * 24 : 0),
                  t_vprev = tmp.take((size_t)nv * 4), t_vnext = tmp.take((size_t)nv * 4), t_code = tmp.take((size_t)n * 4), t_code2 = tmp.take((size_t)n * 4),
@@ -638,8 +632,8 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
                  t_c0 = tmp.take(max_ranges * 8), t_c1 = tmp.take(max_ranges * 8), t_o0 = tmp.take(max_ranges * 4), t_o1 = tmp.take(max_ranges * 4),
                  t_slot_of = tmp.take(n_slots * 4), t_flag = tmp.take(n_slots * 4), t_dst = tmp.take(n_slots * 4), t_sums = tmp.take((size_t)S.n_all * sizeof(B2Sums)), t_fixed = tmp.take((size_t)S.n_all * sizeof(B2Fixed)),
                  t_rp = tmp.take(std::max(std::max(sort_a, sort_b), std::max(scan_c, scan_d)));
-    B2_TRY(hipMalloc((void **)&out.base, out.size));
-    B2_TRY(hipMalloc((void **)&tmp.base, tmp.size));
+    WOST_BUILD_TRY(hipMalloc((void **)&out.base, out.size));
+    WOST_BUILD_TRY(hipMalloc((void **)&tmp.base, tmp.size));
     hipStream_t st = nullptr;
     B2Meta *meta = tmp.at<B2Meta>(t_meta);
     float *verts = tmp.at<float>(t_verts);
@@ -648,9 +642,9 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     int32_t *vprev = tmp.at<int32_t>(t_vprev), *vnext = tmp.at<int32_t>(t_vnext);
     DevFlatSeg *flat = out.at<DevFlatSeg>(o_flat);
     float *flatCol = out.at<float>(o_flatCol);
-    B2_TRY(hipMemcpyAsync(verts, d.verts, (size_t)nv * 8, hipMemcpyHostToDevice, st));
-    B2_TRY(hipMemcpyAsync(segs, d.segs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if (d.colors) B2_TRY(hipMemcpyAsync(colors, d.colors, (size_t)nv * 24, hipMemcpyHostToDevice, st));
+    WOST_BUILD_TRY(hipMemcpyAsync(verts, d.verts, (size_t)nv * 8, hipMemcpyHostToDevice, st));
+    WOST_BUILD_TRY(hipMemcpyAsync(segs, d.segs, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (d.colors) WOST_BUILD_TRY(hipMemcpyAsync(colors, d.colors, (size_t)nv * 24, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(b2_init_kernel, dim3(1), dim3(1), 0, st, meta);
     hipLaunchKernelGGL(b2_fill_i32_kernel, b2_grid(nv), dim3(256), 0, st, vprev, (long long)nv, 0x7fffffff);
     hipLaunchKernelGGL(b2_fill_i32_kernel, b2_grid(nv), dim3(256), 0, st, vnext, (long long)nv, 0x7fffffff);
@@ -660,7 +654,7 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     hipLaunchKernelGGL(b2_code_kernel, b2_grid(n), dim3(256), 0, st, flat, verts, segs, n, meta, tmp.at<uint32_t>(t_code), tmp.at<int32_t>(t_idx), items);
     int32_t *perm = tmp.at<int32_t>(t_perm), *perm2 = tmp.at<int32_t>(t_perm2);
     size_t rp_bytes = sort_a;
-    B2_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint32_t>(t_code), tmp.at<uint32_t>(t_code2), tmp.at<int32_t>(t_idx), perm, (size_t)n, 0u, 32u, st));
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint32_t>(t_code), tmp.at<uint32_t>(t_code2), tmp.at<int32_t>(t_idx), perm, (size_t)n, 0u, 32u, st));
 
     // ---- the refinement, level by level: round A splits every node's range in two, round B each half again ----
     int32_t *rb = tmp.at<int32_t>(t_rb), *re = tmp.at<int32_t>(t_re), *rb2 = tmp.at<int32_t>(t_rb2), *re2 = tmp.at<int32_t>(t_re2);
@@ -672,13 +666,13 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     float4 *fwd = tmp.at<float4>(t_fwd), *rev = tmp.at<float4>(t_rev), *pre = tmp.at<float4>(t_pre), *suf = tmp.at<float4>(t_suf);
     {
         const int32_t r0[2] = {0, n};
-        B2_TRY(hipMemcpyAsync(rb, &r0[0], 4, hipMemcpyHostToDevice, st));
-        B2_TRY(hipMemcpyAsync(re, &r0[1], 4, hipMemcpyHostToDevice, st));
+        WOST_BUILD_TRY(hipMemcpyAsync(rb, &r0[0], 4, hipMemcpyHostToDevice, st));
+        WOST_BUILD_TRY(hipMemcpyAsync(re, &r0[1], 4, hipMemcpyHostToDevice, st));
     }
     auto sort_by = [&](int axis) -> int {
         hipLaunchKernelGGL(b2_key_kernel, b2_grid(n), dim3(256), 0, st, perm, rid, items, range_axis, axis, n, keys);
         size_t bytes = sort_b;
-        B2_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), bytes, keys, keys2, perm, perm2, (size_t)n, 0u, (unsigned)(32 + rid_bits), st));
+        WOST_BUILD_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), bytes, keys, keys2, perm, perm2, (size_t)n, 0u, (unsigned)(32 + rid_bits), st));
         std::swap(perm, perm2);
         return WOST_OK;
     };
@@ -690,9 +684,9 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
             if (rc != WOST_OK) return rc;
             hipLaunchKernelGGL(b2_vals_kernel, b2_grid(n), dim3(256), 0, st, perm, rid, items, n, fwd, rev, rid_rev);
             size_t bytes = scan_c;
-            B2_TRY(rocprim::inclusive_scan_by_key(tmp.at<void>(t_rp), bytes, rid, fwd, pre, (size_t)n, B2BoxOp(), rocprim::equal_to<uint32_t>(), st));
+            WOST_BUILD_TRY(rocprim::inclusive_scan_by_key(tmp.at<void>(t_rp), bytes, rid, fwd, pre, (size_t)n, B2BoxOp(), rocprim::equal_to<uint32_t>(), st));
             bytes = scan_c;
-            B2_TRY(rocprim::inclusive_scan_by_key(tmp.at<void>(t_rp), bytes, rid_rev, rev, suf, (size_t)n, B2BoxOp(), rocprim::equal_to<uint32_t>(), st));
+            WOST_BUILD_TRY(rocprim::inclusive_scan_by_key(tmp.at<void>(t_rp), bytes, rid_rev, rev, suf, (size_t)n, B2BoxOp(), rocprim::equal_to<uint32_t>(), st));
             hipLaunchKernelGGL(b2_cost_min_kernel, b2_grid(n), dim3(256), 0, st, rb, re, rid, pre, suf, n, cap_side, axis, axis == 0 ? c0 : c1);
             hipLaunchKernelGGL(b2_cost_arg_kernel, b2_grid(n), dim3(256), 0, st, rb, re, rid, pre, suf, n, cap_side, axis, axis == 0 ? c0 : c1, axis == 0 ? o0 : o1);
         }
@@ -726,8 +720,8 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     float *nodes = out.at<float>(o_nodes), *cones = out.at<float>(o_cones);
     B2Sums *sums = tmp.at<B2Sums>(t_sums);
     B2Fixed *fixed = tmp.at<B2Fixed>(t_fixed);
-    B2_TRY(hipMemsetAsync(nodes, 0, (size_t)S.n_all * WOST_NODE_FLOATS * 4, st));
-    B2_TRY(hipMemsetAsync(cones, 0, (size_t)S.n_all * 80, st));
+    WOST_BUILD_TRY(hipMemsetAsync(nodes, 0, (size_t)S.n_all * WOST_NODE_FLOATS * 4, st));
+    WOST_BUILD_TRY(hipMemsetAsync(cones, 0, (size_t)S.n_all * 80, st));
     hipLaunchKernelGGL(b2_leaf_kernel, b2_grid(S.cap), dim3(256), 0, st, S, slot_of, flat, flatCol, verts, segs, vprev, vnext, meta, out.at<float4>(o_segA),
                        out.at<float>(o_segInv), out.at<int32_t>(o_segOrig), out.at<float>(o_segCol), out.at<int2>(o_segVerts), nodes, cones, sums, fixed);
     {
@@ -745,12 +739,12 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     int32_t *flag = tmp.at<int32_t>(t_flag), *dst = tmp.at<int32_t>(t_dst);
     hipLaunchKernelGGL(b2_occupied_kernel, b2_grid((long long)n_slots), dim3(256), 0, st, slot_of, (long long)n_slots, flag);
     rp_bytes = scan_d;
-    B2_TRY(rocprim::exclusive_scan(tmp.at<void>(t_rp), rp_bytes, flag, dst, 0, n_slots, rocprim::plus<int32_t>(), st));
+    WOST_BUILD_TRY(rocprim::exclusive_scan(tmp.at<void>(t_rp), rp_bytes, flag, dst, 0, n_slots, rocprim::plus<int32_t>(), st));
     hipLaunchKernelGGL(b2_scan_copy_kernel, b2_grid((long long)std::max(n_slots, n_scan_pad)), dim3(256), 0, st, S, slot_of, dst, nodes, (long long)n_scan_pad,
                        out.at<float4>(o_scanBox), out.at<float>(o_scanHl), out.at<int2>(o_scanId));
-    B2_TRY(hipGetLastError());
+    WOST_BUILD_TRY(hipGetLastError());
     B2Meta hm{};
-    B2_TRY(hipMemcpy(&hm, meta, sizeof(hm), hipMemcpyDeviceToHost));         // the one wait of the build
+    WOST_BUILD_TRY(hipMemcpy(&hm, meta, sizeof(hm), hipMemcpyDeviceToHost));         // the one wait of the build
     if (hm.bad) return set_error(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
     const float ext = std::max(std::max(std::fabs(b2_dec(hm.lo[0])), std::fabs(b2_dec(hm.hi[0]))), std::max(std::fabs(b2_dec(hm.lo[1])), std::fabs(b2_dec(hm.hi[1]))));
     v.n_sil = nv; v.levels = S.levels; v.first_leaf = S.first_leaf; v.emissive = hm.emissive;

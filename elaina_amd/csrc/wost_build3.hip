@@ -766,12 +766,6 @@ struct B3Buffer {               // one allocation, carved in 256-byte steps
 
 }  // namespace
 
-#define B3_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string("mesh build: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static inline dim3 b3_grid(long long count) { return dim3((unsigned)std::max<long long>(1, (count + 255) / 256)); }
 
 // the mesh of `d` built on the current device into s.view; everything the view points at is one allocation (s.allocs)
@@ -816,18 +810,18 @@ static int build_mesh3_device(const wost3_mesh_desc &d, DeviceMesh3 &s)
                  o_cones = out.take((size_t)S.n_nodes * 24 * 4), o_slotEdges = out.take(n_slots * 48 * 4), o_obox = out.take((size_t)obox_total * 32),
                  o_areas = out.take(obox_total ? n4 * 4 : 0), o_samp = out.take(obox_total ? n4 * 48 : 0);
     size_t sort_a = 0, sort_b = 0, scan_c = 0;
-    B3_TRY(rocprim::radix_sort_pairs(nullptr, sort_a, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, 30u));
-    B3_TRY(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n3, 0u,
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(nullptr, sort_a, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, 0u, 30u));
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(nullptr, sort_b, (uint64_t *)nullptr, (uint64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (size_t)n3, 0u,
                                      (unsigned)(2 * S.vbits)));
-    B3_TRY(rocprim::exclusive_scan(nullptr, scan_c, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)n3, rocprim::plus<int32_t>()));
+    WOST_BUILD_TRY(rocprim::exclusive_scan(nullptr, scan_c, (int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)n3, rocprim::plus<int32_t>()));
     const size_t t_meta = tmp.take(sizeof(B3Meta)), t_verts = tmp.take((size_t)nv * 12), t_cen = tmp.take((size_t)n * 12), t_code = tmp.take((size_t)n * 4),
                  t_code2 = tmp.take((size_t)n * 4), t_idx = tmp.take((size_t)n * 4), t_order = tmp.take((size_t)n * 4), t_keys = tmp.take((size_t)n3 * 8),
                  t_keys2 = tmp.take((size_t)n3 * 8), t_vals = tmp.take((size_t)n3 * 4), t_vals2 = tmp.take((size_t)n3 * 4), t_flags = tmp.take((size_t)n3 * 4),
                  t_eid = tmp.take((size_t)n3 * 4), t_edge_of = tmp.take((size_t)n3 * 4), t_first = tmp.take((size_t)n3 * 4),
                  t_nb = tmp.take((size_t)S.n_nodes * 24), t_nsum = tmp.take((size_t)S.n_nodes * sizeof(B3Sum)),
                  t_rp = tmp.take(std::max(sort_a, std::max(sort_b, scan_c)));
-    B3_TRY(hipMalloc((void **)&out.base, out.size));
-    B3_TRY(hipMalloc((void **)&tmp.base, tmp.size));
+    WOST_BUILD_TRY(hipMalloc((void **)&out.base, out.size));
+    WOST_BUILD_TRY(hipMalloc((void **)&tmp.base, tmp.size));
     hipStream_t st = nullptr;
     B3Meta *meta = tmp.at<B3Meta>(t_meta);
     float *verts = tmp.at<float>(t_verts);
@@ -835,34 +829,34 @@ static int build_mesh3_device(const wost3_mesh_desc &d, DeviceMesh3 &s)
     DevTri *flat = out.at<DevTri>(o_flat);
     DevEdge3 *edges = out.at<DevEdge3>(o_edges);
     int32_t *order = tmp.at<int32_t>(t_order), *edge_of = tmp.at<int32_t>(t_edge_of);
-    B3_TRY(hipMemcpyAsync(verts, d.verts, (size_t)nv * 12, hipMemcpyHostToDevice, st));
-    B3_TRY(hipMemcpyAsync(tris, d.tris, (size_t)n3 * 4, hipMemcpyHostToDevice, st));
-    if (d.colors) B3_TRY(hipMemcpyAsync(out.at<float>(o_colors), d.colors, (size_t)nv * 24, hipMemcpyHostToDevice, st));
+    WOST_BUILD_TRY(hipMemcpyAsync(verts, d.verts, (size_t)nv * 12, hipMemcpyHostToDevice, st));
+    WOST_BUILD_TRY(hipMemcpyAsync(tris, d.tris, (size_t)n3 * 4, hipMemcpyHostToDevice, st));
+    if (d.colors) WOST_BUILD_TRY(hipMemcpyAsync(out.at<float>(o_colors), d.colors, (size_t)nv * 24, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(b3_init_kernel, dim3(1), dim3(1), 0, st, meta);
     hipLaunchKernelGGL(b3_tri_kernel, b3_grid(n), dim3(256), 0, st, verts, tris, n, nv, flat, tmp.at<float>(t_cen), meta);
     hipLaunchKernelGGL(b3_morton_kernel, b3_grid(n), dim3(256), 0, st, tmp.at<float>(t_cen), n, meta, tmp.at<uint32_t>(t_code), tmp.at<int32_t>(t_idx));
     size_t rp_bytes = sort_a;
-    B3_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint32_t>(t_code), tmp.at<uint32_t>(t_code2), tmp.at<int32_t>(t_idx), order,
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint32_t>(t_code), tmp.at<uint32_t>(t_code2), tmp.at<int32_t>(t_idx), order,
                                      (size_t)n, 0u, 30u, st));
     // edges
     hipLaunchKernelGGL(b3_edge_key_kernel, b3_grid(n3), dim3(256), 0, st, tris, n3, S.vbits, meta, tmp.at<uint64_t>(t_keys), tmp.at<int32_t>(t_vals));
     rp_bytes = sort_b;
-    B3_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint64_t>(t_keys), tmp.at<uint64_t>(t_keys2), tmp.at<int32_t>(t_vals),
+    WOST_BUILD_TRY(rocprim::radix_sort_pairs(tmp.at<void>(t_rp), rp_bytes, tmp.at<uint64_t>(t_keys), tmp.at<uint64_t>(t_keys2), tmp.at<int32_t>(t_vals),
                                      tmp.at<int32_t>(t_vals2), (size_t)n3, 0u, (unsigned)(2 * S.vbits), st));
     hipLaunchKernelGGL(b3_edge_flag_kernel, b3_grid(n3), dim3(256), 0, st, tmp.at<uint64_t>(t_keys2), n3, S.vbits, tmp.at<int32_t>(t_flags));
     rp_bytes = scan_c;
-    B3_TRY(rocprim::exclusive_scan(tmp.at<void>(t_rp), rp_bytes, tmp.at<int32_t>(t_flags), tmp.at<int32_t>(t_eid), 0, (size_t)n3, rocprim::plus<int32_t>(), st));
-    B3_TRY(hipMemsetAsync(edges, 0, (size_t)n3 * sizeof(DevEdge3), st));
+    WOST_BUILD_TRY(rocprim::exclusive_scan(tmp.at<void>(t_rp), rp_bytes, tmp.at<int32_t>(t_flags), tmp.at<int32_t>(t_eid), 0, (size_t)n3, rocprim::plus<int32_t>(), st));
+    WOST_BUILD_TRY(hipMemsetAsync(edges, 0, (size_t)n3 * sizeof(DevEdge3), st));
     hipLaunchKernelGGL(b3_edge_record_kernel, b3_grid(n3), dim3(256), 0, st, tmp.at<uint64_t>(t_keys2), tmp.at<int32_t>(t_vals2), tmp.at<int32_t>(t_eid), tris,
                        verts, n3, S.vbits, edges, edge_of, meta);
     // slots
     float *tri = out.at<float>(o_tri);
     hipLaunchKernelGGL(b3_fill_kernel, dim3(1024), dim3(256), 0, st, reinterpret_cast<uint32_t *>(tri) + (size_t)n * 12, (n_slots - n) * 12, 0x5d5e0b6bu);
     hipLaunchKernelGGL(b3_fill_kernel, dim3(256), dim3(256), 0, st, out.at<uint32_t>(o_triOrig) + n, n_slots - n, (uint32_t)kFarIndex);
-    B3_TRY(hipMemsetAsync(out.at<char>(o_triVerts), 0, n_slots * 12, st));
-    B3_TRY(hipMemsetAsync(out.at<char>(o_slotEdges), 0, n_slots * 192, st));
-    B3_TRY(hipMemsetAsync(out.at<char>(o_cones), 0, (size_t)S.n_nodes * 96, st));
-    B3_TRY(hipMemsetAsync(tmp.at<char>(t_first), 0xff, (size_t)n3 * 4, st));
+    WOST_BUILD_TRY(hipMemsetAsync(out.at<char>(o_triVerts), 0, n_slots * 12, st));
+    WOST_BUILD_TRY(hipMemsetAsync(out.at<char>(o_slotEdges), 0, n_slots * 192, st));
+    WOST_BUILD_TRY(hipMemsetAsync(out.at<char>(o_cones), 0, (size_t)S.n_nodes * 96, st));
+    WOST_BUILD_TRY(hipMemsetAsync(tmp.at<char>(t_first), 0xff, (size_t)n3 * 4, st));
     hipLaunchKernelGGL(b3_slot_kernel, b3_grid(n), dim3(256), 0, st, order, flat, tris, edge_of, n, meta, tri, out.at<int32_t>(o_triOrig),
                        out.at<int32_t>(o_triVerts), out.at<int32_t>(o_slotOf), tmp.at<uint32_t>(t_first));
     hipLaunchKernelGGL(b3_slot_edge_kernel, b3_grid(n3), dim3(256), 0, st, order, edge_of, tmp.at<uint32_t>(t_first), edges, flat, n, meta,
@@ -887,9 +881,9 @@ static int build_mesh3_device(const wost3_mesh_desc &d, DeviceMesh3 &s)
             hipLaunchKernelGGL(b3_obox_up_kernel, b3_grid(obox_runs[l]), dim3(256), 0, st, obox, obox_off[l - 1], obox_runs[l - 1], obox_off[l], obox_runs[l], meta);
         hipLaunchKernelGGL(b3_samp_kernel, b3_grid((long long)n4), dim3(256), 0, st, flat, n, (long long)n4, meta, out.at<float>(o_areas), out.at<float>(o_samp));
     }
-    B3_TRY(hipGetLastError());
+    WOST_BUILD_TRY(hipGetLastError());
     B3Meta hm{};
-    B3_TRY(hipMemcpy(&hm, meta, sizeof(hm), hipMemcpyDeviceToHost));         // the one wait of the build
+    WOST_BUILD_TRY(hipMemcpy(&hm, meta, sizeof(hm), hipMemcpyDeviceToHost));         // the one wait of the build
     if (hm.bad) return set_error(WOST_ERR_INVALID, "mesh: triangle index out of range or null arrays");
     float ext = 0.0f;
     for (int c = 0; c < 3; ++c) {
@@ -920,23 +914,23 @@ static int upload_mesh3_host(const wost3_mesh_desc &d, DeviceMesh3 &s)
     if (h.n_tris == 0) return WOST_OK;
     v.n_edges = h.n_edges; v.levels = h.levels; v.first_leaf = h.first_leaf; v.emissive = h.emissive ? 1 : 0;
     v.huge2 = 4096.0f * h.ext * h.ext;        // 64 extents
-    W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(h.nodes.data()), h.nodes.size() / 4, &v.nodes));
-    W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(h.tri.data()), h.tri.size() / 4, &v.tri));
-    W3_TRY(upload3(s.allocs, h.triOrig.data(), h.triOrig.size(), &v.triOrig));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(h.nodes.data()), h.nodes.size() / 4, &v.nodes));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(h.tri.data()), h.tri.size() / 4, &v.tri));
+    WOST_TRY(upload(s.allocs, h.triOrig.data(), h.triOrig.size(), &v.triOrig));
     {
         std::vector<int32_t> inv((size_t)std::max(h.n_tris, 1), 0);
         for (size_t k = 0; k < h.triOrig.size(); ++k)
             if (h.triOrig[k] != kFarIndex) inv[(size_t)h.triOrig[k]] = (int32_t)k;
-        W3_TRY(upload3(s.allocs, inv.data(), inv.size(), &v.slotOfOrig));
+        WOST_TRY(upload(s.allocs, inv.data(), inv.size(), &v.slotOfOrig));
     }
-    W3_TRY(upload3(s.allocs, h.triVerts.data(), h.triVerts.size(), &v.triVerts));
-    W3_TRY(upload3(s.allocs, h.colors.data(), h.colors.size(), &v.colors));
-    W3_TRY(upload3(s.allocs, h.flat.data(), h.flat.size(), &v.flat));
-    W3_TRY(upload3(s.allocs, h.edges.data(), h.edges.size(), &v.edges));
-    W3_TRY(upload3(s.allocs, h.flatVerts.data(), h.flatVerts.size(), &v.flatVerts));
-    W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(h.cones.data()), h.cones.size() / 4, &v.cones));
-    W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(h.slotEdges.data()), h.slotEdges.size() / 4, &v.slotEdges));
-    W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(h.obox.data()), h.obox.size() / 4, &v.obox));
+    WOST_TRY(upload(s.allocs, h.triVerts.data(), h.triVerts.size(), &v.triVerts));
+    WOST_TRY(upload(s.allocs, h.colors.data(), h.colors.size(), &v.colors));
+    WOST_TRY(upload(s.allocs, h.flat.data(), h.flat.size(), &v.flat));
+    WOST_TRY(upload(s.allocs, h.edges.data(), h.edges.size(), &v.edges));
+    WOST_TRY(upload(s.allocs, h.flatVerts.data(), h.flatVerts.size(), &v.flatVerts));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(h.cones.data()), h.cones.size() / 4, &v.cones));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(h.slotEdges.data()), h.slotEdges.size() / 4, &v.slotEdges));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(h.obox.data()), h.obox.size() / 4, &v.obox));
     if (!h.obox.empty()) {
         const size_t n4 = (h.flat.size() + 3) / 4 * 4;
         std::vector<float> areas(n4, 0.0f), tri(n4 * 12, 1.0e18f);
@@ -945,8 +939,8 @@ static int upload_mesh3_host(const wost3_mesh_desc &d, DeviceMesh3 &s)
             areas[i] = T.area;
             for (int c = 0; c < 3; ++c) { tri[12 * i + c] = T.p0[c]; tri[12 * i + 4 + c] = T.p1[c]; tri[12 * i + 8 + c] = T.p2[c]; }
         }
-        W3_TRY(upload3(s.allocs, areas.data(), areas.size(), &v.areas));
-        W3_TRY(upload3(s.allocs, reinterpret_cast<const float4 *>(tri.data()), n4 * 3, &v.sampTri));
+        WOST_TRY(upload(s.allocs, areas.data(), areas.size(), &v.areas));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(tri.data()), n4 * 3, &v.sampTri));
     }
     for (int l = 0; l < 12; ++l) v.obox_off[l] = h.obox_off[l];
     v.obox_levels = h.obox_levels;
@@ -990,7 +984,7 @@ int wost3_mesh_build_check(const wost3_mesh_desc *mesh, int device, int32_t repe
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
     if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    W3_TRY(hipSetDevice(device));
+    WOST_TRY(hipSetDevice(device));
     if (mesh->n_tris < 0 || mesh->n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
     struct Owned {
         DeviceMesh3 m;
@@ -1004,14 +998,14 @@ int wost3_mesh_build_check(const wost3_mesh_desc *mesh, int device, int32_t repe
     Owned a, b;
     for (int r = 0; r < std::max(1, repeat); ++r) {
         Owned ha, hb;
-        W3_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t0 = clock::now();
         int rc = upload_mesh3_host(*mesh, ha.m);
-        W3_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t1 = clock::now();
         if (rc != WOST_OK) return rc;
         rc = build_mesh3_device(*mesh, hb.m);
-        W3_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t2 = clock::now();
         if (rc != WOST_OK) return rc;
         best_host = std::min(best_host, std::chrono::duration<double, std::milli>(t1 - t0).count());

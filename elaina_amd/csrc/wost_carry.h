@@ -62,4 +62,92 @@ int carry_adaptive(CarryState &s, const CarryFrame &f, int32_t shard_index, int3
 // wost_solve_carried: host arrays, any of them nullptr
 int carry_read(CarryState &s, const CarryFrame &f, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb, hipStream_t stream);
 
+// ---- the entry points of the continued solve, written once for the 2-D and the 3-D context ----
+// Ctx has device, settings, mask, n_pixels, field, stream and carry.  What a dimension adds: the prefix of its entry points in
+// messages, the walk of a shard (it calls the dimension's solve driver) and, optionally, what a call that made no walk has
+// to tidy up (2-D: the launch list, which would still be that of the solve before it).
+template <class Ctx>
+struct CarryCalls {
+    const char *prefix;
+    CarryWalk (*walk)(Ctx *c, int32_t shard_index, int32_t shard_count);
+    void (*no_walk)(Ctx *c);
+
+    static CarryFrame frame(const Ctx *c) { return CarryFrame{c->device, c->settings.width, c->settings.height, c->mask}; }
+    int driven(Ctx *h, int rc) const
+    {
+        if (rc == WOST_OK && no_walk && h->carry.walks == 0) no_walk(h);
+        return rc;
+    }
+    // the field of a host call: the handle's device field, zero-filled; after the call it travels to the caller
+    static int host_field_begin(Ctx *c)
+    {
+        WOST_TRY(hipSetDevice(c->device));
+        WOST_TRY(hipMemsetAsync(c->field, 0, c->n_pixels * 3 * sizeof(float), c->stream));
+        return WOST_OK;
+    }
+    static int host_field_end(Ctx *c, float *field_rgb, wost_stats *stats, HostClock::time_point t0)
+    {
+        WOST_TRY(hipMemcpyAsync(field_rgb, c->field, c->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        WOST_TRY(hipStreamSynchronize(c->stream));
+        stamp_solve_ms(stats, t0);
+        return WOST_OK;
+    }
+
+    int more_where(Ctx *h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats) const
+    {
+        int rc = carry_check_more(h, field_rgb, more_spp);
+        if (rc != WOST_OK) return rc;
+        const auto t0 = HostClock::now();
+        if ((rc = host_field_begin(h)) != WOST_OK) return rc;
+        rc = driven(h, carry_more_where(h->carry, frame(h), 0, 1, more_spp, select, true, h->field, h->stream, stats, walk(h, 0, 1), prefix));
+        return rc != WOST_OK ? rc : host_field_end(h, field_rgb, stats, t0);
+    }
+    int more_where_sharded(Ctx *h, int32_t shard_index, int32_t shard_count, int32_t more_spp, const uint8_t *select_dev, float *field_rgb_dev,
+                           void *stream, wost_stats *stats) const
+    {
+        int rc = carry_check_more(h, field_rgb_dev, more_spp);
+        if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
+        if (rc != WOST_OK) return rc;
+        return driven(h, carry_more_where(h->carry, frame(h), shard_index, shard_count, more_spp, select_dev, false, field_rgb_dev,
+                                          reinterpret_cast<hipStream_t>(stream), stats, walk(h, shard_index, shard_count), prefix));
+    }
+    int adaptive_sharded(Ctx *h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a, float *field_rgb_dev, void *stream,
+                         wost_stats *stats) const
+    {
+        int rc = carry_check_adaptive(h, a, field_rgb_dev);
+        if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
+        if (rc != WOST_OK) return rc;
+        return driven(h, carry_adaptive(h->carry, frame(h), shard_index, shard_count, *a, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats,
+                                        walk(h, shard_index, shard_count), prefix));
+    }
+    int adaptive(Ctx *h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats) const
+    {
+        int rc = carry_check_adaptive(h, a, field_rgb);
+        if (rc != WOST_OK) return rc;
+        const auto t0 = HostClock::now();
+        if ((rc = host_field_begin(h)) != WOST_OK) return rc;
+        rc = driven(h, carry_adaptive(h->carry, frame(h), 0, 1, *a, h->field, h->stream, stats, walk(h, 0, 1), prefix));
+        if (rc != WOST_OK) return rc;
+        if ((stderr_rgb || spp_map) && (rc = carry_read(h->carry, frame(h), spp_map, nullptr, nullptr, stderr_rgb, h->stream)) != WOST_OK) return rc;
+        return host_field_end(h, field_rgb, stats, t0);
+    }
+    int carried(Ctx *h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        return carry_read(h->carry, frame(h), spp, batches, sum_rgb, stderr_rgb, h->stream);
+    }
+    int restart(Ctx *h) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        carry_restart(h->carry);
+        return WOST_OK;
+    }
+    int progress(Ctx *h, int32_t *spp_done) const
+    {
+        if (!h || !spp_done) return set_error(WOST_ERR_INVALID, "null argument");
+        *spp_done = h->carry.done;
+        return WOST_OK;
+    }
+};
+
 }  // namespace wost

@@ -111,12 +111,6 @@ __global__ __launch_bounds__(256) void carry_kernel(CarryParams P)
     }
 }
 
-#define CARRY_TRY(expr)                                                                                 \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static size_t n_pixels_of(const CarryFrame &f) { return (size_t)f.width * (size_t)f.height; }
 
 void carry_free(CarryState &s)
@@ -137,7 +131,7 @@ static int carry_ready(CarryState &s, const CarryFrame &f, hipStream_t stream)
 {
     const size_t n = n_pixels_of(f), bytes = n * 52;
     if (!s.mem) {
-        CARRY_TRY(hipMalloc(&s.mem, bytes));
+        WOST_TRY(hipMalloc(&s.mem, bytes));
         s.rng = static_cast<uint64_t *>(s.mem);
         s.sum = reinterpret_cast<float *>(s.rng + n);
         s.prev = s.sum + 3 * n;
@@ -147,7 +141,7 @@ static int carry_ready(CarryState &s, const CarryFrame &f, hipStream_t stream)
         s.stale = true;
     }
     if (s.stale) {
-        CARRY_TRY(hipMemsetAsync(s.mem, 0, bytes, stream));
+        WOST_TRY(hipMemsetAsync(s.mem, 0, bytes, stream));
         s.stale = false;
     }
     return WOST_OK;
@@ -157,7 +151,7 @@ static int carry_work_ready(CarryState &s, const CarryFrame &f)
 {
     if (s.work) return WOST_OK;
     const size_t n = n_pixels_of(f), n4 = (n + 3) & ~(size_t)3;
-    CARRY_TRY(hipMalloc(&s.work, 3 * n * sizeof(float) + n * sizeof(int32_t) + sizeof(uint32_t) + 2 * n4));
+    WOST_TRY(hipMalloc(&s.work, 3 * n * sizeof(float) + n * sizeof(int32_t) + sizeof(uint32_t) + 2 * n4));
     s.se = static_cast<float *>(s.work);
     s.ids = reinterpret_cast<int32_t *>(s.se + 3 * n);
     s.count = reinterpret_cast<uint32_t *>(s.ids + n);
@@ -179,12 +173,12 @@ static CarryParams carry_params(const CarryState &s, const CarryFrame &f, int32_
 // The kernel on `stream`, which is idle again when this returns; *count (not nullptr: P.pick is set) receives the pixels selected.
 static int carry_launch(const CarryParams &P, hipStream_t stream, uint32_t *count)
 {
-    if (P.pick != CARRY_PICK_NONE) CARRY_TRY(hipMemsetAsync(P.count, 0, sizeof(uint32_t), stream));
+    if (P.pick != CARRY_PICK_NONE) WOST_TRY(hipMemsetAsync(P.count, 0, sizeof(uint32_t), stream));
     // (256 threads: the kernel's LDS holds the counts of four waves)
     hipLaunchKernelGGL(carry_kernel, dim3((unsigned)((P.n_pixels + 255) / 256)), dim3(256), 0, stream, P);
-    CARRY_TRY(hipGetLastError());
-    if (count) CARRY_TRY(hipMemcpyAsync(count, P.count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    CARRY_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipGetLastError());
+    if (count) WOST_TRY(hipMemcpyAsync(count, P.count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     return WOST_OK;
 }
 
@@ -265,7 +259,7 @@ int carry_more_where(CarryState &s, const CarryFrame &f, int32_t shard_index, in
     int rc = carry_check_call(s, shard_index, shard_count, more_spp, prefix);
     if (rc != WOST_OK) return rc;
     s.walks = 0;
-    CARRY_TRY(hipSetDevice(f.device));
+    WOST_TRY(hipSetDevice(f.device));
     if ((rc = carry_ready(s, f, stream)) != WOST_OK) return rc;
     if (select && (rc = carry_work_ready(s, f)) != WOST_OK) return rc;
     wost_stats st{};
@@ -275,7 +269,7 @@ int carry_more_where(CarryState &s, const CarryFrame &f, int32_t shard_index, in
         if ((rc = carry_walk_and_close(s, P, more_spp, nullptr, 0, field_dev, stream, &st, walk, nullptr)) != WOST_OK) return rc;
     } else {
         if (select_on_host) {
-            CARRY_TRY(hipMemcpyAsync(s.want, select, n_pixels_of(f), hipMemcpyHostToDevice, stream));
+            WOST_TRY(hipMemcpyAsync(s.want, select, n_pixels_of(f), hipMemcpyHostToDevice, stream));
             select = s.want;
         }
         // the selection as the walk wants it -- owned, unmasked pixels only, counted -- and the field of the carried state
@@ -299,7 +293,7 @@ int carry_adaptive(CarryState &s, const CarryFrame &f, int32_t shard_index, int3
     int rc = carry_check_call(s, shard_index, shard_count, 0, prefix);
     if (rc != WOST_OK) return rc;
     s.walks = 0;
-    CARRY_TRY(hipSetDevice(f.device));
+    WOST_TRY(hipSetDevice(f.device));
     if ((rc = carry_ready(s, f, stream)) != WOST_OK) return rc;
     if ((rc = carry_work_ready(s, f)) != WOST_OK) return rc;
     CarryParams P = carry_params(s, f, shard_index, shard_count);
@@ -335,19 +329,19 @@ int carry_read(CarryState &s, const CarryFrame &f, int32_t *spp, int32_t *batche
         if (stderr_rgb) std::fill(stderr_rgb, stderr_rgb + 3 * n, INFINITY);
         return WOST_OK;
     }
-    CARRY_TRY(hipSetDevice(f.device));
+    WOST_TRY(hipSetDevice(f.device));
     if (stderr_rgb) {
         int rc = carry_work_ready(s, f);
         if (rc != WOST_OK) return rc;
         CarryParams P = carry_params(s, f, 0, 1);
         P.se = s.se;
         if ((rc = carry_launch(P, stream, nullptr)) != WOST_OK) return rc;
-        CARRY_TRY(hipMemcpyAsync(stderr_rgb, s.se, 3 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        WOST_TRY(hipMemcpyAsync(stderr_rgb, s.se, 3 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
-    if (spp) CARRY_TRY(hipMemcpyAsync(spp, s.n, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (batches) CARRY_TRY(hipMemcpyAsync(batches, s.batches, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (sum_rgb) CARRY_TRY(hipMemcpyAsync(sum_rgb, s.sum, 3 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    CARRY_TRY(hipStreamSynchronize(stream));
+    if (spp) WOST_TRY(hipMemcpyAsync(spp, s.n, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (batches) WOST_TRY(hipMemcpyAsync(batches, s.batches, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (sum_rgb) WOST_TRY(hipMemcpyAsync(sum_rgb, s.sum, 3 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     return WOST_OK;
 }
 

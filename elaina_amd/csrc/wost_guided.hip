@@ -1117,12 +1117,6 @@ struct wost_guided {
     size_t pts_cap = 0;                   // points it holds
 };
 
-#define G_TRY(expr)                                                                                      \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // release one buffer of device_alloc before the handle goes (a buffer that is replaced by a larger one)
 static void gfree_one(wost_guided *g, void *p)
 {
@@ -1311,7 +1305,7 @@ int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, fl
                           float *dir_pdf, float *normal, uint8_t *on_neumann)
 {
     if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    G_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     *n = (int32_t)h->last_train_n;
     return copy_train_set(h->ts, 2, std::min<size_t>(h->last_train_n, (size_t)capacity), xy, dir, solution, dir_pdf, normal, on_neumann);
 }
@@ -1409,12 +1403,6 @@ static bool fused_shape(const NetLayout *L, FusedNet &Fn)
 
 // intermediate frames belong to the frame solve
 static bool wants_frames(const wost_guided *g, const GuidedPlan &pl) { return g->frame_fn && !pl.job.pts; }
-
-static int env_int(const char *name, int fallback, int at_least)
-{
-    const char *w = std::getenv(name);
-    return w ? std::max(at_least, std::atoi(w)) : fallback;
-}
 
 static GuidedPlan guided_plan(wost_guided *g, const PointJob &job)
 {
@@ -1529,17 +1517,17 @@ static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GP
     const int N = pl.n;
     if (pl.dbg) {
         const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
-        G_TRY(hipMemcpyAsync(g->dbg, init, sizeof(init), hipMemcpyHostToDevice, st));
-        G_TRY(hipStreamSynchronize(st));
+        WOST_TRY(hipMemcpyAsync(g->dbg, init, sizeof(init), hipMemcpyHostToDevice, st));
+        WOST_TRY(hipStreamSynchronize(st));
     }
-    G_TRY(hipMemsetAsync(g->cursor, 0, sizeof(uint32_t), st));
+    WOST_TRY(hipMemsetAsync(g->cursor, 0, sizeof(uint32_t), st));
     // the pixels in the order of wost_order.h (not for the launches of several samples per pixel, whose drain is one walk whatever the order, nor for one rank's shard:
     // seven of eight pixels of the order belong to other ranks and a lane asks eight times for one -- shard 0 of 8 of config 5
     // 0.219 -> 0.246 s; the whole frame, one sample per launch: config 4 1.420 -> 1.400 s in half precision, 2.206 -> 2.174 in fp32)
     const bool ordered = g->walk_order && run.d0_valid && g->view.dm.n_segs > 0 && n_samples == 1 && P.shard_count == 1;
     if (ordered && !run.walk_order) {
-        if (g->order.cap < (size_t)N) G_TRY((hipError_t)order_alloc(g->order, (size_t)N));
-        G_TRY((hipError_t)order_by_distance(g->order, g->d0_d2, (uint32_t)N, st, &run.walk_order));
+        if (g->order.cap < (size_t)N) WOST_TRY((hipError_t)order_alloc(g->order, (size_t)N));
+        WOST_TRY((hipError_t)order_by_distance(g->order, g->d0_d2, (uint32_t)N, st, &run.walk_order));
         run.launches += 2;
     }
     // what varies between the fused launches of a solve: these eight fields, set here and nowhere else
@@ -1548,17 +1536,17 @@ static int launch_fused(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GP
     P.order = ordered ? run.walk_order : nullptr; P.dbg = pl.dbg ? g->dbg : nullptr;
     if (n_samples > 1) {
         // several samples of every pixel in one launch: the pixel state words start at zero, and what a one-sample launch sets on the fly is set before the launch
-        G_TRY(hipMemsetAsync(g->pstate, 0, (size_t)N * sizeof(uint32_t), st));
+        WOST_TRY(hipMemsetAsync(g->pstate, 0, (size_t)N * sizeof(uint32_t), st));
         if (P.first_sample) hipLaunchKernelGGL(guided_init_kernel, dim3((N + 255) / 256), dim3(256), 0, st, P);
-        if (P.training) G_TRY(hipMemsetAsync(g->cur_depth, 0, (size_t)N * (size_t)n_samples * sizeof(uint32_t), st));
+        if (P.training) WOST_TRY(hipMemsetAsync(g->cur_depth, 0, (size_t)N * (size_t)n_samples * sizeof(uint32_t), st));
         run.launches += P.first_sample ? 3 : 2;
     }
     launch_guided(G_FUSED, pl, run, pl.grid_fused, st, P, Fn);
-    G_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     run.d0_valid = true;
     if (pl.dbg) {
         unsigned long long t[4];
-        G_TRY(hipMemcpy(t, g->dbg, sizeof(t), hipMemcpyDeviceToHost));
+        WOST_TRY(hipMemcpy(t, g->dbg, sizeof(t), hipMemcpyDeviceToHost));
         std::fprintf(stderr, "[fused sample %d x%d] %u blocks: first wave out of pixels at %.1f us, last at %.1f us, end %.1f us\n", sample,
                      n_samples, pl.grid_fused, (double)(t[1] - t[0]) / 100.0, (double)(t[2] - t[0]) / 100.0, (double)(t[3] - t[0]) / 100.0);
     }
@@ -1590,11 +1578,11 @@ static int grow_record_sets(wost_guided *g, int sets, hipStream_t stream)
     if (sets <= g->rec_sets) return WOST_OK;
     // (the smaller set goes first: nothing on the device uses it between two solves, and group 16 would otherwise hold
     // 3.2 GB next to the 201 MB it replaces until the handle is destroyed)
-    G_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     gfree_one(g, g->rec); gfree_one(g, g->cur_depth);
     g->rec = nullptr; g->cur_depth = nullptr; g->rec_sets = 0;
-    G_TRY(device_alloc(g->allocs, &g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * g->n_pixels * sets));
-    G_TRY(device_alloc(g->allocs, &g->cur_depth, g->n_pixels * sets));
+    WOST_TRY(device_alloc(g->allocs, &g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * g->n_pixels * sets));
+    WOST_TRY(device_alloc(g->allocs, &g->cur_depth, g->n_pixels * sets));
     g->rec_sets = sets;
     return WOST_OK;
 }
@@ -1616,16 +1604,16 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
     if (!g->train_stream) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);       // lo = least urgent: the training fills what the walk leaves idle
-        G_TRY(hipStreamCreateWithPriority(&g->train_stream, hipStreamNonBlocking, lo));
-        G_TRY(hipEventCreateWithFlags(&g->ev_ts, hipEventDisableTiming));
-        for (hipEvent_t &e : g->ev_train) G_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        G_TRY(g->train_events.init(64));
-        for (uint8_t *&p : g->snap) G_TRY(device_alloc(g->allocs, &p, snap_bytes));
+        WOST_TRY(hipStreamCreateWithPriority(&g->train_stream, hipStreamNonBlocking, lo));
+        WOST_TRY(hipEventCreateWithFlags(&g->ev_ts, hipEventDisableTiming));
+        for (hipEvent_t &e : g->ev_train) WOST_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        WOST_TRY(g->train_events.init(64));
+        for (uint8_t *&p : g->snap) WOST_TRY(device_alloc(g->allocs, &p, snap_bytes));
     }
     // the passes of a group read their training sets while the next group walks over the record sets: one array set per sample
     while ((int)g->ts_more.size() + 1 < pl.group) {
         TrainSet t{};
-        G_TRY(alloc_train_set(g->allocs, t, 2, (size_t)g->n_train_pixels * kMaxTrainDepth));
+        WOST_TRY(alloc_train_set(g->allocs, t, 2, (size_t)g->n_train_pixels * kMaxTrainDepth));
         g->ts_more.push_back(t);
     }
     hipStream_t B = g->train_stream;
@@ -1646,40 +1634,40 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
     const int n_groups = (int)first.size() - 1;
     const GuidePhase ph = phase_of(g, pl, 0);
     // (the training stream starts behind whatever the walk stream has been given so far)
-    G_TRY(hipEventRecord(g->ev_ts, stream));
-    G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
+    WOST_TRY(hipEventRecord(g->ev_ts, stream));
+    WOST_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
     int rc = launch_fused(g, pl, run, P, Fs[0], stream, ph, 0, first[1]);
     for (int j = 0; j < first[1] && rc == WOST_OK; ++j) rc = enqueue_train_set(g, pl, run, stream, j, train_set_of(g, j));
     if (rc != WOST_OK) return rc;
-    G_TRY(hipEventRecord(g->ev_ts, stream));
+    WOST_TRY(hipEventRecord(g->ev_ts, stream));
     for (int k = 0; k < n_groups; ++k) {
         const int size = first[k + 1] - first[k], next_size = k + 1 < n_groups ? first[k + 2] - first[k + 1] : 0;
         if (k + 1 < n_groups) {
             // the walk of group k + 1 reads snap[(k + 1) % 2] = the weights after the passes of group k - 1
-            if (k >= 1) G_TRY(hipStreamWaitEvent(stream, g->ev_train[(k - 1) & 1], 0));
+            if (k >= 1) WOST_TRY(hipStreamWaitEvent(stream, g->ev_train[(k - 1) & 1], 0));
             rc = launch_fused(g, pl, run, P, Fs[(k + 1) & 1], stream, ph, first[k + 1], next_size);
             if (rc != WOST_OK) return rc;
         }
-        G_TRY(hipEventSynchronize(g->ev_ts));          // the training sets of group k are complete; their sizes have arrived
+        WOST_TRY(hipEventSynchronize(g->ev_ts));          // the training sets of group k are complete; their sizes have arrived
         size_t n_of[16];
         for (int j = 0; j < size; ++j) n_of[j] = g->host_counts[1 + j];
-        G_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
+        WOST_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
         const size_t ev = g->train_events.begin(B);
         for (int j = 0; j < size && rc == WOST_OK; ++j) rc = train_passes(g, run, n_of[j], B, train_set_of(g, j));
         if (rc == WOST_OK) rc = net_snapshot_dev(g->net, g->snap[k & 1], B);
         g->train_events.end(ev, B);
         if (rc != WOST_OK) return rc;
-        G_TRY(hipEventRecord(g->ev_train[k & 1], B));
+        WOST_TRY(hipEventRecord(g->ev_train[k & 1], B));
         if (k + 1 < n_groups) {
-            G_TRY(hipStreamWaitEvent(stream, g->ev_train[k & 1], 0));     // the arrays of the training sets are free again
+            WOST_TRY(hipStreamWaitEvent(stream, g->ev_train[k & 1], 0));     // the arrays of the training sets are free again
             for (int j = 0; j < next_size && rc == WOST_OK; ++j) rc = enqueue_train_set(g, pl, run, stream, j, train_set_of(g, j));
             if (rc != WOST_OK) return rc;
-            G_TRY(hipEventRecord(g->ev_ts, stream));
+            WOST_TRY(hipEventRecord(g->ev_ts, stream));
         }
     }
     // what follows (the guiding phase, the resolve) reads the network's own images
-    G_TRY(hipStreamWaitEvent(stream, g->ev_train[(n_groups - 1) & 1], 0));
-    G_TRY(hipStreamSynchronize(B));
+    WOST_TRY(hipStreamWaitEvent(stream, g->ev_train[(n_groups - 1) & 1], 0));
+    WOST_TRY(hipStreamSynchronize(B));
     drain.stream = nullptr;
     run.train_ms += g->train_events.drain();
     return WOST_OK;
@@ -1701,8 +1689,8 @@ static int emit_frame(wost_guided *g, const GuidedPlan &pl, const GuidedRun &run
     if (!due) return WOST_OK;
     launch_resolve(g->sol, N, (float)(sample + 1), g->field, stream);
     std::vector<float> frame((size_t)N * 3);
-    G_TRY(hipMemcpyAsync(frame.data(), g->field, frame.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-    G_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipMemcpyAsync(frame.data(), g->field, frame.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
     for (int kind = 0; kind < 2; ++kind)      // 0: by spp, 1: by time
         if (((due >> kind) & 1) && g->frame_fn(g->frame_user, kind, sample, ms, frame.data()) != 0)
@@ -1732,7 +1720,7 @@ static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, 
     const int N = pl.n;
     P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.first_sample = sample == 0;
     int cur = 0;     // queue holding the evaluation points of this depth
-    G_TRY(hipMemsetAsync(g->counts + cur, 0, sizeof(uint32_t), stream));
+    WOST_TRY(hipMemsetAsync(g->counts + cur, 0, sizeof(uint32_t), stream));
     P.out = g->q[cur]; P.count_out = g->counts + cur;
     hipLaunchKernelGGL(begin_sample_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, P);
     ++run.launches;
@@ -1748,14 +1736,14 @@ static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, 
         if (!P.guiding) {
             // no network from here on: every remaining walker runs to its end in one launch
             launch_guided(G_TAIL, pl, run, grid, stream, P);
-            G_TRY(hipGetLastError());
+            WOST_TRY(hipGetLastError());
             break;
         }
-        G_TRY(hipMemsetAsync(g->counts + nxt, 0, sizeof(uint32_t), stream));
+        WOST_TRY(hipMemsetAsync(g->counts + nxt, 0, sizeof(uint32_t), stream));
         launch_guided(G_SEPARATE, pl, run, grid, stream, P);
         // the out-of-shell queue is the input of the network and of the sampling kernel
-        G_TRY(hipMemcpyAsync(g->depth_counts + depth, g->counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        G_TRY(hipEventRecord(g->depth_events[depth], stream));
+        WOST_TRY(hipMemcpyAsync(g->depth_counts + depth, g->counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        WOST_TRY(hipEventRecord(g->depth_events[depth], stream));
         while (polled < depth && hipEventQuery(g->depth_events[polled + 1]) == hipSuccess) n_cur = g->depth_counts[++polled];
         if (polled == depth && n_cur == 0) break;      // known to be empty
         const uint32_t n_out = n_cur;                  // an upper bound
@@ -1765,7 +1753,7 @@ static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, 
         if (rc != WOST_OK) return rc;      // (counted by the network)
         P.in = g->q[nxt]; P.count_in = g->counts + nxt;
         launch_guided(G_SAMPLE, pl, run, (n_out + 255) / 256, stream, P);
-        G_TRY(hipGetLastError());
+        WOST_TRY(hipGetLastError());
         cur = nxt; n_cur = n_out;
     }
     return WOST_OK;
@@ -1774,16 +1762,16 @@ static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, 
 // trainStep (:618-668) after a launch that walked n_run samples: one record set and one training pass per sample, in order
 static int train_after_walk(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, hipStream_t stream, int n_run)
 {
-    G_TRY(hipStreamSynchronize(stream));     // the walk phase ends here; train_ms counts the training only
+    WOST_TRY(hipStreamSynchronize(stream));     // the walk phase ends here; train_ms counts the training only
     const auto t0 = std::chrono::high_resolution_clock::now();
     for (int j = 0; j < n_run; ++j) {
         int rc = enqueue_train_set(g, pl, run, stream, j, g->ts);
         if (rc != WOST_OK) return rc;
-        G_TRY(hipStreamSynchronize(stream));
+        WOST_TRY(hipStreamSynchronize(stream));
         rc = train_passes(g, run, (size_t)g->host_counts[1 + j], stream, g->ts);
         if (rc != WOST_OK) return rc;
     }
-    G_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     run.train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return WOST_OK;
 }
@@ -1794,12 +1782,12 @@ static int finish_guided(wost_guided *g, const GuidedPlan &pl, const GuidedRun &
     const int N = pl.n;
     if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 2, N, (float)g->gs.spp, g->field, stream);
     else launch_resolve(g->sol, N, (float)g->gs.spp, g->field, stream);
-    G_TRY(hipGetLastError());
-    if (field_host) G_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (field_dev) G_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    WOST_TRY(hipGetLastError());
+    if (field_host) WOST_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (field_dev) WOST_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     std::vector<GStatsDev> copies(kStatCopies);
-    G_TRY(hipMemcpyAsync(copies.data(), g->stats, kStatCopies * sizeof(GStatsDev), hipMemcpyDeviceToHost, stream));
-    G_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipMemcpyAsync(copies.data(), g->stats, kStatCopies * sizeof(GStatsDev), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     wost_guided_stats out{};
     for (const GStatsDev &c : copies) {
         out.walk_steps += c.steps; out.walks_started += c.started; out.walks_absorbed += c.absorbed; out.walks_truncated += c.truncated;
@@ -1820,9 +1808,9 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
 {
     GuidedRun run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
     DivisorGuard divisor{g->net};
-    G_TRY(hipSetDevice(g->device));
+    WOST_TRY(hipSetDevice(g->device));
     hipStream_t stream = g->view.stream;
-    G_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
+    WOST_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
     int rc = sync_rank_count(g);      // (before the plan: a solve that ends here has drawn nothing from the host sampler)
     if (rc != WOST_OK) return rc;
     const GuidedPlan pl = guided_plan(g, job);
@@ -1898,15 +1886,15 @@ int wost_guided_solve_points(wost_guided_handle g, const float *pts_xy, int32_t 
     }
     rc = check_point_capacity(g, n);
     if (rc != WOST_OK) return rc;
-    G_TRY(hipSetDevice(g->device));
+    WOST_TRY(hipSetDevice(g->device));
     if (g->pts_cap < (size_t)n) {
         // (nothing on the device reads the list between two solves)
         gfree_one(g, g->pts_buf);
         g->pts_buf = nullptr; g->pts_cap = 0;
-        G_TRY(device_alloc(g->allocs, &g->pts_buf, (size_t)n * 2));
+        WOST_TRY(device_alloc(g->allocs, &g->pts_buf, (size_t)n * 2));
         g->pts_cap = (size_t)n;
     }
-    G_TRY(hipMemcpyAsync(g->pts_buf, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, g->view.stream));
+    WOST_TRY(hipMemcpyAsync(g->pts_buf, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, g->view.stream));
     return run_guided(g, 0, 1, field_rgb, nullptr, stats, PointJob{g->pts_buf, n, seed_base, seed_width, train_spp_count});
 }
 

@@ -775,8 +775,8 @@ static G3Plan g3_plan(wost3_guided *g, const PointJob &job)
     pl.stack_words = 3 * std::max(d_levels, n_levels) + 4;
     pl.lds = (size_t)pl.stack_words * 256 * sizeof(uint32_t);
     pl.pool_cap = (d_levels <= 11 && n_levels <= 11) ? 512 : 0;
-    if (env3_int("WOST3_WAVE", 1, -INT_MAX, INT_MAX) == 0) pl.pool_cap = 0;
-    if (pl.pool_cap) pl.pool_cap = env3_int("WOST3_POOL_CAP", pl.pool_cap, 96, 4096);
+    if (env_int("WOST3_WAVE", 1, -INT_MAX, INT_MAX) == 0) pl.pool_cap = 0;
+    if (pl.pool_cap) pl.pool_cap = env_int("WOST3_POOL_CAP", pl.pool_cap, 96, 4096);
     pl.pool_offset = pl.stack_words * 256;
     const size_t lds_pools = pool3_lds_bytes(4, pl.pool_cap) + 8;      // (+ 8: g3_pools() starts them at an 8-byte boundary)
     if (pl.pool_cap && pl.lds + lds_pools > 64 * 1024) pl.pool_cap = 0;
@@ -798,7 +798,7 @@ static G3Plan g3_plan(wost3_guided *g, const PointJob &job)
     (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, g->device);
     pl.resident = (uint64_t)n_cus * 2 * 256;
     while (pl.pool_cap > 0 && pl.lane_shift < 3 && ((uint64_t)N << (pl.lane_shift + 1)) <= pl.resident) ++pl.lane_shift;
-    pl.lane_shift = env3_int("WOST3_G_SHIFT", pl.lane_shift, 0, 4);
+    pl.lane_shift = env_int("WOST3_G_SHIFT", pl.lane_shift, 0, 4);
     pl.grid_px = (unsigned)((((uint64_t)N << pl.lane_shift) + 255) / 256); pl.grid_pix = (unsigned)((N + 255) / 256);
     // One launch per sample (g3_fused_kernel) when the network offers its fp32 MFMA fragments and the frame has at most 1.5 walkers per
     // resident lane (196 608 on MI355X): such a solve is bound by its launches -- 30 per sample, each as long as its slowest wave.  A
@@ -876,7 +876,7 @@ static int walk_fused(const G3Plan &pl, G3Run &run, G3Params P, const GuidePhase
     begin_sample(pl, run, P, ph, sample, stream);
     P.max_guided_depth = ph.max_guided_depth;
     launch_g3(G3_FUSED, pl, run, pl.grid_px, stream, P);
-    W3_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -903,14 +903,14 @@ static int walk_per_depth(wost3_guided *g, const G3Plan &pl, G3Run &run, G3Param
             break;
         }
         // the queue's counter and that of the live list this depth's sample kernel writes: two adjacent words
-        W3_TRY(hipMemsetAsync(g->q_count + (depth & 1), 0, 2 * sizeof(uint32_t), stream));
+        WOST_TRY(hipMemsetAsync(g->q_count + (depth & 1), 0, 2 * sizeof(uint32_t), stream));
         P.l_next_pid = g->l_pid + (size_t)(depth & 1) * N; P.l_next_count = g->q_count + 2 * (depth & 1);
         launch_g3(G3_SEPARATE, pl, run, pl.grid_px, stream, P);
         const int rc = net_inference_dev(g->net, g->net_in, P.q_count, (int)n_upper, g->net_out, true, stream, 0);
         if (rc != WOST_OK) return rc;      // (counted by the network)
         launch_g3(G3_SAMPLE, pl, run, (unsigned)((((uint64_t)n_upper << pl.lane_shift) + 255u) / 256u), stream, P);
     }
-    W3_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -926,12 +926,12 @@ static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, hipSt
     run.launches += 3;
     int rc = enqueue_train_set(T, pl.n_train_blocks, stream, g->host_word);
     if (rc != WOST_OK) return rc;
-    W3_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     const size_t n = g->host_word[0];
     g->last_train_n = (uint32_t)n; run.train_samples += n;
     rc = train_passes<3>(g->net, g->ts, n, train_schedule(g->s), TrainSync{nullptr, nullptr}, stream, run.launches);
     if (rc != WOST_OK) return rc;
-    W3_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     run.train_ms += std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return WOST_OK;
 }
@@ -942,12 +942,12 @@ static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, h
     const int N = pl.n;
     if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 3, N, (float)g->s.spp, g->field, stream);
     else launch_resolve(g->sol, N, (float)g->s.spp, g->field, stream);
-    W3_TRY(hipGetLastError());
-    if (field_host) W3_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (field_dev) W3_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    WOST_TRY(hipGetLastError());
+    if (field_host) WOST_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (field_dev) WOST_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     std::vector<GStats3Dev> copies(kStat3Copies);
-    W3_TRY(hipMemcpyAsync(copies.data(), g->stats, kStat3Copies * sizeof(GStats3Dev), hipMemcpyDeviceToHost, stream));
-    W3_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipMemcpyAsync(copies.data(), g->stats, kStat3Copies * sizeof(GStats3Dev), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     wost_guided_stats out{};
     for (const GStats3Dev &k : copies) {
         out.walk_steps += k.steps; out.walks_started += k.started; out.walks_absorbed += k.absorbed; out.walks_truncated += k.truncated;
@@ -967,10 +967,10 @@ static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float 
                        const PointJob &job = PointJob{})
 {
     G3Run run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
-    W3_TRY(hipSetDevice(g->device));
+    WOST_TRY(hipSetDevice(g->device));
     hipStream_t stream = g->scene->stream;
     const G3Plan pl = g3_plan(g, job);      // (the draw of the training-pixel offset: before any launch)
-    W3_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
+    WOST_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
     const G3Params P = g3_base_params(g, pl, shard_index, shard_count);
     for (int sample = 0; sample < g->s.spp; ++sample) {
         const GuidePhase ph = phase_of(g, pl, sample);
@@ -1099,7 +1099,7 @@ int wost3_guided_solve_points(wost3_guided_handle h, const float *pts_xyz, int32
     }
     rc = check_point_capacity3(h, n);
     if (rc != WOST_OK) return rc;
-    W3_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     if (h->pts_cap < (size_t)n) {
         // (nothing on the device reads the list between two solves)
         if (h->pts_buf) {
@@ -1107,10 +1107,10 @@ int wost3_guided_solve_points(wost3_guided_handle h, const float *pts_xyz, int32
             (void)hipFree(h->pts_buf);
         }
         h->pts_buf = nullptr; h->pts_cap = 0;
-        W3_TRY(device_alloc(h->allocs, &h->pts_buf, (size_t)n * 3));
+        WOST_TRY(device_alloc(h->allocs, &h->pts_buf, (size_t)n * 3));
         h->pts_cap = (size_t)n;
     }
-    W3_TRY(hipMemcpyAsync(h->pts_buf, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->scene->stream));
+    WOST_TRY(hipMemcpyAsync(h->pts_buf, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->scene->stream));
     return run_guided3(h, 0, 1, field_rgb, nullptr, stats, PointJob{h->pts_buf, n, seed_base, seed_width, train_spp_count});
 }
 
@@ -1130,7 +1130,7 @@ int wost3_guided_train_set(wost3_guided_handle h, int32_t capacity, int32_t *n, 
                            float *normal, uint8_t *on_neumann)
 {
     if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    W3_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     *n = (int32_t)h->last_train_n;
     return copy_train_set(h->ts, 3, std::min((size_t)capacity, (size_t)h->last_train_n), xyz, dir, solution, dir_pdf, normal, on_neumann);
 }

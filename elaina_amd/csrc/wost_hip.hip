@@ -1157,21 +1157,12 @@ __global__ __launch_bounds__(256) void ray_kernel(DevMesh m, const float *o, con
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
 
-static int fail(int code, const std::string &msg)
+// (declared in wost_host.h: every translation unit of the library reports through it)
+int set_error(int code, const std::string &msg)
 {
     g_last_error = msg;
     return code;
 }
-
-// shared with the other translation units of the library (wost_vmm.hip)
-int set_error(int code, const std::string &msg) { return fail(code, msg); }
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
 
 struct DeviceMeshStorage {
     DevMesh view{};
@@ -1179,20 +1170,6 @@ struct DeviceMeshStorage {
     HostTree host;
 };
 
-
-template <class T>
-static hipError_t upload(std::vector<void *> &allocs, const T *src, size_t count, const T **dst)
-{
-    *dst = nullptr;
-    if (count == 0) return hipSuccess;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e != hipSuccess) return e;
-    allocs.push_back(p);
-    e = hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
-    *dst = reinterpret_cast<const T *>(p);
-    return e;
-}
 
 // the run boxes over consecutive ORIGINAL indices and the sampler's compact copies (an emissive boundary on the tree only):
 // a function of the flat records alone
@@ -1202,14 +1179,14 @@ static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshSto
 // WOST_HOST_BUILD=1 and the tree-quality knobs
 static int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
 {
-    if (d.n_segs < 0 || d.n_verts < 0) return fail(WOST_ERR_INVALID, "negative mesh size");
+    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
     // developer knobs for tree-quality experiments (defaults: refined, minimal depth)
     const char *e_refine = getenv("WOST_TREE_REFINE");
     const char *e_extra = getenv("WOST_TREE_EXTRA_LEVELS");
     const bool refine = e_refine ? atoi(e_refine) != 0 : true;
     const int extra = e_extra ? std::max(0, std::min(3, atoi(e_extra))) : 0;
     if (build_tree(d.n_verts, d.verts, d.n_segs, d.segs, d.colors, &s.host, refine, extra) != 0)
-        return fail(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
+        return set_error(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
     const HostTree &t = s.host;
     DevMesh &v = s.view;
     v = DevMesh{};
@@ -1233,14 +1210,14 @@ static int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
     v.emissive = 0;
     for (float c : t.flatCol)
         if (c != 0.0f) v.emissive = 1;
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.nodes.data()), t.nodes.size() / 4, &v.nodes));
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.segA.data()), t.segA.size() / 4, &v.segA));
-    HIP_TRY(upload(s.allocs, t.segInv.data(), t.segInv.size(), &v.segInv));
-    HIP_TRY(upload(s.allocs, t.segOrig.data(), t.segOrig.size(), &v.segOrig));
-    HIP_TRY(upload(s.allocs, t.segCol.data(), t.segCol.size(), &v.segCol));
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const DevFlatSeg *>(t.flat.data()), t.flat.size(), &v.flat));
-    HIP_TRY(upload(s.allocs, t.flatCol.data(), t.flatCol.size(), &v.flatCol));
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const DevSilVertex *>(t.sil.data()), t.sil.size(), &v.sil));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.nodes.data()), t.nodes.size() / 4, &v.nodes));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.segA.data()), t.segA.size() / 4, &v.segA));
+    WOST_TRY(upload(s.allocs, t.segInv.data(), t.segInv.size(), &v.segInv));
+    WOST_TRY(upload(s.allocs, t.segOrig.data(), t.segOrig.size(), &v.segOrig));
+    WOST_TRY(upload(s.allocs, t.segCol.data(), t.segCol.size(), &v.segCol));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevFlatSeg *>(t.flat.data()), t.flat.size(), &v.flat));
+    WOST_TRY(upload(s.allocs, t.flatCol.data(), t.flatCol.size(), &v.flatCol));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevSilVertex *>(t.sil.data()), t.sil.size(), &v.sil));
     {
         // the normals of every vertex's two segments beside it: the flat silhouette test of a small boundary reads them with the vertex
         std::vector<float> sn(t.sil.size() * 4, 0.0f);
@@ -1249,9 +1226,9 @@ static int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
             if (sv.prev >= 0) { sn[4 * k] = t.flat[(size_t)sv.prev].nx; sn[4 * k + 1] = t.flat[(size_t)sv.prev].ny; }
             if (sv.next >= 0) { sn[4 * k + 2] = t.flat[(size_t)sv.next].nx; sn[4 * k + 3] = t.flat[(size_t)sv.next].ny; }
         }
-        HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(sn.data()), t.sil.size(), &v.silN));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(sn.data()), t.sil.size(), &v.silN));
     }
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.cones.data()), t.cones.size() / 4, &v.cones));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.cones.data()), t.cones.size() / 4, &v.cones));
     {
         // closest_point_wave: the occupied slots, compact; the operands are those of the leaf-level node records
         std::vector<float> box, hl;
@@ -1271,11 +1248,11 @@ static int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
             id.push_back(kFarIndex);
         }
         v.n_scan = (int32_t)hl.size();
-        HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), hl.size(), &v.scanBox));
-        HIP_TRY(upload(s.allocs, hl.data(), hl.size(), &v.scanHl));
-        HIP_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(id.data()), hl.size(), &v.scanId));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), hl.size(), &v.scanBox));
+        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.scanHl));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(id.data()), hl.size(), &v.scanId));
     }
-    HIP_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(t.segVerts.data()), t.segVerts.size() / 2, &v.segVerts));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(t.segVerts.data()), t.segVerts.size() / 2, &v.segVerts));
     if (v.emissive && t.n_segs > WOST_FLAT_MAX) return upload_run_boxes(t.flat, s);
     return WOST_OK;
 }
@@ -1319,7 +1296,7 @@ static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshSto
             if (n_runs <= 1) break;
         }
         v.obox_levels = levels;
-        HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(ob.data()), ob.size() / 4, &v.obox));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(ob.data()), ob.size() / 4, &v.obox));
         const size_t n4 = (flat_recs.size() + 3) / 4 * 4;
         std::vector<float> lens(n4, 0.0f), hl(n4, 0.0f), box(n4 * 4, 1.0e18f);
         for (size_t i = 0; i < flat_recs.size(); ++i) {
@@ -1327,9 +1304,9 @@ static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshSto
             lens[i] = f.len; hl[i] = f.hl;
             box[4 * i] = f.cx; box[4 * i + 1] = f.cy; box[4 * i + 2] = f.ux; box[4 * i + 3] = f.uy;
         }
-        HIP_TRY(upload(s.allocs, lens.data(), lens.size(), &v.lens));
-        HIP_TRY(upload(s.allocs, hl.data(), hl.size(), &v.sampHl));
-        HIP_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), n4, &v.sampBox));
+        WOST_TRY(upload(s.allocs, lens.data(), lens.size(), &v.lens));
+        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.sampHl));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), n4, &v.sampBox));
     }
     return WOST_OK;
 }
@@ -1339,7 +1316,7 @@ static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshSto
 // knobs.  Both give the same arrays bit for bit (wost_mesh_build_check, tests/test_gpu_build2.py).
 static int upload_mesh(const wost_mesh_desc &d, DeviceMeshStorage &s)
 {
-    if (d.n_segs < 0 || d.n_verts < 0) return fail(WOST_ERR_INVALID, "negative mesh size");
+    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
     const char *e_host = getenv("WOST_HOST_BUILD");
     const bool knobs = getenv("WOST_TREE_REFINE") || getenv("WOST_TREE_EXTRA_LEVELS");
     int min_segs = 512;
@@ -1353,7 +1330,7 @@ static int upload_mesh(const wost_mesh_desc &d, DeviceMeshStorage &s)
     if (s.view.emissive && d.n_segs > WOST_FLAT_MAX) {
         // (rare: an emissive boundary on the tree) the run boxes are built on the host from the flat records
         std::vector<FlatSeg> flat_recs((size_t)d.n_segs);
-        HIP_TRY(hipMemcpy(flat_recs.data(), s.view.flat, flat_recs.size() * sizeof(FlatSeg), hipMemcpyDeviceToHost));
+        WOST_TRY(hipMemcpy(flat_recs.data(), s.view.flat, flat_recs.size() * sizeof(FlatSeg), hipMemcpyDeviceToHost));
         return upload_run_boxes(flat_recs, s);
     }
     return WOST_OK;
@@ -1529,12 +1506,12 @@ const char *wost_version(void) { return "wost-hip 0.2 (gfx950)"; }
 
 int wost_mesh_build_check(const wost_mesh_desc *mesh, int device, int32_t repeat, double *host_ms, double *device_ms, int64_t *mismatch)
 {
-    if (!mesh || !mismatch) return fail(WOST_ERR_INVALID, "null argument");
+    if (!mesh || !mismatch) return set_error(WOST_ERR_INVALID, "null argument");
     int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return fail(WOST_ERR_INVALID, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    if (mesh->n_segs < 0 || mesh->n_verts < 0) return fail(WOST_ERR_INVALID, "negative mesh size");
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
+    WOST_TRY(hipSetDevice(device));
+    if (mesh->n_segs < 0 || mesh->n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
     struct Owned {
         DeviceMeshStorage m;
         ~Owned()
@@ -1547,17 +1524,17 @@ int wost_mesh_build_check(const wost_mesh_desc *mesh, int device, int32_t repeat
     Owned a, b;
     for (int r = 0; r < std::max(1, repeat); ++r) {
         Owned ha, hb;
-        HIP_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t0 = clock::now();
         int rc = upload_mesh_host(*mesh, ha.m);
-        HIP_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t1 = clock::now();
         if (rc != WOST_OK) return rc;
         DeviceTree2 t;
         rc = build_tree_device(*mesh, t);
         if (t.alloc) hb.m.allocs.push_back(t.alloc);
         hb.m.view = t.view;
-        HIP_TRY(hipDeviceSynchronize());
+        WOST_TRY(hipDeviceSynchronize());
         auto t2 = clock::now();
         if (rc != WOST_OK) return rc;
         best_host = std::min(best_host, std::chrono::duration<double, std::milli>(t1 - t0).count());
@@ -1596,21 +1573,21 @@ const char *wost_last_error(void) { return g_last_error.c_str(); }
 
 int wost_create(const wost_scene_desc *scene, const wost_settings *settings, int device, wost_handle *out)
 {
-    if (!scene || !settings || !out) return fail(WOST_ERR_INVALID, "null argument");
+    if (!scene || !settings || !out) return set_error(WOST_ERR_INVALID, "null argument");
     *out = nullptr;
     if (settings->width <= 0 || settings->height <= 0 || settings->spp < 0 || settings->max_depth <= 0)
-        return fail(WOST_ERR_INVALID, "bad settings");
+        return set_error(WOST_ERR_INVALID, "bad settings");
     if (settings->spp >= (1 << 20) || settings->max_depth >= (1 << 10))
-        return fail(WOST_ERR_UNSUPPORTED, "spp must be < 2^20 and max_depth < 2^10");
+        return set_error(WOST_ERR_UNSUPPORTED, "spp must be < 2^20 and max_depth < 2^10");
     if ((int64_t)settings->width * settings->height > (1 << 28))
-        return fail(WOST_ERR_UNSUPPORTED, "frame too large");
+        return set_error(WOST_ERR_UNSUPPORTED, "frame too large");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return fail(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return fail(WOST_ERR_INVALID, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
+        return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
+    WOST_TRY(hipSetDevice(device));
     wost_context *c = new (std::nothrow) wost_context();
-    if (!c) return fail(WOST_ERR_NOMEM, "out of host memory");
+    if (!c) return set_error(WOST_ERR_NOMEM, "out of host memory");
     c->device = device;
     c->settings = *settings;
     c->dst = DevSettings{settings->width, settings->height, settings->spp, settings->max_depth, settings->eps_shell,
@@ -1628,10 +1605,7 @@ int wost_create(const wost_scene_desc *scene, const wost_settings *settings, int
 #define HIP_TRY_C(expr)                                                                                  \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            fail(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-            return bail(WOST_ERR_DEVICE);                                                                \
-        }                                                                                                \
+        if (e_ != hipSuccess) return bail(hip_failed(#expr, e_));                                        \
     } while (0)
     if (scene->mask) {
         HIP_TRY_C(hipMalloc((void **)&c->mask, c->n_pixels));
@@ -1640,7 +1614,7 @@ int wost_create(const wost_scene_desc *scene, const wost_settings *settings, int
     if (scene->source.nx > 0 && scene->source.ny > 0) {
         const wost_source_desc &sd = scene->source;
         if (!sd.rgb) {
-            fail(WOST_ERR_INVALID, "source grid without data");
+            set_error(WOST_ERR_INVALID, "source grid without data");
             return bail(WOST_ERR_INVALID);
         }
         const size_t bytes = (size_t)sd.nx * sd.ny * 3 * sizeof(float);
@@ -1700,78 +1674,78 @@ int wost_destroy(wost_handle h)
 
 int wost_set_option(wost_handle h, const char *key, double value)
 {
-    if (!h || !key) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !key) return set_error(WOST_ERR_INVALID, "null argument");
     const std::string k(key);
     if (k == "steps_per_round") {
-        if (value < 0 || value > 32767) return fail(WOST_ERR_INVALID, "steps_per_round must be in 0..32767 (0 = automatic)");
+        if (value < 0 || value > 32767) return set_error(WOST_ERR_INVALID, "steps_per_round must be in 0..32767 (0 = automatic)");
         h->steps_per_round = (int)value;
     } else if (k == "block_size") {
         const int b = (int)value;
-        if (b != 64 && b != 128 && b != 256) return fail(WOST_ERR_INVALID, "block_size must be 64, 128 or 256");
+        if (b != 64 && b != 128 && b != 256) return set_error(WOST_ERR_INVALID, "block_size must be 64, 128 or 256");
         h->block_size = b;
     } else if (k == "wait_weight") {
-        if (value < 1 || value > 512) return fail(WOST_ERR_INVALID, "wait_weight must be in 1..512");
+        if (value < 1 || value > 512) return set_error(WOST_ERR_INVALID, "wait_weight must be in 1..512");
         h->wait_weight = (int)value;
     } else if (k == "trav_burst") {
-        if (value < 1 || value > 16) return fail(WOST_ERR_INVALID, "trav_burst must be in 1..16");
+        if (value < 1 || value > 16) return set_error(WOST_ERR_INVALID, "trav_burst must be in 1..16");
         h->trav_burst = (int)value;
     } else if (k == "spp") {
-        if (value < 0 || value >= (1 << 20)) return fail(WOST_ERR_INVALID, "spp must be in 0..2^20-1");
+        if (value < 0 || value >= (1 << 20)) return set_error(WOST_ERR_INVALID, "spp must be in 0..2^20-1");
         h->settings.spp = (int32_t)value;
         h->dst.spp = (int32_t)value;
     } else if (k == "refill") {
-        if (value != -1 && value != 0 && value != 1) return fail(WOST_ERR_INVALID, "refill must be -1 (auto), 0 or 1");
+        if (value != -1 && value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "refill must be -1 (auto), 0 or 1");
         h->refill = (int)value;
     } else if (k == "persist") {
-        if (value != -1 && value != 0 && value != 1) return fail(WOST_ERR_INVALID, "persist must be -1 (auto), 0 or 1");
+        if (value != -1 && value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "persist must be -1 (auto), 0 or 1");
         h->persist = (int)value;
     } else if (k == "persist_order") {
         h->persist_order = value != 0;
     } else if (k == "few_order") {
         h->few_order = value != 0;
     } else if (k == "long_steps") {
-        if (value < 0 || value > 65528 || ((int)value & 7)) return fail(WOST_ERR_INVALID, "long_steps must be a multiple of 8 in 0..65528 (0 = no pixel runs beside the rounds)");
+        if (value < 0 || value > 65528 || ((int)value & 7)) return set_error(WOST_ERR_INVALID, "long_steps must be a multiple of 8 in 0..65528 (0 = no pixel runs beside the rounds)");
         h->long_steps = (int)value;
     } else if (k == "long_cap") {
-        if (value < 1 || value > (1 << 20)) return fail(WOST_ERR_INVALID, "long_cap must be in 1..2^20");
+        if (value < 1 || value > (1 << 20)) return set_error(WOST_ERR_INVALID, "long_cap must be in 1..2^20");
         h->long_cap = (int)value;
         if (h->long_mem) (void)hipFree(h->long_mem);
         h->long_mem = nullptr;
     } else if (k == "long_thin") {
-        if (value < 0 || value > (1 << 20)) return fail(WOST_ERR_INVALID, "long_thin must be in 0..2^20");
+        if (value < 0 || value > (1 << 20)) return set_error(WOST_ERR_INVALID, "long_thin must be in 0..2^20");
         h->long_thin = (int)value;
     } else if (k == "tail_sort") {
         h->tail_sort = value != 0;
     } else if (k == "dry_stop") {
-        if (value != 0 && value != 1) return fail(WOST_ERR_INVALID, "dry_stop must be 0 or 1");
+        if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "dry_stop must be 0 or 1");
         h->dry_stop = (int)value;
     } else if (k == "dry_cadence") {
         const int v = (int)value;
-        if (value != v || v < 1 || v > 1024 || (v & (v - 1))) return fail(WOST_ERR_INVALID, "dry_cadence must be a power of two in 1..1024");
+        if (value != v || v < 1 || v > 1024 || (v & (v - 1))) return set_error(WOST_ERR_INVALID, "dry_cadence must be a power of two in 1..1024");
         h->dry_cadence = v;
     } else if (k == "resident_blocks") {
-        if (value < 0 || value > 65535) return fail(WOST_ERR_INVALID, "resident_blocks must be in 0..65535 (0 = what the chip holds)");
+        if (value < 0 || value > 65535) return set_error(WOST_ERR_INVALID, "resident_blocks must be in 0..65535 (0 = what the chip holds)");
         h->resident_blocks = (int)value;
     } else if (k == "quad") {
-        if (value != -1 && value != 0 && value != 1) return fail(WOST_ERR_INVALID, "quad must be -1 (auto), 0 or 1");
+        if (value != -1 && value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "quad must be -1 (auto), 0 or 1");
         h->quad = (int)value;
     } else if (k == "quad_fill") {
-        if (!(value > 0) || value > 64) return fail(WOST_ERR_INVALID, "quad_fill must be in (0, 64]");
+        if (!(value > 0) || value > 64) return set_error(WOST_ERR_INVALID, "quad_fill must be in (0, 64]");
         h->quad_fill = value;
     } else if (k == "coop") {
         h->coop = value != 0;
     } else if (k == "pool_cap") {
-        if (value != 0 && (value < 96 || value > 2048)) return fail(WOST_ERR_INVALID, "pool_cap must be 0 (automatic) or in 96..2048");
+        if (value != 0 && (value < 96 || value > 2048)) return set_error(WOST_ERR_INVALID, "pool_cap must be 0 (automatic) or in 96..2048");
         h->pool_cap = (int)value;
     } else if (k == "ray_slot_trigger") {
-        if (value < 1 || value > 64) return fail(WOST_ERR_INVALID, "ray_slot_trigger must be in 1..64");
+        if (value < 1 || value > 64) return set_error(WOST_ERR_INVALID, "ray_slot_trigger must be in 1..64");
         h->ray_slot_trigger = (int)value;
     } else if (k == "thin_waves") {
         h->thin_waves = value != 0;
     } else if (k == "time_kernels") {
         h->time_kernels = value != 0;
     } else {
-        return fail(WOST_ERR_INVALID, "unknown option: " + k);
+        return set_error(WOST_ERR_INVALID, "unknown option: " + k);
     }
     return WOST_OK;
 }
@@ -1921,33 +1895,33 @@ static int hand_over(wost_context *c, const LaunchGeometry &g, hipStream_t strea
     const uint32_t n_long = beside ? std::min<uint32_t>(std::min<uint32_t>(c->host_count[4], (uint32_t)c->long_cap - n_far), p.n_active) : 0u;
     const uint32_t *ord = nullptr;
     if (p.n_active > 0 && (n_long > 0 || c->tail_sort)) {
-        if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
-        HIP_TRY((hipError_t)order_by_estimate(c->order, c->queue[p.cur].est, p.n_active, stream, &ord));
+        if (c->order.cap < c->n_pixels) WOST_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
+        WOST_TRY((hipError_t)order_by_estimate(c->order, c->queue[p.cur].est, p.n_active, stream, &ord));
         p.rp.order = ord + n_long;
     }
     const uint32_t n_beside = n_far + n_long;
     if (n_beside == 0) return WOST_OK;
     if (!c->long_mem) {
-        HIP_TRY(hipMalloc(&c->long_mem, queue_bytes((size_t)c->long_cap)));
+        WOST_TRY(hipMalloc(&c->long_mem, queue_bytes((size_t)c->long_cap)));
         carve_queue(c->long_mem, (size_t)c->long_cap, c->long_queue);
     }
     // the strayed first (most of a pixel ahead of them as a rule), then the long remainders, longest first
     if (n_far > 0) {
         hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_far + 255) / 256), dim3(256), 0, stream, queue_from(c->queue[p.cur], c->n_pixels - n_far),
                            (const uint32_t *)nullptr, n_far, c->long_queue);
-        HIP_TRY(hipGetLastError());
+        WOST_TRY(hipGetLastError());
         p.far = 0; p.beside_far = n_far;
     }
     if (n_long > 0) {
         hipLaunchKernelGGL(gather_walkers_kernel, dim3((n_long + 255) / 256), dim3(256), 0, stream, c->queue[p.cur], ord, n_long, queue_from(c->long_queue, n_far));
-        HIP_TRY(hipGetLastError());
+        WOST_TRY(hipGetLastError());
     }
     const uint32_t n_thin = std::min<uint32_t>(n_beside, (uint32_t)std::max(c->long_thin, 0));
     c->host_count[5] = n_beside;
     c->host_count[6] = p.n_active - n_long;
-    HIP_TRY(hipMemcpyAsync(c->counts + 5, c->host_count + 5, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->long_ev0, stream));
-    HIP_TRY(hipStreamWaitEvent(c->long_stream, c->long_ev0, 0));
+    WOST_TRY(hipMemcpyAsync(c->counts + 5, c->host_count + 5, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    WOST_TRY(hipEventRecord(c->long_ev0, stream));
+    WOST_TRY(hipStreamWaitEvent(c->long_stream, c->long_ev0, 0));
     RoundParams lp = p.rp;
     lp.in = c->long_queue; lp.order = nullptr; lp.count_in = c->counts + 5;
     lp.count_out = lp.count_far = c->counts + 8;       // (nothing comes out: every walker runs to the end of its pixel)
@@ -1958,8 +1932,8 @@ static int hand_over(wost_context *c, const LaunchGeometry &g, hipStream_t strea
     const unsigned lgrid = lp.thin_blocks + (n_beside - n_thin + quads_per_block - 1u) / quads_per_block;
     long_guard.stream = c->long_stream;
     launch_walk(g, WOST_LAUNCH_QUAD, true, lgrid, c->long_stream, lp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->long_ev1, c->long_stream));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipEventRecord(c->long_ev1, c->long_stream));
     p.rp.count_in = c->counts + 6;
     p.n_round = p.n_active - n_long;
     return WOST_OK;
@@ -1972,9 +1946,9 @@ static int hand_over(wost_context *c, const LaunchGeometry &g, hipStream_t strea
 static int launch_strayed(wost_context *c, const LaunchGeometry &g, hipStream_t stream, const Pass &p, SideStreamGuard &far_guard)
 {
     c->host_count[3] = p.far;
-    HIP_TRY(hipMemcpyAsync(c->counts + 3, c->host_count + 3, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->far_ev0, stream));                      // the counters are ready
-    HIP_TRY(hipStreamWaitEvent(c->far_stream, c->far_ev0, 0));
+    WOST_TRY(hipMemcpyAsync(c->counts + 3, c->host_count + 3, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    WOST_TRY(hipEventRecord(c->far_ev0, stream));                      // the counters are ready
+    WOST_TRY(hipStreamWaitEvent(c->far_stream, c->far_ev0, 0));
     RoundParams fp = p.rp;
     fp.order = nullptr; fp.in = queue_from(c->queue[p.cur], c->n_pixels - p.far); fp.count_in = c->counts + 3;
     fp.steps_per_round = std::max(1, c->settings.max_depth);
@@ -1984,8 +1958,8 @@ static int launch_strayed(wost_context *c, const LaunchGeometry &g, hipStream_t 
     fp.lane_shift = p.far <= 4096u ? 6 : 0;
     far_guard.stream = c->far_stream;
     launch_walk(g, WOST_LAUNCH_ROUND, true, (unsigned)((((uint64_t)p.far << fp.lane_shift) + g.bs - 1) / g.bs), c->far_stream, fp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->far_ev1, c->far_stream));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipEventRecord(c->far_ev1, c->far_stream));
     // (not counted in `launches`: kernel_ms / kernel_launches stays the average duration of the ordinary launches)
     return WOST_OK;
 }
@@ -2028,7 +2002,7 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
         rp.lane_shift = 0;
         p.grid = std::min((unsigned)((p.n_active + bs - 1) / bs), g.resident);
         c->host_count[1] = p.grid * (unsigned)bs;      // first unread slot (pinned staging word)
-        HIP_TRY(hipMemcpyAsync(c->cursor, c->host_count + 1, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        WOST_TRY(hipMemcpyAsync(c->cursor, c->host_count + 1, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         rp.cursor = c->cursor;
         rp.steps_per_round = 0x7fffffff;
         rp.reserve = persist ? 0 : 64;
@@ -2041,8 +2015,8 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
         while (rp.dry_shift < 31 && ((uint64_t)std::max(spp, 1) << rp.dry_shift) < (uint64_t)p.grid * (unsigned)bs) ++rp.dry_shift;
         if (persist) set_schedule(c, g.ntree, true, rp);
         if (persist ? c->persist_order : c->few_order) {
-            if (c->order.cap < c->n_pixels) HIP_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
-            HIP_TRY((hipError_t)order_by_distance(c->order, c->queue[p.cur].d0_d2, p.n_active, stream, &rp.order));
+            if (c->order.cap < c->n_pixels) WOST_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
+            WOST_TRY((hipError_t)order_by_distance(c->order, c->queue[p.cur].d0_d2, p.n_active, stream, &rp.order));
         }
     } else if (p.n_round > 0 &&
                (c->quad == 1 || (c->quad == -1 && 4.0 * (double)p.n_round <= c->quad_fill * (double)g.resident_threads))) {
@@ -2060,7 +2034,7 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
     // (the last strayed walkers can outlive the ordinary queue: then only their launch runs)
     if (p.n_round > 0) {
         launch_walk(g, p.kind, false, p.grid, stream, rp);
-        HIP_TRY(hipGetLastError());
+        WOST_TRY(hipGetLastError());
     }
     return WOST_OK;
 }
@@ -2069,17 +2043,17 @@ static int launch_ordinary(wost_context *c, const LaunchGeometry &g, hipStream_t
 // counters) come back, and the pass is recorded for wost_last_launches.
 static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint32_t launches, double &kernel_ms)
 {
-    if (p.far > 0) HIP_TRY(hipStreamWaitEvent(stream, c->far_ev1, 0));
-    if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipMemcpyAsync(c->host_count, c->counts + (p.cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(c->host_count + 2, c->counts + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (p.far > 0) WOST_TRY(hipStreamWaitEvent(stream, c->far_ev1, 0));
+    if (c->time_kernels) WOST_TRY(hipEventRecord(c->ev1, stream));
+    WOST_TRY(hipMemcpyAsync(c->host_count, c->counts + (p.cur ^ 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipMemcpyAsync(c->host_count + 2, c->counts + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     const bool persist = p.kind == WOST_LAUNCH_PERSISTENT;
-    if (persist) HIP_TRY(hipMemcpyAsync(c->host_count + 4, c->counts + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (c->time_kernels) HIP_TRY(hipMemcpyAsync(c->host_stats, c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (persist) WOST_TRY(hipMemcpyAsync(c->host_count + 4, c->counts + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (c->time_kernels) WOST_TRY(hipMemcpyAsync(c->host_stats, c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     if (!c->time_kernels) return WOST_OK;
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    WOST_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     kernel_ms += ms;
     wost_launch_info li{p.kind, p.n_round, p.n_active - p.n_round + p.far + p.beside_far, p.n_round > 0 ? p.grid : 0u, ms, 0};
     li.walk_steps_done = c->steps_before;
@@ -2113,10 +2087,10 @@ static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shar
 static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
     const auto t_start = std::chrono::high_resolution_clock::now();
-    HIP_TRY(hipSetDevice(c->device));
+    WOST_TRY(hipSetDevice(c->device));
     const LaunchGeometry g = launch_geometry(c);
-    HIP_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
-    HIP_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
+    WOST_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
+    WOST_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
     // the plan of the solve takes its sample count from here: the handle's setting, or the count of a continued call
     const bool carried = !fs.points && fs.carry_more > 0;
     DevSettings st = c->dst;
@@ -2134,9 +2108,9 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
         const unsigned init_grid = (unsigned)((n_threads + g.bs - 1) / g.bs);
         hipLaunchKernelGGL(init_kernel, dim3(init_grid), dim3(g.bs), g.lds, stream, ip);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->host_count, c->counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpyAsync(c->host_count, c->counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     uint32_t n_active = c->host_count[0];
 
     double kernel_ms = 0.0;
@@ -2157,13 +2131,13 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     bool handed_over = false;     // the previous launch was persistent: queue[cur] holds what it handed over, with estimates
     while (n_active > 0 || pending_far > 0) {
         const int nxt = cur ^ 1;
-        HIP_TRY(hipMemsetAsync(c->counts + nxt, 0, sizeof(uint32_t), stream));
-        HIP_TRY(hipMemsetAsync(c->counts + 2, 0, sizeof(uint32_t), stream));
+        WOST_TRY(hipMemsetAsync(c->counts + nxt, 0, sizeof(uint32_t), stream));
+        WOST_TRY(hipMemsetAsync(c->counts + 2, 0, sizeof(uint32_t), stream));
         Pass p{};
         p.cur = cur; p.n_active = p.n_round = n_active; p.far = pending_far;
         p.rp = base;
         p.rp.in = c->queue[cur]; p.rp.out = c->queue[nxt]; p.rp.count_in = c->counts + cur; p.rp.count_out = c->counts + nxt;
-        if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev0, stream));
+        if (c->time_kernels) WOST_TRY(hipEventRecord(c->ev0, stream));
         int rc = handed_over ? hand_over(c, g, stream, p, long_guard) : WOST_OK;
         if (rc == WOST_OK && p.far > 0) rc = launch_strayed(c, g, stream, p, far_guard);
         if (rc == WOST_OK) rc = launch_ordinary(c, g, stream, launches == 0, p);
@@ -2177,21 +2151,21 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     }
     if (long_guard.stream) {
         // the long remainders may outlast the rounds: what is left of their launch counts as kernel time of the solve
-        if (c->time_kernels) HIP_TRY(hipEventRecord(c->ev0, stream));
-        HIP_TRY(hipStreamWaitEvent(stream, c->long_ev1, 0));
+        if (c->time_kernels) WOST_TRY(hipEventRecord(c->ev0, stream));
+        WOST_TRY(hipStreamWaitEvent(stream, c->long_ev1, 0));
         if (c->time_kernels) {
-            HIP_TRY(hipEventRecord(c->ev1, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
+            WOST_TRY(hipEventRecord(c->ev1, stream));
+            WOST_TRY(hipStreamSynchronize(stream));
             float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+            WOST_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
             kernel_ms += ms;
             c->last_launches.push_back(wost_launch_info{WOST_LAUNCH_WAIT, 0, 0, 0, ms, 0});
             if (getenv("WOST_TRACE_LAUNCHES")) fprintf(stderr, "waited %.3f ms for the launch of the long remainders\n", ms);
         }
     }
     std::vector<StatsDev> copies(kStatCopies);
-    HIP_TRY(hipMemcpyAsync(copies.data(), c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    WOST_TRY(hipMemcpyAsync(copies.data(), c->stats, kStatCopies * sizeof(StatsDev), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
     // the solve's stream has waited for every side launch (far_ev1, long_ev1): nothing is left running
     long_guard.stream = far_guard.stream = nullptr;
     StatsDev sd{};
@@ -2247,55 +2221,54 @@ static DeviceMeshStorage *pick_mesh(wost_handle h, int which)
     return nullptr;
 }
 
-// small RAII helper for scratch device buffers of the batch queries
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T **p, size_t count)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T) + 16);
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = reinterpret_cast<T *>(q);
-        return e;
-    }
-};
+// ---- the continued frame solve (the drivers: wost_carry.hip; the bodies of the entry points: CarryCalls, wost_carry.h) ----
+// a walk of the carried solve: a pass of the solve driver on the selected pixels (the 2-D walkers are queued by init_kernel from
+// the map; the id list is the 3-D lanes')
+static CarryWalk carry_walk(wost_context *c, int32_t shard_index, int32_t shard_count)
+{
+    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *, uint32_t, float *field_dev, hipStream_t stream,
+                                         wost_stats *stats) {
+        const bool append = c->carry.walks > 0;
+        if (!append) c->steps_before = 0;
+        const int rc = run_solve(c, frame_step(0, (int32_t)c->n_pixels, shard_index, shard_count, c->carry.done, more_spp, sel, append), field_dev, 0,
+                                 stream, stats);
+        if (rc == WOST_OK && stats) c->steps_before += stats->walk_steps;
+        return rc;
+    };
+}
+
+// (a call that made no walk launched nothing: wost_last_launches reports an empty list, not the solve before it)
+static const CarryCalls<wost_context> kCarry{"wost_", carry_walk, [](wost_context *c) { c->last_launches.clear(); }};
 
 extern "C" {
 
 int wost_solve(wost_handle h, int32_t pixel_begin, int32_t pixel_end, float *field_rgb, wost_stats *stats)
 {
-    if (!h || !field_rgb) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
     if (pixel_begin < 0 || pixel_end > (int64_t)h->n_pixels || pixel_begin > pixel_end)
-        return fail(WOST_ERR_INVALID, "pixel range outside the frame");
-    const auto t0 = std::chrono::high_resolution_clock::now();
+        return set_error(WOST_ERR_INVALID, "pixel range outside the frame");
+    const auto t0 = HostClock::now();
     const size_t n = (size_t)(pixel_end - pixel_begin);
     if (n == 0) {
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return WOST_OK;
     }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
+    WOST_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
     int rc = run_solve(h, frame_step(pixel_begin, pixel_end, 0, 1), h->field, pixel_begin, h->stream, stats);
     if (rc != WOST_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (stats)
-        stats->solve_ms =
-            std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    WOST_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    WOST_TRY(hipStreamSynchronize(h->stream));
+    stamp_solve_ms(stats, t0);
     return WOST_OK;
 }
 
 int wost_solve_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, void *stream,
                        wost_stats *stats)
 {
-    if (!h || !field_rgb_dev) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
     if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count)
-        return fail(WOST_ERR_INVALID, "bad shard");
+        return set_error(WOST_ERR_INVALID, "bad shard");
     // NULL is the legacy default stream, which is also torch's default stream
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return run_solve(h, frame_step(0, (int32_t)h->n_pixels, shard_index, shard_count), field_rgb_dev, 0, s, stats);
@@ -2325,118 +2298,47 @@ static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, in
     return WOST_OK;
 }
 
-// ---- the continued frame solve (the drivers: wost_carry.hip) ----
-static CarryFrame carry_frame(const wost_context *c) { return CarryFrame{c->device, c->settings.width, c->settings.height, c->mask}; }
-
-// a walk of the carried solve: a pass of the solve driver on the selected pixels (the 2-D walkers are queued by init_kernel from
-// the map; the id list is the 3-D lanes')
-static CarryWalk carry_walk(wost_context *c, int32_t shard_index, int32_t shard_count)
-{
-    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *, uint32_t, float *field_dev, hipStream_t stream,
-                                         wost_stats *stats) {
-        const bool append = c->carry.walks > 0;
-        if (!append) c->steps_before = 0;
-        const int rc = run_solve(c, frame_step(0, (int32_t)c->n_pixels, shard_index, shard_count, c->carry.done, more_spp, sel, append), field_dev, 0,
-                                 stream, stats);
-        if (rc == WOST_OK && stats) c->steps_before += stats->walk_steps;
-        return rc;
-    };
-}
-
-// the field of a host call: the handle's device field, zero-filled; after the call it travels to the caller
-static int host_field_begin(wost_context *c)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(c->field, 0, c->n_pixels * 3 * sizeof(float), c->stream));
-    return WOST_OK;
-}
-static int host_field_end(wost_context *c, float *field_rgb, wost_stats *stats, std::chrono::high_resolution_clock::time_point t0)
-{
-    HIP_TRY(hipMemcpyAsync(field_rgb, c->field, c->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    return WOST_OK;
-}
-
 int wost_solve_more_where(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
 {
-    int rc = carry_check_more(h, field_rgb, more_spp);
-    if (rc != WOST_OK) return rc;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if ((rc = host_field_begin(h)) != WOST_OK) return rc;
-    rc = carry_more_where(h->carry, carry_frame(h), 0, 1, more_spp, select, true, h->field, h->stream, stats, carry_walk(h, 0, 1), "wost_");
-    if (rc != WOST_OK) return rc;
-    if (h->carry.walks == 0) h->last_launches.clear();
-    return host_field_end(h, field_rgb, stats, t0);
+    return kCarry.more_where(h, more_spp, select, field_rgb, stats);
 }
 
 int wost_solve_more(wost_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
 {
-    return wost_solve_more_where(h, more_spp, nullptr, field_rgb, stats);
+    return kCarry.more_where(h, more_spp, nullptr, field_rgb, stats);
 }
 
 int wost_solve_more_where_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, const uint8_t *select_dev,
                                   float *field_rgb_dev, void *stream, wost_stats *stats)
 {
-    int rc = carry_check_more(h, field_rgb_dev, more_spp);
-    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
-    if (rc != WOST_OK) return rc;
-    rc = carry_more_where(h->carry, carry_frame(h), shard_index, shard_count, more_spp, select_dev, false, field_rgb_dev,
-                          reinterpret_cast<hipStream_t>(stream), stats, carry_walk(h, shard_index, shard_count), "wost_");
-    if (rc == WOST_OK && h->carry.walks == 0) h->last_launches.clear();
-    return rc;
+    return kCarry.more_where_sharded(h, shard_index, shard_count, more_spp, select_dev, field_rgb_dev, stream, stats);
 }
 
 int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
                             wost_stats *stats)
 {
-    return wost_solve_more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
+    return kCarry.more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
 }
 
 int wost_solve_adaptive_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a, float *field_rgb_dev, void *stream,
                                 wost_stats *stats)
 {
-    int rc = carry_check_adaptive(h, a, field_rgb_dev);
-    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
-    if (rc != WOST_OK) return rc;
-    rc = carry_adaptive(h->carry, carry_frame(h), shard_index, shard_count, *a, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats,
-                        carry_walk(h, shard_index, shard_count), "wost_");
-    if (rc == WOST_OK && h->carry.walks == 0) h->last_launches.clear();
-    return rc;
+    return kCarry.adaptive_sharded(h, shard_index, shard_count, a, field_rgb_dev, stream, stats);
 }
 
 int wost_solve_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
 {
-    int rc = carry_check_adaptive(h, a, field_rgb);
-    if (rc != WOST_OK) return rc;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if ((rc = host_field_begin(h)) != WOST_OK) return rc;
-    rc = carry_adaptive(h->carry, carry_frame(h), 0, 1, *a, h->field, h->stream, stats, carry_walk(h, 0, 1), "wost_");
-    if (rc != WOST_OK) return rc;
-    if (h->carry.walks == 0) h->last_launches.clear();
-    if ((stderr_rgb || spp_map) && (rc = carry_read(h->carry, carry_frame(h), spp_map, nullptr, nullptr, stderr_rgb, h->stream)) != WOST_OK) return rc;
-    return host_field_end(h, field_rgb, stats, t0);
+    return kCarry.adaptive(h, a, field_rgb, stderr_rgb, spp_map, stats);
 }
 
 int wost_solve_carried(wost_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
 {
-    if (!h) return fail(WOST_ERR_INVALID, "null argument");
-    return carry_read(h->carry, carry_frame(h), spp, batches, sum_rgb, stderr_rgb, h->stream);
+    return kCarry.carried(h, spp, batches, sum_rgb, stderr_rgb);
 }
 
-int wost_solve_restart(wost_handle h)
-{
-    if (!h) return fail(WOST_ERR_INVALID, "null argument");
-    carry_restart(h->carry);
-    return WOST_OK;
-}
+int wost_solve_restart(wost_handle h) { return kCarry.restart(h); }
 
-int wost_solve_progress(wost_handle h, int32_t *spp_done)
-{
-    if (!h || !spp_done) return fail(WOST_ERR_INVALID, "null argument");
-    *spp_done = h->carry.done;
-    return WOST_OK;
-}
+int wost_solve_progress(wost_handle h, int32_t *spp_done) { return kCarry.progress(h, spp_done); }
 
 int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
                           void *stream, wost_stats *stats)
@@ -2455,28 +2357,26 @@ int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t see
     if (rc != WOST_OK) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return WOST_OK;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    HIP_TRY(hipSetDevice(h->device));
-    Scratch s;
+    const auto t0 = HostClock::now();
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_field;
-    HIP_TRY(s.alloc(&d_pts, (size_t)n * 2));
-    HIP_TRY(s.alloc(&d_field, (size_t)n * 3));
-    HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
+    WOST_TRY(b.in(pts_xy, (size_t)n * 2, &d_pts));
+    WOST_TRY(b.out(&d_field, (size_t)n * 3));
+    WOST_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
     rc = solve_points_dev(h, d_pts, n, seed_base, seed_width, d_field, h->stream, stats);
     if (rc != WOST_OK) {
         (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
         return rc;
     }
-    HIP_TRY(hipMemcpyAsync(field_rgb, d_field, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    return WOST_OK;
+    WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
+    if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
+    return rc;
 }
 
 int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, int32_t *count)
 {
-    if (!h || !count || (capacity > 0 && !out) || capacity < 0) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !count || (capacity > 0 && !out) || capacity < 0) return set_error(WOST_ERR_INVALID, "null argument");
     *count = (int32_t)h->last_launches.size();
     for (int32_t i = 0; i < std::min(*count, capacity); ++i) out[i] = h->last_launches[(size_t)i];
     return WOST_OK;
@@ -2484,10 +2384,10 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
 
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist)
 {
-    if (!h || !out_dist) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !out_dist) return set_error(WOST_ERR_INVALID, "null argument");
     DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return fail(WOST_ERR_INVALID, "unknown mesh selector");
-    HIP_TRY(hipSetDevice(h->device));
+    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
+    WOST_TRY(hipSetDevice(h->device));
     const int bs = 256;
     const int levels = m->view.n_segs > 0 ? m->view.levels : 1;
     const size_t lds = (size_t)(3 * levels + 1) * bs * sizeof(uint32_t);
@@ -2495,116 +2395,104 @@ int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist)
     float *d_out = h->field;  // reuse: n_pixels floats fit in the field buffer
     hipLaunchKernelGGL(sdf_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, h->probe,
                        h->settings.width, h->settings.height, which_mesh, d_out, bs);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_dist, d_out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    Batch b{h->stream};
+    WOST_TRY(b.fetch(out_dist, d_out, (size_t)n));
+    return b.finish();
 }
 
 int wost_render_source(wost_handle h, float *out_rgb)
 {
-    if (!h || !out_rgb) return fail(WOST_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
+    if (!h || !out_rgb) return set_error(WOST_ERR_INVALID, "null argument");
+    WOST_TRY(hipSetDevice(h->device));
     const int n = (int)h->n_pixels;
-    Scratch sc;
+    Batch b{h->stream};
     float *d = nullptr;
-    HIP_TRY(sc.alloc(&d, (size_t)n * 3));
+    WOST_TRY(b.out(&d, (size_t)n * 3));
     hipLaunchKernelGGL(source_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->src, h->probe, h->settings.width,
                        h->settings.height, d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_rgb, d, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_rgb, d, (size_t)n * 3));
+    return b.finish();
 }
 
 int wost_closest_point(wost_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
                        float *out_uv, int32_t *out_side)
 {
-    if (!h || !pts || n < 0) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !pts || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
     DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m || m->view.n_segs == 0) return fail(WOST_ERR_INVALID, "mesh is empty or unknown");
+    if (!m || m->view.n_segs == 0) return set_error(WOST_ERR_INVALID, "mesh is empty or unknown");
     if (n == 0) return WOST_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Scratch s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_dist, *d_uv;
     int32_t *d_idx, *d_side;
-    HIP_TRY(s.alloc(&d_pts, (size_t)n * 2));
-    HIP_TRY(s.alloc(&d_dist, n));
-    HIP_TRY(s.alloc(&d_uv, n));
-    HIP_TRY(s.alloc(&d_idx, n));
-    HIP_TRY(s.alloc(&d_side, n));
-    HIP_TRY(hipMemcpyAsync(d_pts, pts, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    WOST_TRY(b.in(pts, (size_t)n * 2, &d_pts));
+    WOST_TRY(b.out(&d_dist, n));
+    WOST_TRY(b.out(&d_uv, n));
+    WOST_TRY(b.out(&d_idx, n));
+    WOST_TRY(b.out(&d_side, n));
     const int bs = 256;
     const size_t lds = (size_t)(3 * m->view.levels + 1) * bs * sizeof(uint32_t);
     hipLaunchKernelGGL(closest_point_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, n,
                        d_idx, d_dist, d_uv, d_side, bs);
-    HIP_TRY(hipGetLastError());
-    if (out_idx) HIP_TRY(hipMemcpyAsync(out_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, d_dist, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_uv) HIP_TRY(hipMemcpyAsync(out_uv, d_uv, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_side) HIP_TRY(hipMemcpyAsync(out_side, d_side, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_idx, d_idx, n));
+    WOST_TRY(b.fetch(out_dist, d_dist, n));
+    WOST_TRY(b.fetch(out_uv, d_uv, n));
+    WOST_TRY(b.fetch(out_side, d_side, n));
+    return b.finish();
 }
 
 int wost_closest_silhouette(wost_handle h, int which_mesh, const float *pts, const float *rmax, int32_t n,
                             float *out_dist)
 {
-    if (!h || !pts || !out_dist || n < 0) return fail(WOST_ERR_INVALID, "null argument");
+    if (!h || !pts || !out_dist || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
     DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return fail(WOST_ERR_INVALID, "unknown mesh selector");
+    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
     if (n == 0) return WOST_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Scratch s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_rmax = nullptr, *d_out;
-    HIP_TRY(s.alloc(&d_pts, (size_t)n * 2));
-    HIP_TRY(s.alloc(&d_out, n));
-    HIP_TRY(hipMemcpyAsync(d_pts, pts, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (rmax) {
-        HIP_TRY(s.alloc(&d_rmax, n));
-        HIP_TRY(hipMemcpyAsync(d_rmax, rmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
+    WOST_TRY(b.in(pts, (size_t)n * 2, &d_pts));
+    WOST_TRY(b.out(&d_out, n));
+    if (rmax) WOST_TRY(b.in(rmax, n, &d_rmax));
     const int bs = 256;
     const size_t lds = (size_t)(3 * (m->view.n_segs > 0 ? m->view.levels : 1) + 1) * bs * sizeof(uint32_t);
     hipLaunchKernelGGL(silhouette_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, d_rmax, n,
                        d_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_dist, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_dist, d_out, n));
+    return b.finish();
 }
 
 int wost_ray_intersect(wost_handle h, int which_mesh, const float *origins, const float *dirs, const float *tmax,
                        int32_t n, int32_t *out_hit, float *out_t, int32_t *out_idx)
 {
     if (!h || !origins || !dirs || !tmax || !out_hit || !out_t || !out_idx || n < 0)
-        return fail(WOST_ERR_INVALID, "null argument");
+        return set_error(WOST_ERR_INVALID, "null argument");
     DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return fail(WOST_ERR_INVALID, "unknown mesh selector");
+    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
     if (n == 0) return WOST_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    Scratch s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_o, *d_d, *d_tm, *d_t;
     int32_t *d_hit, *d_idx;
-    HIP_TRY(s.alloc(&d_o, (size_t)n * 2));
-    HIP_TRY(s.alloc(&d_d, (size_t)n * 2));
-    HIP_TRY(s.alloc(&d_tm, n));
-    HIP_TRY(s.alloc(&d_t, n));
-    HIP_TRY(s.alloc(&d_hit, n));
-    HIP_TRY(s.alloc(&d_idx, n));
-    HIP_TRY(hipMemcpyAsync(d_o, origins, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_d, dirs, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_tm, tmax, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    WOST_TRY(b.in(origins, (size_t)n * 2, &d_o));
+    WOST_TRY(b.in(dirs, (size_t)n * 2, &d_d));
+    WOST_TRY(b.in(tmax, n, &d_tm));
+    WOST_TRY(b.out(&d_t, n));
+    WOST_TRY(b.out(&d_hit, n));
+    WOST_TRY(b.out(&d_idx, n));
     const int bs = 256;
     const size_t lds = (size_t)(3 * (m->view.n_segs > 0 ? m->view.levels : 1) + 1) * bs * sizeof(uint32_t);
     hipLaunchKernelGGL(ray_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit,
                        d_t, d_idx);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(out_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_hit, d_hit, n));
+    WOST_TRY(b.fetch(out_t, d_t, n));
+    WOST_TRY(b.fetch(out_idx, d_idx, n));
+    return b.finish();
 }
 
 }  // extern "C"

@@ -790,14 +790,14 @@ static Walk3Plan walk3_plan(const wost3_context *c, int n)
     pl.emissive = c->nm.view.n_tris > 0 && c->nm.view.emissive; pl.source = c->src.rgb != nullptr; pl.ntree = c->nm.view.n_tris > WOST3_FLAT_MAX;
     // a step that answers its Neumann queries on the tree is long and divergent: it waits until eight ninths of the
     // busy walkers of the wave stand at it (tools/probes/bench3d_shell.py: 1.8x over the Dirichlet-only setting on a 1280-triangle shell)
-    pl.wait_weight = env3_int("WOST3_WAIT_WEIGHT", pl.ntree ? 1 : c->wait_weight, 1, big);
-    pl.trav_burst = env3_int("WOST3_TRAV_BURST", c->trav_burst, 1, big);
-    pl.cp_slot_trigger = env3_int("WOST3_CP_TRIGGER", 64, 1, 64);
-    pl.ray_slot_trigger = env3_int("WOST3_RAY_TRIGGER", 32, 1, 64);
-    pl.pool_cap = env3_int("WOST3_POOL_CAP", 512, 96, 4096);      // (64 roots must fit)
-    pl.coop = pl.ntree ? env3_int("WOST3_COOP", 2, 0, 2) : 0;
+    pl.wait_weight = env_int("WOST3_WAIT_WEIGHT", pl.ntree ? 1 : c->wait_weight, 1, big);
+    pl.trav_burst = env_int("WOST3_TRAV_BURST", c->trav_burst, 1, big);
+    pl.cp_slot_trigger = env_int("WOST3_CP_TRIGGER", 64, 1, 64);
+    pl.ray_slot_trigger = env_int("WOST3_RAY_TRIGGER", 32, 1, 64);
+    pl.pool_cap = env_int("WOST3_POOL_CAP", 512, 96, 4096);      // (64 roots must fit)
+    pl.coop = pl.ntree ? env_int("WOST3_COOP", 2, 0, 2) : 0;
     if (c->nm.view.levels > 11) pl.coop = 0;      // (node and slot indices of a task: 26 bits, 4^(levels + 1) slots)
-    pl.wave = c->dm.view.n_tris > 0 && c->dm.view.levels <= 11 && env3_int("WOST3_WAVE", 1, -big, big) != 0;
+    pl.wave = c->dm.view.n_tris > 0 && c->dm.view.levels <= 11 && env_int("WOST3_WAVE", 1, -big, big) != 0;
     pl.stack_words = (3 * lv + 1) * bs;
     pl.lds = (size_t)pl.stack_words * sizeof(uint32_t);
     const size_t lds_pools = pool3_lds_bytes(bs / 64, pl.pool_cap);
@@ -806,9 +806,9 @@ static Walk3Plan walk3_plan(const wost3_context *c, int n)
     // persistent blocks: as many as the chip holds (LDS stacks and registers allow about four per CU), or fewer for small frames
     int n_cus = 256;
     (void)hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    pl.grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * env3_int("WOST3_BLOCKS_PER_CU", 4, 1, big));
+    pl.grid = (unsigned)std::min((n + bs - 1) / bs, n_cus * env_int("WOST3_BLOCKS_PER_CU", 4, 1, big));
     // developer knob for tests: at most this many blocks, so that every lane takes many pixels one after another (refills)
-    if (const int cap = env3_int("WOST3_MAX_BLOCKS", 0, 0, big)) pl.grid = std::min(pl.grid, (unsigned)cap);
+    if (const int cap = env_int("WOST3_MAX_BLOCKS", 0, 0, big)) pl.grid = std::min(pl.grid, (unsigned)cap);
     return pl;
 }
 
@@ -845,9 +845,9 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
 {
     const int32_t pixel_begin = fs.pixel_begin, pixel_end = fs.pixel_end, shard_index = fs.shard_index, shard_count = fs.shard_count;
     const auto t0 = std::chrono::high_resolution_clock::now();
-    W3_TRY(hipSetDevice(c->device));
-    W3_TRY(hipMemsetAsync(c->stats, 0, kStat3Copies * sizeof(Stats3Dev), stream));
-    W3_TRY(hipMemsetAsync(c->cursor, 0, sizeof(uint32_t), stream));
+    WOST_TRY(hipSetDevice(c->device));
+    WOST_TRY(hipMemsetAsync(c->stats, 0, kStat3Copies * sizeof(Stats3Dev), stream));
+    WOST_TRY(hipMemsetAsync(c->cursor, 0, sizeof(uint32_t), stream));
     // (the lanes a launch needs: those of the selection where a continued call has one)
     const int n = fs.carry_more > 0 && fs.carry_ids ? fs.carry_n_ids : pixel_end - pixel_begin;
     float ms = 0.0f;
@@ -868,20 +868,20 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
         P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
         P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
         void *args[] = {&P};
-        W3_TRY(hipEventRecord(c->ev0, stream));
+        WOST_TRY(hipEventRecord(c->ev0, stream));
         (void)hipLaunchKernel(fs.points ? walk3_kernel_of<true>(pl) : carried ? walk3_kernel_of<false, true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
-        W3_TRY(hipGetLastError());
-        W3_TRY(hipEventRecord(c->ev1, stream));
+        WOST_TRY(hipGetLastError());
+        WOST_TRY(hipEventRecord(c->ev1, stream));
     }
     std::vector<Stats3Dev> copies(kStat3Copies);
-    W3_TRY(hipMemcpyAsync(copies.data(), c->stats, kStat3Copies * sizeof(Stats3Dev), hipMemcpyDeviceToHost, stream));
-    W3_TRY(hipStreamSynchronize(stream));
-    if (n > 0) W3_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    WOST_TRY(hipMemcpyAsync(copies.data(), c->stats, kStat3Copies * sizeof(Stats3Dev), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
+    if (n > 0) WOST_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
 #ifdef WOST3_PROFILE
     {
         unsigned long long prof[16], zero[16] = {0};
-        W3_TRY(hipMemcpyFromSymbol(prof, HIP_SYMBOL(g_prof3), sizeof(prof)));
-        W3_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof3), zero, sizeof(zero)));
+        WOST_TRY(hipMemcpyFromSymbol(prof, HIP_SYMBOL(g_prof3), sizeof(prof)));
+        WOST_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_prof3), zero, sizeof(zero)));
         std::fprintf(stderr, "[wost3 profile] wave cycles: silhouette %llu source %llu neumann-sample %llu walk-ray %llu | step trips %llu (cycles %llu, lanes %llu) trav trips %llu (cycles %llu, lanes %llu) | kernel total %llu, %.1f ms\n",
                      prof[0], prof[1], prof[2], prof[3], prof[8], prof[4], prof[9], prof[10], prof[5], prof[11], prof[6], ms);
         std::fprintf(stderr, "[wost3 profile] silhouette queries %llu: inner visits %llu, leaf visits %llu\n", prof[14], prof[12], prof[13]);
@@ -905,6 +905,22 @@ static DeviceMesh3 *pick3(wost3_handle h, int which)
     return which == WOST_MESH_DIRICHLET ? &h->dm : which == WOST_MESH_NEUMANN ? &h->nm : nullptr;
 }
 
+// ---- the continued frame solve (wost_solve_more & co. in 3-D: the same drivers, wost_carry.hip, and the same bodies of the
+// entry points, CarryCalls of wost_carry.h) ----
+// a walk of the carried solve: one launch, its lanes on the pixels of the id list where the call has a selection
+static CarryWalk carry_walk3(wost3_context *c, int32_t shard_index, int32_t shard_count)
+{
+    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *ids, uint32_t n_sel, float *field_dev, hipStream_t stream,
+                                         wost_stats *stats) {
+        FirstStep3 fs{0, (int32_t)c->n_pixels, shard_index, shard_count, nullptr, 0, 0};
+        fs.carry_done = c->carry.done; fs.carry_more = more_spp;
+        if (sel) { fs.carry_ids = ids; fs.carry_n_ids = (int32_t)n_sel; }
+        return run_solve3(c, fs, field_dev, 0, stream, stats);
+    };
+}
+
+static const CarryCalls<wost3_context> kCarry3{"wost3_", carry_walk3, nullptr};
+
 extern "C" {
 
 int wost3_create(const wost3_scene_desc *scene, const wost_settings *settings, int device, wost3_handle *out)
@@ -918,7 +934,7 @@ int wost3_create(const wost3_scene_desc *scene, const wost_settings *settings, i
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
     if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    W3_TRY(hipSetDevice(device));
+    WOST_TRY(hipSetDevice(device));
     wost3_context *c = new (std::nothrow) wost3_context();
     if (!c) return set_error(WOST_ERR_NOMEM, "out of host memory");
     c->device = device;
@@ -973,17 +989,19 @@ int wost3_solve(wost3_handle h, int32_t pixel_begin, int32_t pixel_end, float *f
     if (!h || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
     if (pixel_begin < 0 || pixel_end > (int64_t)h->n_pixels || pixel_begin > pixel_end)
         return set_error(WOST_ERR_INVALID, "pixel range outside the frame");
+    const auto t0 = HostClock::now();
     const size_t n = (size_t)(pixel_end - pixel_begin);
     if (n == 0) {
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return WOST_OK;
     }
-    W3_TRY(hipSetDevice(h->device));
-    W3_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
+    WOST_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
     const int rc = run_solve3(h, FirstStep3{pixel_begin, pixel_end, 0, 1, nullptr, 0, 0}, h->field, pixel_begin, h->stream, stats);
     if (rc != WOST_OK) return rc;
-    W3_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
+    WOST_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    WOST_TRY(hipStreamSynchronize(h->stream));
+    stamp_solve_ms(stats, t0);
     return WOST_OK;
 }
 
@@ -994,108 +1012,47 @@ int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count
     return run_solve3(h, FirstStep3{0, (int32_t)h->n_pixels, shard_index, shard_count, nullptr, 0, 0}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
 }
 
-// ---- the continued frame solve (wost_solve_more & co. in 3-D: the same drivers, wost_carry.hip) ----
-static CarryFrame carry_frame3(const wost3_context *c) { return CarryFrame{c->device, c->settings.width, c->settings.height, c->mask}; }
-
-// a walk of the carried solve: one launch, its lanes on the pixels of the id list where the call has a selection
-static CarryWalk carry_walk3(wost3_context *c, int32_t shard_index, int32_t shard_count)
-{
-    return [c, shard_index, shard_count](int32_t more_spp, const uint8_t *sel, const int32_t *ids, uint32_t n_sel, float *field_dev, hipStream_t stream,
-                                         wost_stats *stats) {
-        FirstStep3 fs{0, (int32_t)c->n_pixels, shard_index, shard_count, nullptr, 0, 0};
-        fs.carry_done = c->carry.done; fs.carry_more = more_spp;
-        if (sel) { fs.carry_ids = ids; fs.carry_n_ids = (int32_t)n_sel; }
-        return run_solve3(c, fs, field_dev, 0, stream, stats);
-    };
-}
-
-static int host_field_begin3(wost3_context *c)
-{
-    W3_TRY(hipSetDevice(c->device));
-    W3_TRY(hipMemsetAsync(c->field, 0, c->n_pixels * 3 * sizeof(float), c->stream));
-    return WOST_OK;
-}
-static int host_field_end3(wost3_context *c, float *field_rgb, wost_stats *stats, std::chrono::high_resolution_clock::time_point t0)
-{
-    W3_TRY(hipMemcpyAsync(field_rgb, c->field, c->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    W3_TRY(hipStreamSynchronize(c->stream));
-    if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    return WOST_OK;
-}
-
 int wost3_solve_more_where(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
 {
-    int rc = carry_check_more(h, field_rgb, more_spp);
-    if (rc != WOST_OK) return rc;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if ((rc = host_field_begin3(h)) != WOST_OK) return rc;
-    rc = carry_more_where(h->carry, carry_frame3(h), 0, 1, more_spp, select, true, h->field, h->stream, stats, carry_walk3(h, 0, 1), "wost3_");
-    if (rc != WOST_OK) return rc;
-    return host_field_end3(h, field_rgb, stats, t0);
+    return kCarry3.more_where(h, more_spp, select, field_rgb, stats);
 }
 
 int wost3_solve_more(wost3_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats)
 {
-    return wost3_solve_more_where(h, more_spp, nullptr, field_rgb, stats);
+    return kCarry3.more_where(h, more_spp, nullptr, field_rgb, stats);
 }
 
 int wost3_solve_more_where_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, const uint8_t *select_dev,
                                    float *field_rgb_dev, void *stream, wost_stats *stats)
 {
-    int rc = carry_check_more(h, field_rgb_dev, more_spp);
-    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
-    if (rc != WOST_OK) return rc;
-    return carry_more_where(h->carry, carry_frame3(h), shard_index, shard_count, more_spp, select_dev, false, field_rgb_dev,
-                            reinterpret_cast<hipStream_t>(stream), stats, carry_walk3(h, shard_index, shard_count), "wost3_");
+    return kCarry3.more_where_sharded(h, shard_index, shard_count, more_spp, select_dev, field_rgb_dev, stream, stats);
 }
 
 int wost3_solve_more_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp, float *field_rgb_dev, void *stream,
                              wost_stats *stats)
 {
-    return wost3_solve_more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
+    return kCarry3.more_where_sharded(h, shard_index, shard_count, more_spp, nullptr, field_rgb_dev, stream, stats);
 }
 
 int wost3_solve_adaptive_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a, float *field_rgb_dev, void *stream,
                                  wost_stats *stats)
 {
-    int rc = carry_check_adaptive(h, a, field_rgb_dev);
-    if (rc == WOST_OK) rc = carry_check_shard(shard_index, shard_count);
-    if (rc != WOST_OK) return rc;
-    return carry_adaptive(h->carry, carry_frame3(h), shard_index, shard_count, *a, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats,
-                          carry_walk3(h, shard_index, shard_count), "wost3_");
+    return kCarry3.adaptive_sharded(h, shard_index, shard_count, a, field_rgb_dev, stream, stats);
 }
 
 int wost3_solve_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
 {
-    int rc = carry_check_adaptive(h, a, field_rgb);
-    if (rc != WOST_OK) return rc;
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if ((rc = host_field_begin3(h)) != WOST_OK) return rc;
-    rc = carry_adaptive(h->carry, carry_frame3(h), 0, 1, *a, h->field, h->stream, stats, carry_walk3(h, 0, 1), "wost3_");
-    if (rc != WOST_OK) return rc;
-    if ((stderr_rgb || spp_map) && (rc = carry_read(h->carry, carry_frame3(h), spp_map, nullptr, nullptr, stderr_rgb, h->stream)) != WOST_OK) return rc;
-    return host_field_end3(h, field_rgb, stats, t0);
+    return kCarry3.adaptive(h, a, field_rgb, stderr_rgb, spp_map, stats);
 }
 
 int wost3_solve_carried(wost3_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
 {
-    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
-    return carry_read(h->carry, carry_frame3(h), spp, batches, sum_rgb, stderr_rgb, h->stream);
+    return kCarry3.carried(h, spp, batches, sum_rgb, stderr_rgb);
 }
 
-int wost3_solve_restart(wost3_handle h)
-{
-    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
-    carry_restart(h->carry);
-    return WOST_OK;
-}
+int wost3_solve_restart(wost3_handle h) { return kCarry3.restart(h); }
 
-int wost3_solve_progress(wost3_handle h, int32_t *spp_done)
-{
-    if (!h || !spp_done) return set_error(WOST_ERR_INVALID, "null argument");
-    *spp_done = h->carry.done;
-    return WOST_OK;
-}
+int wost3_solve_progress(wost3_handle h, int32_t *spp_done) { return kCarry3.progress(h, spp_done); }
 
 int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
                            void *stream, wost_stats *stats)
@@ -1114,21 +1071,21 @@ int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t 
     if (rc != WOST_OK) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(h->device));
-    Scratch3 s;
+    const auto t0 = HostClock::now();
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_field;
-    W3_TRY(s.alloc(&d_pts, (size_t)n * 3));
-    W3_TRY(s.alloc(&d_field, (size_t)n * 3));
-    W3_TRY(hipMemcpyAsync(d_pts, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    W3_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
+    WOST_TRY(b.in(pts_xyz, (size_t)n * 3, &d_pts));
+    WOST_TRY(b.out(&d_field, (size_t)n * 3));
+    WOST_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
     rc = run_solve3(h, FirstStep3{0, n, 0, 1, d_pts, seed_base, seed_width}, d_field, 0, h->stream, stats);
     if (rc != WOST_OK) {
         (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
         return rc;
     }
-    W3_TRY(hipMemcpyAsync(field_rgb, d_field, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
+    if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
+    return rc;
 }
 
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist, float *out_uv,
@@ -1138,23 +1095,21 @@ int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_
     DeviceMesh3 *m = pick3(h, which_mesh);
     if (!m || m->view.n_tris == 0) return set_error(WOST_ERR_INVALID, "mesh is empty or unknown");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(h->device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_dist, *d_uv;
     int32_t *d_idx, *d_side;
-    W3_TRY(s.alloc(&d_pts, (size_t)n * 3)); W3_TRY(s.alloc(&d_dist, n)); W3_TRY(s.alloc(&d_uv, (size_t)n * 2));
-    W3_TRY(s.alloc(&d_idx, n)); W3_TRY(s.alloc(&d_side, n));
-    W3_TRY(hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
+    WOST_TRY(b.in(pts, (size_t)n * 3, &d_pts)); WOST_TRY(b.out(&d_dist, n)); WOST_TRY(b.out(&d_uv, (size_t)n * 2));
+    WOST_TRY(b.out(&d_idx, n)); WOST_TRY(b.out(&d_side, n));
     const int bs = 256;
     const size_t lds = (size_t)(3 * m->view.levels + 1) * bs * sizeof(uint32_t);
     hipLaunchKernelGGL(closest_point3_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, n, d_idx, d_dist, d_uv, d_side);
-    W3_TRY(hipGetLastError());
-    if (out_idx) W3_TRY(hipMemcpyAsync(out_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_dist) W3_TRY(hipMemcpyAsync(out_dist, d_dist, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_uv) W3_TRY(hipMemcpyAsync(out_uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (out_side) W3_TRY(hipMemcpyAsync(out_side, d_side, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_idx, d_idx, n));
+    WOST_TRY(b.fetch(out_dist, d_dist, n));
+    WOST_TRY(b.fetch(out_uv, d_uv, (size_t)n * 2));
+    WOST_TRY(b.fetch(out_side, d_side, n));
+    return b.finish();
 }
 
 int wost3_closest_silhouette(wost3_handle h, int which_mesh, const float *pts, const float *rmax, int32_t n, float *out_dist)
@@ -1163,24 +1118,19 @@ int wost3_closest_silhouette(wost3_handle h, int which_mesh, const float *pts, c
     DeviceMesh3 *m = pick3(h, which_mesh);
     if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(h->device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_pts, *d_rmax = nullptr, *d_out;
-    W3_TRY(s.alloc(&d_pts, (size_t)n * 3)); W3_TRY(s.alloc(&d_out, n));
-    W3_TRY(hipMemcpyAsync(d_pts, pts, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
-    if (rmax) {
-        W3_TRY(s.alloc(&d_rmax, n));
-        W3_TRY(hipMemcpyAsync(d_rmax, rmax, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    }
+    WOST_TRY(b.in(pts, (size_t)n * 3, &d_pts)); WOST_TRY(b.out(&d_out, n));
+    if (rmax) WOST_TRY(b.in(rmax, n, &d_rmax));
     {
         const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
         if (m->view.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((silhouette3_kernel<true>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_pts, d_rmax, n, d_out);
         else hipLaunchKernelGGL((silhouette3_kernel<false>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_pts, d_rmax, n, d_out);
     }
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpyAsync(out_dist, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_dist, d_out, n));
+    return b.finish();
 }
 
 int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist)
@@ -1188,33 +1138,31 @@ int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist)
     if (!h || !out_dist) return set_error(WOST_ERR_INVALID, "null argument");
     DeviceMesh3 *m = pick3(h, which_mesh);
     if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    W3_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     const int n = (int)h->n_pixels;
-    Scratch3 s;
+    Batch b{h->stream};
     float *d_out;
-    W3_TRY(s.alloc(&d_out, n));
+    WOST_TRY(b.out(&d_out, n));
     const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
     hipLaunchKernelGGL(render3_sdf_kernel, dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, h->probe, h->settings.width, h->settings.height,
                        which_mesh == WOST_MESH_NEUMANN ? 1 : 0, d_out);
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpyAsync(out_dist, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_dist, d_out, n));
+    return b.finish();
 }
 
 int wost3_render_source(wost3_handle h, float *out_rgb)
 {
     if (!h || !out_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    W3_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     const int n = (int)h->n_pixels;
-    Scratch3 s;
+    Batch b{h->stream};
     float *d_out;
-    W3_TRY(s.alloc(&d_out, (size_t)n * 3));
+    WOST_TRY(b.out(&d_out, (size_t)n * 3));
     hipLaunchKernelGGL(render3_source_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->src, h->probe, h->settings.width, h->settings.height, d_out);
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpyAsync(out_rgb, d_out, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_rgb, d_out, (size_t)n * 3));
+    return b.finish();
 }
 
 int wost3_ray_intersect(wost3_handle h, int which_mesh, const float *origins, const float *dirs, const float *tmax, int32_t n,
@@ -1224,26 +1172,22 @@ int wost3_ray_intersect(wost3_handle h, int which_mesh, const float *origins, co
     DeviceMesh3 *m = pick3(h, which_mesh);
     if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(h->device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(h->device));
+    Batch b{h->stream};
     float *d_o, *d_d, *d_tm, *d_t;
     int32_t *d_hit, *d_idx;
-    W3_TRY(s.alloc(&d_o, (size_t)n * 3)); W3_TRY(s.alloc(&d_d, (size_t)n * 3)); W3_TRY(s.alloc(&d_tm, n)); W3_TRY(s.alloc(&d_t, n));
-    W3_TRY(s.alloc(&d_hit, n)); W3_TRY(s.alloc(&d_idx, n));
-    W3_TRY(hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
-    W3_TRY(hipMemcpyAsync(d_d, dirs, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
-    W3_TRY(hipMemcpyAsync(d_tm, tmax, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    WOST_TRY(b.in(origins, (size_t)n * 3, &d_o)); WOST_TRY(b.in(dirs, (size_t)n * 3, &d_d)); WOST_TRY(b.in(tmax, n, &d_tm));
+    WOST_TRY(b.out(&d_t, n)); WOST_TRY(b.out(&d_hit, n)); WOST_TRY(b.out(&d_idx, n));
     {
         const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
         if (m->view.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((ray3_kernel<true>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit, d_t, d_idx);
         else hipLaunchKernelGGL((ray3_kernel<false>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit, d_t, d_idx);
     }
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpyAsync(out_hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipMemcpyAsync(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipMemcpyAsync(out_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    W3_TRY(hipStreamSynchronize(h->stream));
-    return WOST_OK;
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(b.fetch(out_hit, d_hit, n));
+    WOST_TRY(b.fetch(out_t, d_t, n));
+    WOST_TRY(b.fetch(out_idx, d_idx, n));
+    return b.finish();
 }
 
 }  // extern "C"

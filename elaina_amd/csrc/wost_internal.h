@@ -10,11 +10,9 @@
 
 #include "../../include/wost.h"
 #include "wost_device.h"
+#include "wost_host.h"
 
 namespace wost {
-
-// records the message returned by wost_last_error() on this thread; returns `code`
-int set_error(int code, const std::string &msg);
 
 // The argument rules of the point solves (wost_solve_points & co., include/wost.h), checked before any device work:
 // WOST_OK, or WOST_ERR_INVALID with its message recorded

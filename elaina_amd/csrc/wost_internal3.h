@@ -1,5 +1,5 @@
 // wost_internal3.h -- host-side declarations shared by the translation units of the 3-D path (not part of the C-ABI): the
-// uploaded mesh, the context behind wost3_handle, the error macro.
+// uploaded mesh, the context behind wost3_handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,27 +34,8 @@ struct DeviceMesh3 {
     std::vector<void *> allocs;
 };
 
-template <class T>
-static hipError_t upload3(std::vector<void *> &allocs, const T *src, size_t count, const T **dst)
-{
-    *dst = nullptr;
-    if (count == 0) return hipSuccess;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e != hipSuccess) return e;
-    allocs.push_back(p);
-    *dst = reinterpret_cast<const T *>(p);
-    return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
-}
-
 // LDS bytes of the task pools (WavePool3) of a block of `waves` waves: per wave two pools of pool_cap tasks and the owners' words
 inline size_t pool3_lds_bytes(int waves, int pool_cap) { return (size_t)waves * (2 * (size_t)pool_cap + kPool3OwnerWords) * sizeof(uint32_t); }
-// an environment switch of the 3-D drivers as an integer clamped to lo..hi; `fallback` when it is not set
-inline int env3_int(const char *name, int fallback, int lo, int hi)
-{
-    const char *w = std::getenv(name);
-    return w ? std::min(hi, std::max(lo, std::atoi(w))) : fallback;
-}
 
 }  // namespace wost
 
@@ -78,12 +59,6 @@ struct wost3_context {
     wost::CarryState carry;
 };
 
-#define W3_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 namespace wost {
 // wost_build3.hip: the mesh of `d` built on the current device (records, Morton order, tree, cones) into s.view
 int upload_mesh3(const wost3_mesh_desc &d, DeviceMesh3 &s);
@@ -91,23 +66,3 @@ int upload_mesh3(const wost3_mesh_desc &d, DeviceMesh3 &s);
 void launch_vmm3_loss_gradients(hipStream_t stream, const float *raw, const float *dir, const float *li, const float *dir_pdf,
                                 const unsigned char *on_neumann, const float *normal, int n, float loss_scale, float *dl_draw, float *likelihood);
 }  // namespace wost
-
-// device scratch of the batch entry points (freed on every return path)
-struct Scratch3 {
-    std::vector<void *> ptrs;
-    ~Scratch3()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T **p, size_t count)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T) + 16);
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = reinterpret_cast<T *>(q);
-        return e;
-    }
-};
-
-

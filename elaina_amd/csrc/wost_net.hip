@@ -1543,7 +1543,6 @@ struct TrainPlan {
     std::vector<GridGradStep> fallback;  // grid_grad_kernel: one launch per level group
 };
 
-static int env_int(const char *name, int unset) { const char *e = std::getenv(name); return e ? std::atoi(e) : unset; }
 // LDS of a group's 8-byte accumulators: 72 KB (two blocks per CU), a larger level alone up to 150 KB (one block); all levels of a box
 constexpr size_t kGroupSmall = 72 * 1024, kGroupBig = 150 * 1024, kBin3LdsCap = 152 * 1024;
 static size_t level_bytes(const NetLayout &L, int l, int nq) { return (size_t)(L.level_off[l + 1] - L.level_off[l]) * nq * sizeof(fx_t); }
@@ -1668,12 +1667,6 @@ struct wost_net {
     size_t cap_points = 0;
 };
 
-#define NET_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // the shape the MFMA kernels are instantiated for (eight_by_four: as 8 levels x 4 features, which the half-precision kernels need on top)
 static bool reference_shape(const NetLayout &L, bool eight_by_four) { return L.enc == 32 && L.n_neurons == 64 && L.n_hidden == 3 && L.n_out_padded == 48 && (!eight_by_four || (L.n_features == 4 && L.n_levels == 8)); }
 
@@ -1692,7 +1685,7 @@ static int launch_forward_h(wost_net *h, const float *p, const uint2 *image, con
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(kHalfFwdThreads), lds, stream, L, p, image, xy_dev, n, n_dev, out_dev, ldp, ldf, enc_out);
     ++h->n_launches;
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -1713,18 +1706,18 @@ static int enable_half(wost_net *h, bool training)
     if (!reference_shape(L, true))
         return set_error(WOST_ERR_UNSUPPORTED, std::string("half-precision ") + (training ? "training" : "inference") +
                                                    " is built for the reference's network shape only (8 levels x 4 features, 3 x 64, two or three inputs)");
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     const size_t image = half_image_entries(L) * sizeof(uint2);
     if (L.dims == 2 && image > 158 * 1024)
         return set_error(WOST_ERR_UNSUPPORTED, "half-precision network: weights and grid must fit into 158 KB of LDS");
-    if (!training && !h->inference_h) NET_TRY(hipMalloc((void **)&h->inference_h, image));
-    if (training && !h->params_h) NET_TRY(hipMalloc((void **)&h->params_h, image));
-    if (training && !h->params_hb) NET_TRY(hipMalloc((void **)&h->params_hb, (size_t)L.n_mlp / 4 * sizeof(uint2)));
-    if (training && !h->train_partial) NET_TRY(hipMalloc((void **)&h->train_partial, (size_t)256 * L.n_mlp * sizeof(float)));
+    if (!training && !h->inference_h) WOST_TRY(hipMalloc((void **)&h->inference_h, image));
+    if (training && !h->params_h) WOST_TRY(hipMalloc((void **)&h->params_h, image));
+    if (training && !h->params_hb) WOST_TRY(hipMalloc((void **)&h->params_hb, (size_t)L.n_mlp / 4 * sizeof(uint2)));
+    if (training && !h->train_partial) WOST_TRY(hipMalloc((void **)&h->train_partial, (size_t)256 * L.n_mlp * sizeof(float)));
     (training ? h->train_precision : h->precision) = 16;
     refresh_half(h, nullptr);
-    NET_TRY(hipGetLastError());
-    NET_TRY(hipDeviceSynchronize());
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipDeviceSynchronize());
     return WOST_OK;
 }
 
@@ -1739,7 +1732,7 @@ static int refresh_transposed(wost_net *h, hipStream_t stream)
         hipLaunchKernelGGL(fragment_mlp_t_kernel, dim3(g), dim3(256), 0, stream, h->L, h->params, h->params_fb);
     }
     refresh_half(h, stream);
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -1785,7 +1778,7 @@ static int launch_forward(wost_net *h, bool use_inference_params, const float *x
                            n, n_dev, out_dev, acts_dev, ldp, ldf);
     }
     ++h->n_launches;
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -1796,18 +1789,18 @@ static int ensure_points(wost_net *h, size_t n)
         if (*p) { (void)hipFree(*p); *p = nullptr; }
     h->cap_points = 0;
     const NetLayout &L = h->L;
-    NET_TRY(hipMalloc((void **)&h->d_xy, n * 3 * sizeof(float)));
-    NET_TRY(hipMalloc((void **)&h->d_out, n * L.n_out * sizeof(float)));
-    NET_TRY(hipMalloc((void **)&h->d_dl, n * L.n_out * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_xy, n * 3 * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_out, n * L.n_out * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_dl, n * L.n_out * sizeof(float)));
     const size_t n64 = (n + 63) / 64 * 64;     // the MFMA training layout works in whole 64-point spans
-    NET_TRY(hipMalloc((void **)&h->d_acts, n64 * (size_t)(L.enc + L.n_hidden * L.n_neurons) * sizeof(float)));
-    NET_TRY(hipMalloc((void **)&h->d_deltas, n64 * (size_t)(L.n_out_padded + L.n_hidden * L.n_neurons) * sizeof(float)));
-    NET_TRY(hipMalloc((void **)&h->d_denc, n * (size_t)L.enc * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_acts, n64 * (size_t)(L.enc + L.n_hidden * L.n_neurons) * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_deltas, n64 * (size_t)(L.n_out_padded + L.n_hidden * L.n_neurons) * sizeof(float)));
+    WOST_TRY(hipMalloc((void **)&h->d_denc, n * (size_t)L.enc * sizeof(float)));
     if (h->d_mask) { (void)hipFree(h->d_mask); h->d_mask = nullptr; }
-    NET_TRY(hipMalloc((void **)&h->d_mask, n * 4 * sizeof(unsigned long long)));
+    WOST_TRY(hipMalloc((void **)&h->d_mask, n * 4 * sizeof(unsigned long long)));
     if (h->d_bin_order) { (void)hipFree(h->d_bin_order); h->d_bin_order = nullptr; }
-    if (L.dims == 3) NET_TRY(hipMalloc((void **)&h->d_bin_order, n * sizeof(uint32_t)));
-    if (h->plan.bin3.bins && !h->d_bin_tab) NET_TRY(hipMalloc((void **)&h->d_bin_tab, (2 * 4096 + 1 + 2 * 4097) * sizeof(uint32_t)));      // box tables, up to 16^3 boxes
+    if (L.dims == 3) WOST_TRY(hipMalloc((void **)&h->d_bin_order, n * sizeof(uint32_t)));
+    if (h->plan.bin3.bins && !h->d_bin_tab) WOST_TRY(hipMalloc((void **)&h->d_bin_tab, (2 * 4096 + 1 + 2 * 4097) * sizeof(uint32_t)));      // box tables, up to 16^3 boxes
     h->cap_points = n;
     return WOST_OK;
 }
@@ -1865,11 +1858,11 @@ int net_apply_update_dev(wost_net *h, float loss_scale, hipStream_t stream)
         std::vector<float> tab((size_t)cap + 1, 0.0f);
         for (int s_ = 1; s_ <= cap; ++s_)
             tab[s_] = c.learning_rate * std::sqrt(1.0f - std::pow(c.beta2, (float)s_)) / (1.0f - std::pow(c.beta1, (float)s_));
-        NET_TRY(hipStreamSynchronize(stream));
+        WOST_TRY(hipStreamSynchronize(stream));
         if (h->lr_table) (void)hipFree(h->lr_table);
         h->lr_table = nullptr;
-        NET_TRY(hipMalloc((void **)&h->lr_table, tab.size() * sizeof(float)));
-        NET_TRY(hipMemcpy(h->lr_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        WOST_TRY(hipMalloc((void **)&h->lr_table, tab.size() * sizeof(float)));
+        WOST_TRY(hipMemcpy(h->lr_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
         h->lr_cap = cap;
     }
     const float debias = 1.0f / (1.0f - std::pow(c.ema_decay, (float)h->step));
@@ -1885,7 +1878,7 @@ int net_apply_update_dev(wost_net *h, float loss_scale, hipStream_t stream)
                        h->m2, h->ema_raw, h->inference, h->grad, h->lr_table, h->param_steps, c.beta1, c.beta2, c.epsilon,
                        c.l2_reg, c.ema_decay, debias, loss_scale, h->grad_div, D);
     ++h->n_launches;
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -1950,7 +1943,7 @@ static int grid_gradient(wost_net *h, const float *xy_dev, int n, hipStream_t st
     } else if (P.bin3.bins && h->d_bin_order && (size_t)n <= h->cap_points) {
         const GridBin3Plan &bp = P.bin3;
         const int nb = bp.bins * bp.bins * bp.bins;
-        NET_TRY(hipMemsetAsync(h->d_bin_tab, 0, (2 * (size_t)nb + 1) * sizeof(uint32_t), stream));
+        WOST_TRY(hipMemsetAsync(h->d_bin_tab, 0, (2 * (size_t)nb + 1) * sizeof(uint32_t), stream));
         const unsigned gc = (unsigned)((n + kBin3CountPoints - 1) / kBin3CountPoints);
         hipLaunchKernelGGL(grid_bin3_count_kernel, dim3(gc), dim3(1024), (size_t)std::max(nb, 2048) * sizeof(uint32_t), stream, xy_dev, n, bp.bins,
                            bp.chunk, h->d_bin_tab);
@@ -1971,7 +1964,7 @@ static int grid_gradient(wost_net *h, const float *xy_dev, int n, hipStream_t st
             ++h->n_launches;
         }
     }
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return WOST_OK;
 }
 
@@ -2006,14 +1999,14 @@ static void weight_gradients(wost_net *h, int n, hipStream_t stream)
 // backward pass of the step whose forward pass net_forward_train_dev ran, dL/dout in place: the sums in h->grad, then (apply_update) Adam
 int net_backward_update_dev(wost_net *h, const float *xy_dev, int n, float loss_scale, int apply_update, hipStream_t stream)
 {
-    NET_TRY(hipMemsetAsync(h->grad, 0, (size_t)h->n_params * sizeof(fx_t), stream));
+    WOST_TRY(hipMemsetAsync(h->grad, 0, (size_t)h->n_params * sizeof(fx_t), stream));
     ++h->n_launches;
     backward_pass(h, xy_dev, n, stream);
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     const int rc = grid_gradient(h, xy_dev, n, stream);
     if (rc != WOST_OK) return rc;
     weight_gradients(h, n, stream);
-    NET_TRY(hipGetLastError());
+    WOST_TRY(hipGetLastError());
     return apply_update ? net_apply_update_dev(h, loss_scale, stream) : WOST_OK;
 }
 
@@ -2064,11 +2057,11 @@ int net_snapshot_dev(wost_net *h, void *dst, hipStream_t stream)
 {
     if (!h || !dst) return set_error(WOST_ERR_INVALID, "null argument");
     if (h->precision == 16 && h->inference_h) {
-        NET_TRY(hipMemcpyAsync(dst, h->inference_h, half_image_entries(h->L) * sizeof(uint2), hipMemcpyDeviceToDevice, stream));
+        WOST_TRY(hipMemcpyAsync(dst, h->inference_h, half_image_entries(h->L) * sizeof(uint2), hipMemcpyDeviceToDevice, stream));
     } else if (h->use_mfma && h->inference_f && h->L.dims == 2) {
         float *d = reinterpret_cast<float *>(dst);
-        NET_TRY(hipMemcpyAsync(d, h->inference_f, (size_t)h->L.n_mlp * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        NET_TRY(hipMemcpyAsync(d + h->L.n_mlp, h->inference + h->L.n_mlp, (size_t)(h->n_params - h->L.n_mlp) * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        WOST_TRY(hipMemcpyAsync(d, h->inference_f, (size_t)h->L.n_mlp * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        WOST_TRY(hipMemcpyAsync(d + h->L.n_mlp, h->inference + h->L.n_mlp, (size_t)(h->n_params - h->L.n_mlp) * sizeof(float), hipMemcpyDeviceToDevice, stream));
     } else {
         return set_error(WOST_ERR_UNSUPPORTED, "this network has no image to copy");
     }
@@ -2127,7 +2120,7 @@ static int net_create_dims(int device, const wost_net_config *cfg, uint64_t seed
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
     if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    NET_TRY(hipSetDevice(device));
+    WOST_TRY(hipSetDevice(device));
     wost_net *h = new (std::nothrow) wost_net();
     if (!h) return set_error(WOST_ERR_NOMEM, "out of host memory");
     h->device = device;
@@ -2207,26 +2200,26 @@ int wost_net_n_params(wost_net_handle h, uint64_t *n_total, uint64_t *n_mlp)
 int wost_net_get_params(wost_net_handle h, int which, float *host)
 {
     if (!h || !host || which < 0 || which > 2) return set_error(WOST_ERR_INVALID, "bad argument");
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     if (which == 2) {
         std::vector<fx_t> fx(h->n_params);
-        NET_TRY(hipMemcpy(fx.data(), h->grad, (size_t)h->n_params * sizeof(fx_t), hipMemcpyDeviceToHost));
+        WOST_TRY(hipMemcpy(fx.data(), h->grad, (size_t)h->n_params * sizeof(fx_t), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < h->n_params; ++i) host[i] = (float)((double)fx[i] / kFxScale);
         return WOST_OK;
     }
     const float *src = which == 0 ? h->params : h->inference;
-    NET_TRY(hipMemcpy(host, src, (size_t)h->n_params * sizeof(float), hipMemcpyDeviceToHost));
+    WOST_TRY(hipMemcpy(host, src, (size_t)h->n_params * sizeof(float), hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
 int wost_net_set_gradient_buffer(wost_net_handle h, void *dev_int64)
 {
     if (!h) return set_error(WOST_ERR_INVALID, "null argument");
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     if (!dev_int64) {                     // back to an internal buffer
         if (!h->grad_owned) {
             h->grad = nullptr;
-            NET_TRY(hipMalloc((void **)&h->grad, (size_t)h->n_params * sizeof(fx_t)));
+            WOST_TRY(hipMalloc((void **)&h->grad, (size_t)h->n_params * sizeof(fx_t)));
             h->grad_owned = true;
         }
         return WOST_OK;
@@ -2240,16 +2233,16 @@ int wost_net_set_gradient_buffer(wost_net_handle h, void *dev_int64)
 int wost_net_set_params(wost_net_handle h, const float *host)
 {
     if (!h || !host) return set_error(WOST_ERR_INVALID, "null argument");
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     const size_t bytes = (size_t)h->n_params * sizeof(float);
-    NET_TRY(hipMemcpy(h->params, host, bytes, hipMemcpyHostToDevice));
-    NET_TRY(hipMemcpy(h->inference, host, bytes, hipMemcpyHostToDevice));
-    for (float *p : {h->m1, h->m2, h->ema_raw}) NET_TRY(hipMemset(p, 0, bytes));
-    NET_TRY(hipMemset(h->param_steps, 0, (size_t)h->n_params * sizeof(uint32_t)));
+    WOST_TRY(hipMemcpy(h->params, host, bytes, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(h->inference, host, bytes, hipMemcpyHostToDevice));
+    for (float *p : {h->m1, h->m2, h->ema_raw}) WOST_TRY(hipMemset(p, 0, bytes));
+    WOST_TRY(hipMemset(h->param_steps, 0, (size_t)h->n_params * sizeof(uint32_t)));
     h->step = 0;
     int rc = refresh_transposed(h, nullptr);
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipDeviceSynchronize());
+    WOST_TRY(hipDeviceSynchronize());
     return WOST_OK;
 }
 
@@ -2271,10 +2264,10 @@ int wost_net_inference(wost_net_handle h, const float *xy, int32_t n, float *out
 {
     if (!h || !xy || !out || n < 0) return set_error(WOST_ERR_INVALID, "bad argument");
     if (n == 0) return WOST_OK;
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     int rc = ensure_points(h, (size_t)n);
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipMemcpy(h->d_xy, xy, (size_t)n * h->L.dims * sizeof(float), hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(h->d_xy, xy, (size_t)n * h->L.dims * sizeof(float), hipMemcpyHostToDevice));
     if (!use_inference_params && h->train_precision == 16) {
         // the training weights as a half-precision training step evaluates them
         float *o = nullptr, *dl = nullptr;
@@ -2283,7 +2276,7 @@ int wost_net_inference(wost_net_handle h, const float *xy, int32_t n, float *out
         rc = launch_forward(h, use_inference_params != 0, h->d_xy, n, nullptr, h->d_out, nullptr, nullptr);
     }
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipMemcpy(out, h->d_out, (size_t)n * h->L.n_out * sizeof(float), hipMemcpyDeviceToHost));
+    WOST_TRY(hipMemcpy(out, h->d_out, (size_t)n * h->L.n_out * sizeof(float), hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -2291,17 +2284,17 @@ int wost_net_train_step(wost_net_handle h, const float *xy, const float *dl_dout
                         int apply_update)
 {
     if (!h || !xy || !dl_dout || n <= 0 || !(loss_scale > 0.0f)) return set_error(WOST_ERR_INVALID, "bad argument");
-    NET_TRY(hipSetDevice(h->device));
+    WOST_TRY(hipSetDevice(h->device));
     int rc = ensure_points(h, (size_t)n);
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipMemcpy(h->d_xy, xy, (size_t)n * h->L.dims * sizeof(float), hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(h->d_xy, xy, (size_t)n * h->L.dims * sizeof(float), hipMemcpyHostToDevice));
     float *out = nullptr, *dl = nullptr;
     rc = wost::net_forward_train_dev(h, h->d_xy, n, nullptr, &out, &dl);
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipMemcpy(dl, dl_dout, (size_t)n * h->L.n_out * sizeof(float), hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(dl, dl_dout, (size_t)n * h->L.n_out * sizeof(float), hipMemcpyHostToDevice));
     rc = wost::net_backward_update_dev(h, h->d_xy, n, loss_scale, apply_update, nullptr);
     if (rc != WOST_OK) return rc;
-    NET_TRY(hipDeviceSynchronize());
+    WOST_TRY(hipDeviceSynchronize());
     return WOST_OK;
 }
 

@@ -135,20 +135,14 @@ __global__ void resolve_points_kernel(const float *sol, const float *points, int
     for (int k = 0; k < 3; ++k) field[3 * (size_t)i + k] = finite ? sol[3 * (size_t)i + k] / spp : __builtin_nanf("");
 }
 
-#define TRAIN_TRY(expr)                                                                                 \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 template <int D>
 int enqueue_train_set(const TrainSetParams<D> &T, int n_blocks, hipStream_t st, uint32_t *host_total)
 {
     hipLaunchKernelGGL((train_set_kernel<D, false>), dim3(n_blocks), dim3(256), 0, st, T);
     hipLaunchKernelGGL(train_scan_kernel, dim3(1), dim3(256), 0, st, T.block_sums, n_blocks);
     hipLaunchKernelGGL((train_set_kernel<D, true>), dim3(n_blocks), dim3(256), 0, st, T);
-    TRAIN_TRY(hipGetLastError());
-    TRAIN_TRY(hipMemcpyAsync(host_total, T.block_sums + n_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpyAsync(host_total, T.block_sums + n_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     return WOST_OK;
 }
 
@@ -186,7 +180,7 @@ int train_passes(wost_net_handle net, const TrainSet &ts, size_t n, const TrainS
         if (rc != WOST_OK) return rc;
         if (!sync.fn) continue;
         // sum the fixed-point gradients of all ranks (integer sums: the same network everywhere, bit for bit), then step
-        TRAIN_TRY(hipStreamSynchronize(st));
+        WOST_TRY(hipStreamSynchronize(st));
         uint64_t count = 0;
         void *gbuf = net_gradient_buffer(net, &count);
         if (sync.fn(sync.user, WOST_SYNC_SUM_I64_DEVICE, gbuf, count) != 0)
@@ -230,12 +224,12 @@ int copy_train_set(const TrainSet &ts, int dim, size_t m, float *x, float *dir, 
 {
     const size_t d = (size_t)dim;
     if (m == 0) return WOST_OK;
-    if (x) TRAIN_TRY(hipMemcpy(x, ts.x, m * d * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir) TRAIN_TRY(hipMemcpy(dir, ts.dir, m * d * sizeof(float), hipMemcpyDeviceToHost));
-    if (solution) TRAIN_TRY(hipMemcpy(solution, ts.sol, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dir_pdf) TRAIN_TRY(hipMemcpy(dir_pdf, ts.pdf, m * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal) TRAIN_TRY(hipMemcpy(normal, ts.nrm, m * d * sizeof(float), hipMemcpyDeviceToHost));
-    if (on_neumann) TRAIN_TRY(hipMemcpy(on_neumann, ts.onn, m, hipMemcpyDeviceToHost));
+    if (x) WOST_TRY(hipMemcpy(x, ts.x, m * d * sizeof(float), hipMemcpyDeviceToHost));
+    if (dir) WOST_TRY(hipMemcpy(dir, ts.dir, m * d * sizeof(float), hipMemcpyDeviceToHost));
+    if (solution) WOST_TRY(hipMemcpy(solution, ts.sol, m * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (dir_pdf) WOST_TRY(hipMemcpy(dir_pdf, ts.pdf, m * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal) WOST_TRY(hipMemcpy(normal, ts.nrm, m * d * sizeof(float), hipMemcpyDeviceToHost));
+    if (on_neumann) WOST_TRY(hipMemcpy(on_neumann, ts.onn, m, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 

@@ -205,12 +205,6 @@ struct DevBufs {
     }
 };
 
-#define VMM_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_error(WOST_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static int pick_device(int device)
 {
     int n_dev = 0;
@@ -236,18 +230,18 @@ int wost_vonmises_eval(int device, const float *kappa, const float *cos_theta, i
     if (rc != WOST_OK) return rc;
     DevBufs b;
     float *dk, *dc, *o0, *o1, *o2, *o3;
-    VMM_TRY(b.in(&dk, kappa, n));
-    VMM_TRY(b.in(&dc, cos_theta, n));
-    VMM_TRY(b.out(&o0, log_i0, n));
-    VMM_TRY(b.out(&o1, log_i1, n));
-    VMM_TRY(b.out(&o2, log_pdf, n));
-    VMM_TRY(b.out(&o3, dlogpdf_dkappa, n));
+    WOST_TRY(b.in(&dk, kappa, n));
+    WOST_TRY(b.in(&dc, cos_theta, n));
+    WOST_TRY(b.out(&o0, log_i0, n));
+    WOST_TRY(b.out(&o1, log_i1, n));
+    WOST_TRY(b.out(&o2, log_pdf, n));
+    WOST_TRY(b.out(&o3, dlogpdf_dkappa, n));
     hipLaunchKernelGGL(vonmises_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dk, dc, n, o0, o1, o2, o3);
-    VMM_TRY(hipGetLastError());
-    if (log_i0) VMM_TRY(hipMemcpy(log_i0, o0, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (log_i1) VMM_TRY(hipMemcpy(log_i1, o1, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (log_pdf) VMM_TRY(hipMemcpy(log_pdf, o2, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (dlogpdf_dkappa) VMM_TRY(hipMemcpy(dlogpdf_dkappa, o3, (size_t)n * 4, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    if (log_i0) WOST_TRY(hipMemcpy(log_i0, o0, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (log_i1) WOST_TRY(hipMemcpy(log_i1, o1, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (log_pdf) WOST_TRY(hipMemcpy(log_pdf, o2, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (dlogpdf_dkappa) WOST_TRY(hipMemcpy(dlogpdf_dkappa, o3, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -260,12 +254,12 @@ int wost_vonmises_sample(int device, const float *kappa, const uint64_t *seed, i
     DevBufs b;
     float *dk, *dt;
     uint64_t *ds;
-    VMM_TRY(b.in(&dk, kappa, n));
-    VMM_TRY(b.in(&ds, seed, n));
-    VMM_TRY(b.out(&dt, theta, (size_t)n * per_point));
+    WOST_TRY(b.in(&dk, kappa, n));
+    WOST_TRY(b.in(&ds, seed, n));
+    WOST_TRY(b.out(&dt, theta, (size_t)n * per_point));
     hipLaunchKernelGGL(vonmises_sample_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, dk, ds, n, per_point, dt);
-    VMM_TRY(hipGetLastError());
-    VMM_TRY(hipMemcpy(theta, dt, (size_t)n * per_point * 4, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpy(theta, dt, (size_t)n * per_point * 4, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -279,15 +273,15 @@ int wost_vmm_pdf_sample(int device, const float *raw, const float *wi, const uin
     DevBufs b;
     float *dr, *dw, *dp, *dd;
     uint64_t *ds;
-    VMM_TRY(b.in(&dr, raw, (size_t)n * 32));
-    VMM_TRY(b.in(&dw, wi, (size_t)n * 2));
-    VMM_TRY(b.in(&ds, seed, n));
-    VMM_TRY(b.out(&dp, pdf, n));
-    VMM_TRY(b.out(&dd, sample_dir, (size_t)n * 2));
+    WOST_TRY(b.in(&dr, raw, (size_t)n * 32));
+    WOST_TRY(b.in(&dw, wi, (size_t)n * 2));
+    WOST_TRY(b.in(&ds, seed, n));
+    WOST_TRY(b.out(&dp, pdf, n));
+    WOST_TRY(b.out(&dd, sample_dir, (size_t)n * 2));
     hipLaunchKernelGGL(vmm_pdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dr, dw, ds, n, dp, dd);
-    VMM_TRY(hipGetLastError());
-    if (pdf) VMM_TRY(hipMemcpy(pdf, dp, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (sample_dir) VMM_TRY(hipMemcpy(sample_dir, dd, (size_t)n * 8, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    if (pdf) WOST_TRY(hipMemcpy(pdf, dp, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (sample_dir) WOST_TRY(hipMemcpy(sample_dir, dd, (size_t)n * 8, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -303,19 +297,19 @@ int wost_vmm_loss_gradients(int device, const float *raw, const float *dir, cons
     DevBufs b;
     float *dr, *dd, *dli, *dp, *dn, *dg, *dl;
     uint8_t *don;
-    VMM_TRY(b.in(&dr, raw, (size_t)n * 33));
-    VMM_TRY(b.in(&dd, dir, (size_t)n * 2));
-    VMM_TRY(b.in(&dli, li, n));
-    VMM_TRY(b.in(&dp, dir_pdf, n));
-    VMM_TRY(b.in(&don, on_neumann, n));
-    VMM_TRY(b.in(&dn, normal, (size_t)n * 2));
-    VMM_TRY(b.out(&dg, dl_draw, (size_t)n * 33));
-    VMM_TRY(b.out(&dl, likelihood, n));
+    WOST_TRY(b.in(&dr, raw, (size_t)n * 33));
+    WOST_TRY(b.in(&dd, dir, (size_t)n * 2));
+    WOST_TRY(b.in(&dli, li, n));
+    WOST_TRY(b.in(&dp, dir_pdf, n));
+    WOST_TRY(b.in(&don, on_neumann, n));
+    WOST_TRY(b.in(&dn, normal, (size_t)n * 2));
+    WOST_TRY(b.out(&dg, dl_draw, (size_t)n * 33));
+    WOST_TRY(b.out(&dl, likelihood, n));
     hipLaunchKernelGGL(vmm_loss_gradients_kernel, dim3((n + kLossBlock - 1) / kLossBlock), dim3(kLossBlock), 0, 0, dr, dd, dli, dp, don, dn, n,
                        loss_scale, dg, dl);
-    VMM_TRY(hipGetLastError());
-    VMM_TRY(hipMemcpy(dl_draw, dg, (size_t)n * 33 * 4, hipMemcpyDeviceToHost));
-    if (likelihood) VMM_TRY(hipMemcpy(likelihood, dl, (size_t)n * 4, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpy(dl_draw, dg, (size_t)n * 33 * 4, hipMemcpyDeviceToHost));
+    if (likelihood) WOST_TRY(hipMemcpy(likelihood, dl, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 

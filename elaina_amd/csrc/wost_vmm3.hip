@@ -146,15 +146,15 @@ int wost3_vmf_eval(int device, const float *kappa, const float *cos_theta, int32
 {
     if (!kappa || !cos_theta || !pdf || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(device));
+    Scratch s;
     float *d_k, *d_c, *d_p;
-    W3_TRY(s.alloc(&d_k, n)); W3_TRY(s.alloc(&d_c, n)); W3_TRY(s.alloc(&d_p, n));
-    W3_TRY(hipMemcpy(d_k, kappa, (size_t)n * 4, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_c, cos_theta, (size_t)n * 4, hipMemcpyHostToDevice));
+    WOST_TRY(s.alloc(&d_k, n)); WOST_TRY(s.alloc(&d_c, n)); WOST_TRY(s.alloc(&d_p, n));
+    WOST_TRY(hipMemcpy(d_k, kappa, (size_t)n * 4, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_c, cos_theta, (size_t)n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(vmf_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_k, d_c, n, d_p);
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpy(pdf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpy(pdf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -162,17 +162,17 @@ int wost3_vmf_sample(int device, const float *kappa, const float *mu, const uint
 {
     if (!kappa || !mu || !seed || !dirs || n < 0 || per_point < 1) return set_error(WOST_ERR_INVALID, "null argument");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(device));
+    Scratch s;
     float *d_k, *d_m, *d_o;
     uint64_t *d_s;
-    W3_TRY(s.alloc(&d_k, n)); W3_TRY(s.alloc(&d_m, (size_t)n * 3)); W3_TRY(s.alloc(&d_s, n)); W3_TRY(s.alloc(&d_o, (size_t)n * per_point * 3));
-    W3_TRY(hipMemcpy(d_k, kappa, (size_t)n * 4, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_m, mu, (size_t)n * 12, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_s, seed, (size_t)n * 8, hipMemcpyHostToDevice));
+    WOST_TRY(s.alloc(&d_k, n)); WOST_TRY(s.alloc(&d_m, (size_t)n * 3)); WOST_TRY(s.alloc(&d_s, n)); WOST_TRY(s.alloc(&d_o, (size_t)n * per_point * 3));
+    WOST_TRY(hipMemcpy(d_k, kappa, (size_t)n * 4, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_m, mu, (size_t)n * 12, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_s, seed, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(vmf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_k, d_m, d_s, n, per_point, d_o);
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpy(dirs, d_o, (size_t)n * per_point * 12, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpy(dirs, d_o, (size_t)n * per_point * 12, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -180,22 +180,22 @@ int wost3_vmm_pdf_sample(int device, const float *raw, const float *wi, const ui
 {
     if (!raw || !wi || (sample_dir && !seed) || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(device));
+    Scratch s;
     float *d_r, *d_w, *d_p = nullptr, *d_d = nullptr;
     uint64_t *d_s = nullptr;
-    W3_TRY(s.alloc(&d_r, (size_t)n * 40)); W3_TRY(s.alloc(&d_w, (size_t)n * 3));
-    W3_TRY(hipMemcpy(d_r, raw, (size_t)n * 160, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_w, wi, (size_t)n * 12, hipMemcpyHostToDevice));
-    if (pdf) W3_TRY(s.alloc(&d_p, n));
+    WOST_TRY(s.alloc(&d_r, (size_t)n * 40)); WOST_TRY(s.alloc(&d_w, (size_t)n * 3));
+    WOST_TRY(hipMemcpy(d_r, raw, (size_t)n * 160, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_w, wi, (size_t)n * 12, hipMemcpyHostToDevice));
+    if (pdf) WOST_TRY(s.alloc(&d_p, n));
     if (sample_dir) {
-        W3_TRY(s.alloc(&d_d, (size_t)n * 3)); W3_TRY(s.alloc(&d_s, n));
-        W3_TRY(hipMemcpy(d_s, seed, (size_t)n * 8, hipMemcpyHostToDevice));
+        WOST_TRY(s.alloc(&d_d, (size_t)n * 3)); WOST_TRY(s.alloc(&d_s, n));
+        WOST_TRY(hipMemcpy(d_s, seed, (size_t)n * 8, hipMemcpyHostToDevice));
     }
     hipLaunchKernelGGL(vmm3_pdf_sample_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_r, d_w, d_s, n, d_p, d_d);
-    W3_TRY(hipGetLastError());
-    if (pdf) W3_TRY(hipMemcpy(pdf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (sample_dir) W3_TRY(hipMemcpy(sample_dir, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    if (pdf) WOST_TRY(hipMemcpy(pdf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (sample_dir) WOST_TRY(hipMemcpy(sample_dir, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 
@@ -204,26 +204,26 @@ int wost3_vmm_loss_gradients(int device, const float *raw, const float *dir, con
 {
     if (!raw || !dir || !li || !dir_pdf || !dl_draw || (on_neumann && !normal) || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
     if (n == 0) return WOST_OK;
-    W3_TRY(hipSetDevice(device));
-    Scratch3 s;
+    WOST_TRY(hipSetDevice(device));
+    Scratch s;
     float *d_r, *d_d, *d_l, *d_p, *d_n = nullptr, *d_g, *d_k = nullptr;
     unsigned char *d_o = nullptr;
-    W3_TRY(s.alloc(&d_r, (size_t)n * 41)); W3_TRY(s.alloc(&d_d, (size_t)n * 3)); W3_TRY(s.alloc(&d_l, n)); W3_TRY(s.alloc(&d_p, n));
-    W3_TRY(s.alloc(&d_g, (size_t)n * 41));
-    W3_TRY(hipMemcpy(d_r, raw, (size_t)n * 164, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_l, li, (size_t)n * 4, hipMemcpyHostToDevice));
-    W3_TRY(hipMemcpy(d_p, dir_pdf, (size_t)n * 4, hipMemcpyHostToDevice));
+    WOST_TRY(s.alloc(&d_r, (size_t)n * 41)); WOST_TRY(s.alloc(&d_d, (size_t)n * 3)); WOST_TRY(s.alloc(&d_l, n)); WOST_TRY(s.alloc(&d_p, n));
+    WOST_TRY(s.alloc(&d_g, (size_t)n * 41));
+    WOST_TRY(hipMemcpy(d_r, raw, (size_t)n * 164, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_l, li, (size_t)n * 4, hipMemcpyHostToDevice));
+    WOST_TRY(hipMemcpy(d_p, dir_pdf, (size_t)n * 4, hipMemcpyHostToDevice));
     if (on_neumann) {
-        W3_TRY(s.alloc(&d_o, n)); W3_TRY(s.alloc(&d_n, (size_t)n * 3));
-        W3_TRY(hipMemcpy(d_o, on_neumann, (size_t)n, hipMemcpyHostToDevice));
-        W3_TRY(hipMemcpy(d_n, normal, (size_t)n * 12, hipMemcpyHostToDevice));
+        WOST_TRY(s.alloc(&d_o, n)); WOST_TRY(s.alloc(&d_n, (size_t)n * 3));
+        WOST_TRY(hipMemcpy(d_o, on_neumann, (size_t)n, hipMemcpyHostToDevice));
+        WOST_TRY(hipMemcpy(d_n, normal, (size_t)n * 12, hipMemcpyHostToDevice));
     }
-    if (likelihood) W3_TRY(s.alloc(&d_k, n));
+    if (likelihood) WOST_TRY(s.alloc(&d_k, n));
     hipLaunchKernelGGL(vmm3_loss_gradients_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_r, d_d, d_l, d_p, d_o, d_n, n, loss_scale, d_g, d_k);
-    W3_TRY(hipGetLastError());
-    W3_TRY(hipMemcpy(dl_draw, d_g, (size_t)n * 164, hipMemcpyDeviceToHost));
-    if (likelihood) W3_TRY(hipMemcpy(likelihood, d_k, (size_t)n * 4, hipMemcpyDeviceToHost));
+    WOST_TRY(hipGetLastError());
+    WOST_TRY(hipMemcpy(dl_draw, d_g, (size_t)n * 164, hipMemcpyDeviceToHost));
+    if (likelihood) WOST_TRY(hipMemcpy(likelihood, d_k, (size_t)n * 4, hipMemcpyDeviceToHost));
     return WOST_OK;
 }
 

@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .carried import CarriedSolves
-from .capi import MeshDesc, SceneDesc, Settings, Stats, _check, _fp, _ip
+from .capi import MeshDesc, SceneDesc, Settings, _check, _fp, _ip
+from .uniform import UniformCalls
 
 
 class UniformIntegratorSettings:
@@ -67,8 +67,8 @@ def scene_desc(keep, problem, w, h):
     return sc
 
 
-class UniformIntegrator(CarriedSolves):
-    _prefix = "wost_"      # (CarriedSolves: solve_more_where, carried, solve_adaptive)
+class UniformIntegrator(UniformCalls):
+    _prefix, _dim = "wost_", 2      # (UniformCalls: the solves, the carried solve, the batch queries, close)
     VectorType = tuple
 
     def __init__(self, problem, settings, device=0):
@@ -85,78 +85,6 @@ class UniformIntegrator(CarriedSolves):
         self.last_stats = None
         self.solution = None
 
-    # -- reference surface ------------------------------------------------------------------
-    def solve(self, pixel_begin=0, pixel_end=None):
-        """returns wall milliseconds like the reference; the field is in self.solution"""
-        if pixel_end is None:
-            pixel_end = self.n_pixels
-        field = np.zeros((pixel_end - pixel_begin, 3), dtype=np.float32)
-        st = Stats()
-        _check(self.lib.wost_solve(self._handle, pixel_begin, pixel_end, _fp(field), C.byref(st)), "wost_solve")
-        self.solution = field
-        self.last_stats = st.as_dict()
-        return int(st.solve_ms)
-
-    def solve_sharded(self, shard_index, shard_count, field_dev_ptr, stream_ptr=None):
-        """field_dev_ptr: device pointer (int) to a zero-filled width*height*3 float buffer"""
-        st = Stats()
-        _check(self.lib.wost_solve_sharded(self._handle, shard_index, shard_count, C.c_void_p(field_dev_ptr),
-                                           C.c_void_p(stream_ptr or 0), C.byref(st)), "wost_solve_sharded")
-        self.last_stats = st.as_dict()
-        return self.last_stats
-
-    def solve_points(self, points, seed_base=0, seed_width=None):
-        """the solve at the caller's evaluation points ([n, 2] floats) instead of the frame's pixels (wost_solve_points):
-        point i runs on the random stream of pixel seed_base + i in a frame seed_width wide (default: the frame's width);
-        returns the (n, 3) float32 field"""
-        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
-        field = np.zeros((len(p), 3), dtype=np.float32)
-        st = Stats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost_solve_points(self._handle, _fp(p), len(p), int(seed_base), int(width), _fp(field), C.byref(st)),
-               "wost_solve_points")
-        self.last_stats = st.as_dict()
-        return field
-
-    def solve_points_dev(self, points_ptr, n, field_ptr, stream_ptr=None, seed_base=0, seed_width=None):
-        """the same on device pointers (ints): n * 2 floats of points, n * 3 floats of field, on the caller's stream"""
-        st = Stats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost_solve_points_dev(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), int(width), C.c_void_p(field_ptr),
-                                               C.c_void_p(stream_ptr or 0), C.byref(st)), "wost_solve_points_dev")
-        self.last_stats = st.as_dict()
-        return self.last_stats
-
-    # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
-    def solve_more(self, more_spp):
-        """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- wost_solve's at
-        spp = spp_done, bit for bit -- is in self.solution; returns wall milliseconds"""
-        field = np.zeros((self.n_pixels, 3), dtype=np.float32)
-        st = Stats()
-        _check(self.lib.wost_solve_more(self._handle, int(more_spp), _fp(field), C.byref(st)), "wost_solve_more")
-        self.solution = field
-        self.last_stats = st.as_dict()
-        return int(st.solve_ms)
-
-    def solve_more_sharded(self, shard_index, shard_count, more_spp, field_dev_ptr, stream_ptr=None):
-        """the same for one shard (as solve_sharded): the carried solve belongs to the shard of its first call"""
-        st = Stats()
-        _check(self.lib.wost_solve_more_sharded(self._handle, shard_index, shard_count, int(more_spp), C.c_void_p(field_dev_ptr),
-                                                C.c_void_p(stream_ptr or 0), C.byref(st)), "wost_solve_more_sharded")
-        self.last_stats = st.as_dict()
-        return self.last_stats
-
-    def restart(self):
-        """forget the carried solve: spp_done = 0, no shard"""
-        _check(self.lib.wost_solve_restart(self._handle), "wost_solve_restart")
-
-    @property
-    def spp_done(self):
-        """samples per pixel of the carried solve so far"""
-        n = C.c_int32(0)
-        _check(self.lib.wost_solve_progress(self._handle, C.byref(n)), "wost_solve_progress")
-        return n.value
-
     def renderDirichletSDF(self):
         out = np.zeros(self.n_pixels, dtype=np.float32)
         _check(self.lib.wost_render_sdf(self._handle, capi.MESH_DIRICHLET, _fp(out)), "wost_render_sdf")
@@ -171,42 +99,6 @@ class UniformIntegrator(CarriedSolves):
         out = np.zeros((self.n_pixels, 3), dtype=np.float32)
         _check(self.lib.wost_render_source(self._handle, _fp(out)), "wost_render_source")
         return out
-
-    def queryNetwork(self, p):
-        raise NotImplementedError("uniform integrator has no network (reference integrator.cu:661-664)")
-
-    # -- lbvh query call sites, batched ---------------------------------------------------------
-    def closest_point(self, pts, which=capi.MESH_DIRICHLET):
-        p = np.ascontiguousarray(pts, dtype=np.float32)
-        n = len(p)
-        idx = np.zeros(n, dtype=np.int32)
-        dist = np.zeros(n, dtype=np.float32)
-        uv = np.zeros(n, dtype=np.float32)
-        side = np.zeros(n, dtype=np.int32)
-        _check(self.lib.wost_closest_point(self._handle, which, _fp(p), n, _ip(idx), _fp(dist), _fp(uv), _ip(side)),
-               "wost_closest_point")
-        return idx, dist, uv, side
-
-    def closest_silhouette(self, pts, rmax=None, which=capi.MESH_NEUMANN):
-        p = np.ascontiguousarray(pts, dtype=np.float32)
-        n = len(p)
-        out = np.zeros(n, dtype=np.float32)
-        r = None if rmax is None else np.ascontiguousarray(rmax, dtype=np.float32)
-        _check(self.lib.wost_closest_silhouette(self._handle, which, _fp(p), _fp(r) if r is not None else None, n,
-                                                _fp(out)), "wost_closest_silhouette")
-        return out
-
-    def ray_intersect(self, origins, dirs, tmax, which=capi.MESH_NEUMANN):
-        o = np.ascontiguousarray(origins, dtype=np.float32)
-        d = np.ascontiguousarray(dirs, dtype=np.float32)
-        t = np.ascontiguousarray(tmax, dtype=np.float32)
-        n = len(o)
-        hit = np.zeros(n, dtype=np.int32)
-        tt = np.zeros(n, dtype=np.float32)
-        idx = np.zeros(n, dtype=np.int32)
-        _check(self.lib.wost_ray_intersect(self._handle, which, _fp(o), _fp(d), _fp(t), n, _ip(hit), _fp(tt),
-                                           _ip(idx)), "wost_ray_intersect")
-        return hit, tt, idx
 
     def set_option(self, key, value):
         _check(self.lib.wost_set_option(self._handle, key.encode(), float(value)), "wost_set_option")
@@ -227,17 +119,6 @@ class UniformIntegrator(CarriedSolves):
                 prev = d["walk_steps_done"]
             out.append(d)
         return out
-
-    def close(self):
-        if self._handle:
-            self.lib.wost_destroy(self._handle)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MESH_BUILD_ARRAYS2 = ("nodes", "cones", "segA", "segInv", "segOrig", "segCol", "segVerts", "flat", "flatCol", "sil", "silN", "scanBox", "scanHl", "scanId",

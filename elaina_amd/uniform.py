@@ -1,0 +1,181 @@
+"""What UniformIntegrator and UniformIntegrator3 have in common: every method whose entry points exist as wost_* and wost3_*
+(include/wost.h) with the same arguments -- the frame solve, the point solves, the carried solve with its selections and
+adaptive variant, the batch queries.  The two classes differ in the prefix of the entry points and in the columns of a point."""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .capi import Adaptive, Stats, _check, _fp, _ip
+
+
+class UniformCalls:
+    """base of an integrator with .lib, ._handle, .n_pixels, .settings, ._prefix ("wost_" or "wost3_") and ._dim (2 or 3)"""
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name), self._prefix + name
+
+    def _host_solve(self, entry, n, *args):
+        """a host entry point whose last arguments are an (n, 3) field and the stats -> (field, stats)"""
+        fn, name = self._fn(entry)
+        field = np.zeros((n, 3), dtype=np.float32)
+        st = Stats()
+        _check(fn(self._handle, *args, _fp(field), C.byref(st)), name)
+        self.last_stats = st.as_dict()
+        return field, st
+
+    def _dev_solve(self, entry, *args):
+        """an entry point on device pointers whose last argument is the stats -> the stats as a dict"""
+        fn, name = self._fn(entry)
+        st = Stats()
+        _check(fn(self._handle, *args, C.byref(st)), name)
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
+    def _points(self, a):
+        """an array of points as the entry points read it; the 2-D queries take the caller's array as it is"""
+        p = np.ascontiguousarray(a, dtype=np.float32)
+        return p if self._dim == 2 else p.reshape(-1, 3)
+
+    def _seed_width(self, seed_width):
+        return int(self.settings.frameSize[0] if seed_width is None else seed_width)
+
+    # -- reference surface ------------------------------------------------------------------
+    def solve(self, pixel_begin=0, pixel_end=None):
+        """returns wall milliseconds like the reference; the field is in self.solution"""
+        if pixel_end is None:
+            pixel_end = self.n_pixels
+        self.solution, st = self._host_solve("solve", pixel_end - pixel_begin, pixel_begin, pixel_end)
+        return int(st.solve_ms)
+
+    def solve_sharded(self, shard_index, shard_count, field_dev_ptr, stream_ptr=None):
+        """field_dev_ptr: device pointer (int) to a zero-filled width*height*3 float buffer"""
+        return self._dev_solve("solve_sharded", shard_index, shard_count, C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    def solve_points(self, points, seed_base=0, seed_width=None):
+        """the solve at the caller's evaluation points ([n, dim] floats) instead of the frame's pixels (wost_solve_points,
+        wost3_solve_points): point i runs on the random stream of pixel seed_base + i in a frame seed_width wide (default: the
+        frame's width); returns the (n, 3) float32 field"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        return self._host_solve("solve_points", len(p), _fp(p), len(p), int(seed_base), self._seed_width(seed_width))[0]
+
+    def solve_points_dev(self, points_ptr, n, field_ptr, stream_ptr=None, seed_base=0, seed_width=None):
+        """the same on device pointers (ints): n * dim floats of points, n * 3 floats of field, on the caller's stream"""
+        return self._dev_solve("solve_points_dev", C.c_void_p(points_ptr), int(n), int(seed_base), self._seed_width(seed_width),
+                               C.c_void_p(field_ptr), C.c_void_p(stream_ptr or 0))
+
+    # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
+    def solve_more(self, more_spp):
+        """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at
+        spp = spp_done, bit for bit -- is in self.solution; returns wall milliseconds"""
+        self.solution, st = self._host_solve("solve_more", self.n_pixels, int(more_spp))
+        return int(st.solve_ms)
+
+    def solve_more_sharded(self, shard_index, shard_count, more_spp, field_dev_ptr, stream_ptr=None):
+        """the same for one shard (as solve_sharded): the carried solve belongs to the shard of its first call"""
+        return self._dev_solve("solve_more_sharded", shard_index, shard_count, int(more_spp), C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    def restart(self):
+        """forget the carried solve: spp_done = 0, no shard"""
+        fn, name = self._fn("solve_restart")
+        _check(fn(self._handle), name)
+
+    @property
+    def spp_done(self):
+        """samples per pixel of the carried solve so far"""
+        fn, name = self._fn("solve_progress")
+        n = C.c_int32(0)
+        _check(fn(self._handle, C.byref(n)), name)
+        return n.value
+
+    def solve_more_where(self, more_spp, select=None):
+        """more_spp samples on the pixels whose entry in select (n_pixels values, nonzero = continue) is set; None: every
+        pixel, which is solve_more.  Every pixel's field at its own count is in self.solution; returns wall milliseconds"""
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, dtype=np.uint8)
+            if sel.size != self.n_pixels:
+                raise ValueError("select has %d entries, the frame %d pixels" % (sel.size, self.n_pixels))
+        ptr = sel.ctypes.data_as(C.POINTER(C.c_uint8)) if sel is not None else None
+        self.solution, st = self._host_solve("solve_more_where", self.n_pixels, int(more_spp), ptr)
+        return int(st.solve_ms)
+
+    def solve_more_where_sharded(self, shard_index, shard_count, more_spp, select_dev_ptr, field_dev_ptr, stream_ptr=None):
+        """the same for one shard on device pointers (ints): n_pixels bytes of selection (0: every pixel), a zero-filled field"""
+        return self._dev_solve("solve_more_where_sharded", shard_index, shard_count, int(more_spp), C.c_void_p(select_dev_ptr or 0),
+                               C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    def carried(self):
+        """the per-pixel state of the carried solve: {"spp": samples done, "batches": calls that walked the pixel, "sum": the
+        raw sums (n, 3), "stderr": the batch-means standard error of sum / spp (n, 3), +inf below two batches}"""
+        fn, name = self._fn("solve_carried")
+        out = {"spp": np.zeros(self.n_pixels, np.int32), "batches": np.zeros(self.n_pixels, np.int32),
+               "sum": np.zeros((self.n_pixels, 3), np.float32), "stderr": np.zeros((self.n_pixels, 3), np.float32)}
+        _check(fn(self._handle, _ip(out["spp"]), _ip(out["batches"]), _fp(out["sum"]), _fp(out["stderr"])), name)
+        return out
+
+    def _adaptive(self, batch_spp, max_spp, abs_tol, rel_tol, min_batches):
+        return Adaptive(int(batch_spp), int(min_batches), int(max_spp), float(abs_tol), float(rel_tol))
+
+    def solve_adaptive(self, batch_spp, max_spp, abs_tol=0.0, rel_tol=0.0, min_batches=4):
+        """batches of batch_spp samples on the pixels whose standard error is above max(abs_tol, rel_tol * |mean|) in some
+        channel (or that have fewer than min_batches batches) and that have room under max_spp, until none is left; starts from
+        the carried solve as it stands.  The field is in self.solution, the standard errors in self.stderr, the per-pixel
+        sample counts in self.spp_map; returns wall milliseconds"""
+        fn, name = self._fn("solve_adaptive")
+        field = np.zeros((self.n_pixels, 3), dtype=np.float32)
+        se = np.zeros((self.n_pixels, 3), dtype=np.float32)
+        spp = np.zeros(self.n_pixels, dtype=np.int32)
+        st = Stats()
+        a = self._adaptive(batch_spp, max_spp, abs_tol, rel_tol, min_batches)
+        _check(fn(self._handle, C.byref(a), _fp(field), _fp(se), _ip(spp), C.byref(st)), name)
+        self.solution, self.stderr, self.spp_map = field, se, spp
+        self.last_stats = st.as_dict()
+        return int(st.solve_ms)
+
+    def solve_adaptive_sharded(self, shard_index, shard_count, batch_spp, max_spp, field_dev_ptr, stream_ptr=None, abs_tol=0.0, rel_tol=0.0,
+                               min_batches=4):
+        """the same for one shard into a zero-filled device field"""
+        a = self._adaptive(batch_spp, max_spp, abs_tol, rel_tol, min_batches)
+        return self._dev_solve("solve_adaptive_sharded", shard_index, shard_count, C.byref(a), C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    # -- lbvh query call sites, batched ---------------------------------------------------------
+    def closest_point(self, pts, which=capi.MESH_DIRICHLET):
+        fn, name = self._fn("closest_point")
+        p = self._points(pts)
+        n = len(p)
+        idx, dist, side = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        uv = np.zeros(n if self._dim == 2 else (n, 2), np.float32)      # a segment's parameter / a triangle's barycentrics
+        _check(fn(self._handle, which, _fp(p), n, _ip(idx), _fp(dist), _fp(uv), _ip(side)), name)
+        return idx, dist, uv, side
+
+    def closest_silhouette(self, pts, rmax=None, which=capi.MESH_NEUMANN):
+        fn, name = self._fn("closest_silhouette")
+        p = self._points(pts)
+        out = np.zeros(len(p), np.float32)
+        r = None if rmax is None else np.ascontiguousarray(rmax, dtype=np.float32)
+        _check(fn(self._handle, which, _fp(p), _fp(r) if r is not None else None, len(p), _fp(out)), name)
+        return out
+
+    def ray_intersect(self, origins, dirs, tmax, which=capi.MESH_NEUMANN):
+        fn, name = self._fn("ray_intersect")
+        o, d = self._points(origins), self._points(dirs)
+        t = np.ascontiguousarray(tmax, dtype=np.float32)
+        n = len(o)
+        hit, tt, idx = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        _check(fn(self._handle, which, _fp(o), _fp(d), _fp(t), n, _ip(hit), _fp(tt), _ip(idx)), name)
+        return hit, tt, idx
+
+    def queryNetwork(self, p):
+        raise NotImplementedError("uniform integrator has no network (reference integrator.cu:661-664)")
+
+    def close(self):
+        if self._handle:
+            self._fn("destroy")[0](self._handle)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
