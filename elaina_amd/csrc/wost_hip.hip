@@ -121,6 +121,9 @@ struct RoundParams {
     uint64_t *carry_rng;
     float *carry_sum;
     int32_t carry_total;
+    // the chained start (wost_set_option "chain_start"): a lane whose walk is absorbed takes the depth-0 step of its pixel's
+    // next sample in the same step trip (step_finish); 0 = that step waits for the wave's next step trip
+    int32_t chain;
 };
 
 struct InitParams {
@@ -309,16 +312,25 @@ struct LaneStats {
 // of lbvh nearest() for L.px,L.py (ignored when there is no Dirichlet boundary).
 // Returns STEP_* status bits (STEP_ENDED when the walk ended in this step); the caller keeps
 // the statistics, so no counter is ever touched inside a divergent branch.
+// `chain` (the chained start): a walk that is absorbed here does not leave the function.  The next sample of the pixel starts
+// at the evaluation point, whose closest point is cached (d0_d2, d0_slot), so its depth-0 step needs no query: the lane takes
+// that sample's state and falls through the rest of the function as its depth-0 step, beside the lanes of the wave that are
+// in the middle of a walk -- instead of waiting, masked off, for the wave's next step trip to do the same arithmetic there
+// (STEP_ABSORBED | STEP_CHAINED, and STEP_ENDED only if the chained step itself ends its walk).  Not for the pixel's last
+// sample, and not where the evaluation point lies inside the shell (or its distance is a NaN): that depth-0 step absorbs
+// again and stays on the old path; with r0 >= eps the in-shell test that the chained step skips is false whatever uv is.
 // status bits returned by step_finish
-enum : uint32_t { STEP_ENDED = 1u, STEP_ABSORBED = 2u, STEP_TRUNCATED = 4u, STEP_NEUMANN_HIT = 8u };
+enum : uint32_t { STEP_ENDED = 1u, STEP_ABSORBED = 2u, STEP_TRUNCATED = 4u, STEP_NEUMANN_HIT = 8u, STEP_CHAINED = 16u };
 
 template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE = false, class STK = LdsColumn>
 __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh &nm, const DevSettings &st, Lane &L,
-                                                const Closest cp, const STK &stk, const DevSource &src = DevSource{})
+                                                const Closest cp, const STK &stk, const DevSource &src = DevSource{},
+                                                const bool chain = false)
 {
     const bool has_d = dm.n_segs > 0, has_n = nm.n_segs > 0;
     const float eps = st.eps;
-    const float px = L.px, py = L.py;
+    float px = L.px, py = L.py;
+    uint32_t chained = 0u;
 
     // ---- separateEvaluationPoint -------------------------------------------------------
     float R_D = WOST_INF;
@@ -339,14 +351,23 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
             r *= st.dirichlet_intensity; g *= st.dirichlet_intensity; b *= st.dirichlet_intensity;
             r *= L.thp; g *= L.thp; b *= L.thp;
             L.sr = r + L.sr; L.sg = g + L.sg; L.sb = b + L.sb;
-            return STEP_ENDED | STEP_ABSORBED;
+            const float r0 = sqrtf(L.d0_d2);
+            if (!(chain && L.sample + 1u < (uint32_t)st.spp && r0 >= eps)) return STEP_ENDED | STEP_ABSORBED;
+            // ---- the chained start: generateEvaluationPoints for the next sample, and its depth-0 step from here ----
+            L.sample++;
+            px = L.x0; py = L.y0;
+            L.depth = 0; L.on_n = false; L.nx = 0.0f; L.ny = 0.0f;
+            L.thp = 1.0f;
+            L.hint = L.d0_slot;
+            R_D = r0;
+            chained = STEP_ABSORBED | STEP_CHAINED;
         }
     }
     float R_N = WOST_INF;
     if (has_n) R_N = closest_silhouette<NEUMANN_TREE>(nm, px, py, R_D, stk);
     float R_B = fmaxf(WOST_R_B_FLOOR, fminf(R_D, R_N));
     R_B *= WOST_R_B_SHRINK;
-    if (isinf(R_B)) return STEP_ENDED;
+    if (isinf(R_B)) return STEP_ENDED | chained;
 
     // ---- sampleSource (problems with a source term only) ------------------------------------
     if (SOURCE) {
@@ -379,7 +400,7 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
     L.on_n = hit; L.nx = hnx; L.ny = hny;
     L.depth++;
     const bool truncated = L.depth == (uint32_t)st.max_depth;
-    return (truncated ? (STEP_ENDED | STEP_TRUNCATED) : 0u) | (hit_count ? STEP_NEUMANN_HIT : 0u);
+    return (truncated ? (STEP_ENDED | STEP_TRUNCATED) : 0u) | (hit_count ? STEP_NEUMANN_HIT : 0u) | chained;
 }
 
 // step_finish for ALL lanes of a wave at once, `stepping` marking those that take the step: the same statements in the same
@@ -741,10 +762,18 @@ __device__ __forceinline__ void walk_round_body(const RoundParams &P)
             if (mode == MODE_WAIT && !fresh) {
                 {
                     const uint32_t status = (NEUMANN_TREE && P.coop) ? wave_status
-                                                                     : step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src);
+                                                                     : step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src, P.chain && budget > 1);
                     const bool ended = (status & STEP_ENDED) != 0u;
                     S.b += ((status >> 1) & 1u) | (((status >> 2) & 1u) << 16);
                     S.c += (status >> 3) & 1u;
+                    // a chained start is two walk steps: the absorbed one, counted when its query began, and the next sample's
+                    // depth-0 step -- one step and one walk started, and a unit of the budget of its own.  (budget > 1 above:
+                    // the lane stays within steps_per_round and its 16-bit counters, a round of one step takes the old path, a
+                    // wave that has stopped -- budget 0 -- starts nothing.)
+                    if (status & STEP_CHAINED) {
+                        S.a += 0x10001u;
+                        --budget;
+                    }
                     if (ended) {
                         // next sample of this pixel starts right away (generateEvaluationPoints,
                         // reference integrator.cu:90-99 + workqueue.h:99-110)
@@ -814,7 +843,8 @@ __device__ __forceinline__ void walk_round_body(const RoundParams &P)
                 // queue is far from dry -- R unread slots last at least R >> dry_shift steps -- and every dry_cadence steps at the
                 // end.  The steps are counted where they are counted already: every lane gets the number of steps to the next look
                 // as its budget above kLookBase, and the first lane to use them up (a budget in 1 .. kLookBase; a wave that has
-                // stopped has none above 0) makes the wave look.
+                // stopped has none above 0) makes the wave look.  (A chained start takes two units in one trip: from kLookBase + 1
+                // the budget lands on kLookBase - 1, still inside 1 .. kLookBase, so no look is skipped.)
                 const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(P.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 if (cur >= n_in) WOST_DRAIN_STOP();
                 budget = cur >= n_in ? 0 : kLookBase + (int)max((uint32_t)P.dry_cadence, (n_in - cur) >> P.dry_shift);
@@ -975,10 +1005,14 @@ __device__ __forceinline__ void walk_quad_body(const RoundParams &P)
             ++step_trips;
             if (mode == MODE_WAIT && !fresh) {       // (beside the next branch, not around it: see walk_round_kernel)
                 {
-                    const uint32_t status = step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src);
+                    const uint32_t status = step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src, P.chain && budget > 1);
                     const bool ended = (status & STEP_ENDED) != 0u;
                     S.b += ((status >> 1) & 1u) | (((status >> 2) & 1u) << 16);
                     S.c += (status >> 3) & 1u;
+                    if (status & STEP_CHAINED) {       // the next sample's depth-0 step as well (see walk_round_kernel)
+                        S.a += 0x10001u;
+                        --budget;
+                    }
                     if (ended) {
                         L.sample++;
                         L.px = L.x0; L.py = L.y0;
@@ -1376,6 +1410,8 @@ struct wost_context {
     int dry_stop = 1;      // the persistent launch: once its input queue is dry every wave stops at its next look at the cursor (1), or only a
                            //   wave that needs a refill does (0: the rule until this option existed; comparison runs)
     int dry_cadence = 4;   // ... a wave looks again after dry_cadence walk steps of its busiest lane (a power of two), less often while the queue is far from dry
+    int chain_start = 1;   // the round and quad kernels: a lane whose walk is absorbed takes the depth-0 step of its pixel's next sample in the
+                           //   same step trip (1), or in the wave's next one (0: the rule until this option existed; comparison runs)
     int resident_blocks = 0;  // blocks of a one-launch / persistent launch; 0 = as many as the chip holds (tests: a few blocks drain a small frame)
     // what a persistent launch hands over (run_solve): the pixels expected to need `long_steps` walk steps or more run to their end at
     // once, four lanes to a walker, on a stream of higher priority beside the rounds of the others (0 = none do); the first round
@@ -1723,6 +1759,9 @@ int wost_set_option(wost_handle h, const char *key, double value)
         const int v = (int)value;
         if (value != v || v < 1 || v > 1024 || (v & (v - 1))) return set_error(WOST_ERR_INVALID, "dry_cadence must be a power of two in 1..1024");
         h->dry_cadence = v;
+    } else if (k == "chain_start") {
+        if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "chain_start must be 0 or 1");
+        h->chain_start = (int)value;
     } else if (k == "resident_blocks") {
         if (value < 0 || value > 65535) return set_error(WOST_ERR_INVALID, "resident_blocks must be in 0..65535 (0 = what the chip holds)");
         h->resident_blocks = (int)value;
@@ -1826,6 +1865,7 @@ static RoundParams base_params(const wost_context *c, const LaunchGeometry &g, f
     // otherwise (shorter rounds only added launches: 128^2 at 1 spp 0.95 -> 1.39 ms with 8-step rounds)
     rp.steps_per_round = c->steps_per_round > 0 ? c->steps_per_round : 256;
     rp.stack_stride = g.bs;
+    rp.chain = c->chain_start;
     set_schedule(c, g.ntree, false, rp);
     rp.coop = g.coop; rp.pool_cap = g.pool_cap; rp.pool_offset = (int32_t)(g.lds / sizeof(uint32_t)); rp.ray_slot_trigger = c->ray_slot_trigger;
     return rp;

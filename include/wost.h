@@ -503,7 +503,10 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
  * one-launch path of few samples per pixel takes the pixels longest-first too; "resident_blocks": workgroups of those launches
  * (0 = what the chip holds); "dry_stop" (1): once the input queue of the persistent launch is dry every wave stops at its next
  * look at the queue's cursor and hands its pixels over (0: only a wave that needs a refill does), "dry_cadence" (a power of two
- * in 1..1024, default 4): near the end of the queue a wave looks again after that many walk steps of its busiest lane.
+ * in 1..1024, default 4): near the end of the queue a wave looks again after that many walk steps of its busiest lane;
+ * "chain_start" (1): a lane whose walk is absorbed takes the first step of its pixel's next sample, whose closest point is cached,
+ * in the same pass over the step code (0: in the wave's next one).  The 2-D uniform walk kernels only, and not the steps a wave
+ * takes together for a Neumann mesh on the tree.
  * "spp" changes samplesPerPixel of an existing handle (a pixel's first k samples do not depend on
  * the total, so solving with spp = k reproduces the state of a longer solve after k samples: the
  * host mirror uses this for saveSppMetrics frames). */
