@@ -191,7 +191,8 @@ EXPORTS = [
     "wost3_net_create", "wost3_guided_create", "wost3_guided_destroy", "wost3_guided_network", "wost3_guided_solve", "wost3_guided_solve_sharded", "wost3_guided_solve_points", "wost3_guided_solve_points_dev",
     "wost3_guided_query_network", "wost3_guided_train_set", "wost3_guided_scene",
     "wost_last_error", "wost_version", "wost_mesh_build_check",
-]
+] + [pre + "points_" + f for pre in ("wost_", "wost3_")
+     for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")]
 
 _lib = None
 
@@ -234,6 +235,16 @@ def load():
         getattr(L, pre + "solve_carried").argtypes = [C.c_void_p, ip, ip, fp, fp]
         getattr(L, pre + "solve_adaptive").argtypes = [C.c_void_p, C.POINTER(Adaptive), fp, fp, ip, C.POINTER(Stats)]
         getattr(L, pre + "solve_adaptive_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        # the carried point list (wost_points_carry & co.)
+        getattr(L, pre + "points_carry").argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32]
+        getattr(L, pre + "points_carry_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        getattr(L, pre + "points_more").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), fp, C.POINTER(Stats)]
+        getattr(L, pre + "points_more_dev").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        getattr(L, pre + "points_carried").argtypes = [C.c_void_p, ip, ip, fp, fp]
+        getattr(L, pre + "points_adaptive").argtypes = [C.c_void_p, C.POINTER(Adaptive), fp, fp, ip, C.POINTER(Stats)]
+        getattr(L, pre + "points_adaptive_dev").argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        getattr(L, pre + "points_restart").argtypes = [C.c_void_p]
+        getattr(L, pre + "points_progress").argtypes = [C.c_void_p, ip, ip]
     L.wost_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
     L.wost_render_source.argtypes = [C.c_void_p, fp]
     L.wost_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]

@@ -1,6 +1,7 @@
 // wost_carry.hip -- the kernel that closes a continued call of a carried frame solve, and the drivers built on it
 // (wost_carry.h; include/wost.h "The continued frame solve").  Cold path: one thread per pixel of the
-// frame, once per call; the walk kernels do not know of it.
+// frame, once per call; the walk kernels do not know of it.  At the end: the bind of a carried point list, whose
+// calls the same kernel closes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@ struct CarryParams {
     uint32_t *n, *batches;
     float *prev, *q;
     const uint8_t *mask;
+    int32_t nan_masked;        // a point list: the field of a masked entry (a point that is not finite) is NaN
     int32_t width, n_pixels, shard_index, shard_count;
     // the call that has just walked: m samples (0: none, the kernel only reports and selects) on the pixels of `walked`
     // (nullptr: every pixel)
@@ -72,7 +74,8 @@ __global__ __launch_bounds__(256) void carry_kernel(CarryParams P)
         if (owned && P.field) {
             // the division of the resolve: a pixel that every call walked keeps the bits of the single solve
             float *f = P.field + 3 * (size_t)pid;
-            for (int ch = 0; ch < 3; ++ch) f[ch] = n > 0u ? s[ch] / N : 0.0f;
+            const float unwalked = P.nan_masked && !live ? __int_as_float(0x7fc00000) : 0.0f;
+            for (int ch = 0; ch < 3; ++ch) f[ch] = n > 0u ? s[ch] / N : unwalked;
         }
         if (P.se || P.pick == CARRY_PICK_TOLERANCE) {
             bool converged = K >= (uint32_t)P.min_batches;
@@ -164,7 +167,7 @@ static CarryParams carry_params(const CarryState &s, const CarryFrame &f, int32_
 {
     CarryParams P{};
     P.sum = s.sum; P.n = s.n; P.batches = s.batches; P.prev = s.prev; P.q = s.q;
-    P.mask = f.mask; P.width = f.width; P.n_pixels = (int32_t)n_pixels_of(f);
+    P.mask = f.mask; P.nan_masked = f.nan_masked ? 1 : 0; P.width = f.width; P.n_pixels = (int32_t)n_pixels_of(f);
     P.shard_index = shard_index; P.shard_count = shard_count;
     P.sel = s.sel; P.ids = s.ids; P.count = s.count;
     return P;
@@ -342,6 +345,72 @@ int carry_read(CarryState &s, const CarryFrame &f, int32_t *spp, int32_t *batche
     if (batches) WOST_TRY(hipMemcpyAsync(batches, s.batches, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     if (sum_rgb) WOST_TRY(hipMemcpyAsync(sum_rgb, s.sum, 3 * n * sizeof(float), hipMemcpyDeviceToHost, stream));
     WOST_TRY(hipStreamSynchronize(stream));
+    return WOST_OK;
+}
+
+// ---- the carried point list (wost_points_carry & co., wost_carry.h) ----
+// the map of the finite points of a list, built once when the list is bound: one thread per point
+__global__ __launch_bounds__(256) void points_finite_kernel(const float *pts, int32_t n, int32_t dim, uint8_t *finite)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool ok = true;
+    for (int k = 0; k < dim; ++k) ok = ok && isfinite(pts[(size_t)i * dim + k]);
+    finite[i] = ok ? 1 : 0;
+}
+
+void points_free(PointList &l)
+{
+    if (l.pts) (void)hipFree(l.pts);      // (one allocation: the points, the field, the map)
+    carry_free(l.carry);
+    l = PointList{};
+}
+
+int points_check_bind(const void *h, const float *pts, int32_t n, int32_t seed_base, int32_t seed_width)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    if (n < 0) return set_error(WOST_ERR_INVALID, "negative number of points");
+    if (n > 0 && !pts) return set_error(WOST_ERR_INVALID, "null argument");
+    if (seed_width <= 0) return set_error(WOST_ERR_INVALID, "seed_width must be positive");
+    if (seed_base < 0 || (int64_t)seed_base + n > ((int64_t)1 << 28))
+        return set_error(WOST_ERR_INVALID, "seed_base must be >= 0 and seed_base + n at most 2^28");
+    return WOST_OK;
+}
+
+int points_bind(PointList &l, int device, int dim, const float *pts, bool pts_on_host, int32_t n, int32_t seed_base, int32_t seed_width,
+                hipStream_t stream)
+{
+    if (n == 0) {
+        if (l.pts || l.carry.mem || l.carry.work) {
+            WOST_TRY(hipSetDevice(device));
+            points_free(l);
+        }
+        l = PointList{};
+        return WOST_OK;
+    }
+    WOST_TRY(hipSetDevice(device));
+    // the new list first, whole; the old one goes only when the new one stands
+    const size_t n_pts = (size_t)n * (size_t)dim, n_field = (size_t)n * 3;
+    void *mem = nullptr;
+    WOST_TRY(hipMalloc(&mem, (n_pts + n_field) * sizeof(float) + (size_t)n));
+    PointList fresh;
+    fresh.pts = static_cast<float *>(mem);
+    fresh.field = fresh.pts + n_pts;
+    fresh.finite = reinterpret_cast<uint8_t *>(fresh.field + n_field);
+    fresh.n = n; fresh.seed_base = seed_base; fresh.seed_width = seed_width;
+    hipError_t e = hipMemcpyAsync(fresh.pts, pts, n_pts * sizeof(float), pts_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(fresh.field, 0, n_field * sizeof(float), stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(points_finite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fresh.pts, n, (int32_t)dim, fresh.finite);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        (void)hipFree(mem);
+        return hip_failed("binding the point list", e);
+    }
+    points_free(l);
+    l = fresh;
     return WOST_OK;
 }
 

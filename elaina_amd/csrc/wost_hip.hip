@@ -220,6 +220,13 @@ struct InitPointsParams {
     int32_t first, n;
     int32_t seed_base, seed_width;
     int32_t stack_stride;
+    // a call on a carried point list (wost_points_more & co., carry_n != nullptr), as in InitParams: a point with carry_n[i] > 0
+    // samples behind it starts from its carried generator state and raw sums (its depth-0 closest point is queried again); a
+    // point whose byte in select (nullptr: every point) is 0 is not queued.  The kernel that closes the call writes the field.
+    const uint64_t *carry_rng;
+    const float *carry_sum;
+    const uint32_t *carry_n;
+    const uint8_t *select;
 };
 
 // Thread t takes point i = first + t of the call: the stream of pixel seed_base + i in a
@@ -240,7 +247,7 @@ __global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
         y0 = P.points[2 * (size_t)pid + 1];
     }
     const bool finite = isfinite(x0) && isfinite(y0);
-    const bool active = owned && finite && P.st.spp > 0;
+    const bool active = owned && finite && P.st.spp > 0 && (P.select == nullptr || P.select[pid] != 0);
     if (owned && !active) {
         float *f = P.field + 3 * (size_t)pid;
         const float z = finite ? 0.0f / (float)P.st.spp : __int_as_float(0x7fc00000);
@@ -264,6 +271,12 @@ __global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
         if ((int)(threadIdx.x & 63) == src) c0 = r;
         hb &= hb - 1;
     }
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f;
+    if (active && P.carry_n != nullptr && P.carry_n[pid] > 0u) {
+        rng.state = P.carry_rng[pid];
+        const float *cs = P.carry_sum + 3 * (size_t)pid;
+        sr = cs[0]; sg = cs[1]; sb = cs[2];
+    }
     const uint32_t s = block_push(active, P.count_out);
     if (active) {
         WalkQueue &q = P.out;
@@ -275,7 +288,7 @@ __global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
         q.nx[s] = 0.0f; q.ny[s] = 0.0f;
         q.hint[s] = c0.slot;
         q.thp[s] = 1.0f;
-        q.sr[s] = 0.0f; q.sg[s] = 0.0f; q.sb[s] = 0.0f;
+        q.sr[s] = sr; q.sg[s] = sg; q.sb[s] = sb;
         q.d0_d2[s] = c0.d2;
         q.d0_slot[s] = c0.slot;
     }
@@ -1443,6 +1456,8 @@ struct wost_context {
     uint64_t steps_before = 0;                 // a point solve in chunks: the walk steps of its earlier chunks (wost_launch_info::walk_steps_done)
     // the carried frame solve (wost_solve_more & co., wost_carry.h)
     wost::CarryState carry;
+    // ... and, beside it, the carried point list (wost_points_carry & co.)
+    wost::PointList list;
 };
 
 namespace wost {
@@ -1501,6 +1516,7 @@ static void destroy_ctx(wost_context *c)
     if (c->field) (void)hipFree(c->field);
     if (c->cursor) (void)hipFree(c->cursor);
     carry_free(c->carry);
+    points_free(c->list);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -1537,7 +1553,8 @@ int64_t differing_bytes2(const T *a, const T *b, size_t count, int64_t *compared
 extern "C" {
 
 // 0.2: the sync callback of a shared guiding network is also asked for the number of ranks (WOST_SYNC_RANKS_I64_HOST)
-const char *wost_version(void) { return "wost-hip 0.2 (gfx950)"; }
+// 0.3: the carried point list (wost_points_carry & co., wost3_points_carry & co.)
+const char *wost_version(void) { return "wost-hip 0.3 (gfx950)"; }
 
 
 int wost_mesh_build_check(const wost_mesh_desc *mesh, int device, int32_t repeat, double *host_ms, double *device_ms, int64_t *mismatch)
@@ -2108,6 +2125,8 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
 // A frame step with carry_more > 0 is a call of a continued solve (wost_solve_more & co.): carry_more samples on top of those in
 // the handle's carried buffers -- the solve runs with spp = carry_more, whatever the handle's own setting -- on the pixels of the
 // device map carry_select (nullptr: every pixel).  carry_append: not the first walk of its call, it appends to last_launches.
+// A point step with carry_more > 0 is the same on a chunk of the handle's carried point list (wost_points_more & co.): the
+// buffers are the list's, the map is indexed by the point's index in the list.
 struct FirstStep {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
@@ -2132,12 +2151,14 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     WOST_TRY(hipMemsetAsync(c->counts, 0, 12 * sizeof(uint32_t), stream));
     WOST_TRY(hipMemsetAsync(c->stats, 0, kStatCopies * sizeof(StatsDev), stream));
     // the plan of the solve takes its sample count from here: the handle's setting, or the count of a continued call
-    const bool carried = !fs.points && fs.carry_more > 0;
+    const bool carried = fs.carry_more > 0;
+    const CarryState &cs = fs.points ? c->list.carry : c->carry;
     DevSettings st = c->dst;
     if (carried) st.spp = fs.carry_more;
 
     if (fs.points) {
-        const InitPointsParams ip{c->dm.view, c->dst, c->queue[0], c->counts + 0, fs.points, field_dev, fs.first, fs.n, fs.seed_base, fs.seed_width, g.bs};
+        const InitPointsParams ip{c->dm.view, st, c->queue[0], c->counts + 0, fs.points, field_dev, fs.first, fs.n, fs.seed_base, fs.seed_width, g.bs,
+                                  cs.rng, cs.sum, carried ? cs.n : nullptr, carried ? fs.carry_select : nullptr};
         hipLaunchKernelGGL(init_points_kernel, dim3((unsigned)(((long long)fs.n + g.bs - 1) / g.bs)), dim3(g.bs), g.lds, stream, ip);
     } else {
         const int tiles_x = (c->settings.width + 7) / 8, tiles_y = (c->settings.height + 7) / 8;
@@ -2164,7 +2185,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     RoundParams base = base_params(c, g, field_dev, field_base);
     base.st = st;
     if (carried) {
-        base.carry_rng = c->carry.rng; base.carry_sum = c->carry.sum; base.carry_total = fs.carry_done + fs.carry_more;
+        base.carry_rng = cs.rng; base.carry_sum = cs.sum; base.carry_total = fs.carry_done + fs.carry_more;
     }
     SideStreamGuard long_guard, far_guard;   // armed: a launch of the long remainders / of strayed walkers was queued
     uint32_t pending_far = 0;     // walkers at the far end of queue[cur] that the previous launch could not serve (launch_strayed)
@@ -2280,7 +2301,79 @@ static CarryWalk carry_walk(wost_context *c, int32_t shard_index, int32_t shard_
 // (a call that made no walk launched nothing: wost_last_launches reports an empty list, not the solve before it)
 static const CarryCalls<wost_context> kCarry{"wost_", carry_walk, [](wost_context *c) { c->last_launches.clear(); }};
 
+// ---- the carried point list (wost_points_carry & co.; the bodies of the entry points: PointCalls, wost_carry.h) ----
+// A walk of the list: chunks of at most n_pixels points by index range, as the point solve cuts them -- each a pass of the solve
+// driver on the chunk's selected points.  A chunk in which nothing is selected queues no walker and launches no walk.
+static CarryWalk points_walk(PointListCtx<wost_context> *x, int32_t, int32_t)
+{
+    wost_context *c = x->h;
+    return [c](int32_t more_spp, const uint8_t *sel, const int32_t *, uint32_t, float *field_dev, hipStream_t stream, wost_stats *stats) {
+        const PointList &l = c->list;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        bool append = l.carry.walks > 0;
+        if (!append) c->steps_before = 0;
+        wost_stats total{};
+        const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
+        for (int32_t first = 0; first < l.n; first += cap) {
+            const FirstStep fs{0, 0, 0, 1, l.pts, first, std::min(cap, l.n - first), l.seed_base, l.seed_width, l.carry.done, more_spp, sel, append};
+            wost_stats st{};
+            const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
+            if (rc != WOST_OK) return rc;
+            total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
+            total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
+            total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
+            total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
+            c->steps_before += st.walk_steps;
+            append = true;
+        }
+        total.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+        if (stats) *stats = total;
+        return WOST_OK;
+    };
+}
+
+static const PointCalls<wost_context> kPoints{{"wost_points_", points_walk, [](PointListCtx<wost_context> *x) { x->h->last_launches.clear(); }}, 2};
+
 extern "C" {
+
+int wost_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width)
+{
+    return kPoints.bind(h, pts_xy, true, n, seed_base, seed_width, nullptr);
+}
+
+int wost_points_carry_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width, void *stream)
+{
+    return kPoints.bind(h, pts_xy_dev, false, n, seed_base, seed_width, stream);
+}
+
+int wost_points_more(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
+{
+    return kPoints.more(h, more_spp, select, field_rgb, stats);
+}
+
+int wost_points_more_dev(wost_handle h, int32_t more_spp, const uint8_t *select_dev, float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    return kPoints.more_dev(h, more_spp, select_dev, field_rgb_dev, stream, stats);
+}
+
+int wost_points_carried(wost_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
+{
+    return kPoints.carried(h, spp, batches, sum_rgb, stderr_rgb);
+}
+
+int wost_points_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
+{
+    return kPoints.adaptive(h, a, field_rgb, stderr_rgb, spp_map, stats);
+}
+
+int wost_points_adaptive_dev(wost_handle h, const wost_adaptive *a, float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    return kPoints.adaptive_dev(h, a, field_rgb_dev, stream, stats);
+}
+
+int wost_points_restart(wost_handle h) { return kPoints.restart(h); }
+
+int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done) { return kPoints.progress(h, n_points, spp_done); }
 
 int wost_solve(wost_handle h, int32_t pixel_begin, int32_t pixel_end, float *field_rgb, wost_stats *stats)
 {

@@ -63,7 +63,8 @@ struct Walk3Params {
     // starts from its carried generator state and raw sums; a resolved pixel leaves both under its pixel id and its field entry is
     // sum / carry_total (the kernel that closes the call writes the pixel's own: wost_carry.hip); st.spp is this call's count and a
     // lane counts the call's samples from 0.  ids != nullptr: the call walks a selection -- slot s is pixel ids[s] of n_ids, every
-    // one owned and unmasked.  (At the end, like the points.)
+    // one owned and unmasked.  (At the end, like the points.)  POINTS and CARRY together: a call on the handle's carried point
+    // list (wost3_points_more & co.) -- the buffers are the list's, indexed like `points`; ids lists the selected, finite points.
     uint64_t *carry_rng;
     float *carry_sum;
     int32_t carry_done, carry_total;
@@ -398,7 +399,8 @@ __device__ __forceinline__ Closest closest_triangle_wave(const DevMesh3 &m, V3 q
 // the loop is then "all queries of the wave, then one step for every walker": no lane waits for another's descent.
 // POINTS = true: the launch of a point solve (wost3_solve_points) -- a refill takes a caller's point instead of a pixel of the frame.
 // A template flag, not a test of P.points: with the test every frame instantiation held two more registers (EXPERIMENTS).
-// CARRY = true (frame forms only): the launch of a continued solve (wost3_solve_more, Walk3Params::carry_rng).
+// CARRY = true: the launch of a continued solve (wost3_solve_more, Walk3Params::carry_rng); with POINTS, of a call on the carried
+// point list (wost3_points_more).
 template <bool EMISSIVE, bool SOURCE, bool NTREE, bool WAVE = false, bool POINTS = false, bool CARRY = false>
 #ifndef WOST3_WAVES
 #define WOST3_WAVES 1       // waves per SIMD walk3_kernel is compiled for (tuning builds override it)
@@ -478,7 +480,7 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                 } else if (POINTS) {
                     // a caller's point.  One with a non-finite coordinate is never walked -- no NaN walker in a persistent
                     // launch -- and its field entry is NaN; the lane asks again on the next trip
-                    const int pid = P.pixel_begin + (int)s2;
+                    const int pid = CARRY && P.ids != nullptr ? P.ids[s2] : P.pixel_begin + (int)s2;
                     const V3 q = v3(P.points[3 * (size_t)pid], P.points[3 * (size_t)pid + 1], P.points[3 * (size_t)pid + 2]);
                     const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
                     if (!finite || P.st.spp <= 0) {
@@ -491,6 +493,11 @@ __global__ __launch_bounds__(kWalk3Threads, WOST3_WAVES) void walk3_kernel(Walk3
                         L.pid = pid;
                         L.rng = Pcg{0, 1};
                         pcg_seed_pixel(L.rng, P.seed_base + pid, P.seed_width);
+                        if (CARRY && P.carry_n[pid] > 0u) {
+                            L.rng.state = P.carry_rng[pid];
+                            const float *cs = P.carry_sum + 3 * (size_t)pid;
+                            L.sol[0] = cs[0]; L.sol[1] = cs[1]; L.sol[2] = cs[2];
+                        }
                         L.p_eval = q;
                         L.hint = L.hint0 = -1;
                         L.sample = 0;
@@ -764,6 +771,7 @@ static void destroy3(wost3_context *c)
     if (c->stats) (void)hipFree(c->stats);
     if (c->cursor) (void)hipFree(c->cursor);
     carry_free(c->carry);
+    points_free(c->list);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -812,8 +820,8 @@ static Walk3Plan walk3_plan(const wost3_context *c, int n)
     return pl;
 }
 
-// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are, the sixteen of a point solve and the
-// sixteen of a continued frame solve beside them
+// the kernel of the solve: all sixteen walk3_kernel<EMISSIVE, SOURCE, NTREE, WAVE> there are, the sixteen of a point solve, the
+// sixteen of a continued frame solve and the sixteen of a call on a carried point list beside them
 template <bool E, bool S, bool PTS, bool CARRY>
 static const void *walk3_kernel_of(bool ntree, bool wave)
 {
@@ -831,7 +839,8 @@ static const void *walk3_kernel_of(const Walk3Plan &pl)
 // (points != nullptr) the points [pixel_begin, pixel_end) of a caller's list with their seeds.
 // A frame step with carry_more > 0 is a call of a continued solve (wost3_solve_more & co.): carry_more samples on top of those in
 // the handle's carried buffers -- the launch runs with spp = carry_more, whatever the handle's own setting -- on the carry_n_ids
-// pixels of the device list carry_ids (nullptr: every pixel of the shard).
+// pixels of the device list carry_ids (nullptr: every pixel of the shard).  A point step with carry_more > 0 is the same on the
+// handle's carried point list (wost3_points_more & co.): the buffers are the list's, the ids are indices into the list.
 struct FirstStep3 {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
@@ -859,17 +868,18 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
         P.shard_index = shard_index; P.shard_count = shard_count; P.stats = c->stats; P.cursor = c->cursor;
         P.tiled = (!fs.points && pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
         P.points = fs.points; P.seed_base = fs.seed_base; P.seed_width = fs.seed_width;
-        const bool carried = !fs.points && fs.carry_more > 0;
+        const bool carried = fs.carry_more > 0;
         if (carried) {
+            const CarryState &cs = fs.points ? c->list.carry : c->carry;
             P.st.spp = fs.carry_more;
-            P.carry_rng = c->carry.rng; P.carry_sum = c->carry.sum; P.carry_done = fs.carry_done; P.carry_total = fs.carry_done + fs.carry_more;
-            P.carry_n = c->carry.n; P.ids = fs.carry_ids; P.n_ids = fs.carry_n_ids;
+            P.carry_rng = cs.rng; P.carry_sum = cs.sum; P.carry_done = fs.carry_done; P.carry_total = fs.carry_done + fs.carry_more;
+            P.carry_n = cs.n; P.ids = fs.carry_ids; P.n_ids = fs.carry_n_ids;
         }
         P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.coop = pl.coop; P.pool_cap = pl.pool_cap; P.stack_words = pl.stack_words;
         P.ray_slot_trigger = pl.ray_slot_trigger; P.cp_slot_trigger = pl.cp_slot_trigger;
         void *args[] = {&P};
         WOST_TRY(hipEventRecord(c->ev0, stream));
-        (void)hipLaunchKernel(fs.points ? walk3_kernel_of<true>(pl) : carried ? walk3_kernel_of<false, true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
+        (void)hipLaunchKernel(fs.points ? (carried ? walk3_kernel_of<true, true>(pl) : walk3_kernel_of<true>(pl)) : carried ? walk3_kernel_of<false, true>(pl) : walk3_kernel_of<false>(pl), dim3(pl.grid), dim3(kWalk3Threads), args, pl.lds, stream);
         WOST_TRY(hipGetLastError());
         WOST_TRY(hipEventRecord(c->ev1, stream));
     }
@@ -921,7 +931,62 @@ static CarryWalk carry_walk3(wost3_context *c, int32_t shard_index, int32_t shar
 
 static const CarryCalls<wost3_context> kCarry3{"wost3_", carry_walk3, nullptr};
 
+// ---- the carried point list (wost3_points_carry & co.; the bodies of the entry points: PointCalls, wost_carry.h) ----
+// a walk of the list: one launch, its lanes on the points of the id list where the call has a selection
+static CarryWalk points_walk3(PointListCtx<wost3_context> *x, int32_t, int32_t)
+{
+    wost3_context *c = x->h;
+    return [c](int32_t more_spp, const uint8_t *sel, const int32_t *ids, uint32_t n_sel, float *field_dev, hipStream_t stream, wost_stats *stats) {
+        const PointList &l = c->list;
+        FirstStep3 fs{0, l.n, 0, 1, l.pts, l.seed_base, l.seed_width};
+        fs.carry_done = l.carry.done; fs.carry_more = more_spp;
+        if (sel) { fs.carry_ids = ids; fs.carry_n_ids = (int32_t)n_sel; }
+        return run_solve3(c, fs, field_dev, 0, stream, stats);
+    };
+}
+
+static const PointCalls<wost3_context> kPoints3{{"wost3_points_", points_walk3, nullptr}, 3};
+
 extern "C" {
+
+int wost3_points_carry(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width)
+{
+    return kPoints3.bind(h, pts_xyz, true, n, seed_base, seed_width, nullptr);
+}
+
+int wost3_points_carry_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, void *stream)
+{
+    return kPoints3.bind(h, pts_xyz_dev, false, n, seed_base, seed_width, stream);
+}
+
+int wost3_points_more(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
+{
+    return kPoints3.more(h, more_spp, select, field_rgb, stats);
+}
+
+int wost3_points_more_dev(wost3_handle h, int32_t more_spp, const uint8_t *select_dev, float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    return kPoints3.more_dev(h, more_spp, select_dev, field_rgb_dev, stream, stats);
+}
+
+int wost3_points_carried(wost3_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb)
+{
+    return kPoints3.carried(h, spp, batches, sum_rgb, stderr_rgb);
+}
+
+int wost3_points_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map, wost_stats *stats)
+{
+    return kPoints3.adaptive(h, a, field_rgb, stderr_rgb, spp_map, stats);
+}
+
+int wost3_points_adaptive_dev(wost3_handle h, const wost_adaptive *a, float *field_rgb_dev, void *stream, wost_stats *stats)
+{
+    return kPoints3.adaptive_dev(h, a, field_rgb_dev, stream, stats);
+}
+
+int wost3_points_restart(wost3_handle h) { return kPoints3.restart(h); }
+
+int wost3_points_progress(wost3_handle h, int32_t *n_points, int32_t *spp_done) { return kPoints3.progress(h, n_points, spp_done); }
 
 int wost3_create(const wost3_scene_desc *scene, const wost_settings *settings, int device, wost3_handle *out)
 {

@@ -57,6 +57,8 @@ struct wost3_context {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the carried frame solve (wost3_solve_more & co., wost_carry.h)
     wost::CarryState carry;
+    // ... and, beside it, the carried point list (wost3_points_carry & co.)
+    wost::PointList list;
 };
 
 namespace wost {

@@ -139,6 +139,86 @@ class UniformCalls:
         a = self._adaptive(batch_spp, max_spp, abs_tol, rel_tol, min_batches)
         return self._dev_solve("solve_adaptive_sharded", shard_index, shard_count, C.byref(a), C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
 
+    # -- the carried point list (wost_points_carry & co.) ------------------------------------------
+    def points_carry(self, points, seed_base=0, seed_width=None):
+        """bind a list of evaluation points ([n, dim] floats) to the integrator: the library copies them; point i runs on the
+        random stream of pixel seed_base + i in a frame seed_width wide (default: the frame's width), as in solve_points.  The
+        list replaces the one bound before, state included; an empty list releases it."""
+        fn, name = self._fn("points_carry")
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        _check(fn(self._handle, _fp(p), len(p), int(seed_base), self._seed_width(seed_width)), name)
+
+    def points_carry_dev(self, points_ptr, n, stream_ptr=None, seed_base=0, seed_width=None):
+        """the same from a device pointer (int) to n * dim floats, copied on the caller's stream; a point with a non-finite
+        coordinate is never walked and answers NaN"""
+        fn, name = self._fn("points_carry_dev")
+        _check(fn(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), self._seed_width(seed_width), C.c_void_p(stream_ptr or 0)), name)
+
+    def _points_progress(self):
+        fn, name = self._fn("points_progress")
+        n, done = C.c_int32(0), C.c_int32(0)
+        _check(fn(self._handle, C.byref(n), C.byref(done)), name)
+        return n.value, done.value
+
+    @property
+    def n_points(self):
+        """points of the bound list (0: none is bound)"""
+        return self._points_progress()[0]
+
+    @property
+    def points_done(self):
+        """the sum of more_spp over the calls on the list since it was bound or restarted"""
+        return self._points_progress()[1]
+
+    def points_more(self, more_spp, select=None):
+        """more_spp samples on the listed points whose entry in select (n values, nonzero = continue) is set; None: every
+        point.  Returns the (n, 3) field: every point's mean at its own count, solve_points' at that spp bit for bit"""
+        n = self.n_points
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, dtype=np.uint8)
+            if sel.size != n:
+                raise ValueError("select has %d entries, the list %d points" % (sel.size, n))
+        ptr = sel.ctypes.data_as(C.POINTER(C.c_uint8)) if sel is not None else None
+        return self._host_solve("points_more", n, int(more_spp), ptr)[0]
+
+    def points_more_dev(self, more_spp, field_dev_ptr, select_dev_ptr=None, stream_ptr=None):
+        """the same on device pointers (ints): n bytes of selection (None: every point), n * 3 floats of field"""
+        return self._dev_solve("points_more_dev", int(more_spp), C.c_void_p(select_dev_ptr or 0), C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    def points_carried(self):
+        """the per-point state of the list, with the keys of carried(): "spp", "batches", "sum", "stderr" """
+        fn, name = self._fn("points_carried")
+        n = self.n_points
+        out = {"spp": np.zeros(n, np.int32), "batches": np.zeros(n, np.int32),
+               "sum": np.zeros((n, 3), np.float32), "stderr": np.zeros((n, 3), np.float32)}
+        _check(fn(self._handle, _ip(out["spp"]), _ip(out["batches"]), _fp(out["sum"]), _fp(out["stderr"])), name)
+        return out
+
+    def points_adaptive(self, batch_spp, max_spp, abs_tol=0.0, rel_tol=0.0, min_batches=4):
+        """solve_adaptive over the listed points, from the list's state as it stands; returns (field, stderr, spp): (n, 3),
+        (n, 3) and n entries"""
+        fn, name = self._fn("points_adaptive")
+        n = self.n_points
+        field = np.zeros((n, 3), dtype=np.float32)
+        se = np.zeros((n, 3), dtype=np.float32)
+        spp = np.zeros(n, dtype=np.int32)
+        st = Stats()
+        a = self._adaptive(batch_spp, max_spp, abs_tol, rel_tol, min_batches)
+        _check(fn(self._handle, C.byref(a), _fp(field), _fp(se), _ip(spp), C.byref(st)), name)
+        self.last_stats = st.as_dict()
+        return field, se, spp
+
+    def points_adaptive_dev(self, batch_spp, max_spp, field_dev_ptr, stream_ptr=None, abs_tol=0.0, rel_tol=0.0, min_batches=4):
+        """the same into a device field of n * 3 floats on the caller's stream"""
+        a = self._adaptive(batch_spp, max_spp, abs_tol, rel_tol, min_batches)
+        return self._dev_solve("points_adaptive_dev", C.byref(a), C.c_void_p(field_dev_ptr), C.c_void_p(stream_ptr or 0))
+
+    def points_restart(self):
+        """keep the list, forget its samples"""
+        fn, name = self._fn("points_restart")
+        _check(fn(self._handle), name)
+
     # -- lbvh query call sites, batched ---------------------------------------------------------
     def closest_point(self, pts, which=capi.MESH_DIRICHLET):
         fn, name = self._fn("closest_point")

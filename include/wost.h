@@ -162,7 +162,7 @@ int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int
  *     a later call with another shard is refused with WOST_ERR_INVALID and a message that names the carried shard.
  *   - wost_solve_restart forgets the carried solve (done = 0, no shard); wost_solve_progress reports done.
  *   - a call that fails after device work has begun drops the carried solve (done = 0) and says so in wost_last_error.
- * Not carried: the guided integrators, point lists; a carried solve cannot be saved. */
+ * Not carried: the guided integrators; a carried solve cannot be saved.  (A caller's points: the carried point list below.) */
 int wost_solve_more(wost_handle h, int32_t more_spp, float *field_rgb, wost_stats *stats);
 int wost_solve_more_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, int32_t more_spp,
                             float *field_rgb_dev, void *stream, wost_stats *stats);
@@ -207,6 +207,62 @@ int wost_solve_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb,
                         wost_stats *stats);
 int wost_solve_adaptive_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a,
                                 float *field_rgb_dev, void *stream, wost_stats *stats);
+
+/* The carried point list: the continued, selective and adaptive solves above on n evaluation points of the caller instead of the
+ * pixels of the frame.  wost_points_carry binds a list to the handle: the library copies the points (pts_xy: n * 2 floats) and
+ * owns the copy; n == 0 (pts_xy may be NULL) releases the list.  wost_points_carry_dev takes DEVICE points and copies them on the
+ * caller's stream (NULL = default stream); it returns when the copy is complete.
+ *   Point identity.  Point i is walked with the handle's settings and meshes exactly as a pixel is; its samples share the PCG32
+ *     stream of pixel seed_base + i of a frame seed_width wide -- the rule of wost_solve_points.  The frame's mask, tiles and
+ *     shards do not apply (they are properties of the frame).  The handle's own spp setting is neither read nor changed.
+ *   Bits.  A point continues its own stream and fp32 sums whenever a call takes it up, so after any sequence of calls a point
+ *     with n_i samples behind it has the field entry sum / n_i, which is that of wost_solve_points on a handle with spp = n_i, bit
+ *     for bit, whatever the other points did; the entry is 0 while n_i = 0.  Over the calls walk_steps, walks_started,
+ *     walks_absorbed, walks_truncated and neumann_hits sum to those of the single point solves.  The result of a point does not
+ *     depend on how a list is cut into lists, as long as seed_base moves with the cut.
+ *   State.  Every point carries the 52 bytes of a pixel of the carried frame solve; its n, K and standard error follow the formulas
+ *     above (batch means, fp32, in that order, +inf while K < 2), and the same kernel closes every call.
+ *   - wost_points_more: more_spp samples on the listed points whose byte in select (n host bytes) is nonzero; NULL = every point.
+ *     field_rgb (n * 3 host floats) receives every point's sum / n_i.  more_spp >= 1, and the sum of more_spp over the calls since
+ *     the bind or the restart is at most 2^20 - 1 (wost_points_progress reports it, beside the length of the list); anything else
+ *     is refused with the state untouched.  An empty selection returns WOST_OK with zeroed stats and the field of the state, and
+ *     launches no walk: wost_last_launches is empty.  wost_points_more_dev: select_dev and field_rgb_dev are DEVICE arrays, the
+ *     work runs on the caller's stream and is complete when the call returns.
+ *   - wost_points_carried copies the state to host arrays of n (spp, batches) and n * 3 (sum_rgb, stderr_rgb) entries; any of them
+ *     may be NULL.
+ *   - wost_points_adaptive is the loop of wost_solve_adaptive over the listed points: the same convergence test, the same room
+ *     test n_i + batch_spp <= max_spp, one count read back per round, resumption by a second call, and the same refusals before
+ *     the handle is read.  stderr_rgb and spp_map (host, may be NULL) receive se and n_i.
+ *   - wost_stats describes the call (an adaptive call sums its rounds; solve_ms covers the whole call) and wost_last_launches
+ *     lists the launches of the call in order, walk_steps_done cumulative.  A list longer than the frame runs in chunks of
+ *     width * height points, cut by index; a chunk in which nothing is selected launches no walk.  The bound of the 16-bit lane
+ *     counters on a persistent launch applies to more_spp * max_depth, as in a continued frame call.
+ *   One list per handle, beside the carried frame solve: the list has its own state, its own device field and its own copy of the
+ *     points.  wost_solve, wost_solve_sharded, wost_solve_points[_dev], the whole wost_solve_more family (wost_solve_restart
+ *     included) and wost_set_option leave the list alone, and the wost_points_* calls leave the carried frame solve alone.
+ *     wost_points_restart keeps the list and forgets its samples.  Binding a new list replaces the old one, state included; a
+ *     bind that is refused leaves the old list as it was.  wost_destroy frees everything.
+ *   Arguments of a bind, checked in this order before the handle is read or a device is asked for: a null handle; n < 0; n > 0
+ *     with null points; seed_width <= 0; seed_base < 0 or seed_base + n > 2^28.  A more / adaptive / carried call without a bound
+ *     list is WOST_ERR_INVALID with a message that says so.  A call that fails after device work has begun drops the samples
+ *     (not the list) and says so in wost_last_error.
+ *   Non-finite coordinates.  wost_points_carry scans the list and refuses it (WOST_ERR_INVALID names the first bad index).  After
+ *     wost_points_carry_dev such a point is never walked and never selected, by a caller's map or by the tolerance: it keeps
+ *     n = 0, K = 0, zero sums and +inf standard error, and its field entry is NaN after every call, as wost_solve_points_dev
+ *     answers it.
+ * Not carried: the guided integrators; a list cannot be saved, and one list is not split into shards -- a multi-GPU caller cuts
+ * the list itself and moves seed_base with the cut. */
+int wost_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width);
+int wost_points_carry_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width, void *stream);
+int wost_points_more(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats);
+int wost_points_more_dev(wost_handle h, int32_t more_spp, const uint8_t *select_dev, float *field_rgb_dev, void *stream,
+                         wost_stats *stats);
+int wost_points_carried(wost_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb);
+int wost_points_adaptive(wost_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map,
+                         wost_stats *stats);
+int wost_points_adaptive_dev(wost_handle h, const wost_adaptive *a, float *field_rgb_dev, void *stream, wost_stats *stats);
+int wost_points_restart(wost_handle h);
+int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done);
 
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
@@ -579,6 +635,21 @@ int wost3_solve_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rg
                          wost_stats *stats);
 int wost3_solve_adaptive_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, const wost_adaptive *a,
                                  float *field_rgb_dev, void *stream, wost_stats *stats);
+/* The carried point list in 3-D: wost_points_carry & co. with the same rules in every clause (pts_xyz: n * 3 floats, which need not
+ * lie on one slice; one list per handle beside the carried frame solve; a point's field after any sequence of calls is
+ * wost3_solve_points' at spp = n_i, bit for bit).  Lanes hold the walkers, so a call on a list of any length is one launch, sized
+ * by the selection. */
+int wost3_points_carry(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width);
+int wost3_points_carry_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, void *stream);
+int wost3_points_more(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats);
+int wost3_points_more_dev(wost3_handle h, int32_t more_spp, const uint8_t *select_dev, float *field_rgb_dev, void *stream,
+                          wost_stats *stats);
+int wost3_points_carried(wost3_handle h, int32_t *spp, int32_t *batches, float *sum_rgb, float *stderr_rgb);
+int wost3_points_adaptive(wost3_handle h, const wost_adaptive *a, float *field_rgb, float *stderr_rgb, int32_t *spp_map,
+                          wost_stats *stats);
+int wost3_points_adaptive_dev(wost3_handle h, const wost_adaptive *a, float *field_rgb_dev, void *stream, wost_stats *stats);
+int wost3_points_restart(wost3_handle h);
+int wost3_points_progress(wost3_handle h, int32_t *n_points, int32_t *spp_done);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
