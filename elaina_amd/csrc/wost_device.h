@@ -91,6 +91,57 @@ struct DevSettings {
     float dirichlet_intensity, neumann_intensity;
 };
 
+// ---- wave-uniform fetches of tables that no kernel of the launch writes --------------------------
+// *p read through the constant address space: with a wave-uniform address the compiler issues a scalar load (one fetch per wave
+// into SGPRs, beside the vector-memory path that the tree gathers need) where the plain read of a kernel with stores in its loop
+// is a vector load of 64 identical addresses, waited for.  With a divergent address it is still a correct per-lane load.
+// LEGAL ONLY for memory that no kernel of the same launch writes: the scalar cache is not coherent with the stores of the launch.
+// The mesh tables of DevMesh are such memory -- written by wost_create or the device builders, in earlier launches.
+// The read is made in dwords, so T is any record of whole dwords (2, 3, 4, 8 or 16 of them).
+template <class T>
+__device__ __forceinline__ T uniform_load(const T *p)
+{
+    static_assert(sizeof(T) % 4 == 0 && alignof(T) >= 4, "whole dwords");
+    typedef uint32_t Words __attribute__((ext_vector_type(sizeof(T) / 4)));
+    typedef Words AlignedWords __attribute__((aligned(alignof(T))));
+    const AlignedWords w = *(const __attribute__((address_space(4))) AlignedWords *)p;
+    T r;
+    __builtin_memcpy(&r, &w, sizeof(T));
+    return r;
+}
+template <>
+__device__ __forceinline__ float uniform_load<float>(const float *p)
+{
+    return *(const __attribute__((address_space(4))) float *)p;
+}
+
+// A table's base pointer, once per query: the compiler may not assume that it is the pointer of the last query, so the loads
+// through it stay where they are written -- inside the step -- instead of being hoisted in front of the scheduler loop, where
+// their results would live in SGPRs that the walk kernels do not have (they spill 50-110 of them to VGPR lanes already).
+template <class T>
+__device__ __forceinline__ const T *uniform_table(const T *p)
+{
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+// The flat Neumann queries below take UNI, a compile-time choice of the kernel: true where the kernel stores to global memory
+// inside its scheduler loop (the refilling round kernels, the persistent launch among them), so that the compiler cannot prove
+// the tables unchanged and reads them per lane; false where it proves that by itself and issues scalar loads already -- there
+// the plain read stays, and so does the kernel's code.
+template <bool UNI, class T>
+__device__ __forceinline__ T table_load(const T *p)
+{
+    if (UNI) return uniform_load(p);
+    return *p;
+}
+template <bool UNI, class T>
+__device__ __forceinline__ const T *table_base(const T *p)
+{
+    if (UNI) return uniform_table(p);
+    return p;
+}
+
 // ---- block-level stream compaction (shared by the uniform and the guided kernels) --------------
 // Up to 1024 threads, every thread of the block must call it: ballot + popcount inside a wave, one
 // atomic per block on the queue counter; returns the output slot of this lane (valid when `keep`).
@@ -423,14 +474,23 @@ __device__ __forceinline__ Closest closest_point_wave(const DevMesh &m, float qx
     return Closest{bd, bs};
 }
 
-// Brute-force variant for tiny meshes (wave-uniform loop over the flat records, which the
-// compiler turns into scalar loads).  Returns the ORIGINAL index in .slot.
+// the operands of seg_d2 from a record of a flat table: (cx, cy, ux, uy) in one load, hl in a second, nothing else of the 64 bytes
+template <bool UNI>
+__device__ __forceinline__ float flat_seg_d2(const DevFlatSeg *s, float qx, float qy)
+{
+    const float4 b = table_load<UNI>(reinterpret_cast<const float4 *>(&s->cx));
+    const float hl = table_load<UNI>(&s->hl);
+    return obb_d2(b.x, b.y, b.z, b.w, hl, 0.0f, qx, qy);
+}
+
+// Brute-force variant for tiny meshes (wave-uniform loop over the flat records: scalar loads).  Returns the ORIGINAL index in .slot.
+template <bool UNI = false>
 __device__ __forceinline__ Closest closest_point_flat(const DevMesh &m, float qx, float qy)
 {
     Closest best{WOST_INF, -1};
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     for (int i = 0; i < m.n_segs; ++i) {
-        const DevFlatSeg s = m.flat[i];
-        float d = seg_d2(s, qx, qy);
+        float d = flat_seg_d2<UNI>(flat + i, qx, qy);
         if (d < best.d2) {  // ascending i: strict < keeps the lowest index on ties
             best.d2 = d;
             best.slot = i;
@@ -442,6 +502,7 @@ __device__ __forceinline__ Closest closest_point_flat(const DevMesh &m, float qx
 // ---- closest silhouette vertex (reference call site integrator.cu:189) ------------------
 // Distance to the nearest vertex of the mesh that is a silhouette as seen from q, limited
 // to vertices within rmax; +inf when there is none.  Test = FCPW isSilhouetteVertex.
+template <bool UNI = false>
 __device__ __forceinline__ float closest_silhouette_flat(const DevMesh &m, float qx, float qy, float rmax)
 {
 #ifdef WOST_EXP_NO_SIL
@@ -454,14 +515,17 @@ __device__ __forceinline__ float closest_silhouette_flat(const DevMesh &m, float
         // segments' records, with scalar loads each trip waits for; it costs 3-4 % of config 2 (a build without it: EXPERIMENTS 16)
         // although nearly every test ends with "farther than R_D" or "not a silhouette".  Here the four vertices and the normals of
         // their segments come with TWO loads that wait for nothing, and the loop's body runs on them unrolled: the same tests in the
-        // same order on the same numbers, so the same result.
+        // same order on the same numbers, so the same result.  (UNI: the two loads of a vertex stay in its turn -- all eight
+        // records fetched at the head of the query hold 32 SGPRs at once and were slower, EXPERIMENTS 42.)
 #ifdef WOST_EXP_SIL_FAST_ALWAYS
         return WOST_INF;      // developer experiment: the cost of everything below
 #endif
+        const DevSilVertex *sil = table_base<UNI>(m.sil);
+        const float4 *silN = table_base<UNI>(m.silN);
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-            const DevSilVertex sv = m.sil[v];
-            const float4 nn = m.silN[v];
+            const DevSilVertex sv = table_load<UNI>(sil + v);
+            const float4 nn = table_load<UNI>(silN + v);
             if (sv.prev < 0 && sv.next < 0) continue;
             const float vx = qx - sv.x, vy = qy - sv.y;
             const float d2 = dot2(vx, vy, vx, vy);
@@ -487,23 +551,27 @@ __device__ __forceinline__ float closest_silhouette_flat(const DevMesh &m, float
         }
         return found ? sqrtf(best2) : WOST_INF;
     }
+    const DevSilVertex *sil = table_base<UNI>(m.sil);
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     for (int v = 0; v < m.n_sil; ++v) {
-        const DevSilVertex sv = m.sil[v];
+        const DevSilVertex sv = table_load<UNI>(sil + v);
         if (sv.prev < 0 && sv.next < 0) continue;  // vertex without segments
         float vx = qx - sv.x, vy = qy - sv.y;
         float d2 = dot2(vx, vy, vx, vy);
         if (d2 > best2) continue;
         bool is_sil = (sv.prev < 0 || sv.next < 0);
         if (!is_sil) {
-            const DevFlatSeg s0 = m.flat[sv.prev], s1 = m.flat[sv.next];
+            // (nx, ny) of the vertex's two segments (sv.prev and sv.next are the same in every lane)
+            const float2 n0 = table_load<UNI>(reinterpret_cast<const float2 *>(&flat[sv.prev].nx));
+            const float2 n1 = table_load<UNI>(reinterpret_cast<const float2 *>(&flat[sv.next].nx));
             float d = sqrtf(d2);
             if (d <= WOST_SIL_PRECISION) {
-                float det = cross2(s0.nx, s0.ny, s1.nx, s1.ny);
+                float det = cross2(n0.x, n0.y, n1.x, n1.y);
                 is_sil = (-det > WOST_SIL_PRECISION);
             } else {
                 float ux = vx / d, uy = vy / d;
-                float dot0 = dot2(ux, uy, s0.nx, s0.ny);
-                float dot1 = dot2(ux, uy, s1.nx, s1.ny);
+                float dot0 = dot2(ux, uy, n0.x, n0.y);
+                float dot1 = dot2(ux, uy, n1.x, n1.y);
                 if (fabsf(dot0) <= WOST_SIL_PRECISION || fabsf(dot1) <= WOST_SIL_PRECISION) is_sil = false;
                 else is_sil = (dot0 * dot1 < 0.0f);
             }
@@ -543,14 +611,26 @@ __device__ __forceinline__ bool seg_ray(const DevFlatSeg &s, float ox, float oy,
     return true;
 }
 
+// seg_ray on a record of a flat table: (ax, ay, ex, ey) in one load, nothing else of the 64 bytes
+template <bool UNI>
+__device__ __forceinline__ bool flat_seg_ray(const DevFlatSeg *s, float ox, float oy, float dx, float dy, float tmax, float &t)
+{
+    const float4 a = table_load<UNI>(reinterpret_cast<const float4 *>(s));
+    float uv, dv;
+    if (!seg_ray_hits(a.x, a.y, a.z, a.w, ox, oy, dx, dy, tmax, uv, dv)) return false;
+    t = uv / dv;
+    return true;
+}
+
 // The four-segment boundary of every shipped scene (a box): the loops below unrolled -- the four records fetched with loads that
 // do not wait for one another, the same tests in the same order, the division only for a segment that is hit.
-template <bool ANY_HIT>
+template <bool ANY_HIT, bool UNI>
 __device__ __forceinline__ bool ray_box_flat(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax, float &t_out, int &idx_out)
 {
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     float4 a[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const float4 *>(&m.flat[i]);      // ax ay ex ey
+    for (int i = 0; i < 4; ++i) a[i] = table_load<UNI>(reinterpret_cast<const float4 *>(flat + i));      // ax ay ex ey
     bool hit = false;
     float bt = WOST_INF;
     int bi = -1;
@@ -575,17 +655,18 @@ __device__ __forceinline__ bool ray_box_flat(const DevMesh &m, float ox, float o
     return hit;
 }
 
+template <bool UNI = false>
 __device__ __forceinline__ bool ray_closest_flat(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax,
                                                  float &t_out, int &idx_out)
 {
-    if (m.n_segs == 4) return ray_box_flat<false>(m, ox, oy, dx, dy, tmax, t_out, idx_out);
+    if (m.n_segs == 4) return ray_box_flat<false, UNI>(m, ox, oy, dx, dy, tmax, t_out, idx_out);
     bool hit = false;
     float bt = WOST_INF;
     int bi = -1;
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     for (int i = 0; i < m.n_segs; ++i) {
-        const DevFlatSeg s = m.flat[i];
         float t;
-        if (seg_ray(s, ox, oy, dx, dy, tmax, t)) {
+        if (flat_seg_ray<UNI>(flat + i, ox, oy, dx, dy, tmax, t)) {
             if (!hit || t < bt) {
                 bt = t;
                 bi = i;
@@ -598,32 +679,35 @@ __device__ __forceinline__ bool ray_closest_flat(const DevMesh &m, float ox, flo
     return hit;
 }
 
+template <bool UNI = false>
 __device__ __forceinline__ bool ray_any_flat(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax)
 {
     bool hit = false;
     if (m.n_segs == 4) {
         float t;
         int i;
-        return ray_box_flat<true>(m, ox, oy, dx, dy, tmax, t, i);
+        return ray_box_flat<true, UNI>(m, ox, oy, dx, dy, tmax, t, i);
     }
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     for (int i = 0; i < m.n_segs; ++i) {
-        const DevFlatSeg s = m.flat[i];
         float t;
-        hit = hit || seg_ray(s, ox, oy, dx, dy, tmax, t);
+        hit = hit || flat_seg_ray<UNI>(flat + i, ox, oy, dx, dy, tmax, t);
     }
     return hit;
 }
 
 // ---- primitive sampling in a ball (reference call site integrator.cu:349-354) ------------
+template <bool UNI = false>
 __device__ __forceinline__ int sample_in_sphere_flat(const DevMesh &m, float qx, float qy, float R, float u,
                                                      float &pdf)
 {
     float R2 = R * R;
     float total = 0.0f;
+    const DevFlatSeg *flat = table_base<UNI>(m.flat);
     for (int i = 0; i < m.n_segs; ++i) {
-        const DevFlatSeg s = m.flat[i];
-        float d2 = seg_d2(s, qx, qy);
-        if (d2 <= R2 && s.len > 0.0f) total += s.len;
+        const float len = table_load<UNI>(&flat[i].len);
+        float d2 = flat_seg_d2<UNI>(flat + i, qx, qy);
+        if (d2 <= R2 && len > 0.0f) total += len;
     }
     pdf = 0.0f;
     if (!(total > 0.0f)) return -1;
@@ -632,15 +716,15 @@ __device__ __forceinline__ int sample_in_sphere_flat(const DevMesh &m, float qx,
     int last = -1;
     bool done = false;
     for (int i = 0; i < m.n_segs; ++i) {
-        const DevFlatSeg s = m.flat[i];
-        float d2 = seg_d2(s, qx, qy);
-        if (!done && d2 <= R2 && s.len > 0.0f) {
-            cum += s.len;
+        const float len = table_load<UNI>(&flat[i].len);
+        float d2 = flat_seg_d2<UNI>(flat + i, qx, qy);
+        if (!done && d2 <= R2 && len > 0.0f) {
+            cum += len;
             last = i;
             if (target < cum) done = true;
         }
     }
-    float len = m.flat[last].len;
+    float len = m.flat[last].len;      // (`last` differs from lane to lane: an ordinary load)
     pdf = (len / total) / len;
     return last;
 }
@@ -970,25 +1054,26 @@ __device__ __forceinline__ bool ray_tree(const DevMesh &m, float ox, float oy, f
 
 // TREE is a compile-time choice (the host picks the kernel instantiation from the mesh size):
 // kernels for small boundary meshes carry no traversal code and keep their register budget.
-template <bool TREE, class STK>
+// UNI: how a flat mesh's tables are read (table_load)
+template <bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ float closest_silhouette(const DevMesh &m, float qx, float qy, float rmax, const STK &stk)
 {
-    if (!TREE) return closest_silhouette_flat(m, qx, qy, rmax);
+    if (!TREE) return closest_silhouette_flat<UNI>(m, qx, qy, rmax);
     return closest_silhouette_tree(m, qx, qy, rmax, stk);
 }
 
-template <bool TREE, class STK>
+template <bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ bool ray_closest(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax, float &t_out,
                                             int &idx_out, const STK &stk)
 {
-    if (!TREE) return ray_closest_flat(m, ox, oy, dx, dy, tmax, t_out, idx_out);
+    if (!TREE) return ray_closest_flat<UNI>(m, ox, oy, dx, dy, tmax, t_out, idx_out);
     return ray_tree<false>(m, ox, oy, dx, dy, tmax, t_out, idx_out, stk);
 }
 
-template <bool TREE, class STK>
+template <bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ bool ray_any(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax, const STK &stk)
 {
-    if (!TREE) return ray_any_flat(m, ox, oy, dx, dy, tmax);
+    if (!TREE) return ray_any_flat<UNI>(m, ox, oy, dx, dy, tmax);
     float t;
     int i;
     return ray_tree<true>(m, ox, oy, dx, dy, tmax, t, i, stk);

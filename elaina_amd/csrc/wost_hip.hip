@@ -335,7 +335,9 @@ struct LaneStats {
 // status bits returned by step_finish
 enum : uint32_t { STEP_ENDED = 1u, STEP_ABSORBED = 2u, STEP_TRUNCATED = 4u, STEP_NEUMANN_HIT = 8u, STEP_CHAINED = 16u };
 
-template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE = false, class STK = LdsColumn>
+// UNI: the tables of a flat Neumann mesh through the scalar path (wost_device.h: table_load) -- for the kernels that store to
+// global memory inside their scheduler loop, where the compiler reads them per lane otherwise.
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE = false, bool UNI = false, class STK = LdsColumn>
 __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh &nm, const DevSettings &st, Lane &L,
                                                 const Closest cp, const STK &stk, const DevSource &src = DevSource{},
                                                 const bool chain = false)
@@ -377,7 +379,7 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
         }
     }
     float R_N = WOST_INF;
-    if (has_n) R_N = closest_silhouette<NEUMANN_TREE>(nm, px, py, R_D, stk);
+    if (has_n) R_N = closest_silhouette<NEUMANN_TREE, UNI>(nm, px, py, R_D, stk);
     float R_B = fmaxf(WOST_R_B_FLOOR, fminf(R_D, R_N));
     R_B *= WOST_R_B_SHRINK;
     if (isinf(R_B)) return STEP_ENDED | chained;
@@ -385,7 +387,7 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
     // ---- sampleSource (problems with a source term only) ------------------------------------
     if (SOURCE) {
         float cr_, cg_, cb_;
-        if (source_sample<NEUMANN_TREE>(src, nm, eps, px, py, R_B, L.on_n, L.nx, L.ny, L.thp, L.rng, stk, cr_, cg_, cb_)) {
+        if (source_sample<NEUMANN_TREE, UNI>(src, nm, eps, px, py, R_B, L.on_n, L.nx, L.ny, L.thp, L.rng, stk, cr_, cg_, cb_)) {
             L.sr = cr_ + L.sr; L.sg = cg_ + L.sg; L.sb = cb_ + L.sb;
         }
     }
@@ -393,8 +395,8 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
     // ---- sampleNeumann -------------------------------------------------------------------
     if (has_n) {
         float cr_, cg_, cb_;
-        if (neumann_sample<NEUMANN_EMISSIVE, NEUMANN_TREE>(nm, st.neumann_intensity, eps, px, py, R_B, L.on_n, L.nx, L.ny,
-                                                           L.thp, L.rng, stk, cr_, cg_, cb_)) {
+        if (neumann_sample<NEUMANN_EMISSIVE, NEUMANN_TREE, UNI>(nm, st.neumann_intensity, eps, px, py, R_B, L.on_n, L.nx, L.ny,
+                                                                L.thp, L.rng, stk, cr_, cg_, cb_)) {
             L.sr = cr_ + L.sr; L.sg = cg_ + L.sg; L.sb = cb_ + L.sb;
         }
     }
@@ -403,8 +405,8 @@ __device__ __forceinline__ uint32_t step_finish(const DevMesh &dm, const DevMesh
     float dirx, diry, pdf, alpha;
     uniform_direction(L.on_n, L.nx, L.ny, L.rng, dirx, diry, pdf, alpha);
     float nxt_x, nxt_y, hnx, hny;
-    const bool hit = walk_advance<NEUMANN_TREE>(nm, eps, px, py, R_B, L.on_n, L.nx, L.ny, dirx, diry, stk, nxt_x, nxt_y,
-                                                hnx, hny);
+    const bool hit = walk_advance<NEUMANN_TREE, UNI>(nm, eps, px, py, R_B, L.on_n, L.nx, L.ny, dirx, diry, stk, nxt_x, nxt_y,
+                                                     hnx, hny);
     const uint32_t hit_count = hit ? 1u : 0u;
     // 1/pdf/alpha/2pi is exactly 1.0f in fp32 for both branches (tests/test_oracle_units.py),
     // so a unit throughput stays a unit throughput without three IEEE divisions
@@ -775,7 +777,7 @@ __device__ __forceinline__ void walk_round_body(const RoundParams &P)
             if (mode == MODE_WAIT && !fresh) {
                 {
                     const uint32_t status = (NEUMANN_TREE && P.coop) ? wave_status
-                                                                     : step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, T.best, stk, P.src, P.chain && budget > 1);
+                                                                     : step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE, REFILL>(P.dm, P.nm, P.st, L, T.best, stk, P.src, P.chain && budget > 1);
                     const bool ended = (status & STEP_ENDED) != 0u;
                     S.b += ((status >> 1) & 1u) | (((status >> 2) & 1u) << 16);
                     S.c += (status >> 3) & 1u;

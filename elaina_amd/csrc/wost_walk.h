@@ -12,7 +12,8 @@ namespace wost {
 // 384-493): two draws from the pixel's stream whether or not the boundary emits (:343-347),
 // object sampling in the ball, visibility, Green's-function weight.  Returns true when the
 // sample contributes; (cr, cg, cb) is then the term to ADD to the solution (already negated).
-template <bool EMISSIVE, bool TREE, class STK>
+// UNI (here and below): how a flat Neumann mesh's tables are read (wost_device.h: table_load)
+template <bool EMISSIVE, bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ bool neumann_sample(const DevMesh &nm, float neumann_intensity, float eps, float px, float py,
                                                float R_B, bool on_n, float nx, float ny, float thp, Pcg &rng,
                                                const STK &stk, float &cr, float &cg, float &cb)
@@ -24,7 +25,7 @@ __device__ __forceinline__ bool neumann_sample(const DevMesh &nm, float neumann_
     const float u0 = pcg_next_float(rng);
     const float u1 = pcg_next_float(rng);
     float pdf;
-    const int oi = (TREE && nm.obox_levels > 0) ? sample_in_sphere_tree(nm, px, py, R_B, u0, pdf) : sample_in_sphere_flat(nm, px, py, R_B, u0, pdf);
+    const int oi = (TREE && nm.obox_levels > 0) ? sample_in_sphere_tree(nm, px, py, R_B, u0, pdf) : sample_in_sphere_flat<UNI>(nm, px, py, R_B, u0, pdf);
     if (!(oi != -1 && pdf > 0)) return false;
     const DevFlatSeg so = nm.flat[oi];
     const float spx = __builtin_fmaf(u1, so.ex, so.ax), spy = __builtin_fmaf(u1, so.ey, so.ay);
@@ -36,7 +37,7 @@ __device__ __forceinline__ bool neumann_sample(const DevMesh &nm, float neumann_
     float dx = spx - ox, dy = spy - oy;
     const float cd = sqrtf(dot2(dx, dy, dx, dy));
     if (cd > 0) { dx /= cd; dy /= cd; }
-    if (ray_any<TREE>(nm, ox, oy, dx, dy, cd - eps, stk)) return false;
+    if (ray_any<TREE, UNI>(nm, ox, oy, dx, dy, cd - eps, stk)) return false;
     const float crs = cross2(so.ex, so.ey, px - so.ax, py - so.ay);
     int side = (0.0f < crs) - (crs < 0.0f);
     const float uv = dot2(spx - so.ax, spy - so.ay, so.ex, so.ey) * so.inv_len2;
@@ -82,7 +83,7 @@ __device__ __forceinline__ void source_eval(const DevSource &src, float x, float
 
 __device__ __forceinline__ void uniform_direction(bool on_n, float nx, float ny, Pcg &rng, float &dirx, float &diry,
                                                   float &pdf, float &alpha);
-template <bool TREE, class STK>
+template <bool TREE, bool UNI, class STK>
 __device__ __forceinline__ bool ray_closest(const DevMesh &m, float ox, float oy, float dx, float dy, float tmax, float &t_out,
                                             int &idx_out, const STK &stk);
 
@@ -91,7 +92,7 @@ __device__ __forceinline__ bool ray_closest(const DevMesh &m, float ox, float oy
 // rejection sampler of HarmonicGreenBall<2> (util/green.h:44-73: two draws per trial, at most
 // 1000 trials), the source value there.  Returns true and the term to ADD to the solution when
 // the sampled point lies inside the star-shaped region.
-template <bool TREE, class STK>
+template <bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ bool source_sample(const DevSource &src, const DevMesh &nm, float eps, float px, float py, float R_B,
                                               bool on_n, float nx, float ny, float thp, Pcg &rng, const STK &stk, float &cr,
                                               float &cg, float &cb)
@@ -102,7 +103,7 @@ __device__ __forceinline__ bool source_sample(const DevSource &src, const DevMes
     if (nm.n_segs > 0) {
         float t;
         int hi;
-        if (ray_closest<TREE>(nm, px + eps * dirx, py + eps * diry, dirx, diry, dist, t, hi, stk)) dist = fminf(t, dist);
+        if (ray_closest<TREE, UNI>(nm, px + eps * dirx, py + eps * diry, dirx, diry, dist, t, hi, stk)) dist = fminf(t, dist);
     }
     const float norm = R_B * R_B / 4.0f, bound = 1.5f / R_B;
     float r = 0.0f;
@@ -153,7 +154,7 @@ __device__ __forceinline__ void uniform_direction(bool on_n, float nx, float ny,
 
 // The tail of oneStepWalk (integrator/uniform/integrator.cu:479-513): move R_B along the
 // direction, or to the first Neumann hit of the ray started at x (+ eps n on the boundary).
-template <bool TREE, class STK>
+template <bool TREE, bool UNI = false, class STK>
 __device__ __forceinline__ bool walk_advance(const DevMesh &nm, float eps, float px, float py, float R_B, bool on_n,
                                              float nx, float ny, float dirx, float diry, const STK &stk, float &nxt_x,
                                              float &nxt_y, float &hnx, float &hny)
@@ -171,7 +172,7 @@ __device__ __forceinline__ bool walk_advance(const DevMesh &nm, float eps, float
     if (nm.n_segs > 0) {
         float t;
         int hi;
-        hit = ray_closest<TREE>(nm, cxp, cyp, dirx, diry, R_B, t, hi, stk);
+        hit = ray_closest<TREE, UNI>(nm, cxp, cyp, dirx, diry, R_B, t, hi, stk);
         if (hit) {
             hnx = nm.flat[hi].nx;
             hny = nm.flat[hi].ny;

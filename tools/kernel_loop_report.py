@@ -8,6 +8,9 @@ prints, for every kernel whose (mangled or demangled) name matches a pattern, on
   instructions                                   static instruction count
   v_mov, lane_moves, scratch                     v_mov_*, v_readlane/v_writelane and scratch_* among them
   in_loop: {instructions, v_mov, lane_moves, scratch}   the same counts over the basic blocks that lie inside a loop
+  memory, in_loop_memory: {vector_loads, scalar_loads, vmcnt0_waits}
+                                                 global_/flat_/buffer_load_*, s_load_*/s_buffer_load_* and the s_waitcnt that
+                                                 wait for vmcnt(0), over the kernel and over the blocks inside a loop
   loop_list                                      every loop on its own: position, nesting depth, instructions and v_mov with
                                                  and without the loops nested inside it
 
@@ -129,6 +132,20 @@ def _kind(op):
     return None
 
 
+_VMCNT0 = re.compile(r"\bvmcnt\(0\)")
+
+
+def _memory_kind(op, line):
+    """vector_loads / scalar_loads / vmcnt0_waits, or None: what brings operands in and what waits for them"""
+    if op.startswith(("global_load_", "flat_load_", "buffer_load_")):
+        return "vector_loads"
+    if op.startswith(("s_load_", "s_buffer_load_")):
+        return "scalar_loads"
+    if op == "s_waitcnt" and _VMCNT0.search(line):
+        return "vmcnt0_waits"
+    return None
+
+
 def count_function(lines):
     """static instruction counts of one function body, whole and restricted to the blocks inside a loop"""
     label_at = {}
@@ -160,13 +177,21 @@ def count_function(lines):
 
     total = {"instructions": 0, "v_mov": 0, "lane_moves": 0, "scratch": 0}
     loop = dict(total)
+    mem = {"vector_loads": 0, "scalar_loads": 0, "vmcnt0_waits": 0}
+    loop_mem = dict(mem)
     for i, op in instrs:
         k = _kind(op)
-        for d in ([total, loop] if inside(i) else [total]):
+        mk = _memory_kind(op, lines[i])
+        for d, md in ([(total, mem), (loop, loop_mem)] if inside(i) else [(total, mem)]):
             d["instructions"] += 1
             if k:
                 d[k] += 1
+            if mk:
+                md[mk] += 1
     total["in_loop"] = loop
+    # beside in_loop, not inside it: the four counts of in_loop are compared as a whole by tests/test_kernel_codegen.py
+    total["memory"] = mem
+    total["in_loop_memory"] = loop_mem
     total["loops"] = len(merged)
     # every loop on its own (spans that share a head are one loop with several back edges): where it starts, as the number of
     # instructions before its head, how deep it is nested, and what it holds -- `own` without the loops nested inside it.
