@@ -83,6 +83,12 @@ class Adaptive(C.Structure):
     _fields_ = [("batch_spp", C.c_int32), ("min_batches", C.c_int32), ("max_spp", C.c_int32), ("abs_tol", C.c_float), ("rel_tol", C.c_float)]
 
 
+class GradientOut(C.Structure):
+    """wost_gradient_out: host pointers for the host form, device pointers for the _dev form; only grad is required"""
+    _fields_ = [("grad", C.c_void_p), ("grad_stderr", C.c_void_p), ("field_rgb", C.c_void_p), ("radius", C.c_void_p),
+                ("first_pts", C.c_void_p)]
+
+
 class Mesh3Desc(C.Structure):
     """wost3_mesh_desc (include/wost.h)"""
     _fields_ = [("n_verts", C.c_int32), ("n_tris", C.c_int32), ("verts", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_int32)),
@@ -192,7 +198,8 @@ EXPORTS = [
     "wost3_guided_query_network", "wost3_guided_train_set", "wost3_guided_scene",
     "wost_last_error", "wost_version", "wost_mesh_build_check",
 ] + [pre + "points_" + f for pre in ("wost_", "wost3_")
-     for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")]
+     for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")
+     ] + [pre + "solve_gradient_points" + f for pre in ("wost_", "wost3_") for f in ("", "_dev")]
 
 _lib = None
 
@@ -245,6 +252,11 @@ def load():
         getattr(L, pre + "points_adaptive_dev").argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         getattr(L, pre + "points_restart").argtypes = [C.c_void_p]
         getattr(L, pre + "points_progress").argtypes = [C.c_void_p, ip, ip]
+        # the gradient at the caller's points (wost_solve_gradient_points & co.)
+        getattr(L, pre + "solve_gradient_points").argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GradientOut),
+                                                               C.POINTER(Stats)]
+        getattr(L, pre + "solve_gradient_points_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                   C.POINTER(GradientOut), C.c_void_p, C.POINTER(Stats)]
     L.wost_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
     L.wost_render_source.argtypes = [C.c_void_p, fp]
     L.wost_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]

@@ -196,6 +196,36 @@ __device__ __forceinline__ Closest closest_triangle(const DevMesh3 &m, V3 q, int
     return T.best;
 }
 
+// The closest triangle to q -- the same point in all 64 lanes -- by a scan of every slot of the leaf level, the lanes sharing
+// them: the exact distances of a leaf visit, the lowest ORIGINAL index among equal ones.  For a walker that strayed so far
+// (DevMesh3::huge2) that all triangles lie within the rounding of one another, where the descent -- its boxes pruned with a
+// relative slack -- opens every box, one lane and one node at a time.  Returns the same answer in every lane.
+__device__ __forceinline__ Closest closest_triangle_wave(const DevMesh3 &m, V3 q)
+{
+    const int lane = threadIdx.x & 63;
+    const int n_slots = 4 << (2 * m.levels);
+    float bd = WOST_INF;
+    int32_t bs = -1, bo = WOST_FAR_INDEX;
+    for (int k = lane; k < n_slots; k += 64) {
+        const int32_t o = m.triOrig[k];
+        if (o == WOST_FAR_INDEX) continue;
+        const float4 a = m.tri[3 * (size_t)k], b = m.tri[3 * (size_t)k + 1], c = m.tri[3 * (size_t)k + 2];
+        const float d = tri_d2(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), q);
+        if (d < bd || (d == bd && o < bo)) {
+            bd = d; bs = k; bo = o;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float od = __shfl_xor(bd, off);
+        const int32_t os = __shfl_xor(bs, off), oo = __shfl_xor(bo, off);
+        if (od < bd || (od == bd && oo < bo)) {
+            bd = od; bs = os; bo = oo;
+        }
+    }
+    return Closest{bd, bs};
+}
+
 // checkPointSide / computeProjectionRatio for triangles
 __device__ __forceinline__ int tri_side(V3 p0, V3 nraw, V3 q)
 {

@@ -1,0 +1,369 @@
+// wost_grad.hip -- the gradient of the solution at a caller's points (wost_grad.h; include/wost.h "The gradient at the caller's
+// points"): the kernel in front of the point solve -- per point the radius of its first ball, per walk a direction
+// and the first point on that ball -- in 2-D and 3-D, the kernel behind it -- per point the weighted reduction of its walks'
+// results and the standard error of that estimate --, and the driver that cuts a call into blocks of floor(n_pixels / spp)
+// points.  Cold path: one thread per point in front, one wave per point behind; the walk kernels do not know of it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "wost_device3.h"
+#include "wost_grad.h"
+
+namespace wost {
+
+#define WOST_NAN __int_as_float(0x7fc00000)
+
+// ---- the kernels in front ----------------------------------------------------------------------------------------------------
+// The distance of a point to a mesh as wost_closest_point answers it, for every lane with `active` (all lanes of the wave must
+// call): the descent seeded with slot 0, or -- beyond huge2, where the descent opens every box -- the scan by the wave, through
+// the ballot loop of init_points_kernel: the same candidates and tie rule, hence the same bits.  An empty mesh: +inf.
+__device__ __forceinline__ float depth0_distance(const DevMesh &m, float x, float y, bool active, uint32_t *stack, int stride)
+{
+    if (m.n_segs <= 0) return WOST_INF;
+    Closest c{WOST_INF, -1};
+    bool huge = false;
+    if (active) {
+        c = slot_candidate(m, 0, x, y);
+        huge = c.d2 > m.huge2;
+        if (!huge) c = closest_point(m, x, y, c, stack, stride);
+    }
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_point_wave(m, __shfl(x, src), __shfl(y, src));
+        if ((int)(threadIdx.x & 63) == src) c = r;
+        hb &= hb - 1;
+    }
+    return sqrtf(c.d2);
+}
+
+// ... and in 3-D, as wost3_closest_point answers it (the descent without a hint).  The mesh is beyond huge2 when the boxes of
+// the root's four children all are: a box is never farther than its triangles, and the scan gives the bits of the descent.
+__device__ __forceinline__ float depth0_distance3(const DevMesh3 &m, V3 q, bool active, const LdsColumn &stk)
+{
+    if (m.n_tris <= 0) return WOST_INF;
+    Closest c{WOST_INF, -1};
+    bool huge = false;
+    if (active) {
+        const float4 LX = m.nodes[0], LY = m.nodes[1], LZ = m.nodes[2], HX = m.nodes[3], HY = m.nodes[4], HZ = m.nodes[5];
+        const float d0 = aabb_d2(LX.x, LY.x, LZ.x, HX.x, HY.x, HZ.x, q), d1 = aabb_d2(LX.y, LY.y, LZ.y, HX.y, HY.y, HZ.y, q);
+        const float d2 = aabb_d2(LX.z, LY.z, LZ.z, HX.z, HY.z, HZ.z, q), d3 = aabb_d2(LX.w, LY.w, LZ.w, HX.w, HY.w, HZ.w, q);
+        huge = fminf(fminf(d0, d1), fminf(d2, d3)) > m.huge2;
+        if (!huge) c = closest_triangle(m, q, -1, stk);
+    }
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_triangle_wave(m, v3(__shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src)));
+        if ((int)(threadIdx.x & 63) == src) c = r;
+        hb &= hb - 1;
+    }
+    return sqrtf(c.d2);
+}
+
+// R = min(dD, 0.875 dN); a point is degenerate -- its walks start at the point itself, its gradient is NaN -- when R is not
+// finite or within the shell
+__device__ __forceinline__ float ball_radius(float dD, float dN) { return fminf(dD, kGradNeumannShrink * dN); }
+__device__ __forceinline__ bool ball_degenerate(float R, float eps) { return !(R > eps) || !isfinite(R); }
+
+struct GradPrepParams2 {
+    DevMesh dm, nm;
+    GradPrep p;
+    int32_t stack_stride;
+};
+
+// Thread j takes point first + j of the call: its radius, then spp draws from the stream of pixel seed_base + first + j --
+// walk s of the point gets the direction (cos, sin) of sincos_2pi(u) and the first point fmaf(R, n, x).  A point with a
+// non-finite coordinate makes no query; its radius and first points are NaN, so the point step never queues its walks.
+__global__ __launch_bounds__(256) void grad_prep2_kernel(GradPrepParams2 P)
+{
+    extern __shared__ uint32_t lds_stack[];
+    uint32_t *stack = lds_stack + threadIdx.x;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool owned = j < P.p.count;
+    float x = 0.0f, y = 0.0f;
+    if (owned) {
+        x = P.p.pts[2 * (size_t)(P.p.first + j)];
+        y = P.p.pts[2 * (size_t)(P.p.first + j) + 1];
+    }
+    const bool finite = isfinite(x) && isfinite(y);
+    const float dD = depth0_distance(P.dm, x, y, owned && finite, stack, P.stack_stride);
+    const float dN = depth0_distance(P.nm, x, y, owned && finite, stack, P.stack_stride);
+    if (!owned) return;
+    const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
+    const bool degenerate = ball_degenerate(R, P.p.eps);
+    P.p.radius[j] = R;
+    Pcg rng{0, 1};
+    pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
+    float *dirs = P.p.dirs + 2 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 2 * (size_t)j * P.p.spp;
+    for (int s = 0; s < P.p.spp; ++s) {
+        float c, sn;
+        sincos_2pi(pcg_next_float(rng), c, sn);
+        dirs[2 * s] = c; dirs[2 * s + 1] = sn;
+        fp[2 * s] = !finite ? WOST_NAN : degenerate ? x : __builtin_fmaf(R, c, x);
+        fp[2 * s + 1] = !finite ? WOST_NAN : degenerate ? y : __builtin_fmaf(R, sn, y);
+    }
+}
+
+struct GradPrepParams3 {
+    DevMesh3 dm, nm;
+    GradPrep p;
+};
+
+// The same in 3-D: two draws per walk, the walk's own uniform direction (step3_b0)
+__global__ __launch_bounds__(256) void grad_prep3_kernel(GradPrepParams3 P)
+{
+    extern __shared__ uint32_t lds_stack[];
+    const LdsColumn stk(lds_stack + threadIdx.x, blockDim.x);
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool owned = j < P.p.count;
+    V3 q = v3(0.0f, 0.0f, 0.0f);
+    if (owned) q = ld3(P.p.pts + 3 * (size_t)(P.p.first + j));
+    const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    const float dD = depth0_distance3(P.dm, q, owned && finite, stk);
+    const float dN = depth0_distance3(P.nm, q, owned && finite, stk);
+    if (!owned) return;
+    const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
+    const bool degenerate = ball_degenerate(R, P.p.eps);
+    P.p.radius[j] = R;
+    Pcg rng{0, 1};
+    pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
+    float *dirs = P.p.dirs + 3 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 3 * (size_t)j * P.p.spp;
+    for (int s = 0; s < P.p.spp; ++s) {
+        const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
+        float c, sn;
+        sincos_2pi(u2, c, sn);
+        const float z = 1 - 2 * u1, r = sqrtf(1 - z * z);
+        const V3 n = v3(r * c, r * sn, z);
+        const V3 f = !finite ? v3(WOST_NAN, WOST_NAN, WOST_NAN) : degenerate ? q : madd3(q, R, n);
+        dirs[3 * s] = n.x; dirs[3 * s + 1] = n.y; dirs[3 * s + 2] = n.z;
+        fp[3 * s] = f.x; fp[3 * s + 1] = f.y; fp[3 * s + 2] = f.z;
+    }
+}
+
+// the stack columns of a block of 256 threads for the deeper of the two trees
+static size_t prep_lds(int32_t levels_d, bool has_d, int32_t levels_n, bool has_n)
+{
+    const int lv = std::max(has_d ? levels_d : 1, has_n ? levels_n : 1);
+    return (size_t)(3 * lv + 1) * 256 * sizeof(uint32_t);
+}
+
+int grad_prep2(const DevMesh &dm, const DevMesh &nm, const GradPrep &p, hipStream_t stream)
+{
+    const GradPrepParams2 P{dm, nm, p, 256};
+    hipLaunchKernelGGL(grad_prep2_kernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), prep_lds(dm.levels, dm.n_segs > 0, nm.levels, nm.n_segs > 0),
+                       stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+int grad_prep3(const DevMesh3 &dm, const DevMesh3 &nm, const GradPrep &p, hipStream_t stream)
+{
+    const GradPrepParams3 P{dm, nm, p};
+    hipLaunchKernelGGL(grad_prep3_kernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), prep_lds(dm.levels, dm.n_tris > 0, nm.levels, nm.n_tris > 0),
+                       stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+// ---- the kernel behind ---------------------------------------------------------------------------------------------------------
+struct GradReduceParams {
+    // the block: count points of spp walks each -- results (RGB), directions and first points per walk, radii per point
+    const float *w, *dirs, *first_pts, *radius;
+    int32_t first, count, spp;
+    float eps;
+    // the call's outputs, indexed by the point's index in the call; nullptr: not wanted (grad always is)
+    float *grad, *grad_stderr, *field, *radius_out, *first_out;
+};
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One wave per point, its lanes over the point's walks, three passes (the mean, the estimate, its two-pass variance):
+//   mean_c = sum_s W_sc / S,   t_s = n_sk (W_sc - mean_c),   grad_kc = DIM / (R (S - 1)) sum_s t_s,
+//   stderr_kc = DIM / R sqrt(sum_s (t_s - mean t)^2 / (S - 1) / S);   a degenerate point: NaN, NaN and its mean.
+// The sums run in fp64 and the results are rounded once.  The control variate subtracts numbers of the size of u and leaves
+// differences of the size of R |grad u|: a mean rounded to fp32 would sit in t_s with |u| / (R |grad u|) ulps, and the standard
+// error of a point close to the boundary would lose that factor of its precision.
+template <int DIM>
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (j >= P.count) return;      // (the whole wave)
+    const int S = P.spp;
+    const size_t i = (size_t)P.first + (size_t)j;
+    const float *w = P.w + 3 * (size_t)j * S, *d = P.dirs + DIM * (size_t)j * S;
+    const double dS = (double)S;
+    double mean[3] = {0.0, 0.0, 0.0};
+    for (int s = lane; s < S; s += 64)
+        for (int c = 0; c < 3; ++c) mean[c] += (double)w[3 * s + c];
+    for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
+    double t[DIM * 3], v[DIM * 3];
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = v[e] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) t[e] += (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]);
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) {
+            const double dev = (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]) - t[e] / dS;
+            v[e] += dev * dev;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) v[e] = wave_sum(v[e]);
+    const float R = P.radius[j];
+    const bool degenerate = ball_degenerate(R, P.eps);
+    if (lane == 0) {
+        const double scale = (double)DIM / ((double)R * (dS - 1.0)), scale_se = (double)DIM / (double)R;
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) {
+            P.grad[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
+            if (P.grad_stderr) P.grad_stderr[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)(scale_se * sqrt(v[e] / (dS - 1.0) / dS));
+        }
+        if (P.field)
+            for (int c = 0; c < 3; ++c) P.field[3 * i + c] = (float)mean[c];
+        if (P.radius_out) P.radius_out[i] = R;
+    }
+    if (P.first_out)
+        for (int s = lane; s < DIM * S; s += 64) P.first_out[(size_t)DIM * S * i + s] = P.first_pts[(size_t)DIM * S * j + s];
+}
+
+// ---- the driver ----------------------------------------------------------------------------------------------------------------
+void grad_free(GradScratch &s)
+{
+    if (s.mem) (void)hipFree(s.mem);
+    for (hipEvent_t e : s.ev)
+        if (e) (void)hipEventDestroy(e);
+    s = GradScratch{};
+}
+
+static int grad_ready(GradScratch &s, size_t n_pixels, int dim)
+{
+    if (s.mem) return WOST_OK;
+    const size_t floats = n_pixels * (size_t)(2 * dim + 3) + n_pixels / 2 + 1;
+    for (hipEvent_t &e : s.ev)
+        if (!e) WOST_TRY(hipEventCreate(&e));
+    WOST_TRY(hipMalloc(&s.mem, floats * sizeof(float)));
+    s.first = static_cast<float *>(s.mem);
+    s.dirs = s.first + n_pixels * dim;
+    s.w = s.dirs + n_pixels * dim;
+    s.radius = s.w + n_pixels * 3;
+    return WOST_OK;
+}
+
+int grad_check(const void *h, const float *pts, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+               const wost_gradient_out *out)
+{
+    if (!h || !pts || !out || !out->grad) return set_error(WOST_ERR_INVALID, "null argument");
+    if (n < 0) return set_error(WOST_ERR_INVALID, "negative number of points");
+    if (seed_width <= 0) return set_error(WOST_ERR_INVALID, "seed_width must be positive");
+    if (seed_base < 0 || walk_seed_base < 0) return set_error(WOST_ERR_INVALID, "seed_base and walk_seed_base must be >= 0");
+    if ((int64_t)seed_base + n > ((int64_t)1 << 28)) return set_error(WOST_ERR_INVALID, "seed_base + n must be at most 2^28");
+    return WOST_OK;
+}
+
+// the rules that need the handle: its spp setting S and its frame
+int grad_check_handle(const GradCall &c, int32_t n, int32_t seed_base, int32_t walk_seed_base)
+{
+    const std::string name = std::string(c.prefix) + "solve_gradient_points: ";
+    if (c.has_source)
+        return set_error(WOST_ERR_UNSUPPORTED, name + "a scene with a source term is not covered (the in-ball term of the gradient is not built)");
+    const int64_t S = c.spp, walks = S * (int64_t)n;
+    if (S < 2) return set_error(WOST_ERR_INVALID, name + "the handle's spp is " + std::to_string(S) + ", the estimator needs spp >= 2 walks per point");
+    if ((uint64_t)S > (uint64_t)c.n_pixels)
+        return set_error(WOST_ERR_INVALID, name + "the handle's spp (" + std::to_string(S) + ") exceeds n_pixels (" + std::to_string(c.n_pixels) +
+                                               "): a point's walks must fit one point step");
+    if ((int64_t)walk_seed_base + walks > ((int64_t)1 << 28))
+        return set_error(WOST_ERR_INVALID, name + "walk_seed_base + n * spp (" + std::to_string((int64_t)walk_seed_base + walks) + ") must be at most 2^28");
+    if ((int64_t)seed_base < (int64_t)walk_seed_base + walks && (int64_t)walk_seed_base < (int64_t)seed_base + n)
+        return set_error(WOST_ERR_INVALID, name + "the seeds of the directions [seed_base, seed_base + n) overlap those of the walks [walk_seed_base, "
+                                                  "walk_seed_base + n * spp)");
+    return WOST_OK;
+}
+
+int grad_solve_dev(const GradCall &c, const float *pts_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                   const wost_gradient_out &out, hipStream_t stream, wost_stats *stats)
+{
+    const auto t0 = HostClock::now();
+    WOST_TRY(hipSetDevice(c.device));
+    GradScratch &s = *c.scratch;
+    int rc = grad_ready(s, c.n_pixels, c.dim);
+    if (rc != WOST_OK) return rc;
+    const int32_t S = c.spp, per_block = (int32_t)(c.n_pixels / (size_t)S);
+    wost_stats total{};
+    for (int32_t a = 0; a < n; a += per_block) {
+        const int32_t m = std::min(per_block, n - a), walks = m * S;
+        WOST_TRY(hipEventRecord(s.ev[0], stream));
+        if ((rc = c.prep(GradPrep{pts_dev, a, m, S, seed_base, seed_width, c.eps, s.radius, s.dirs, s.first}, stream)) != WOST_OK) return rc;
+        WOST_TRY(hipEventRecord(s.ev[1], stream));
+        WOST_TRY(hipMemsetAsync(s.w, 0, (size_t)walks * 3 * sizeof(float), stream));
+        wost_stats st{};
+        if ((rc = c.walk(s.first, walks, walk_seed_base + a * S, seed_width, s.w, stream, &st)) != WOST_OK) return rc;
+        const GradReduceParams rp{s.w, s.dirs, s.first, s.radius, a, m, S, c.eps, out.grad, out.grad_stderr, out.field_rgb, out.radius, out.first_pts};
+        WOST_TRY(hipEventRecord(s.ev[2], stream));
+        if (c.dim == 2) hipLaunchKernelGGL(grad_reduce_kernel<2>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, rp);
+        else hipLaunchKernelGGL(grad_reduce_kernel<3>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, rp);
+        WOST_TRY(hipGetLastError());
+        WOST_TRY(hipEventRecord(s.ev[3], stream));
+        WOST_TRY(hipEventSynchronize(s.ev[3]));
+        float ms_front = 0.0f, ms_behind = 0.0f;
+        WOST_TRY(hipEventElapsedTime(&ms_front, s.ev[0], s.ev[1]));
+        WOST_TRY(hipEventElapsedTime(&ms_behind, s.ev[2], s.ev[3]));
+        total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
+        total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
+        total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
+        total.kernel_ms += st.kernel_ms + (double)ms_front + (double)ms_behind;
+        total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
+    }
+    if (stats) {
+        *stats = total;
+        stamp_solve_ms(stats, t0);
+    }
+    return WOST_OK;
+}
+
+int grad_solve_host(const GradCall &c, const float *pts, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                    const wost_gradient_out &out, wost_stats *stats)
+{
+    const auto t0 = HostClock::now();
+    WOST_TRY(hipSetDevice(c.device));
+    const size_t N = (size_t)n, dim = (size_t)c.dim, S = (size_t)c.spp;
+    Batch b{c.stream};
+    float *d_pts = nullptr;
+    wost_gradient_out d{};
+    WOST_TRY(b.in(pts, N * dim, &d_pts));
+    WOST_TRY(b.out(&d.grad, N * dim * 3));
+    if (out.grad_stderr) WOST_TRY(b.out(&d.grad_stderr, N * dim * 3));
+    if (out.field_rgb) WOST_TRY(b.out(&d.field_rgb, N * 3));
+    if (out.radius) WOST_TRY(b.out(&d.radius, N));
+    if (out.first_pts) WOST_TRY(b.out(&d.first_pts, N * S * dim));
+    int rc = grad_solve_dev(c, d_pts, n, seed_base, walk_seed_base, seed_width, d, c.stream, stats);
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(c.stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    WOST_TRY(b.fetch(out.grad, d.grad, N * dim * 3));
+    WOST_TRY(b.fetch(out.grad_stderr, d.grad_stderr, N * dim * 3));
+    WOST_TRY(b.fetch(out.field_rgb, d.field_rgb, N * 3));
+    WOST_TRY(b.fetch(out.radius, d.radius, N));
+    WOST_TRY(b.fetch(out.first_pts, d.first_pts, N * S * dim));
+    if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
+    return rc;
+}
+
+}  // namespace wost

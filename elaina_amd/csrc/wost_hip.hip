@@ -38,6 +38,7 @@
 #include "wost_device.h"
 #include "wost_internal.h"
 #include "wost_carry.h"
+#include "wost_grad.h"
 #include "wost_walk.h"
 #include "wost_quad.h"
 #include "wost_coop.h"
@@ -1460,6 +1461,8 @@ struct wost_context {
     wost::CarryState carry;
     // ... and, beside it, the carried point list (wost_points_carry & co.)
     wost::PointList list;
+    // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
+    wost::GradScratch grad;
 };
 
 namespace wost {
@@ -1519,6 +1522,7 @@ static void destroy_ctx(wost_context *c)
     if (c->cursor) (void)hipFree(c->cursor);
     carry_free(c->carry);
     points_free(c->list);
+    grad_free(c->grad);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -2129,6 +2133,7 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
 // device map carry_select (nullptr: every pixel).  carry_append: not the first walk of its call, it appends to last_launches.
 // A point step with carry_more > 0 is the same on a chunk of the handle's carried point list (wost_points_more & co.): the
 // buffers are the list's, the map is indexed by the point's index in the list.
+// spp > 0: the samples of a step that carries nothing, whatever the handle's setting (the walks of a gradient call: one each).
 struct FirstStep {
     int32_t pixel_begin, pixel_end, shard_index, shard_count;
     const float *points;
@@ -2136,6 +2141,7 @@ struct FirstStep {
     int32_t carry_done, carry_more;
     const uint8_t *carry_select;
     bool carry_append;
+    int32_t spp = 0;
 };
 static FirstStep frame_step(int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, int32_t carry_done = 0,
                             int32_t carry_more = 0, const uint8_t *carry_select = nullptr, bool carry_append = false)
@@ -2157,6 +2163,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     const CarryState &cs = fs.points ? c->list.carry : c->carry;
     DevSettings st = c->dst;
     if (carried) st.spp = fs.carry_more;
+    else if (fs.spp > 0) st.spp = fs.spp;
 
     if (fs.points) {
         const InitPointsParams ip{c->dm.view, st, c->queue[0], c->counts + 0, fs.points, field_dev, fs.first, fs.n, fs.seed_base, fs.seed_width, g.bs,
@@ -2336,6 +2343,19 @@ static CarryWalk points_walk(PointListCtx<wost_context> *x, int32_t, int32_t)
 
 static const PointCalls<wost_context> kPoints{{"wost_points_", points_walk, [](PointListCtx<wost_context> *x) { x->h->last_launches.clear(); }}, 2};
 
+// ---- the gradient at the caller's points (the driver and its kernels: wost_grad.hip; the body of the entry points: grad_entry) ----
+// what the 2-D context adds: the kernel in front on its meshes, and a point step of one sample per walk on the handle's queues
+static GradCall grad_call(wost_context *c)
+{
+    GradCall g{"wost_", 2, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->stream, &c->grad, nullptr, nullptr};
+    g.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep2(c->dm.view, c->nm.view, p, stream); };
+    g.walk = [c](const float *first_pts, int32_t n_walks, int32_t seed_base, int32_t seed_width, float *w_rgb, hipStream_t stream, wost_stats *stats) {
+        const FirstStep fs{0, 0, 0, 1, first_pts, 0, n_walks, seed_base, seed_width, 0, 0, nullptr, false, 1};
+        return run_solve(c, fs, w_rgb, 0, stream, stats);
+    };
+    return g;
+}
+
 extern "C" {
 
 int wost_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width)
@@ -2507,6 +2527,18 @@ int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t see
     WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
     if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
     return rc;
+}
+
+int wost_solve_gradient_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                               const wost_gradient_out *out, wost_stats *stats)
+{
+    return grad_entry(h, grad_call, 2, pts_xy, true, n, seed_base, walk_seed_base, seed_width, out, nullptr, stats);
+}
+
+int wost_solve_gradient_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                                   const wost_gradient_out *out, void *stream, wost_stats *stats)
+{
+    return grad_entry(h, grad_call, 2, pts_xy_dev, false, n, seed_base, walk_seed_base, seed_width, out, stream, stats);
 }
 
 int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, int32_t *count)

@@ -365,36 +365,6 @@ __device__ __forceinline__ bool step3(const Walk3Params &P, Lane3 &L, Closest cp
 
 constexpr int kWalk3Threads = 256;
 
-// The closest triangle to q -- the same point in all 64 lanes -- by a scan of every slot of the leaf level, the lanes sharing
-// them: the exact distances of a leaf visit, the lowest ORIGINAL index among equal ones.  For a walker that strayed so far
-// (DevMesh3::huge2) that all triangles lie within the rounding of one another, where the descent -- its boxes pruned with a
-// relative slack -- opens every box, one lane and one node at a time.  Returns the same answer in every lane.
-__device__ __forceinline__ Closest closest_triangle_wave(const DevMesh3 &m, V3 q)
-{
-    const int lane = threadIdx.x & 63;
-    const int n_slots = 4 << (2 * m.levels);
-    float bd = WOST_INF;
-    int32_t bs = -1, bo = WOST_FAR_INDEX;
-    for (int k = lane; k < n_slots; k += 64) {
-        const int32_t o = m.triOrig[k];
-        if (o == WOST_FAR_INDEX) continue;
-        const float4 a = m.tri[3 * (size_t)k], b = m.tri[3 * (size_t)k + 1], c = m.tri[3 * (size_t)k + 2];
-        const float d = tri_d2(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), q);
-        if (d < bd || (d == bd && o < bo)) {
-            bd = d; bs = k; bo = o;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float od = __shfl_xor(bd, off);
-        const int32_t os = __shfl_xor(bs, off), oo = __shfl_xor(bo, off);
-        if (od < bd || (od == bd && oo < bo)) {
-            bd = od; bs = os; bo = oo;
-        }
-    }
-    return Closest{bd, bs};
-}
-
 // WAVE = true: the closest-point queries are answered by the wave as a whole as well (closest_triangle_pool) -- every trip of
 // the loop is then "all queries of the wave, then one step for every walker": no lane waits for another's descent.
 // POINTS = true: the launch of a point solve (wost3_solve_points) -- a refill takes a caller's point instead of a pixel of the frame.
@@ -772,6 +742,7 @@ static void destroy3(wost3_context *c)
     if (c->cursor) (void)hipFree(c->cursor);
     carry_free(c->carry);
     points_free(c->list);
+    grad_free(c->grad);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -848,6 +819,7 @@ struct FirstStep3 {
     int32_t carry_done = 0, carry_more = 0;
     const int32_t *carry_ids = nullptr;
     int32_t carry_n_ids = 0;
+    int32_t spp = 0;         // > 0: the samples of a step that carries nothing, whatever the handle's setting (the walks of a gradient call: one each)
 };
 
 static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, int32_t field_base, hipStream_t stream, wost_stats *stats)
@@ -869,6 +841,7 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
         P.tiled = (!fs.points && pixel_begin == 0 && pixel_end == (int32_t)c->n_pixels && ((c->settings.width | c->settings.height) & 7) == 0) ? 1 : 0;
         P.points = fs.points; P.seed_base = fs.seed_base; P.seed_width = fs.seed_width;
         const bool carried = fs.carry_more > 0;
+        if (!carried && fs.spp > 0) P.st.spp = fs.spp;
         if (carried) {
             const CarryState &cs = fs.points ? c->list.carry : c->carry;
             P.st.spp = fs.carry_more;
@@ -946,6 +919,20 @@ static CarryWalk points_walk3(PointListCtx<wost3_context> *x, int32_t, int32_t)
 }
 
 static const PointCalls<wost3_context> kPoints3{{"wost3_points_", points_walk3, nullptr}, 3};
+
+// ---- the gradient at the caller's points (the driver and its kernels: wost_grad.hip; the body of the entry points: grad_entry) ----
+// what the 3-D context adds: the kernel in front on its meshes, and a point step of one sample per walk
+static GradCall grad_call3(wost3_context *c)
+{
+    GradCall g{"wost3_", 3, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->stream, &c->grad, nullptr, nullptr};
+    g.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep3(c->dm.view, c->nm.view, p, stream); };
+    g.walk = [c](const float *first_pts, int32_t n_walks, int32_t seed_base, int32_t seed_width, float *w_rgb, hipStream_t stream, wost_stats *stats) {
+        FirstStep3 fs{0, n_walks, 0, 1, first_pts, seed_base, seed_width};
+        fs.spp = 1;
+        return run_solve3(c, fs, w_rgb, 0, stream, stats);
+    };
+    return g;
+}
 
 extern "C" {
 
@@ -1151,6 +1138,18 @@ int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t 
     WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
     if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
     return rc;
+}
+
+int wost3_solve_gradient_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                                const wost_gradient_out *out, wost_stats *stats)
+{
+    return grad_entry(h, grad_call3, 3, pts_xyz, true, n, seed_base, walk_seed_base, seed_width, out, nullptr, stats);
+}
+
+int wost3_solve_gradient_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                                    const wost_gradient_out *out, void *stream, wost_stats *stats)
+{
+    return grad_entry(h, grad_call3, 3, pts_xyz_dev, false, n, seed_base, walk_seed_base, seed_width, out, stream, stats);
 }
 
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist, float *out_uv,

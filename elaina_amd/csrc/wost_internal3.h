@@ -13,6 +13,7 @@
 #include "wost_device3.h"
 #include "wost_internal.h"
 #include "wost_carry.h"
+#include "wost_grad.h"
 
 namespace wost {
 
@@ -59,6 +60,8 @@ struct wost3_context {
     wost::CarryState carry;
     // ... and, beside it, the carried point list (wost3_points_carry & co.)
     wost::PointList list;
+    // the scratch of the gradient calls (wost3_solve_gradient_points & co., wost_grad.h)
+    wost::GradScratch grad;
 };
 
 namespace wost {

@@ -64,6 +64,45 @@ class UniformCalls:
         return self._dev_solve("solve_points_dev", C.c_void_p(points_ptr), int(n), int(seed_base), self._seed_width(seed_width),
                                C.c_void_p(field_ptr), C.c_void_p(stream_ptr or 0))
 
+    # -- the gradient at the caller's points (wost_solve_gradient_points & co.) -------------------
+    GRADIENT_OUTPUTS = ("stderr", "field", "radius", "first_pts")
+
+    def _gradient_seeds(self, n, seed_base, walk_seed_base, seed_width):
+        seed_base = int(seed_base)
+        return seed_base, int(seed_base + n if walk_seed_base is None else walk_seed_base), self._seed_width(seed_width)
+
+    def solve_gradient_points(self, points, seed_base=0, walk_seed_base=None, seed_width=None, want=("stderr", "field", "radius"), spp=None):
+        """grad u at the caller's points ([n, dim] floats) by the walk-on-spheres estimator with spp walks per point
+        (wost_solve_gradient_points, wost3_solve_gradient_points; include/wost.h has the estimator).  Point i draws its directions
+        from the stream of pixel seed_base + i, its walks run on the streams of pixels walk_seed_base + i * spp + s (default:
+        seed_base + n, right behind the directions') in a frame seed_width wide (default: the frame's width).  Returns a dict of
+        float32 arrays: "grad" (n, dim, 3) = d u_c / d x_k, and what `want` names of "stderr" (n, dim, 3), "field" (n, 3) the
+        mean of the point's walks, "radius" (n,) and "first_pts" (n, spp, dim) -- the last sized by `spp` (default: the spp the
+        integrator was made with; pass it after set_option("spp", ...))"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        n, S = len(p), int(self.settings.samplesPerPixel if spp is None else spp)
+        unknown = set(want) - set(self.GRADIENT_OUTPUTS)
+        if unknown:
+            raise ValueError("unknown gradient outputs %s (known: %s)" % (sorted(unknown), ", ".join(self.GRADIENT_OUTPUTS)))
+        shapes = {"grad": (n, self._dim, 3), "stderr": (n, self._dim, 3), "field": (n, 3), "radius": (n,), "first_pts": (n, S, self._dim)}
+        out = {k: np.zeros(shapes[k], np.float32) for k in ("grad",) + tuple(k for k in self.GRADIENT_OUTPUTS if k in want)}
+        ptr = {k: out[k].ctypes.data if k in out else None for k in shapes}
+        go = capi.GradientOut(ptr["grad"], ptr["stderr"], ptr["field"], ptr["radius"], ptr["first_pts"])
+        fn, name = self._fn("solve_gradient_points")
+        st = Stats()
+        _check(fn(self._handle, _fp(p), n, *self._gradient_seeds(n, seed_base, walk_seed_base, seed_width), C.byref(go), C.byref(st)), name)
+        self.last_stats = st.as_dict()
+        return out
+
+    def solve_gradient_points_dev(self, points_ptr, n, grad_ptr, stream_ptr=None, seed_base=0, walk_seed_base=None, seed_width=None,
+                                  stderr_ptr=None, field_ptr=None, radius_ptr=None, first_pts_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: n * dim floats of points, n * dim * 3 of grad and, where
+        given, n * dim * 3 of stderr, n * 3 of field, n of radius, n * spp * dim of first points; a point with a non-finite
+        coordinate is never walked and answers NaN in every output.  Returns the stats as a dict"""
+        go = capi.GradientOut(grad_ptr, stderr_ptr or None, field_ptr or None, radius_ptr or None, first_pts_ptr or None)
+        return self._dev_solve("solve_gradient_points_dev", C.c_void_p(points_ptr), int(n),
+                               *self._gradient_seeds(int(n), seed_base, walk_seed_base, seed_width), C.byref(go), C.c_void_p(stream_ptr or 0))
+
     # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
     def solve_more(self, more_spp):
         """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at

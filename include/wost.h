@@ -264,6 +264,49 @@ int wost_points_adaptive_dev(wost_handle h, const wost_adaptive *a, float *field
 int wost_points_restart(wost_handle h);
 int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done);
 
+/* The gradient at the caller's points: grad u at n points (pts_xy: n * 2 floats) by the walk-on-spheres estimator
+ *     grad u(x) = (d / R) E[ n u(x + R n) ]      (u harmonic in the ball B(x, R), n uniform on the unit sphere, d = DIM = 2 or 3)
+ * with S = the handle's spp walks per point.  The reference has no counterpart.
+ *   - Radius.  dD, dN: the distances wost_closest_point answers for the point on the Dirichlet and the Neumann mesh, the same bits
+ *     (+inf for a mesh the scene does not have); R = min(dD, 0.875f * dN), so the first ball never touches the Neumann boundary.
+ *     A point is degenerate when R <= eps_shell or R is not finite.
+ *   - Directions.  S consecutive draws from the PCG32 stream of pixel seed_base + i in a frame seed_width wide: in 2-D one float
+ *     u and n = (cos, sin)(2 pi u), in 3-D u1, u2 and the walk's own uniform direction (z = 1 - 2 u1, r = sqrt(1 - z z),
+ *     n = (r cos, r sin, z)(2 pi u2)).
+ *   - First points.  y_s = fmaf(R, n_s, x) per component (a degenerate point: y_s = x), and walk (i, s) is wost_solve_points of ONE
+ *     sample at y_s on the stream of pixel walk_seed_base + i * S + s in a frame seed_width wide; its result is W_s (RGB).
+ *   - Per point, axis k and channel c: mean_c = sum_s W_sc / S, t_s = n_sk (W_sc - mean_c),
+ *         grad = d / (R (S - 1)) sum_s t_s          (the sample mean is a control variate; S - 1 keeps the estimate unbiased)
+ *         grad_stderr = (d / R) sqrt( sum_s (t_s - mean t)^2 / (S - 1) / S )
+ *     and field_rgb = mean.  A degenerate point has NaN grad and grad_stderr and still its mean.  The fp32 sums are taken in an
+ *     order of the library's choice.
+ *   - A list is walked in blocks of floor(width * height / S) points; a point's outputs do not depend on the cut, and a caller who
+ *     cuts a list at point a moves seed_base by a and walk_seed_base by a * S and gets the same bits.  wost_stats sums the blocks
+ *     (walks_started is n * S for finite points; kernel_ms includes the two kernels around the walks); wost_last_launches
+ *     describes the walks of the LAST block only.
+ *   - Not covered: a scene with a source term (the in-ball term of the gradient is not built): WOST_ERR_UNSUPPORTED.  Neumann
+ *     data needs nothing extra.  The frame's mask does not apply.  The carried frame solve, the carried point list and the options
+ *     of the handle are left alone.
+ *   Arguments, checked in this order before the handle is read or a device is asked for: null h / pts / out / out->grad; n < 0;
+ *     seed_width <= 0; seed_base < 0 or walk_seed_base < 0; seed_base + n > 2^28; the host forms then scan for a non-finite
+ *     coordinate (WOST_ERR_INVALID names the first bad point); n == 0: WOST_OK and zeroed stats.  With the handle: S < 2;
+ *     S > width * height; walk_seed_base + n * S > 2^28; [seed_base, seed_base + n) overlapping [walk_seed_base, walk_seed_base +
+ *     n * S): WOST_ERR_INVALID, the message names the quantity.  A refused call writes no output.
+ * wost_solve_gradient_points: host arrays.  wost_solve_gradient_points_dev: DEVICE arrays in pts and out, the caller's stream as
+ * in wost_solve_points_dev; the call returns after the stream work has completed; a point with a non-finite coordinate is never
+ * walked, all its outputs are NaN. */
+typedef struct wost_gradient_out {   /* host pointers for the host form, device pointers for the _dev form; only grad is required */
+    float *grad;          /* n * DIM * 3: grad[(i*DIM + k)*3 + c] = d u_c / d x_k at point i                      */
+    float *grad_stderr;   /* n * DIM * 3 or NULL: the standard error of each entry                                */
+    float *field_rgb;     /* n * 3 or NULL: the mean of the point's walks                                         */
+    float *radius;        /* n or NULL: the ball radius R_i                                                       */
+    float *first_pts;     /* n * S * DIM or NULL: the S first points of point i, walk s at (i*S + s)*DIM          */
+} wost_gradient_out;
+int wost_solve_gradient_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t walk_seed_base,
+                               int32_t seed_width, const wost_gradient_out *out, wost_stats *stats);
+int wost_solve_gradient_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base,
+                                   int32_t seed_width, const wost_gradient_out *out, void *stream, wost_stats *stats);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -530,7 +573,8 @@ int wost_guided_destroy(wost_guided_handle h);
 
 /* The launches of the last wost_solve / wost_solve_sharded / wost_solve_points[_dev] of this handle, in order (bench.py prices the dominant one against
  * the roofline; the reference has no counterpart: its solveImpl issues 2 + 5 * depth full-frame launches per sample,
- * integrator/uniform/integrator.cu:529-623).  Writes min(*count, capacity) records. */
+ * integrator/uniform/integrator.cu:529-623).  Writes min(*count, capacity) records.  After wost_solve_gradient_points[_dev]: the
+ * walk launches of the call's LAST block of points only. */
 typedef struct wost_launch_info {
     int32_t kind;             /* WOST_LAUNCH_* */
     uint32_t walkers;         /* walkers (pixels in flight) the launch started with                                      */
@@ -650,6 +694,12 @@ int wost3_points_adaptive(wost3_handle h, const wost_adaptive *a, float *field_r
 int wost3_points_adaptive_dev(wost3_handle h, const wost_adaptive *a, float *field_rgb_dev, void *stream, wost_stats *stats);
 int wost3_points_restart(wost3_handle h);
 int wost3_points_progress(wost3_handle h, int32_t *n_points, int32_t *spp_done);
+/* The gradient at the caller's points in 3-D: wost_solve_gradient_points with the same rules in every clause (pts_xyz: n * 3
+ * floats; DIM = 3, so grad holds n * 9 floats; the distances are wost3_closest_point's; every block is one launch). */
+int wost3_solve_gradient_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t walk_seed_base,
+                                int32_t seed_width, const wost_gradient_out *out, wost_stats *stats);
+int wost3_solve_gradient_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base,
+                                    int32_t seed_width, const wost_gradient_out *out, void *stream, wost_stats *stats);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
