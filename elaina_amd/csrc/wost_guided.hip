@@ -37,6 +37,7 @@
 #include "wost_internal.h"
 #include "wost_order.h"
 #include "wost_train.h"
+#include "wost_guided_calls.h"
 #include "wost_net_device.h"
 #include "wost_vmm_device.h"
 #include "wost_walk.h"
@@ -51,14 +52,6 @@ struct GQueue {
     uint32_t *pid;     // pixel id | kOnNeumann; kDead = entry dropped
     float *x, *y, *thp, *nx, *ny, *rb;
     int32_t *hint;     // slot of the closest Dirichlet segment of the previous step
-};
-
-// Counters of a solve.  Atomics on ONE cache line are served one after the other by its L2 channel
-// (measured: about 120 M/s, 270 us for the 16 384 waves of one launch), so the counters exist in
-// kStatCopies copies 256 bytes apart, a wave adds to the copy of its block, and the host sums them.
-constexpr int kStatCopies = 64;
-struct alignas(256) GStatsDev {
-    unsigned long long steps, started, absorbed, truncated, nhits, guided, net_points;
 };
 
 // HIP-event pairs around selected launches, read back lazily: a pair is only waited for when its
@@ -150,7 +143,7 @@ struct GParams {
     float *net_in;            // [2 * slot]
     const float *net_out;     // [33][net_ld]: output o of queue slot s at net_out[o * net_ld + s]
     size_t net_ld;
-    GStatsDev *stats;
+    GuidedStatsDev *stats;    // (wost_guided_calls.h)
     int32_t n_pixels;
     int32_t depth;
     int32_t stack_stride;
@@ -277,7 +270,7 @@ __device__ __forceinline__ void wave_count(bool pred, unsigned long long *counte
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(counter, (unsigned long long)__popcll(bal));
 }
 
-__device__ __forceinline__ GStatsDev *my_stats(GStatsDev *stats) { return stats + (blockIdx.x & (kStatCopies - 1)); }
+__device__ __forceinline__ GuidedStatsDev *my_stats(GuidedStatsDev *stats) { return stats + (blockIdx.x & (kGuidedStatCopies - 1)); }
 
 // ---- start of a sample: every unmasked pixel queues its evaluation point ---------------------
 // (reference prepareSolve :112-128 on the first sample, reset + generateEvaluationPoints
@@ -497,7 +490,7 @@ __global__ __launch_bounds__(256) void tail_kernel(GParams P)
     }
     const uint32_t s_steps = wave_sum(steps), s_abs = wave_sum(absorbed), s_tr = wave_sum(truncated), s_hit = wave_sum(hits);
     if ((threadIdx.x & 63) == 0) {
-        GStatsDev *st = my_stats(P.stats);
+        GuidedStatsDev *st = my_stats(P.stats);
         if (s_steps) atomicAdd(&st->steps, (unsigned long long)s_steps);
         if (s_abs) atomicAdd(&st->absorbed, (unsigned long long)s_abs);
         if (s_tr) atomicAdd(&st->truncated, (unsigned long long)s_tr);
@@ -1046,7 +1039,7 @@ __global__ __launch_bounds__(fused_threads(HALF)) void guided_sample_kernel(GPar
     const uint32_t s_steps = wave_sum(c_steps), s_st = wave_sum(c_started), s_abs = wave_sum(c_abs), s_tr = wave_sum(c_trunc),
                    s_hit = wave_sum(c_hits), s_g = wave_sum(c_guided), s_net = wave_sum(c_net);
     if (lane == 0) {
-        GStatsDev *st = my_stats(P.stats);
+        GuidedStatsDev *st = my_stats(P.stats);
         if (s_steps) atomicAdd(&st->steps, (unsigned long long)s_steps);
         if (s_st) atomicAdd(&st->started, (unsigned long long)s_st);
         if (s_abs) atomicAdd(&st->absorbed, (unsigned long long)s_abs);
@@ -1063,10 +1056,11 @@ using namespace wost;
 
 struct wost_guided {
     int device = 0;
-    wost_guided_settings gs{};
+    wost_guided_settings s{};
     wost_handle scene = nullptr;       // owns the uploaded meshes
     wost_net_handle net = nullptr;
     SceneView view{};
+    hipStream_t stream = nullptr;      // the scene's
     size_t n_pixels = 0;
     std::vector<void *> allocs;
     GQueue q[2]{};
@@ -1082,13 +1076,12 @@ struct wost_guided {
     uint32_t *cursor = nullptr;        // fused sample kernel: next pixel slot of the launch
     uint32_t *pstate = nullptr;        // fused sample kernel, several samples per launch: arrived / complete counts per pixel
     unsigned long long *dbg = nullptr; // fused sample kernel: WOST_GUIDED_DEBUG timeline
-    GStatsDev *stats = nullptr;
+    GuidedStatsDev *stats = nullptr;
     uint32_t *block_sums = nullptr;
     int n_train_blocks = 0, n_train_pixels = 0;
     uint64_t host_rng_state = 0, host_rng_inc = 3;   // mGuiding.sampler of the reference (trainPixelOffset draws)
     TrainSet ts{};
     uint32_t last_train_n = 0;
-    uint32_t last_train_offset = 0;    // trainPixelOffset of the most recent solve
     GAabb box{};
     wost_sync_fn sync = nullptr;       // shared-network mode: collective hooks of the caller
     void *sync_user = nullptr;
@@ -1116,18 +1109,6 @@ struct wost_guided {
     float *pts_buf = nullptr;             // wost_guided_solve_points: the caller's host list on the device (grown on demand)
     size_t pts_cap = 0;                   // points it holds
 };
-
-// release one buffer of device_alloc before the handle goes (a buffer that is replaced by a larger one)
-static void gfree_one(wost_guided *g, void *p)
-{
-    if (!p) return;
-    for (size_t i = 0; i < g->allocs.size(); ++i)
-        if (g->allocs[i] == p) {
-            g->allocs.erase(g->allocs.begin() + (long)i);
-            (void)hipFree(p);
-            return;
-        }
-}
 
 static void guided_free(wost_guided *g)
 {
@@ -1169,7 +1150,7 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
     wost_guided *g = new (std::nothrow) wost_guided();
     if (!g) return set_error(WOST_ERR_NOMEM, "out of host memory");
     g->device = device;
-    g->gs = *s;
+    g->s = *s;
     auto bail = [&](int code) {
         guided_free(g);
         return code;
@@ -1181,6 +1162,7 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
     rc = wost_net_create(device, net, net_seed, &g->net);
     if (rc != WOST_OK) return bail(rc);
     g->view = scene_view(g->scene);
+    g->stream = g->view.stream;
     g->n_pixels = (size_t)s->width * s->height;
     const size_t N = g->n_pixels;
     {
@@ -1201,7 +1183,7 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
     }
     GA(g->counts, 2); GA(g->rng, N); GA(g->sol, 3 * N); GA(g->field, 3 * N);
     GA(g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * N);
-    GA(g->net_in, 2 * N); GA(g->net_out, 33 * N); GA(g->cur_depth, N); GA(g->hint0, N); GA(g->stats, kStatCopies);
+    GA(g->net_in, 2 * N); GA(g->net_out, 33 * N); GA(g->cur_depth, N); GA(g->hint0, N); GA(g->stats, kGuidedStatCopies);
     GA(g->dbg, 4); GA(g->d0_d2, N); GA(g->cursor, 1); GA(g->pstate, N);
     // sized for offset 0 (the largest set); the offset of a solve may be drawn per solve (run_guided)
     g->n_train_pixels = (int)((N + (size_t)s->train_pixel_stride - 1) / (size_t)s->train_pixel_stride);
@@ -1235,13 +1217,6 @@ int wost_guided_create(const wost_scene_desc *scene, const wost_guided_settings 
 int wost_guided_destroy(wost_guided_handle h)
 {
     guided_free(h);
-    return WOST_OK;
-}
-
-int wost_guided_network(wost_guided_handle h, wost_net_handle *net)
-{
-    if (!h || !net) return set_error(WOST_ERR_INVALID, "null argument");
-    *net = h->net;
     return WOST_OK;
 }
 
@@ -1282,35 +1257,7 @@ int wost_guided_set_option(wost_guided_handle h, const char *key, double value)
     return set_error(WOST_ERR_INVALID, "unknown option '" + k + "'");
 }
 
-int wost_guided_scene(wost_guided_handle h, wost_handle *scene)
-{
-    if (!h || !scene) return set_error(WOST_ERR_INVALID, "null argument");
-    *scene = h->scene;
-    return WOST_OK;
-}
-
-int wost_guided_query_network(wost_guided_handle h, const float *pts, int32_t n, float *raw)
-{
-    if (!h || !pts || !raw || n < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    std::vector<float> xy((size_t)n * 2);
-    const GAabb &b = h->box;
-    for (int i = 0; i < n; ++i) {
-        xy[2 * (size_t)i] = 0.5f + (pts[2 * (size_t)i] - b.cx) / b.ex;
-        xy[2 * (size_t)i + 1] = 0.5f + (pts[2 * (size_t)i + 1] - b.cy) / b.ey;
-    }
-    return wost_net_inference(h->net, xy.data(), n, raw, 1);
-}
-
-int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, float *xy, float *dir, float *solution,
-                          float *dir_pdf, float *normal, uint8_t *on_neumann)
-{
-    if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    WOST_TRY(hipSetDevice(h->device));
-    *n = (int32_t)h->last_train_n;
-    return copy_train_set(h->ts, 2, std::min<size_t>(h->last_train_n, (size_t)capacity), xy, dir, solution, dir_pdf, normal, on_neumann);
-}
-
-}  // extern "C"
+}  // extern "C" (the entry points both dimensions have: at the end of the file)
 
 // ---- the solve driver.  First everything that is fixed for one solve.  guided_plan() fills it once per solve and is the only place that reads the driver's
 // environment switches -- at solve time, not at handle creation: they may change between two solves on one handle.
@@ -1341,21 +1288,8 @@ struct GuidedPlan {
     int train_spp_count;
 };
 
-// the guiding state of sample `sample` of this solve
-static GuidePhase phase_of(const wost_guided *g, const GuidedPlan &pl, int sample)
-{
-    wost_guided_settings s = g->gs;
-    s.train_spp_count = pl.train_spp_count;
-    return phase_at(s, sample);
-}
-
 // what the steps of a solve count and hand to each other
-struct GuidedRun {
-    std::chrono::high_resolution_clock::time_point t_start;
-    uint64_t net_launches_before; int opt_before;      // the network's counters when the solve began
-    uint32_t launches = 0;                  // of this file; the network counts its own
-    double train_ms = 0.0;
-    uint64_t train_samples = 0;
+struct GuidedRun : GuidedRunBase {
     const uint32_t *walk_order = nullptr;   // built once per solve, when the cache of the evaluation points' queries is full ...
     bool d0_valid = false;                  // ... which the first fused launch of the solve fills
 };
@@ -1364,21 +1298,20 @@ struct GuidedRun {
 // H(alf).  These are all the walk instantiations there are:
 //   G_FUSED  guided_sample_kernel<E, T, S, H, P(oints)>   G_SEPARATE  separate_kernel<E, T, S>   G_TAIL  tail_kernel<E, T, S>   G_SAMPLE  sample_kernel<T>
 enum GKernel { G_FUSED, G_SEPARATE, G_TAIL, G_SAMPLE };
-template <bool E, bool T, bool S>
-static const void *guided_kernel_of(GKernel kind, bool half, bool points)
-{
-    if (kind == G_FUSED && points) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, true>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, true>);
-    if (kind == G_FUSED) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, false>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, false>);
-    if (kind == G_SEPARATE) return reinterpret_cast<const void *>(separate_kernel<E, T, S>);
-    return kind == G_TAIL ? reinterpret_cast<const void *>(tail_kernel<E, T, S>) : reinterpret_cast<const void *>(sample_kernel<T>);
-}
+struct GuidedKernelOf {
+    GKernel kind; bool half, points;
+    template <bool E, bool T, bool S>
+    const void *of() const
+    {
+        if (kind == G_FUSED && points) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, true>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, true>);
+        if (kind == G_FUSED) return half ? reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, true, false>) : reinterpret_cast<const void *>(guided_sample_kernel<E, T, S, false, false>);
+        if (kind == G_SEPARATE) return reinterpret_cast<const void *>(separate_kernel<E, T, S>);
+        return kind == G_TAIL ? reinterpret_cast<const void *>(tail_kernel<E, T, S>) : reinterpret_cast<const void *>(sample_kernel<T>);
+    }
+};
 static const void *guided_kernel(GKernel k, const GuidedPlan &pl)
 {
-    const bool h = pl.fused_half, p = pl.job.pts != nullptr;
-    if (pl.emissive && pl.tree) return pl.source ? guided_kernel_of<true, true, true>(k, h, p) : guided_kernel_of<true, true, false>(k, h, p);
-    if (pl.emissive) return pl.source ? guided_kernel_of<true, false, true>(k, h, p) : guided_kernel_of<true, false, false>(k, h, p);
-    if (pl.tree) return pl.source ? guided_kernel_of<false, true, true>(k, h, p) : guided_kernel_of<false, true, false>(k, h, p);
-    return pl.source ? guided_kernel_of<false, false, true>(k, h, p) : guided_kernel_of<false, false, false>(k, h, p);
+    return by_scene_flags(pl.emissive, pl.tree, pl.source, GuidedKernelOf{k, pl.fused_half, pl.job.pts != nullptr});
 }
 // one launch of a walk kernel, counted; Fn: the network image of a G_FUSED launch (the kernels per depth take P alone)
 static void launch_guided(GKernel kind, const GuidedPlan &pl, GuidedRun &run, unsigned grid, hipStream_t st, GParams P, FusedNet Fn = FusedNet{})
@@ -1406,7 +1339,7 @@ static bool wants_frames(const wost_guided *g, const GuidedPlan &pl) { return g-
 
 static GuidedPlan guided_plan(wost_guided *g, const PointJob &job)
 {
-    const wost_guided_settings &s = g->gs;
+    const wost_guided_settings &s = g->s;
     const SceneView &v = g->view;
     const size_t N = job.pts ? (size_t)job.n : g->n_pixels;
     GuidedPlan pl{};
@@ -1423,7 +1356,6 @@ static GuidedPlan guided_plan(wost_guided *g, const PointJob &job)
         x.u = (host_pcg_next(g->host_rng_state, g->host_rng_inc) >> 9) | 0x3f800000u;
         pl.train_offset = (uint32_t)((x.f - 1.0f) * (float)s.train_pixel_stride);
     }
-    g->last_train_offset = pl.train_offset;
     // (a list may be shorter than the offset: no training pixel, and one block that finds none)
     pl.n_train_pixels = N > pl.train_offset ? (int)((N - pl.train_offset + (size_t)s.train_pixel_stride - 1) / (size_t)s.train_pixel_stride) : 0;
     pl.n_train_blocks = std::max(1, (pl.n_train_pixels + 255) / 256);
@@ -1484,7 +1416,7 @@ static GParams base_params(const wost_guided *g, const GuidedPlan &pl, int shard
     // (rec_ld and net_ld are the arrays' allocated leading dimensions; n_pixels counts the walkers of this solve: record set j starts at column j * n_pixels)
     P.rec_ld = N * (size_t)g->rec_sets; P.net_in = g->net_in; P.net_out = g->net_out; P.net_ld = N; P.stats = g->stats; P.n_pixels = (int32_t)pl.n; P.stack_stride = 256;
     P.points = pl.job.pts; P.seed_base = pl.job.seed_base; P.seed_width = pl.job.seed_width;
-    P.max_train_depth = g->gs.max_train_depth; P.train_offset = pl.train_offset; P.train_stride = (uint32_t)g->gs.train_pixel_stride; P.shard_index = shard_index; P.shard_count = shard_count;
+    P.max_train_depth = g->s.max_train_depth; P.train_offset = pl.train_offset; P.train_stride = (uint32_t)g->s.train_pixel_stride; P.shard_index = shard_index; P.shard_count = shard_count;
     P.d0_d2 = g->d0_d2; P.cursor = g->cursor; P.pstate = g->pstate; P.stack_words = pl.fused_stack_words;
     P.wait_weight = pl.wait_weight; P.trav_burst = pl.trav_burst; P.tail_chunk = pl.tail_chunk; P.tail_margin_pct = pl.tail_margin_pct;
     return P;
@@ -1560,7 +1492,7 @@ static int enqueue_train_set(wost_guided *g, const GuidedPlan &pl, GuidedRun &ru
     const GAabb &b = g->box;
     TrainSetParams<2> T{{b.minx, b.miny}, {b.maxx, b.maxy}, {b.cx, b.cy}, {b.ex, b.ey}};
     T.rec = g->rec + (size_t)j * n; T.rec_ld = g->n_pixels * (size_t)g->rec_sets; T.cur_depth = g->cur_depth + (size_t)j * n;
-    T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->gs.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
+    T.train_offset = pl.train_offset; T.train_stride = (uint32_t)g->s.train_pixel_stride; T.n_train_pixels = pl.n_train_pixels; T.block_sums = g->block_sums; T.ts = ts;
     run.launches += 3;
     return wost::enqueue_train_set(T, pl.n_train_blocks, st, g->host_counts + 1 + j);
 }
@@ -1569,7 +1501,7 @@ static int enqueue_train_set(wost_guided *g, const GuidedPlan &pl, GuidedRun &ru
 static int train_passes(wost_guided *g, GuidedRun &run, size_t n, hipStream_t st, const TrainSet &ts)
 {
     g->last_train_n = (uint32_t)n; run.train_samples += n;
-    return wost::train_passes<2>(g->net, ts, n, train_schedule(g->gs), TrainSync{g->sync, g->sync_user}, st, run.launches);
+    return wost::train_passes<2>(g->net, ts, n, train_schedule(g->s), TrainSync{g->sync, g->sync_user}, st, run.launches);
 }
 
 // one record set per sample of a training launch (201 MB each at 1024^2: sized for 288 GB of HBM)
@@ -1579,7 +1511,7 @@ static int grow_record_sets(wost_guided *g, int sets, hipStream_t stream)
     // (the smaller set goes first: nothing on the device uses it between two solves, and group 16 would otherwise hold
     // 3.2 GB next to the 201 MB it replaces until the handle is destroyed)
     WOST_TRY(hipStreamSynchronize(stream));
-    gfree_one(g, g->rec); gfree_one(g, g->cur_depth);
+    device_release(g->allocs, g->rec); device_release(g->allocs, g->cur_depth);
     g->rec = nullptr; g->cur_depth = nullptr; g->rec_sets = 0;
     WOST_TRY(device_alloc(g->allocs, &g->rec, (size_t)kMaxTrainDepth * Rec2::kFields * g->n_pixels * sets));
     WOST_TRY(device_alloc(g->allocs, &g->cur_depth, g->n_pixels * sets));
@@ -1632,7 +1564,7 @@ static int train_pipelined(wost_guided *g, const GuidedPlan &pl, GuidedRun &run,
     std::vector<int> first(1, 0);      // group k: the samples first[k] .. first[k + 1] - 1
     while (first.back() < pl.n_trained) first.push_back(first.back() + group_at(pl, first.back()));
     const int n_groups = (int)first.size() - 1;
-    const GuidePhase ph = phase_of(g, pl, 0);
+    const GuidePhase ph = phase_of(g->s, pl.train_spp_count, 0);
     // (the training stream starts behind whatever the walk stream has been given so far)
     WOST_TRY(hipEventRecord(g->ev_ts, stream));
     WOST_TRY(hipStreamWaitEvent(B, g->ev_ts, 0));
@@ -1705,7 +1637,7 @@ static int samples_this_launch(const wost_guided *g, const GuidedPlan &pl, const
     if (!ph.training) {
         // nothing is trained between the remaining samples: one launch runs them all, up to the next intermediate frame the caller asked for
         int last = sample;
-        while (last < g->gs.spp - 1 && !frame_due(g, pl, last)) ++last;
+        while (last < g->s.spp - 1 && !frame_due(g, pl, last)) ++last;
         n_run = std::min(last - sample + 1, pl.samples_per_launch);
     }
     n_run = std::min(n_run, 0xffff);      // a pixel's state word counts the samples of a launch in 16 bits (arrived << 16 | complete)
@@ -1716,7 +1648,7 @@ static int samples_this_launch(const wost_guided *g, const GuidedPlan &pl, const
 // needs the network any more.
 static int walk_per_depth(wost_guided *g, const GuidedPlan &pl, GuidedRun &run, GParams P, const GuidePhase &ph, int sample, hipStream_t stream)
 {
-    const wost_guided_settings &s = g->gs;
+    const wost_guided_settings &s = g->s;
     const int N = pl.n;
     P.training = ph.training ? 1 : 0; P.uniform_fraction = ph.uniform_fraction; P.first_sample = sample == 0;
     int cur = 0;     // queue holding the evaluation points of this depth
@@ -1776,41 +1708,19 @@ static int train_after_walk(wost_guided *g, const GuidedPlan &pl, GuidedRun &run
     return WOST_OK;
 }
 
-// resolve, the copies of the field, the counters folded and the stats
-static int finish_guided(wost_guided *g, const GuidedPlan &pl, const GuidedRun &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
-{
-    const int N = pl.n;
-    if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 2, N, (float)g->gs.spp, g->field, stream);
-    else launch_resolve(g->sol, N, (float)g->gs.spp, g->field, stream);
-    WOST_TRY(hipGetLastError());
-    if (field_host) WOST_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (field_dev) WOST_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    std::vector<GStatsDev> copies(kStatCopies);
-    WOST_TRY(hipMemcpyAsync(copies.data(), g->stats, kStatCopies * sizeof(GStatsDev), hipMemcpyDeviceToHost, stream));
-    WOST_TRY(hipStreamSynchronize(stream));
-    wost_guided_stats out{};
-    for (const GStatsDev &c : copies) {
-        out.walk_steps += c.steps; out.walks_started += c.started; out.walks_absorbed += c.absorbed; out.walks_truncated += c.truncated;
-        out.neumann_hits += c.nhits; out.guided_steps += c.guided; out.net_points += c.net_points;
-    }
-    out.train_samples = run.train_samples; out.train_ms = run.train_ms; out.net_infer_ms = g->net_events.drain();
-    out.optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - run.opt_before); out.reserved = g->last_train_offset;
-    out.kernel_launches = run.launches + (uint32_t)(net_launch_count(g->net) - run.net_launches_before);
-    out.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
-    if (stats) *stats = out;
-    return WOST_OK;
-}
+// device time of the network-evaluating launches of the solve that ends (finish_guided_solve)
+static double drain_net_events(wost_guided *g) { return g->net_events.drain(); }
 
 // the shared driver: field_host (n*3 floats for the n walkers of the solve, may be null) and/or field_dev (device, n*3); `job`: the
 // caller's points instead of the frame's pixels (no shards then)
 static int run_guided(wost_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats,
-                      const PointJob &job = PointJob{})
+                      const PointJob &job)
 {
-    GuidedRun run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
+    GuidedRun run{{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)}};
     DivisorGuard divisor{g->net};
     WOST_TRY(hipSetDevice(g->device));
-    hipStream_t stream = g->view.stream;
-    WOST_TRY(hipMemsetAsync(g->stats, 0, kStatCopies * sizeof(GStatsDev), stream));
+    hipStream_t stream = g->stream;
+    WOST_TRY(hipMemsetAsync(g->stats, 0, kGuidedStatCopies * sizeof(GuidedStatsDev), stream));
     int rc = sync_rank_count(g);      // (before the plan: a solve that ends here has drawn nothing from the host sampler)
     if (rc != WOST_OK) return rc;
     const GuidedPlan pl = guided_plan(g, job);
@@ -1823,8 +1733,8 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
         if (rc != WOST_OK) return rc;
         sample = pl.n_trained;
     }
-    for (; sample < g->gs.spp; ++sample) {
-        const GuidePhase ph = phase_of(g, pl, sample);
+    for (; sample < g->s.spp; ++sample) {
+        const GuidePhase ph = phase_of(g->s, pl.train_spp_count, sample);
         // both paths give the same results; the fused one is used whenever it exists
         const int n_run = pl.fused ? samples_this_launch(g, pl, ph, sample) : 1;      // samples this iteration covers
         rc = pl.fused ? launch_fused(g, pl, run, P, pl.F, stream, ph, sample, n_run) : walk_per_depth(g, pl, run, P, ph, sample, stream);
@@ -1833,69 +1743,43 @@ static int run_guided(wost_guided *g, int shard_index, int shard_count, float *f
         if (rc == WOST_OK) rc = emit_frame(g, pl, run, stream, sample);
         if (rc != WOST_OK) return rc;
     }
-    return finish_guided(g, pl, run, stream, field_host, field_dev, stats);
+    return finish_guided_solve(g, run, 2, pl.job, pl.train_offset, stream, field_host, field_dev, stats, drain_net_events);
 }
+
+// ---- the entry points both dimensions have (their bodies: GuidedCalls, wost_guided_calls.h).  What 2-D adds: its driver and its box.
+static const GuidedCalls<wost_guided> kGuided{run_guided, 2, [](const wost_guided *g) { return GuidedBox{{g->box.cx, g->box.cy}, {g->box.ex, g->box.ey}}; }};
 
 extern "C" {
 
-int wost_guided_solve(wost_guided_handle g, float *field_rgb, wost_guided_stats *stats)
+int wost_guided_network(wost_guided_handle h, wost_net_handle *net) { return kGuided.network(h, net); }
+
+int wost_guided_scene(wost_guided_handle h, wost_handle *scene) { return kGuided.scene(h, scene); }
+
+int wost_guided_solve(wost_guided_handle h, float *field_rgb, wost_guided_stats *stats) { return kGuided.solve(h, field_rgb, stats); }
+
+int wost_guided_solve_sharded(wost_guided_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, wost_guided_stats *stats)
 {
-    if (!g || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    return run_guided(g, 0, 1, field_rgb, nullptr, stats);
+    return kGuided.solve_sharded(h, shard_index, shard_count, field_rgb_dev, stats);
 }
 
-int wost_guided_solve_sharded(wost_guided_handle g, int32_t shard_index, int32_t shard_count, float *field_rgb_dev,
-                              wost_guided_stats *stats)
-{
-    if (!g || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
-    return run_guided(g, shard_index, shard_count, nullptr, field_rgb_dev, stats);
-}
-
-// the check of a point solve that needs the handle: the per-pixel state, the record sets and the queues are sized by the frame
-static int check_point_capacity(const wost_guided *g, int32_t n)
-{
-    if ((size_t)n > g->n_pixels)
-        return set_error(WOST_ERR_INVALID, "a guided point solve takes at most width * height = " + std::to_string(g->n_pixels) + " points per call (the handle's capacity); got " + std::to_string(n));
-    return WOST_OK;
-}
-
-int wost_guided_solve_points_dev(wost_guided_handle g, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
+int wost_guided_solve_points_dev(wost_guided_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width,
                                  int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats)
 {
-    int rc = check_guided_point_solve(g, pts_xy_dev, field_rgb_dev, n, seed_base, seed_width, train_spp_count);
-    if (rc != WOST_OK) return rc;
-    if (n == 0) {
-        if (stats) *stats = wost_guided_stats{};
-        return WOST_OK;
-    }
-    rc = check_point_capacity(g, n);
-    if (rc != WOST_OK) return rc;
-    return run_guided(g, 0, 1, nullptr, field_rgb_dev, stats, PointJob{pts_xy_dev, n, seed_base, seed_width, train_spp_count});
+    return kGuided.solve_points(h, pts_xy_dev, false, n, seed_base, seed_width, train_spp_count, field_rgb_dev, stats);
 }
 
-int wost_guided_solve_points(wost_guided_handle g, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width,
+int wost_guided_solve_points(wost_guided_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width,
                              int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats)
 {
-    int rc = check_guided_point_solve(g, pts_xy, field_rgb, n, seed_base, seed_width, train_spp_count);
-    if (rc == WOST_OK) rc = check_points_finite(pts_xy, n, 2);
-    if (rc != WOST_OK) return rc;
-    if (n == 0) {
-        if (stats) *stats = wost_guided_stats{};
-        return WOST_OK;
-    }
-    rc = check_point_capacity(g, n);
-    if (rc != WOST_OK) return rc;
-    WOST_TRY(hipSetDevice(g->device));
-    if (g->pts_cap < (size_t)n) {
-        // (nothing on the device reads the list between two solves)
-        gfree_one(g, g->pts_buf);
-        g->pts_buf = nullptr; g->pts_cap = 0;
-        WOST_TRY(device_alloc(g->allocs, &g->pts_buf, (size_t)n * 2));
-        g->pts_cap = (size_t)n;
-    }
-    WOST_TRY(hipMemcpyAsync(g->pts_buf, pts_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, g->view.stream));
-    return run_guided(g, 0, 1, field_rgb, nullptr, stats, PointJob{g->pts_buf, n, seed_base, seed_width, train_spp_count});
+    return kGuided.solve_points(h, pts_xy, true, n, seed_base, seed_width, train_spp_count, field_rgb, stats);
+}
+
+int wost_guided_query_network(wost_guided_handle h, const float *pts, int32_t n, float *raw) { return kGuided.query_network(h, pts, n, raw); }
+
+int wost_guided_train_set(wost_guided_handle h, int32_t capacity, int32_t *n, float *xy, float *dir, float *solution,
+                          float *dir_pdf, float *normal, uint8_t *on_neumann)
+{
+    return kGuided.train_set(h, capacity, n, xy, dir, solution, dir_pdf, normal, on_neumann);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "wost_internal3.h"
 #include "wost_net_device.h"
 #include "wost_train.h"
+#include "wost_guided_calls.h"
 #include "wost_vmm3_device.h"
 
 // =====================================================================================================================
@@ -35,10 +36,6 @@
 namespace wost {
 
 using Rec3 = Rec<3>;                 // the fields of a training record (wost_train.h)
-
-struct alignas(256) GStats3Dev {
-    unsigned long long steps, started, absorbed, truncated, nhits, guided, net_points;
-};
 
 struct G3Box {
     float min[3], max[3];     // scene.aabb: contains()
@@ -70,7 +67,7 @@ struct G3Params {
     const uint32_t *l_pid, *l_count;
     uint32_t *l_next_pid, *l_next_count;
     float *net_in, *net_out;
-    GStats3Dev *stats;
+    GuidedStatsDev *stats;    // (wost_guided_calls.h)
     int32_t training, train_offset, train_stride, max_train_depth;
     int32_t depth, guiding, first_sample, stack_stride;
     int32_t max_guided_depth;      // (g3_fused_kernel: the depths below it ask the network)
@@ -103,7 +100,7 @@ __device__ __forceinline__ WavePool3 g3_pools(const G3Params &P, uint32_t *lds)
     return WavePool3{pw + kPool3OwnerWords, pw + kPool3OwnerWords + P.pool_cap, pw, P.pool_cap};
 }
 
-__device__ __forceinline__ GStats3Dev *g3_stats(GStats3Dev *s) { return s + (blockIdx.x & (kStat3Copies - 1)); }
+__device__ __forceinline__ GuidedStatsDev *g3_stats(GuidedStatsDev *s) { return s + (blockIdx.x & (kGuidedStatCopies - 1)); }
 
 __device__ __forceinline__ void g3_count(bool pred, unsigned long long *counter)
 {
@@ -512,7 +509,7 @@ __device__ __forceinline__ bool g3_sample_body(const G3Params &P, int depth, boo
         }
         P.rng[p] = rng.state;
     }
-    GStats3Dev *st = g3_stats(P.stats);
+    GuidedStatsDev *st = g3_stats(P.stats);
     g3_count(guided, &st->guided);
     g3_count(hit, &st->nhits);
     g3_count(moved && depth == P.st.max_depth - 1, &st->truncated);
@@ -687,7 +684,9 @@ using namespace wost;
 struct wost3_guided {
     int device = 0;
     wost3_handle scene = nullptr;
+    hipStream_t stream = nullptr;       // the scene's
     wost3_guided_settings s{};
+    size_t n_pixels = 0;
     wost_net_handle net = nullptr;
     G3Box box{};
     std::vector<void *> allocs;
@@ -697,7 +696,7 @@ struct wost3_guided {
     int32_t *state = nullptr, *whint = nullptr, *hint0 = nullptr;
     uint8_t *won = nullptr;
     TrainSet ts{};
-    GStats3Dev *stats = nullptr;
+    GuidedStatsDev *stats = nullptr;
     uint32_t *host_word = nullptr;      // pinned
     uint32_t last_train_n = 0;
     uint64_t host_rng = 0;
@@ -736,31 +735,20 @@ struct G3Plan {
     int train_spp_count;
 };
 
-// the guiding state of sample `sample` of this solve
-static GuidePhase phase_of(const wost3_guided *g, const G3Plan &pl, int sample)
-{
-    wost3_guided_settings s = g->s;
-    s.train_spp_count = pl.train_spp_count;
-    return phase_at(s, sample);
-}
-
 // The kernel of a launch: the scene's flags become the template arguments E(missive), T(ree), S(ource).  These are all the walk instantiations there are:
 //   G3_FUSED  g3_fused_kernel<E, T, S>   G3_SEPARATE  g3_separate_kernel<E, T, S>   G3_TAIL  g3_tail_kernel<E, T, S>   G3_SAMPLE  g3_sample_kernel<T>
 enum G3Kernel { G3_FUSED, G3_SEPARATE, G3_TAIL, G3_SAMPLE };
-template <bool E, bool T, bool S>
-static const void *g3_kernel_of(G3Kernel kind)
-{
-    if (kind == G3_FUSED) return reinterpret_cast<const void *>(g3_fused_kernel<E, T, S>);
-    if (kind == G3_SEPARATE) return reinterpret_cast<const void *>(g3_separate_kernel<E, T, S>);
-    return kind == G3_TAIL ? reinterpret_cast<const void *>(g3_tail_kernel<E, T, S>) : reinterpret_cast<const void *>(g3_sample_kernel<T>);
-}
-static const void *g3_kernel(G3Kernel k, const G3Plan &pl)
-{
-    if (pl.emissive && pl.ntree) return pl.source ? g3_kernel_of<true, true, true>(k) : g3_kernel_of<true, true, false>(k);
-    if (pl.emissive) return pl.source ? g3_kernel_of<true, false, true>(k) : g3_kernel_of<true, false, false>(k);
-    if (pl.ntree) return pl.source ? g3_kernel_of<false, true, true>(k) : g3_kernel_of<false, true, false>(k);
-    return pl.source ? g3_kernel_of<false, false, true>(k) : g3_kernel_of<false, false, false>(k);
-}
+struct G3KernelOf {
+    G3Kernel kind;
+    template <bool E, bool T, bool S>
+    const void *of() const
+    {
+        if (kind == G3_FUSED) return reinterpret_cast<const void *>(g3_fused_kernel<E, T, S>);
+        if (kind == G3_SEPARATE) return reinterpret_cast<const void *>(g3_separate_kernel<E, T, S>);
+        return kind == G3_TAIL ? reinterpret_cast<const void *>(g3_tail_kernel<E, T, S>) : reinterpret_cast<const void *>(g3_sample_kernel<T>);
+    }
+};
+static const void *g3_kernel(G3Kernel k, const G3Plan &pl) { return by_scene_flags(pl.emissive, pl.ntree, pl.source, G3KernelOf{k}); }
 
 static G3Plan g3_plan(wost3_guided *g, const PointJob &job)
 {
@@ -829,12 +817,7 @@ static G3Plan g3_plan(wost3_guided *g, const PointJob &job)
 }
 
 // what the steps of a solve count and hand to each other
-struct G3Run {
-    std::chrono::high_resolution_clock::time_point t_start;
-    uint64_t net_launches_before; int opt_before;      // the network's counters when the solve began
-    uint32_t launches = 0;                  // of this file; the network counts its own
-    double train_ms = 0.0; uint64_t train_samples = 0;
-};
+struct G3Run : GuidedRunBase {};
 
 // one launch of a walk kernel, counted (the kernels per depth take P alone; `grid` blocks: the frame's, or the queue's for G3_SAMPLE)
 static void launch_g3(G3Kernel kind, const G3Plan &pl, G3Run &run, unsigned grid, hipStream_t st, G3Params P)
@@ -936,50 +919,25 @@ static int train_after_walk(wost3_guided *g, const G3Plan &pl, G3Run &run, hipSt
     return WOST_OK;
 }
 
-// resolve (not counted), the copies of the field, the counters folded and the stats
-static int finish_guided3(wost3_guided *g, const G3Plan &pl, const G3Run &run, hipStream_t stream, float *field_host, float *field_dev, wost_guided_stats *stats)
-{
-    const int N = pl.n;
-    if (pl.job.pts) launch_resolve_points(g->sol, pl.job.pts, 3, N, (float)g->s.spp, g->field, stream);
-    else launch_resolve(g->sol, N, (float)g->s.spp, g->field, stream);
-    WOST_TRY(hipGetLastError());
-    if (field_host) WOST_TRY(hipMemcpyAsync(field_host, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (field_dev) WOST_TRY(hipMemcpyAsync(field_dev, g->field, (size_t)N * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    std::vector<GStats3Dev> copies(kStat3Copies);
-    WOST_TRY(hipMemcpyAsync(copies.data(), g->stats, kStat3Copies * sizeof(GStats3Dev), hipMemcpyDeviceToHost, stream));
-    WOST_TRY(hipStreamSynchronize(stream));
-    wost_guided_stats out{};
-    for (const GStats3Dev &k : copies) {
-        out.walk_steps += k.steps; out.walks_started += k.started; out.walks_absorbed += k.absorbed; out.walks_truncated += k.truncated;
-        out.neumann_hits += k.nhits; out.guided_steps += k.guided; out.net_points += k.net_points;
-    }
-    out.train_samples = run.train_samples; out.train_ms = run.train_ms;
-    out.optimizer_steps = (uint64_t)(net_optimizer_steps(g->net) - run.opt_before); out.reserved = pl.train_offset;
-    out.kernel_launches = run.launches + (uint32_t)(net_launch_count(g->net) - run.net_launches_before);
-    out.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - run.t_start).count();
-    if (stats) *stats = out;
-    return WOST_OK;
-}
-
 // the shared driver: field_host (n*3 floats for the n walkers of the solve, may be null) and/or field_dev (device, n*3); `job`: the
 // caller's points instead of the frame's pixels (no shards then)
 static int run_guided3(wost3_guided *g, int shard_index, int shard_count, float *field_host, float *field_dev, wost_guided_stats *stats,
-                       const PointJob &job = PointJob{})
+                       const PointJob &job)
 {
-    G3Run run{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)};
+    G3Run run{{std::chrono::high_resolution_clock::now(), net_launch_count(g->net), net_optimizer_steps(g->net)}};
     WOST_TRY(hipSetDevice(g->device));
-    hipStream_t stream = g->scene->stream;
+    hipStream_t stream = g->stream;
     const G3Plan pl = g3_plan(g, job);      // (the draw of the training-pixel offset: before any launch)
-    WOST_TRY(hipMemsetAsync(g->stats, 0, kStat3Copies * sizeof(GStats3Dev), stream));
+    WOST_TRY(hipMemsetAsync(g->stats, 0, kGuidedStatCopies * sizeof(GuidedStatsDev), stream));
     const G3Params P = g3_base_params(g, pl, shard_index, shard_count);
     for (int sample = 0; sample < g->s.spp; ++sample) {
-        const GuidePhase ph = phase_of(g, pl, sample);
+        const GuidePhase ph = phase_of(g->s, pl.train_spp_count, sample);
         // both paths give the same results
         int rc = pl.fused ? walk_fused(pl, run, P, ph, sample, stream) : walk_per_depth(g, pl, run, P, ph, sample, stream);
         if (rc == WOST_OK && ph.training) rc = train_after_walk(g, pl, run, stream);
         if (rc != WOST_OK) return rc;
     }
-    return finish_guided3(g, pl, run, stream, field_host, field_dev, stats);
+    return finish_guided_solve(g, run, 3, pl.job, pl.train_offset, stream, field_host, field_dev, stats);
 }
 
 extern "C" {
@@ -999,7 +957,7 @@ int wost3_guided_create(const wost3_scene_desc *scene, const wost3_guided_settin
     if (rc != WOST_OK) return rc;
     wost3_guided *g = new (std::nothrow) wost3_guided();
     if (!g) { (void)wost3_destroy(sc); return set_error(WOST_ERR_NOMEM, "out of host memory"); }
-    g->device = device; g->scene = sc; g->s = *s;
+    g->device = device; g->scene = sc; g->stream = sc->stream; g->s = *s; g->n_pixels = (size_t)s->width * s->height;
     g->host_rng = 0x853c49e6748fea9bULL ^ net_seed;
     rc = wost3_net_create(device, net, net_seed, &g->net);
     if (rc != WOST_OK) { g3_free(g); return rc; }
@@ -1013,12 +971,12 @@ int wost3_guided_create(const wost3_scene_desc *scene, const wost3_guided_settin
             g->box.c[a] = (lo + hi) / 2.0f; g->box.e[a] = hi - lo;
         }
     }
-    const size_t N = (size_t)s->width * s->height;
+    const size_t N = g->n_pixels;
     hipError_t e = hipSuccess;
 #define G3A(p, n) if (e == hipSuccess) e = device_alloc(g->allocs, &g->p, (n))
     G3A(rng, N); G3A(sol, 3 * N); G3A(cur_depth, N); G3A(rec, (size_t)kMaxTrainDepth * Rec3::kFields * N); G3A(state, N); G3A(wx, 3 * N); G3A(wn, 3 * N);
     G3A(wthp, N); G3A(wrb, N); G3A(won, N); G3A(whint, N); G3A(hint0, N); G3A(q_pid, N); G3A(l_pid, 2 * N); G3A(q_count, 4); G3A(net_in, 3 * N); G3A(net_out, 41 * N);
-    G3A(field, 3 * N); G3A(stats, kStat3Copies); G3A(block_sums, N / 256 + 4);
+    G3A(field, 3 * N); G3A(stats, kGuidedStatCopies); G3A(block_sums, N / 256 + 4);
 #undef G3A
     if (e == hipSuccess) e = alloc_train_set(g->allocs, g->ts, 3, N * kMaxTrainDepth);
     if (e == hipSuccess) e = hipHostMalloc((void **)&g->host_word, 4 * sizeof(uint32_t));
@@ -1037,102 +995,44 @@ int wost3_guided_destroy(wost3_guided_handle h)
     return WOST_OK;
 }
 
-int wost3_guided_network(wost3_guided_handle h, wost_net_handle *net)
-{
-    if (!h || !net) return set_error(WOST_ERR_INVALID, "null argument");
-    *net = h->net;
-    return WOST_OK;
-}
+}  // extern "C"
 
-int wost3_guided_scene(wost3_guided_handle h, wost3_handle *scene)
-{
-    if (!h || !scene) return set_error(WOST_ERR_INVALID, "null argument");
-    *scene = h->scene;
-    return WOST_OK;
-}
+// ---- the entry points both dimensions have (their bodies: GuidedCalls, wost_guided_calls.h).  What 3-D adds: its driver and its box.
+static const GuidedCalls<wost3_guided> kGuided3{run_guided3, 3, [](const wost3_guided *g) {
+    return GuidedBox{{g->box.c[0], g->box.c[1], g->box.c[2]}, {g->box.e[0], g->box.e[1], g->box.e[2]}};
+}};
 
-int wost3_guided_solve(wost3_guided_handle h, float *field_rgb, wost_guided_stats *stats)
-{
-    if (!h || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    return run_guided3(h, 0, 1, field_rgb, nullptr, stats);
-}
+extern "C" {
+
+int wost3_guided_network(wost3_guided_handle h, wost_net_handle *net) { return kGuided3.network(h, net); }
+
+int wost3_guided_scene(wost3_guided_handle h, wost3_handle *scene) { return kGuided3.scene(h, scene); }
+
+int wost3_guided_solve(wost3_guided_handle h, float *field_rgb, wost_guided_stats *stats) { return kGuided3.solve(h, field_rgb, stats); }
 
 int wost3_guided_solve_sharded(wost3_guided_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, wost_guided_stats *stats)
 {
-    if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
-    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
-    return run_guided3(h, shard_index, shard_count, nullptr, field_rgb_dev, stats);
-}
-
-// the check of a point solve that needs the handle: the per-pixel state, the records and the queues are sized by the frame
-static int check_point_capacity3(const wost3_guided *g, int32_t n)
-{
-    const size_t cap = (size_t)g->s.width * g->s.height;
-    if ((size_t)n > cap)
-        return set_error(WOST_ERR_INVALID, "a guided point solve takes at most width * height = " + std::to_string(cap) + " points per call (the handle's capacity); got " + std::to_string(n));
-    return WOST_OK;
+    return kGuided3.solve_sharded(h, shard_index, shard_count, field_rgb_dev, stats);
 }
 
 int wost3_guided_solve_points_dev(wost3_guided_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width,
                                   int32_t train_spp_count, float *field_rgb_dev, wost_guided_stats *stats)
 {
-    int rc = check_guided_point_solve(h, pts_xyz_dev, field_rgb_dev, n, seed_base, seed_width, train_spp_count);
-    if (rc != WOST_OK) return rc;
-    if (n == 0) {
-        if (stats) *stats = wost_guided_stats{};
-        return WOST_OK;
-    }
-    rc = check_point_capacity3(h, n);
-    if (rc != WOST_OK) return rc;
-    return run_guided3(h, 0, 1, nullptr, field_rgb_dev, stats, PointJob{pts_xyz_dev, n, seed_base, seed_width, train_spp_count});
+    return kGuided3.solve_points(h, pts_xyz_dev, false, n, seed_base, seed_width, train_spp_count, field_rgb_dev, stats);
 }
 
 int wost3_guided_solve_points(wost3_guided_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width,
                               int32_t train_spp_count, float *field_rgb, wost_guided_stats *stats)
 {
-    int rc = check_guided_point_solve(h, pts_xyz, field_rgb, n, seed_base, seed_width, train_spp_count);
-    if (rc == WOST_OK) rc = check_points_finite(pts_xyz, n, 3);
-    if (rc != WOST_OK) return rc;
-    if (n == 0) {
-        if (stats) *stats = wost_guided_stats{};
-        return WOST_OK;
-    }
-    rc = check_point_capacity3(h, n);
-    if (rc != WOST_OK) return rc;
-    WOST_TRY(hipSetDevice(h->device));
-    if (h->pts_cap < (size_t)n) {
-        // (nothing on the device reads the list between two solves)
-        if (h->pts_buf) {
-            h->allocs.erase(std::find(h->allocs.begin(), h->allocs.end(), (void *)h->pts_buf));
-            (void)hipFree(h->pts_buf);
-        }
-        h->pts_buf = nullptr; h->pts_cap = 0;
-        WOST_TRY(device_alloc(h->allocs, &h->pts_buf, (size_t)n * 3));
-        h->pts_cap = (size_t)n;
-    }
-    WOST_TRY(hipMemcpyAsync(h->pts_buf, pts_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->scene->stream));
-    return run_guided3(h, 0, 1, field_rgb, nullptr, stats, PointJob{h->pts_buf, n, seed_base, seed_width, train_spp_count});
+    return kGuided3.solve_points(h, pts_xyz, true, n, seed_base, seed_width, train_spp_count, field_rgb, stats);
 }
 
-// queryNetwork(Vector3f) (exec.cu:175-186, guided/integrator.cu:566-615): the raw mixture parameters (41 per point) of the
-// inference weights at world positions
-int wost3_guided_query_network(wost3_guided_handle h, const float *pts, int32_t n, float *raw)
-{
-    if (!h || !pts || !raw || n < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    std::vector<float> in((size_t)n * 3);
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) in[3 * (size_t)i + a] = 0.5f + (pts[3 * (size_t)i + a] - h->box.c[a]) / h->box.e[a];
-    return wost_net_inference(h->net, in.data(), n, raw, 1);
-}
+int wost3_guided_query_network(wost3_guided_handle h, const float *pts, int32_t n, float *raw) { return kGuided3.query_network(h, pts, n, raw); }
 
-// the training set of the most recent training pass, (pixel, record) order; arrays may be NULL; *n = its size
 int wost3_guided_train_set(wost3_guided_handle h, int32_t capacity, int32_t *n, float *xyz, float *dir, float *solution, float *dir_pdf,
                            float *normal, uint8_t *on_neumann)
 {
-    if (!h || !n || capacity < 0) return set_error(WOST_ERR_INVALID, "bad argument");
-    WOST_TRY(hipSetDevice(h->device));
-    *n = (int32_t)h->last_train_n;
-    return copy_train_set(h->ts, 3, std::min((size_t)capacity, (size_t)h->last_train_n), xyz, dir, solution, dir_pdf, normal, on_neumann);
+    return kGuided3.train_set(h, capacity, n, xyz, dir, solution, dir_pdf, normal, on_neumann);
 }
 
 }  // extern "C"

@@ -114,6 +114,14 @@ hipError_t device_alloc(std::vector<void *> &allocs, T **p, size_t count)
     }
     return e;
 }
+// ... and one of them released before the handle goes (a buffer that is replaced by a larger one); p may be null
+inline void device_release(std::vector<void *> &allocs, void *p)
+{
+    const auto it = std::find(allocs.begin(), allocs.end(), p);
+    if (!p || it == allocs.end()) return;
+    allocs.erase(it);
+    (void)hipFree(p);
+}
 
 // the seven arrays of a training set of up to `capacity` entries in `dim` dimensions
 hipError_t alloc_train_set(std::vector<void *> &allocs, TrainSet &ts, int dim, size_t capacity);

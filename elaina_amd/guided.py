@@ -181,41 +181,56 @@ class _BorrowedNetwork(GuidingNetwork):
         self._h = C.c_void_p()
 
 
-class GuidedIntegrator:
-    """Mirror of GuidedIntegrator<2> (reference integrator/guided/integrator.h:77-256): ctor +
-    resetNetwork, solve(), queryNetwork(); `aabb` is scene.aabb of the JSON configuration."""
+def guided_settings(struct, settings):
+    """a capi.GuidedSettings or capi.Guided3Settings with every field the two have in common filled in (the box is the caller's)"""
+    w, h = settings.frameSize
+    gs = struct(w, h, settings.samplesPerPixel, settings.maxWalkingDepth, settings.epsilonShell, settings.trainSppCount,
+                settings.uniformFractionInTrainingPhase, settings.uniformFractionInGuidingPhase, settings.maxGuidedDepthInTrainingPhase,
+                settings.maxGuidedDepthInGuidingPhase)
+    gs.max_train_depth, gs.batch_size, gs.min_batch_size = settings.maxTrainDepth, settings.batchSize, settings.minBatchSize
+    gs.batches_per_spp, gs.train_pixel_stride = settings.batchPerFrame, settings.trainPixelStride
+    gs.train_pixel_offset, gs.loss_scale = settings.trainPixelOffset, settings.lossScale
+    return gs
 
-    def __init__(self, problem, settings, aabb, network_config=None, seed=42, device=0):
-        from .integrator import scene_desc
-        self.lib = capi.load()
-        self.problem, self.settings = problem, settings
-        keep = []
-        w, h = settings.frameSize
-        sc = scene_desc(keep, problem, w, h)
-        gs = capi.GuidedSettings(w, h, settings.samplesPerPixel, settings.maxWalkingDepth, settings.epsilonShell,
-                                 settings.trainSppCount, settings.uniformFractionInTrainingPhase,
-                                 settings.uniformFractionInGuidingPhase, settings.maxGuidedDepthInTrainingPhase,
-                                 settings.maxGuidedDepthInGuidingPhase)
-        (gs.aabb_min[0], gs.aabb_min[1]), (gs.aabb_max[0], gs.aabb_max[1]) = aabb
-        gs.max_train_depth, gs.batch_size, gs.min_batch_size = settings.maxTrainDepth, settings.batchSize, settings.minBatchSize
-        gs.batches_per_spp, gs.train_pixel_stride = settings.batchPerFrame, settings.trainPixelStride
-        gs.train_pixel_offset, gs.loss_scale = settings.trainPixelOffset, settings.lossScale
-        self.network_config = network_config or default_net_config()
+
+class GuidedCalls:
+    """What GuidedIntegrator and GuidedIntegrator3 have in common: every method whose entry points exist as wost_guided_* and
+    wost3_guided_* (include/wost.h) with the same arguments.  Base of an integrator with .lib, ._handle, .n_pixels, .settings,
+    .network, ._prefix ("wost_guided_" or "wost3_guided_"), ._dim (2 or 3), ._n_out (raw network outputs per point) and ._pos_key
+    (the training set's position key)."""
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name), self._prefix + name
+
+    def _open(self, scene, gs, network_config, seed, device):
+        """the handle of a new integrator and its network, borrowed"""
+        self.network_config = network_config
         self._handle = C.c_void_p()
-        _check(self.lib.wost_guided_create(C.byref(sc), C.byref(gs), C.byref(self.network_config), seed, device,
-                                           C.byref(self._handle)), "wost_guided_create")
+        fn, name = self._fn("create")
+        _check(fn(C.byref(scene), C.byref(gs), C.byref(network_config), seed, device, C.byref(self._handle)), name)
         nh = C.c_void_p()
-        _check(self.lib.wost_guided_network(self._handle, C.byref(nh)), "wost_guided_network")
-        self.network = _BorrowedNetwork(self.lib, nh, self.network_config)
-        self.n_pixels = w * h
-        self.aabb = aabb
-        self.solution = None
-        self.last_stats = None
+        fn, name = self._fn("network")
+        _check(fn(self._handle, C.byref(nh)), name)
+        self.network = _BorrowedNetwork(self.lib, nh, network_config, dims=self._dim)
+        self.n_pixels = self.settings.frameSize[0] * self.settings.frameSize[1]
+        self.solution, self.last_stats = None, None
+
+    def _solve(self, entry, *args):
+        """an entry point whose last argument is the stats -> the stats"""
+        fn, name = self._fn(entry)
+        st = capi.GuidedStats()
+        _check(fn(self._handle, *args, C.byref(st)), name)
+        self.last_stats = st.as_dict()
+        return st
+
+    def _point_seeds(self, seed_base, seed_width, train_spp):
+        width = self.settings.frameSize[0] if seed_width is None else seed_width
+        return int(seed_base), int(width), -1 if train_spp is None else int(train_spp)
 
     def close(self):
         if self._handle:
             self.network.close()
-            self.lib.wost_guided_destroy(self._handle)
+            self._fn("destroy")[0](self._handle)
             self._handle = C.c_void_p()
 
     def __del__(self):
@@ -224,53 +239,80 @@ class GuidedIntegrator:
         except Exception:
             pass
 
-    def set_option(self, key, value):
-        """wost_guided_set_option: "pipeline" 1 = the pipelined training order (sample k + 1 walks with the weights of training
-        pass k - 1 while pass k trains on a second stream; statistically equivalent, never the parity mode)"""
-        _check(self.lib.wost_guided_set_option(self._handle, key.encode(), float(value)), "wost_guided_set_option")
-
     def solve(self):
         """returns wall milliseconds like the reference; the field is in self.solution"""
         field = np.zeros((self.n_pixels, 3), dtype=np.float32)
-        st = capi.GuidedStats()
-        _check(self.lib.wost_guided_solve(self._handle, _fp(field), C.byref(st)), "wost_guided_solve")
+        st = self._solve("solve", _fp(field))
         self.solution = field
-        self.last_stats = st.as_dict()
         return int(st.solve_ms)
 
     def solve_sharded(self, shard_index, shard_count, field_dev_ptr):
         """field_dev_ptr: device pointer (int) to a width*height*3 float buffer; returns the stats"""
-        st = capi.GuidedStats()
-        _check(self.lib.wost_guided_solve_sharded(self._handle, shard_index, shard_count, C.c_void_p(field_dev_ptr),
-                                                  C.byref(st)), "wost_guided_solve_sharded")
-        self.last_stats = st.as_dict()
+        self._solve("solve_sharded", shard_index, shard_count, C.c_void_p(field_dev_ptr))
         return self.last_stats
 
     def solve_points(self, points, seed_base=0, seed_width=None, train_spp=None):
-        """the guided solve at the caller's evaluation points ([n, 2] floats, at most frame width * height of them) instead of the
-        frame's pixels (wost_guided_solve_points): point i takes the place of pixel i of a solve over n pixels, on the random stream of
-        pixel seed_base + i in a frame seed_width wide (default: the frame's width).  train_spp: None = the settings' trainSppCount,
-        otherwise the number of training samples of this call -- 0 probes with the network as it is and leaves it unchanged.
-        Returns the (n, 3) float32 field; the counters are in last_stats"""
-        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        """the guided solve at the caller's evaluation points ([n, dim] floats, at most frame width * height of them) instead of the
+        frame's pixels (wost_guided_solve_points, wost3_guided_solve_points): point i takes the place of pixel i of a solve over n
+        pixels, on the random stream of pixel seed_base + i in a frame seed_width wide (default: the frame's width).  train_spp:
+        None = the settings' trainSppCount, otherwise the number of training samples of this call -- 0 probes with the network as
+        it is and leaves it unchanged.  Returns the (n, 3) float32 field; the counters are in last_stats"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
         field = np.zeros((len(p), 3), dtype=np.float32)
-        st = capi.GuidedStats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost_guided_solve_points(self._handle, _fp(p), len(p), int(seed_base), int(width), -1 if train_spp is None else int(train_spp),
-               _fp(field), C.byref(st)), "wost_guided_solve_points")
-        self.last_stats = st.as_dict()
+        self._solve("solve_points", _fp(p), len(p), *self._point_seeds(seed_base, seed_width, train_spp), _fp(field))
         return field
 
     def solve_points_dev(self, points_ptr, n, field_ptr, seed_base=0, seed_width=None, train_spp=None):
-        """the same on device pointers (ints): n * 2 floats of points, complete when the call is made, and n * 3 floats of field; runs
-        on the integrator's own stream and returns the stats when the work is complete.  A point with a non-finite coordinate is
-        not walked: its field entry is NaN"""
-        st = capi.GuidedStats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost_guided_solve_points_dev(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), int(width),
-               -1 if train_spp is None else int(train_spp), C.c_void_p(field_ptr), C.byref(st)), "wost_guided_solve_points_dev")
-        self.last_stats = st.as_dict()
+        """the same on device pointers (ints): n * dim floats of points, complete when the call is made, and n * 3 floats of field;
+        runs on the integrator's own stream and returns the stats when the work is complete.  A point with a non-finite coordinate
+        is not walked: its field entry is NaN"""
+        self._solve("solve_points_dev", C.c_void_p(points_ptr), int(n), *self._point_seeds(seed_base, seed_width, train_spp), C.c_void_p(field_ptr))
         return self.last_stats
+
+    def train_set(self):
+        """training set of the most recent training pass, (pixel, record) order"""
+        fn, name = self._fn("train_set")
+        n = C.c_int32()
+        _check(fn(self._handle, 0, C.byref(n), None, None, None, None, None, None), name)
+        m, d = n.value, self._dim
+        out = {self._pos_key: np.zeros((m, d), np.float32), "dir": np.zeros((m, d), np.float32),
+               "solution": np.zeros((m, 3), np.float32), "dir_pdf": np.zeros(m, np.float32),
+               "normal": np.zeros((m, d), np.float32), "on_neumann": np.zeros(m, np.uint8)}
+        if m:
+            _check(fn(self._handle, m, C.byref(n), _fp(out[self._pos_key]), _fp(out["dir"]), _fp(out["solution"]), _fp(out["dir_pdf"]),
+                      _fp(out["normal"]), out["on_neumann"].ctypes.data_as(C.POINTER(C.c_uint8))), name)
+        return out
+
+    def queryNetwork(self, p):
+        """raw mixture parameters of the guiding network at world position(s) p (reference
+        integrator.cu:566-615 prints the VMM built from them)"""
+        fn, name = self._fn("query_network")
+        pts = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, self._dim)
+        raw = np.zeros((len(pts), self._n_out), dtype=np.float32)
+        _check(fn(self._handle, _fp(pts), len(pts), _fp(raw)), name)
+        return raw if np.ndim(p) > 1 else raw[0]
+
+
+class GuidedIntegrator(GuidedCalls):
+    """Mirror of GuidedIntegrator<2> (reference integrator/guided/integrator.h:77-256): ctor +
+    resetNetwork, solve(), queryNetwork(); `aabb` is scene.aabb of the JSON configuration."""
+    _prefix, _dim, _n_out, _pos_key = "wost_guided_", 2, 33, "xy"      # (GuidedCalls: the solves, the training set, the network, close)
+
+    def __init__(self, problem, settings, aabb, network_config=None, seed=42, device=0):
+        from .integrator import scene_desc
+        self.lib = capi.load()
+        self.problem, self.settings = problem, settings
+        keep = []
+        sc = scene_desc(keep, problem, *settings.frameSize)
+        gs = guided_settings(capi.GuidedSettings, settings)
+        (gs.aabb_min[0], gs.aabb_min[1]), (gs.aabb_max[0], gs.aabb_max[1]) = aabb
+        self._open(sc, gs, network_config or default_net_config(), seed, device)
+        self.aabb = aabb
+
+    def set_option(self, key, value):
+        """wost_guided_set_option: "pipeline" 1 = the pipelined training order (sample k + 1 walks with the weights of training
+        pass k - 1 while pass k trains on a second stream; statistically equivalent, never the parity mode)"""
+        _check(self.lib.wost_guided_set_option(self._handle, key.encode(), float(value)), "wost_guided_set_option")
 
     def share_network(self):
         """Train ONE network across all ranks of the initialised torch.distributed group
@@ -291,27 +333,3 @@ class GuidedIntegrator:
 
         self._sync = capi.SYNC_FN(sync)       # keep the trampoline alive
         _check(self.lib.wost_guided_set_sync(self._handle, self._sync, None), "wost_guided_set_sync")
-
-    def train_set(self):
-        """training set of the most recent training pass, (pixel, record) order"""
-        n = C.c_int32()
-        _check(self.lib.wost_guided_train_set(self._handle, 0, C.byref(n), None, None, None, None, None, None),
-               "wost_guided_train_set")
-        m = n.value
-        out = {"xy": np.zeros((m, 2), np.float32), "dir": np.zeros((m, 2), np.float32),
-               "solution": np.zeros((m, 3), np.float32), "dir_pdf": np.zeros(m, np.float32),
-               "normal": np.zeros((m, 2), np.float32), "on_neumann": np.zeros(m, np.uint8)}
-        if m:
-            _check(self.lib.wost_guided_train_set(self._handle, m, C.byref(n), _fp(out["xy"]), _fp(out["dir"]),
-                                                  _fp(out["solution"]), _fp(out["dir_pdf"]), _fp(out["normal"]),
-                                                  out["on_neumann"].ctypes.data_as(C.POINTER(C.c_uint8))),
-                   "wost_guided_train_set")
-        return out
-
-    def queryNetwork(self, p):
-        """raw mixture parameters of the guiding network at world position(s) p (reference
-        integrator.cu:566-615 prints the VMM built from them)"""
-        pts = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2)
-        raw = np.zeros((len(pts), 33), dtype=np.float32)
-        _check(self.lib.wost_guided_query_network(self._handle, _fp(pts), len(pts), _fp(raw)), "wost_guided_query_network")
-        return raw if np.ndim(p) > 1 else raw[0]

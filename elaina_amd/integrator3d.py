@@ -7,6 +7,7 @@ import numpy as np
 
 from . import capi
 from .capi import Mesh3Desc, Scene3Desc, Settings, _check, _fp, _ip
+from .guided import GuidedCalls, guided_settings
 from .uniform import UniformCalls
 
 
@@ -190,101 +191,17 @@ def default_net_config3(n_levels=8, base_resolution=8, per_level_scale=1.4049999
                           0.9900000095367432, 1.0000000036274937e-15, 9.999999974752427e-07, 0.949999988079071)
 
 
-class GuidedIntegrator3:
+class GuidedIntegrator3(GuidedCalls):
     """Mirror of GuidedIntegrator<3> (reference integrator/guided/integrator.h:77-256 with DIM = 3; exec.cu:102-122): ctor +
     resetNetwork, solve(), queryNetwork(); `aabb` = scene.aabb ((min xyz), (max xyz)); settings: GuidedIntegratorSettings"""
+    _prefix, _dim, _n_out, _pos_key = "wost3_guided_", 3, 41, "xyz"      # (GuidedCalls: the solves, the training set, the network, close)
 
     def __init__(self, problem, settings, aabb, network_config=None, seed=42, device=0):
-        from .guided import _BorrowedNetwork
         self.lib = capi.load()
         self.problem, self.settings = problem, settings
         keep = []
-        w, h = settings.frameSize
-        sc = scene3_desc(keep, problem, w, h)
-        gs = capi.Guided3Settings(w, h, settings.samplesPerPixel, settings.maxWalkingDepth, settings.epsilonShell, settings.trainSppCount,
-                                  settings.uniformFractionInTrainingPhase, settings.uniformFractionInGuidingPhase,
-                                  settings.maxGuidedDepthInTrainingPhase, settings.maxGuidedDepthInGuidingPhase)
+        sc = scene3_desc(keep, problem, *settings.frameSize)
+        gs = guided_settings(capi.Guided3Settings, settings)
         for k in range(3):
             gs.aabb_min[k], gs.aabb_max[k] = float(aabb[0][k]), float(aabb[1][k])
-        gs.max_train_depth, gs.batch_size, gs.min_batch_size = settings.maxTrainDepth, settings.batchSize, settings.minBatchSize
-        gs.batches_per_spp, gs.train_pixel_stride = settings.batchPerFrame, settings.trainPixelStride
-        gs.train_pixel_offset, gs.loss_scale = settings.trainPixelOffset, settings.lossScale
-        self.network_config = network_config or default_net_config3()
-        self._handle = C.c_void_p()
-        _check(self.lib.wost3_guided_create(C.byref(sc), C.byref(gs), C.byref(self.network_config), seed, device, C.byref(self._handle)),
-               "wost3_guided_create")
-        nh = C.c_void_p()
-        _check(self.lib.wost3_guided_network(self._handle, C.byref(nh)), "wost3_guided_network")
-        self.network = _BorrowedNetwork(self.lib, nh, self.network_config, dims=3)
-        self.n_pixels = w * h
-        self.solution, self.last_stats = None, None
-
-    def close(self):
-        if self._handle:
-            self.network.close()
-            self.lib.wost3_guided_destroy(self._handle)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def solve(self):
-        field = np.zeros((self.n_pixels, 3), dtype=np.float32)
-        st = capi.GuidedStats()
-        _check(self.lib.wost3_guided_solve(self._handle, _fp(field), C.byref(st)), "wost3_guided_solve")
-        self.solution, self.last_stats = field, st.as_dict()
-        return int(st.solve_ms)
-
-    def solve_sharded(self, shard_index, shard_count, field_dev_ptr):
-        st = capi.GuidedStats()
-        _check(self.lib.wost3_guided_solve_sharded(self._handle, shard_index, shard_count, C.c_void_p(field_dev_ptr), C.byref(st)),
-               "wost3_guided_solve_sharded")
-        self.last_stats = st.as_dict()
-        return self.last_stats
-
-    def solve_points(self, points, seed_base=0, seed_width=None, train_spp=None):
-        """the guided solve at the caller's evaluation points ([n, 3] floats, at most frame width * height of them) instead of the
-        frame's pixels (wost3_guided_solve_points): point i takes the place of pixel i of a solve over n pixels, on the random stream of
-        pixel seed_base + i in a frame seed_width wide (default: the frame's width).  train_spp: None = the settings' trainSppCount,
-        otherwise the number of training samples of this call -- 0 probes with the network as it is and leaves it unchanged.
-        Returns the (n, 3) float32 field; the counters are in last_stats"""
-        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        field = np.zeros((len(p), 3), dtype=np.float32)
-        st = capi.GuidedStats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost3_guided_solve_points(self._handle, _fp(p), len(p), int(seed_base), int(width), -1 if train_spp is None else int(train_spp),
-               _fp(field), C.byref(st)), "wost3_guided_solve_points")
-        self.last_stats = st.as_dict()
-        return field
-
-    def solve_points_dev(self, points_ptr, n, field_ptr, seed_base=0, seed_width=None, train_spp=None):
-        """the same on device pointers (ints): n * 3 floats of points, complete when the call is made, and n * 3 floats of field; runs
-        on the integrator's own stream and returns the stats when the work is complete.  A point with a non-finite coordinate is
-        not walked: its field entry is NaN"""
-        st = capi.GuidedStats()
-        width = self.settings.frameSize[0] if seed_width is None else seed_width
-        _check(self.lib.wost3_guided_solve_points_dev(self._handle, C.c_void_p(points_ptr), int(n), int(seed_base), int(width),
-               -1 if train_spp is None else int(train_spp), C.c_void_p(field_ptr), C.byref(st)), "wost3_guided_solve_points_dev")
-        self.last_stats = st.as_dict()
-        return self.last_stats
-
-    def queryNetwork(self, p):
-        pts = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
-        raw = np.zeros((len(pts), 41), dtype=np.float32)
-        _check(self.lib.wost3_guided_query_network(self._handle, _fp(pts), len(pts), _fp(raw)), "wost3_guided_query_network")
-        return raw if np.ndim(p) > 1 else raw[0]
-
-    def train_set(self):
-        n = C.c_int32()
-        _check(self.lib.wost3_guided_train_set(self._handle, 0, C.byref(n), None, None, None, None, None, None), "wost3_guided_train_set")
-        m = n.value
-        out = {"xyz": np.zeros((m, 3), np.float32), "dir": np.zeros((m, 3), np.float32), "solution": np.zeros((m, 3), np.float32),
-               "dir_pdf": np.zeros(m, np.float32), "normal": np.zeros((m, 3), np.float32), "on_neumann": np.zeros(m, np.uint8)}
-        if m:
-            _check(self.lib.wost3_guided_train_set(self._handle, m, C.byref(n), _fp(out["xyz"]), _fp(out["dir"]), _fp(out["solution"]),
-                                                   _fp(out["dir_pdf"]), _fp(out["normal"]),
-                                                   out["on_neumann"].ctypes.data_as(C.POINTER(C.c_uint8))), "wost3_guided_train_set")
-        return out
+        self._open(sc, gs, network_config or default_net_config3(), seed, device)
