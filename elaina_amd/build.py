@@ -46,7 +46,7 @@ def build_library(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     headers.append(os.path.join(_HERE, "..", "include", "wost.h"))
     # developer knob: extra -D definitions for kernel-tuning experiments (WOST_HIPCC_DEFS="-DX=1 -DY=2")
-    flags = [f for f in HIPCC_FLAGS if f != "-shared"] + os.environ.get("WOST_HIPCC_DEFS", "").split()
+    flags = _library_flags()
     # objects are only reused under the flags they were compiled with: a library carrying experimental -D variants must
     # never be mistaken for the default build by the next plain build (and the other way round)
     stamp = os.path.join(OBJ_DIR, "flags.stamp")
@@ -79,6 +79,44 @@ def build_library(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     return LIB_PATH
+
+
+def _library_flags():
+    """the flag list build_library() compiles the product's units with"""
+    return [f for f in HIPCC_FLAGS if f != "-shared"] + os.environ.get("WOST_HIPCC_DEFS", "").split()
+
+
+PROBE_SRC = os.path.join(_HERE, "..", "tests", "probe", "wost_probe.hip")
+PROBE_PATH = os.path.join(LIB_DIR, "libwost_probe.so")
+
+
+def build_probe(force=False, verbose=False):
+    """libwost_probe.so (test infrastructure, tests/probe/wost_probe.hip): one elementwise kernel over the inline math functions
+    of csrc/, compiled with exactly the flags of the product's units -- it tests what those flags make of the headers -- and
+    rebuilt when the unit, a header of csrc/ or the flags change."""
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
+    flags = _library_flags()
+    stamp = os.path.join(OBJ_DIR, "probe_flags.stamp")
+    flag_id = hashlib.sha256(" ".join(flags).encode()).hexdigest()
+    try:
+        same_flags = open(stamp).read().strip() == flag_id
+    except OSError:
+        same_flags = False
+    obj = os.path.join(OBJ_DIR, "wost_probe.o")
+    if force or not same_flags or _stale(obj, [PROBE_SRC] + headers):
+        cmd = [_hipcc()] + flags + ["-c", PROBE_SRC, "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        with open(stamp, "w") as f:
+            f.write(flag_id + "\n")
+    if force or _stale(PROBE_PATH, [obj]):
+        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", obj, "-o", PROBE_PATH]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return PROBE_PATH
 
 
 def source_id():
@@ -120,3 +158,4 @@ def build_host(force=False, verbose=False):
 if __name__ == "__main__":
     print(build_host(force=True, verbose=True))
     print(build_library(force=True, verbose=True))
+    print(build_probe(force=True, verbose=True))

@@ -177,6 +177,36 @@ class Pcg(C.Structure):
     _fields_ = [("state", C.c_uint64), ("inc", C.c_uint64)]
 
 
+# the function table of oracle/wost_probe.c and tests/probe/wost_probe.hip:
+# name -> (number, argument dtype, values per argument, result dtype, values per result)
+PROBE_FUNCTIONS = {
+    "sincos_2pi": (0, np.float32, 1, np.float32, 2),
+    "logf": (1, np.float32, 1, np.float32, 1),
+    "expf": (2, np.float32, 1, np.float32, 1),
+    "sincosf": (3, np.float32, 1, np.float32, 2),
+    "cbrt01": (4, np.float32, 1, np.float32, 1),
+    "cospi_d": (5, np.float64, 1, np.float64, 1),
+    "acos_d": (6, np.float64, 1, np.float64, 1),
+    "log_d": (7, np.float64, 1, np.float64, 1),
+    # (initstate, initseq, delta) -> state after seeding, inc, one uint draw, one float draw (its bits), one double draw (its
+    # bits), the state after the three draws, the state after advance(delta), the state after two more discarded draws
+    "pcg": (8, np.uint64, 3, np.uint64, 8),
+    "proposal_r": (9, np.float32, 1, np.float64, 1),
+}
+
+
+def probe_arrays(fn, x):
+    """(number, contiguous argument array, count, empty result array) of one probe call, on either side"""
+    num, din, nin, dout, nout = PROBE_FUNCTIONS[fn]
+    a = np.ascontiguousarray(x, dtype=din)
+    if a.dtype != np.asarray(x).dtype:
+        raise TypeError("probe %s takes %s arguments, got %s" % (fn, np.dtype(din), np.asarray(x).dtype))
+    n = a.size // nin
+    assert a.size == n * nin
+    out = np.empty((n, nout) if nout > 1 else n, dtype=dout)
+    return num, a, n, out
+
+
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -207,6 +237,14 @@ class Oracle:
 
     def version(self):
         return self.lib.wo_version().decode()
+
+    def probe(self, fn, x):
+        """one deterministic math function (a name of PROBE_FUNCTIONS) over an array of arguments, in one call"""
+        num, a, n, out = probe_arrays(fn, x)
+        self.lib.wo_probe.restype = None
+        self.lib.wo_probe.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        self.lib.wo_probe(num, a.ctypes.data, n, out.ctypes.data)
+        return out
 
     # ---- helpers to build the C structs from numpy arrays -------------------
     def _mesh(self, verts, segs, colors):

@@ -555,7 +555,10 @@ int wo_sample_source(const wo_source *src, const pmesh *nm, float eps, float px,
     for (int iter = 0; iter < 1000; ++iter) {
         const float u = wo_pcg_next_float(rng);
         r = wo_pcg_next_float(rng) * R_B;
-        const float pdf = (wo_logf(R_B / r) / WO_2PI) / norm;          /* r == 0 -> +inf: accepted */
+        /* r == 0: wo_logf(+inf) is the finite 128 ln2 = 88.72, not +inf, so that trial is accepted iff u < 236.59 / R_B --
+         * always for R_B <= 236.59, else it may be rejected and drawn again; an accepted r = 0 is clamped below
+         * (tests/test_device_math.py::test_green_sampler_trial_at_radius_zero) */
+        const float pdf = (wo_logf(R_B / r) / WO_2PI) / norm;
         const float pdf_radius = pdf / (1.0f / WO_2PI);
         if (u < pdf_radius / bound) break;
     }

@@ -373,8 +373,7 @@ void wo3_source_eval(const wo3_source *src, float x, float y, float z, float out
     }
 }
 
-/* cube root of x in [0, 1] through the deterministic log / exp (the arithmetic contract's std::cbrt) */
-static float cbrt01(float x) { return x > 0.0f ? wo_expf(wo_logf(x) * (1.0f / 3.0f)) : 0.0f; }
+/* cbrt01 (the arithmetic contract's std::cbrt) lives in wost_detmath.h, where wost_probe.c reaches it too */
 
 typedef struct { uint64_t steps, started, absorbed, truncated, nhits; } pix3_stats;
 
