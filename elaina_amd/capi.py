@@ -89,6 +89,17 @@ class GradientOut(C.Structure):
                 ("first_pts", C.c_void_p)]
 
 
+class GradientCarriedOut(C.Structure):
+    """wost_gradient_carried_out: host pointers for the host forms, device pointers for the _dev forms; only grad is required"""
+    _fields_ = [("grad", C.c_void_p), ("grad_stderr", C.c_void_p), ("field_rgb", C.c_void_p), ("radius", C.c_void_p),
+                ("batches", C.c_void_p)]
+
+
+class GradientAdaptive(C.Structure):
+    """wost_gradient_adaptive (include/wost.h)"""
+    _fields_ = [("min_batches", C.c_int32), ("max_batches", C.c_int32), ("abs_tol", C.c_float), ("rel_tol", C.c_float)]
+
+
 class Mesh3Desc(C.Structure):
     """wost3_mesh_desc (include/wost.h)"""
     _fields_ = [("n_verts", C.c_int32), ("n_tris", C.c_int32), ("verts", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_int32)),
@@ -199,7 +210,9 @@ EXPORTS = [
     "wost_last_error", "wost_version", "wost_mesh_build_check",
 ] + [pre + "points_" + f for pre in ("wost_", "wost3_")
      for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")
-     ] + [pre + "solve_gradient_points" + f for pre in ("wost_", "wost3_") for f in ("", "_dev")]
+     ] + [pre + "solve_gradient_points" + f for pre in ("wost_", "wost3_") for f in ("", "_dev")
+     ] + [pre + "gradient_points_" + f for pre in ("wost_", "wost3_")
+          for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")]
 
 _lib = None
 
@@ -257,6 +270,17 @@ def load():
                                                                C.POINTER(Stats)]
         getattr(L, pre + "solve_gradient_points_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                                    C.POINTER(GradientOut), C.c_void_p, C.POINTER(Stats)]
+        # the carried gradient list (wost_gradient_points_carry & co.)
+        gco, i32 = C.POINTER(GradientCarriedOut), C.c_int32
+        getattr(L, pre + "gradient_points_carry").argtypes = [C.c_void_p, fp, i32, i32, i32, i32, i32, i32, i32]
+        getattr(L, pre + "gradient_points_carry_dev").argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, i32, C.c_void_p]
+        getattr(L, pre + "gradient_points_more").argtypes = [C.c_void_p, C.POINTER(C.c_uint8), gco, C.POINTER(Stats)]
+        getattr(L, pre + "gradient_points_more_dev").argtypes = [C.c_void_p, C.c_void_p, gco, C.c_void_p, C.POINTER(Stats)]
+        getattr(L, pre + "gradient_points_carried").argtypes = [C.c_void_p, gco]
+        getattr(L, pre + "gradient_points_adaptive").argtypes = [C.c_void_p, C.POINTER(GradientAdaptive), gco, C.POINTER(Stats)]
+        getattr(L, pre + "gradient_points_adaptive_dev").argtypes = [C.c_void_p, C.POINTER(GradientAdaptive), gco, C.c_void_p, C.POINTER(Stats)]
+        getattr(L, pre + "gradient_points_restart").argtypes = [C.c_void_p]
+        getattr(L, pre + "gradient_points_progress").argtypes = [C.c_void_p, ip, ip]
     L.wost_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
     L.wost_render_source.argtypes = [C.c_void_p, fp]
     L.wost_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]

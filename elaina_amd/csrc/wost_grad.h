@@ -28,15 +28,54 @@ struct GradScratch {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 void grad_free(GradScratch &s);
+// the scratch allocated (the first call of a handle) for blocks of a frame of n_pixels
+int grad_ready(GradScratch &s, size_t n_pixels, int dim);
+
+// ---- what the kernel behind the walks and the accumulate step of the carried list share -------------------------------------
+// a point is degenerate -- its walks start at the point itself, its gradient is NaN -- when R is not finite or within the shell
+__device__ __forceinline__ bool ball_degenerate(float R, float eps) { return !(R > eps) || !isfinite(R); }
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The first two passes over a point's S walks by the lanes of one wave (all of them call): w their results (RGB), d their
+// directions;  mean_c = sum_s W_sc / S  and  t_kc = sum_s n_sk (W_sc - mean_c), in fp64, the same on every lane.
+template <int DIM>
+__device__ __forceinline__ void grad_point_sums(const float *w, const float *d, int S, int lane, double (&mean)[3], double (&t)[DIM * 3])
+{
+    const double dS = (double)S;
+    for (int c = 0; c < 3; ++c) mean[c] = 0.0;
+    for (int s = lane; s < S; s += 64)
+        for (int c = 0; c < 3; ++c) mean[c] += (double)w[3 * s + c];
+    for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) t[e] += (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]);
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
+}
+// grad_kc = grad_scale * t_kc, rounded to fp32 once
+template <int DIM>
+__device__ __forceinline__ double grad_scale(float R, int S) { return (double)DIM / ((double)R * ((double)S - 1.0)); }
 
 // The kernel in front of the walks, for `count` points of the caller's list from point `first` on, `spp` walks each: point j of
 // the block draws its directions from the stream of pixel seed_base + first + j of a frame seed_width wide.  All pointers on
-// the device; radius, dirs and first_pts are the block's (indexed from 0).
+// the device; radius, dirs and first_pts are the block's (indexed from 0).  sel (a round of the carried gradient list; nullptr:
+// every point) is a map over the caller's list: a point whose byte is 0 makes no query and draws nothing, its radius and first
+// points are NaN, so the point step never queues its walks.  spp == 0 (the bind of a list): the radii alone.
 struct GradPrep {
     const float *pts;
     int32_t first, count, spp, seed_base, seed_width;
     float eps;
     float *radius, *dirs, *first_pts;
+    const uint8_t *sel = nullptr;
 };
 int grad_prep2(const DevMesh &dm, const DevMesh &nm, const GradPrep &p, hipStream_t stream);
 int grad_prep3(const DevMesh3 &dm, const DevMesh3 &nm, const GradPrep &p, hipStream_t stream);
@@ -85,5 +124,110 @@ int grad_entry(H *h, GradCall (*call)(H *), int dim, const float *pts, bool on_h
     if (on_host) return grad_solve_host(c, pts, n, seed_base, walk_seed_base, seed_width, *out, stats);
     return grad_solve_dev(c, pts, n, seed_base, walk_seed_base, seed_width, *out, reinterpret_cast<hipStream_t>(stream), stats);
 }
+
+// ---- the carried gradient list behind wost_gradient_points_carry & co. (wost_grad_carry.hip) --------------------
+// What a handle carries beside the carried frame solve and the carried point list: the library's copy of the caller's points,
+// their radii and the map of the walkable ones (both from the bind), per point the batches K and the fp64 sums of the batches'
+// fp32 results -- G and Q = sum g, sum g^2 per entry of the gradient, F = sum of the batch means per channel --, the work
+// arrays of a call (the selection, a caller's map on its way to the device, the selected points per block, the outputs of a
+// host call) and the rounds done.  One allocation; zeroed sums are a fresh list.
+struct GradList {
+    void *mem = nullptr;
+    double *G = nullptr, *Q = nullptr, *F = nullptr;
+    float *pts = nullptr, *radius = nullptr, *o_grad = nullptr, *o_se = nullptr, *o_field = nullptr;
+    int32_t *K = nullptr;
+    uint32_t *counts = nullptr;                  // n_blocks: the selected points of each block of floor(n_pixels / S) points
+    uint8_t *walkable = nullptr, *sel = nullptr, *want = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};       // around the close / select kernel
+    int dim = 0;
+    int32_t n = 0, S = 0, round_stride = 0, max_rounds = 0, seed_base = 0, walk_seed_base = 0, seed_width = 1;
+    int32_t per_block = 0, n_blocks = 0, rounds = 0;
+    bool stale = false;                          // restarted: K and the sums are zeroed before their next use
+};
+void gradlist_free(GradList &l);
+void gradlist_restart(GradList &l);
+
+// the argument rules that need no look at the handle (include/wost.h), in the order of the header
+int gradlist_check_bind(const void *h, const float *pts, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                        int32_t seed_base, int32_t walk_seed_base, int32_t seed_width);
+int gradlist_check_out(const void *h, const wost_gradient_carried_out *out);
+int gradlist_check_adaptive(const void *h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out);
+// the bind after them (n > 0): the rules that need the handle, then the new list, which replaces the old one when it stands whole
+int gradlist_bind(GradList &l, const GradCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t batch_walks, int32_t round_stride,
+                  int32_t max_rounds, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width, hipStream_t stream);
+// one batch on a selection (select: n bytes on the host or the device, nullptr: every walkable point); out on the same side
+int gradlist_more(GradList &l, const GradCall &c, const uint8_t *select, bool on_host, const wost_gradient_carried_out &out, hipStream_t stream,
+                  wost_stats *stats);
+// batches on the points that have not converged and have room, until none is left or the rounds run out
+int gradlist_adaptive(GradList &l, const GradCall &c, const wost_gradient_adaptive &a, bool on_host, const wost_gradient_carried_out &out,
+                      hipStream_t stream, wost_stats *stats);
+// the state into host arrays
+int gradlist_read(GradList &l, const GradCall &c, const wost_gradient_carried_out &out);
+
+// the bodies of the nine entry points, written once: H is the context (device, stream, glist), `call` what a dimension adds
+template <class H>
+struct GradListCalls {
+    GradCall (*call)(H *);
+    int dim;
+
+    static int bound(const H *h)
+    {
+        if (h->glist.n <= 0) return set_error(WOST_ERR_INVALID, "no gradient list is bound to the handle (gradient_points_carry binds one)");
+        return WOST_OK;
+    }
+    // host points travel on the handle's stream, device points on the caller's
+    int bind(H *h, const float *pts, bool pts_on_host, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds, int32_t seed_base,
+             int32_t walk_seed_base, int32_t seed_width, void *stream) const
+    {
+        int rc = gradlist_check_bind(h, pts, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width);
+        if (rc == WOST_OK && pts_on_host) rc = check_points_finite(pts, n, dim);
+        if (rc != WOST_OK) return rc;
+        if (n == 0) {
+            if (h->glist.mem) {
+                WOST_TRY(hipSetDevice(h->device));
+                gradlist_free(h->glist);
+            }
+            return WOST_OK;
+        }
+        return gradlist_bind(h->glist, call(h), pts, pts_on_host, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width,
+                             pts_on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int more(H *h, const uint8_t *select, bool on_host, const wost_gradient_carried_out *out, void *stream, wost_stats *stats) const
+    {
+        int rc = gradlist_check_out(h, out);
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return gradlist_more(h->glist, call(h), select, on_host, *out, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream), stats);
+    }
+    int adaptive(H *h, const wost_gradient_adaptive *a, bool on_host, const wost_gradient_carried_out *out, void *stream, wost_stats *stats) const
+    {
+        int rc = gradlist_check_adaptive(h, a, out);
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return gradlist_adaptive(h->glist, call(h), *a, on_host, *out, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream), stats);
+    }
+    int carried(H *h, const wost_gradient_carried_out *out) const
+    {
+        int rc = gradlist_check_out(h, out);
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return gradlist_read(h->glist, call(h), *out);
+    }
+    int restart(H *h) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        const int rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        gradlist_restart(h->glist);
+        return WOST_OK;
+    }
+    int progress(H *h, int32_t *n_points, int32_t *rounds_done) const
+    {
+        if (!h || !n_points || !rounds_done) return set_error(WOST_ERR_INVALID, "null argument");
+        *n_points = h->glist.n;
+        *rounds_done = h->glist.rounds;
+        return WOST_OK;
+    }
+};
 
 }  // namespace wost

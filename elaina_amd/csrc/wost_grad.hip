@@ -66,10 +66,8 @@ __device__ __forceinline__ float depth0_distance3(const DevMesh3 &m, V3 q, bool 
     return sqrtf(c.d2);
 }
 
-// R = min(dD, 0.875 dN); a point is degenerate -- its walks start at the point itself, its gradient is NaN -- when R is not
-// finite or within the shell
+// R = min(dD, 0.875 dN) (degenerate or not: ball_degenerate, wost_grad.h)
 __device__ __forceinline__ float ball_radius(float dD, float dN) { return fminf(dD, kGradNeumannShrink * dN); }
-__device__ __forceinline__ bool ball_degenerate(float R, float eps) { return !(R > eps) || !isfinite(R); }
 
 struct GradPrepParams2 {
     DevMesh dm, nm;
@@ -79,7 +77,8 @@ struct GradPrepParams2 {
 
 // Thread j takes point first + j of the call: its radius, then spp draws from the stream of pixel seed_base + first + j --
 // walk s of the point gets the direction (cos, sin) of sincos_2pi(u) and the first point fmaf(R, n, x).  A point with a
-// non-finite coordinate makes no query; its radius and first points are NaN, so the point step never queues its walks.
+// non-finite coordinate makes no query; its radius and first points are NaN, so the point step never queues its walks.  The
+// same holds for a point that the map of a carried list's round (GradPrep::sel) leaves out; it draws nothing either.
 __global__ __launch_bounds__(256) void grad_prep2_kernel(GradPrepParams2 P)
 {
     extern __shared__ uint32_t lds_stack[];
@@ -91,16 +90,22 @@ __global__ __launch_bounds__(256) void grad_prep2_kernel(GradPrepParams2 P)
         x = P.p.pts[2 * (size_t)(P.p.first + j)];
         y = P.p.pts[2 * (size_t)(P.p.first + j) + 1];
     }
+    const bool chosen = owned && (P.p.sel == nullptr || P.p.sel[P.p.first + j] != 0);
     const bool finite = isfinite(x) && isfinite(y);
-    const float dD = depth0_distance(P.dm, x, y, owned && finite, stack, P.stack_stride);
-    const float dN = depth0_distance(P.nm, x, y, owned && finite, stack, P.stack_stride);
+    const float dD = depth0_distance(P.dm, x, y, chosen && finite, stack, P.stack_stride);
+    const float dN = depth0_distance(P.nm, x, y, chosen && finite, stack, P.stack_stride);
     if (!owned) return;
+    float *dirs = P.p.dirs + 2 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 2 * (size_t)j * P.p.spp;
+    if (!chosen) {
+        P.p.radius[j] = WOST_NAN;
+        for (int s = 0; s < 2 * P.p.spp; ++s) fp[s] = WOST_NAN;
+        return;
+    }
     const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
     const bool degenerate = ball_degenerate(R, P.p.eps);
     P.p.radius[j] = R;
     Pcg rng{0, 1};
     pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
-    float *dirs = P.p.dirs + 2 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 2 * (size_t)j * P.p.spp;
     for (int s = 0; s < P.p.spp; ++s) {
         float c, sn;
         sincos_2pi(pcg_next_float(rng), c, sn);
@@ -124,16 +129,22 @@ __global__ __launch_bounds__(256) void grad_prep3_kernel(GradPrepParams3 P)
     const bool owned = j < P.p.count;
     V3 q = v3(0.0f, 0.0f, 0.0f);
     if (owned) q = ld3(P.p.pts + 3 * (size_t)(P.p.first + j));
+    const bool chosen = owned && (P.p.sel == nullptr || P.p.sel[P.p.first + j] != 0);
     const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
-    const float dD = depth0_distance3(P.dm, q, owned && finite, stk);
-    const float dN = depth0_distance3(P.nm, q, owned && finite, stk);
+    const float dD = depth0_distance3(P.dm, q, chosen && finite, stk);
+    const float dN = depth0_distance3(P.nm, q, chosen && finite, stk);
     if (!owned) return;
+    float *dirs = P.p.dirs + 3 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 3 * (size_t)j * P.p.spp;
+    if (!chosen) {
+        P.p.radius[j] = WOST_NAN;
+        for (int s = 0; s < 3 * P.p.spp; ++s) fp[s] = WOST_NAN;
+        return;
+    }
     const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
     const bool degenerate = ball_degenerate(R, P.p.eps);
     P.p.radius[j] = R;
     Pcg rng{0, 1};
     pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
-    float *dirs = P.p.dirs + 3 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 3 * (size_t)j * P.p.spp;
     for (int s = 0; s < P.p.spp; ++s) {
         const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
         float c, sn;
@@ -181,13 +192,6 @@ struct GradReduceParams {
     float *grad, *grad_stderr, *field, *radius_out, *first_out;
 };
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // One wave per point, its lanes over the point's walks, three passes (the mean, the estimate, its two-pass variance):
 //   mean_c = sum_s W_sc / S,   t_s = n_sk (W_sc - mean_c),   grad_kc = DIM / (R (S - 1)) sum_s t_s,
 //   stderr_kc = DIM / R sqrt(sum_s (t_s - mean t)^2 / (S - 1) / S);   a degenerate point: NaN, NaN and its mean.
@@ -204,19 +208,10 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
     const size_t i = (size_t)P.first + (size_t)j;
     const float *w = P.w + 3 * (size_t)j * S, *d = P.dirs + DIM * (size_t)j * S;
     const double dS = (double)S;
-    double mean[3] = {0.0, 0.0, 0.0};
-    for (int s = lane; s < S; s += 64)
-        for (int c = 0; c < 3; ++c) mean[c] += (double)w[3 * s + c];
-    for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
-    double t[DIM * 3], v[DIM * 3];
+    double mean[3], t[DIM * 3], v[DIM * 3];
+    grad_point_sums<DIM>(w, d, S, lane, mean, t);
 #pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) t[e] = v[e] = 0.0;
-    for (int s = lane; s < S; s += 64) {
-#pragma unroll
-        for (int e = 0; e < DIM * 3; ++e) t[e] += (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]);
-    }
-#pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
+    for (int e = 0; e < DIM * 3; ++e) v[e] = 0.0;
     for (int s = lane; s < S; s += 64) {
 #pragma unroll
         for (int e = 0; e < DIM * 3; ++e) {
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
     const float R = P.radius[j];
     const bool degenerate = ball_degenerate(R, P.eps);
     if (lane == 0) {
-        const double scale = (double)DIM / ((double)R * (dS - 1.0)), scale_se = (double)DIM / (double)R;
+        const double scale = grad_scale<DIM>(R, S), scale_se = (double)DIM / (double)R;
 #pragma unroll
         for (int e = 0; e < DIM * 3; ++e) {
             P.grad[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
@@ -252,7 +247,7 @@ void grad_free(GradScratch &s)
     s = GradScratch{};
 }
 
-static int grad_ready(GradScratch &s, size_t n_pixels, int dim)
+int grad_ready(GradScratch &s, size_t n_pixels, int dim)
 {
     if (s.mem) return WOST_OK;
     const size_t floats = n_pixels * (size_t)(2 * dim + 3) + n_pixels / 2 + 1;

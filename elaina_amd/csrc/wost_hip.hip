@@ -1463,6 +1463,8 @@ struct wost_context {
     wost::PointList list;
     // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
     wost::GradScratch grad;
+    // ... and the carried gradient list (wost_gradient_points_carry & co.), which shares it
+    wost::GradList glist;
 };
 
 namespace wost {
@@ -1523,6 +1525,7 @@ static void destroy_ctx(wost_context *c)
     carry_free(c->carry);
     points_free(c->list);
     grad_free(c->grad);
+    gradlist_free(c->glist);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -2356,6 +2359,9 @@ static GradCall grad_call(wost_context *c)
     return g;
 }
 
+// ---- the carried gradient list (wost_gradient_points_carry & co.; the bodies of the entry points: GradListCalls, wost_grad.h) ----
+static const GradListCalls<wost_context> kGradList{grad_call, 2};
+
 extern "C" {
 
 int wost_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width)
@@ -2540,6 +2546,45 @@ int wost_solve_gradient_points_dev(wost_handle h, const float *pts_xy_dev, int32
 {
     return grad_entry(h, grad_call, 2, pts_xy_dev, false, n, seed_base, walk_seed_base, seed_width, out, stream, stats);
 }
+
+int wost_gradient_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                               int32_t seed_base, int32_t walk_seed_base, int32_t seed_width)
+{
+    return kGradList.bind(h, pts_xy, true, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width, nullptr);
+}
+
+int wost_gradient_points_carry_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                                   int32_t seed_base, int32_t walk_seed_base, int32_t seed_width, void *stream)
+{
+    return kGradList.bind(h, pts_xy_dev, false, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width, stream);
+}
+
+int wost_gradient_points_more(wost_handle h, const uint8_t *select, const wost_gradient_carried_out *out, wost_stats *stats)
+{
+    return kGradList.more(h, select, true, out, nullptr, stats);
+}
+
+int wost_gradient_points_more_dev(wost_handle h, const uint8_t *select_dev, const wost_gradient_carried_out *out_dev, void *stream, wost_stats *stats)
+{
+    return kGradList.more(h, select_dev, false, out_dev, stream, stats);
+}
+
+int wost_gradient_points_carried(wost_handle h, const wost_gradient_carried_out *out) { return kGradList.carried(h, out); }
+
+int wost_gradient_points_adaptive(wost_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out, wost_stats *stats)
+{
+    return kGradList.adaptive(h, a, true, out, nullptr, stats);
+}
+
+int wost_gradient_points_adaptive_dev(wost_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out_dev, void *stream,
+                                      wost_stats *stats)
+{
+    return kGradList.adaptive(h, a, false, out_dev, stream, stats);
+}
+
+int wost_gradient_points_restart(wost_handle h) { return kGradList.restart(h); }
+
+int wost_gradient_points_progress(wost_handle h, int32_t *n_points, int32_t *rounds_done) { return kGradList.progress(h, n_points, rounds_done); }
 
 int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, int32_t *count)
 {

@@ -743,6 +743,7 @@ static void destroy3(wost3_context *c)
     carry_free(c->carry);
     points_free(c->list);
     grad_free(c->grad);
+    gradlist_free(c->glist);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -933,6 +934,9 @@ static GradCall grad_call3(wost3_context *c)
     };
     return g;
 }
+
+// ---- the carried gradient list (wost3_gradient_points_carry & co.; the bodies of the entry points: GradListCalls, wost_grad.h) ----
+static const GradListCalls<wost3_context> kGradList3{grad_call3, 3};
 
 extern "C" {
 
@@ -1151,6 +1155,45 @@ int wost3_solve_gradient_points_dev(wost3_handle h, const float *pts_xyz_dev, in
 {
     return grad_entry(h, grad_call3, 3, pts_xyz_dev, false, n, seed_base, walk_seed_base, seed_width, out, stream, stats);
 }
+
+int wost3_gradient_points_carry(wost3_handle h, const float *pts_xyz, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                                int32_t seed_base, int32_t walk_seed_base, int32_t seed_width)
+{
+    return kGradList3.bind(h, pts_xyz, true, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width, nullptr);
+}
+
+int wost3_gradient_points_carry_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                                    int32_t seed_base, int32_t walk_seed_base, int32_t seed_width, void *stream)
+{
+    return kGradList3.bind(h, pts_xyz_dev, false, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width, stream);
+}
+
+int wost3_gradient_points_more(wost3_handle h, const uint8_t *select, const wost_gradient_carried_out *out, wost_stats *stats)
+{
+    return kGradList3.more(h, select, true, out, nullptr, stats);
+}
+
+int wost3_gradient_points_more_dev(wost3_handle h, const uint8_t *select_dev, const wost_gradient_carried_out *out_dev, void *stream, wost_stats *stats)
+{
+    return kGradList3.more(h, select_dev, false, out_dev, stream, stats);
+}
+
+int wost3_gradient_points_carried(wost3_handle h, const wost_gradient_carried_out *out) { return kGradList3.carried(h, out); }
+
+int wost3_gradient_points_adaptive(wost3_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out, wost_stats *stats)
+{
+    return kGradList3.adaptive(h, a, true, out, nullptr, stats);
+}
+
+int wost3_gradient_points_adaptive_dev(wost3_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out_dev, void *stream,
+                                       wost_stats *stats)
+{
+    return kGradList3.adaptive(h, a, false, out_dev, stream, stats);
+}
+
+int wost3_gradient_points_restart(wost3_handle h) { return kGradList3.restart(h); }
+
+int wost3_gradient_points_progress(wost3_handle h, int32_t *n_points, int32_t *rounds_done) { return kGradList3.progress(h, n_points, rounds_done); }
 
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist, float *out_uv,
                         int32_t *out_side)

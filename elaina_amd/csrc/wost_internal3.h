@@ -62,6 +62,8 @@ struct wost3_context {
     wost::PointList list;
     // the scratch of the gradient calls (wost3_solve_gradient_points & co., wost_grad.h)
     wost::GradScratch grad;
+    // ... and the carried gradient list (wost3_gradient_points_carry & co.), which shares it
+    wost::GradList glist;
 };
 
 namespace wost {

@@ -103,6 +103,109 @@ class UniformCalls:
         return self._dev_solve("solve_gradient_points_dev", C.c_void_p(points_ptr), int(n),
                                *self._gradient_seeds(int(n), seed_base, walk_seed_base, seed_width), C.byref(go), C.c_void_p(stream_ptr or 0))
 
+    # -- the carried gradient list (wost_gradient_points_carry & co.) ---------------------------
+    def _gradient_carry_args(self, n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width):
+        n, seed_base, max_rounds = int(n), int(seed_base), int(max_rounds)
+        stride = n if round_stride is None else int(round_stride)
+        # the walks' seeds by default: just behind the direction seeds of the last round
+        walk = seed_base + (max_rounds - 1) * stride + n if walk_seed_base is None else int(walk_seed_base)
+        return n, int(batch_walks), stride, max_rounds, seed_base, walk, self._seed_width(seed_width)
+
+    def gradient_points_carry(self, points, batch_walks, round_stride=None, max_rounds=64, seed_base=0, walk_seed_base=None, seed_width=None):
+        """bind a list of points ([n, dim] floats) whose gradient is estimated in batches of batch_walks walks per point
+        (wost_gradient_points_carry; include/wost.h has the rules): in round r point i draws its directions from the stream of
+        pixel seed_base + r * round_stride + i and walks on the streams of pixels walk_seed_base + (r * round_stride + i) *
+        batch_walks + s.  round_stride defaults to n, walk_seed_base to just behind the direction seeds of the last of the
+        max_rounds rounds.  A rank that holds points [a, b) of a longer list binds them with seed_base + a, walk_seed_base + a *
+        batch_walks and the round_stride of the whole list.  The list replaces the one bound before; an empty list releases it."""
+        fn, name = self._fn("gradient_points_carry")
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        _check(fn(self._handle, _fp(p), *self._gradient_carry_args(len(p), batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width)),
+               name)
+
+    def gradient_points_carry_dev(self, points_ptr, n, batch_walks, stream_ptr=None, round_stride=None, max_rounds=64, seed_base=0,
+                                  walk_seed_base=None, seed_width=None):
+        """the same from a device pointer (int) to n * dim floats, copied on the caller's stream; a point with a non-finite
+        coordinate is never walked and answers NaN"""
+        fn, name = self._fn("gradient_points_carry_dev")
+        _check(fn(self._handle, C.c_void_p(points_ptr), *self._gradient_carry_args(n, batch_walks, round_stride, max_rounds, seed_base, walk_seed_base,
+                                                                                  seed_width), C.c_void_p(stream_ptr or 0)), name)
+
+    def _gradient_progress(self):
+        fn, name = self._fn("gradient_points_progress")
+        n, rounds = C.c_int32(0), C.c_int32(0)
+        _check(fn(self._handle, C.byref(n), C.byref(rounds)), name)
+        return n.value, rounds.value
+
+    @property
+    def gradient_points_done(self):
+        """(points of the bound gradient list, rounds done since it was bound or restarted); (0, 0): none is bound"""
+        return self._gradient_progress()
+
+    def _gradient_carried_host(self, entry, *args, stats=True):
+        """a host entry point of the list whose last arguments are the outputs and, with `stats`, the stats -> the state as a
+        dict of arrays: "grad" and "stderr" (n, dim, 3), "field" (n, 3), "radius" (n,), float32, and "batches" (n,) int32"""
+        fn, name = self._fn(entry)
+        n = self._gradient_progress()[0]
+        m = max(n, 1)      # (with no list bound the call says so; its pointers are still real ones)
+        out = {"grad": np.zeros((m, self._dim, 3), np.float32), "stderr": np.zeros((m, self._dim, 3), np.float32),
+               "field": np.zeros((m, 3), np.float32), "radius": np.zeros(m, np.float32), "batches": np.zeros(m, np.int32)}
+        go = capi.GradientCarriedOut(*[out[k].ctypes.data for k in ("grad", "stderr", "field", "radius", "batches")])
+        st = Stats()
+        _check(fn(self._handle, *args, C.byref(go), *([C.byref(st)] if stats else [])), name)
+        if stats:
+            self.last_stats = st.as_dict()
+        return {k: v[:n] for k, v in out.items()}
+
+    def _select_ptr(self, select, n):
+        if select is None:
+            return None, None
+        sel = np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, dtype=np.uint8)
+        if sel.size != n:
+            raise ValueError("select has %d entries, the list %d points" % (sel.size, n))
+        return sel, sel.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def gradient_points_more(self, select=None):
+        """one batch on the listed points whose entry in select (n values, nonzero = continue) is set and that are walkable;
+        None: every walkable point.  Returns the state after the call (the dict of gradient_points_carried)"""
+        sel, ptr = self._select_ptr(select, self._gradient_progress()[0])
+        return self._gradient_carried_host("gradient_points_more", ptr)
+
+    def gradient_points_carried(self):
+        """the state of the list: {"grad", "stderr", "field", "radius", "batches"}; a point no batch has walked answers NaN
+        (stderr: +inf below two batches; NaN for a point that is never walked)"""
+        return self._gradient_carried_host("gradient_points_carried", stats=False)
+
+    def gradient_points_adaptive(self, max_batches, abs_tol=0.0, rel_tol=0.0, min_batches=4):
+        """batches on the walkable points whose standard error is above max(abs_tol, rel_tol * |grad|) in some entry (or that
+        have fewer than min_batches batches) and that have room under max_batches, until none is left or the list's rounds
+        run out; starts from the state as it stands.  Returns the state after the call"""
+        a = capi.GradientAdaptive(int(min_batches), int(max_batches), float(abs_tol), float(rel_tol))
+        return self._gradient_carried_host("gradient_points_adaptive", C.byref(a))
+
+    def _gradient_carried_dev(self, grad_ptr, stderr_ptr, field_ptr, radius_ptr, batches_ptr):
+        return capi.GradientCarriedOut(grad_ptr, stderr_ptr or None, field_ptr or None, radius_ptr or None, batches_ptr or None)
+
+    def gradient_points_more_dev(self, grad_ptr, select_dev_ptr=None, stream_ptr=None, stderr_ptr=None, field_ptr=None, radius_ptr=None,
+                                 batches_ptr=None):
+        """gradient_points_more on device pointers (ints) on the caller's stream: n bytes of selection (None: every walkable
+        point), n * dim * 3 floats of grad and, where given, of stderr, n * 3 of field, n of radius, n int32 of batches.  Returns
+        the stats as a dict"""
+        go = self._gradient_carried_dev(grad_ptr, stderr_ptr, field_ptr, radius_ptr, batches_ptr)
+        return self._dev_solve("gradient_points_more_dev", C.c_void_p(select_dev_ptr or 0), C.byref(go), C.c_void_p(stream_ptr or 0))
+
+    def gradient_points_adaptive_dev(self, max_batches, grad_ptr, stream_ptr=None, abs_tol=0.0, rel_tol=0.0, min_batches=4, stderr_ptr=None,
+                                     field_ptr=None, radius_ptr=None, batches_ptr=None):
+        """gradient_points_adaptive into device arrays on the caller's stream"""
+        a = capi.GradientAdaptive(int(min_batches), int(max_batches), float(abs_tol), float(rel_tol))
+        go = self._gradient_carried_dev(grad_ptr, stderr_ptr, field_ptr, radius_ptr, batches_ptr)
+        return self._dev_solve("gradient_points_adaptive_dev", C.byref(a), C.byref(go), C.c_void_p(stream_ptr or 0))
+
+    def gradient_points_restart(self):
+        """keep the gradient list, forget its batches and rounds"""
+        fn, name = self._fn("gradient_points_restart")
+        _check(fn(self._handle), name)
+
     # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
     def solve_more(self, more_spp):
         """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at

@@ -307,6 +307,83 @@ int wost_solve_gradient_points(wost_handle h, const float *pts_xy, int32_t n, in
 int wost_solve_gradient_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base,
                                    int32_t seed_width, const wost_gradient_out *out, void *stream, wost_stats *stats);
 
+/* The carried gradient list: the gradient above at n points of the caller, continued in batches of S walks on a
+ * selection of the points, with a per-entry error bar and a loop that stops by it.  wost_gradient_points_carry binds a list to the
+ * handle: the library copies the points (pts_xy: n * 2 floats) and owns the copy; n == 0 (pts_xy may be NULL) releases the list.
+ * wost_gradient_points_carry_dev takes DEVICE points and copies them on the caller's stream (NULL = default stream); both return
+ * when the list stands.  S = batch_walks; the handle's own spp setting is neither read nor changed.  The bind computes the radius
+ * R_i of every point once, with the bits of wost_solve_gradient_points.
+ *   Walkable points.  A point that is degenerate (R <= eps_shell or R not finite) or has a non-finite coordinate (only the _dev
+ *     bind lets one in) is NEVER walked by the calls below: it keeps K = 0, NaN grad, grad_stderr and field_rgb, and its radius.
+ *     This differs on purpose from the single call, which still walks a degenerate point for its mean: a list exists to spend
+ *     walks where they improve an estimate, and such a point has none.
+ *   Rounds and seeds.  The list counts rounds r = 0, 1, ...: a round is one wost_gradient_points_more call, or one trip of the
+ *     adaptive loop, that selects at least one walkable point.  In round r a selected point i gets one batch, which is row i of
+ *     wost_solve_gradient_points(pts, n, seed_base + r * round_stride, walk_seed_base + r * round_stride * S, seed_width) on a
+ *     handle with spp = S, bit for bit: its directions come from the stream of pixel seed_base + r * round_stride + i, its walk s
+ *     runs on the stream of pixel walk_seed_base + (r * round_stride + i) * S + s.  A point's batch does not depend on which other
+ *     points were selected, and a list cut at point a and bound with seed_base + a, walk_seed_base + a * S and the same
+ *     round_stride gives the same bits -- which is how a list is cut over ranks.  The points are walked in blocks of
+ *     floor(width * height / S); a block without a selected point launches nothing; per round the host reads back the selected
+ *     points per block.
+ *   State.  Per point K_i, R_i and fp64 sums.  With g_k the batch's grad rounded to fp32 (what the single call returns) and m_k
+ *     its fp32 field_rgb: per entry G += (double)g_k and Q += (double)g_k * (double)g_k, per channel F += (double)m_k, in round
+ *     order.  Outputs: grad = (float)(G / K), field_rgb = (float)(F / K), grad_stderr = (float)sqrt(max(Q - G G / K, 0) /
+ *     ((K - 1) K)) (batch means), +inf while K < 2.  A walkable point with K = 0 answers NaN grad and field_rgb.
+ *   - wost_gradient_points_more: one batch on the listed points whose byte in select (n host bytes) is nonzero and that are
+ *     walkable; NULL = every walkable point.  out (host arrays; only grad is required) receives the state after the call.  An
+ *     empty selection returns WOST_OK with zeroed stats and the state's outputs, launches no walk and consumes no round.  A call
+ *     at r == max_rounds is refused with the state untouched.  wost_gradient_points_more_dev: select_dev and the arrays of out are
+ *     DEVICE arrays, the work runs on the caller's stream and is complete when the call returns.
+ *   - wost_gradient_points_carried: the state into host arrays.
+ *   - wost_gradient_points_adaptive: select the walkable points that are not converged and have room (K + 1 <= max_batches);
+ *     while any is selected and r < max_rounds, run one batch on them and select again.  Converged: K >= min_batches and for
+ *     every entry grad_stderr <= max(abs_tol, rel_tol * |grad|), evaluated in fp32 on the ROUNDED outputs, so a caller can
+ *     reproduce the decision from what wost_gradient_points_carried returns; a NaN is never converged.  Running out of rounds
+ *     ends the loop with WOST_OK.  A second call with tighter tolerances or a larger max_batches resumes.  Refused before the
+ *     handle is read: min_batches < 2, max_batches < 1, a tolerance that is negative or not finite.  Stopping by the estimate
+ *     biases the result, as in wost_solve_adaptive.
+ *   - wost_gradient_points_restart forgets sums, K and r; the same calls then give the same bits again.
+ *     wost_gradient_points_progress reports the length of the list and the rounds done.
+ *   - wost_stats sums the blocks and rounds of the call (walks_started is S x the batches walked; kernel_ms includes the kernels
+ *     around the walks); wost_last_launches describes the walks of the last block walked.
+ *   One gradient list per handle, beside the carried frame solve and the carried point list.  It shares the scratch of
+ *     wost_solve_gradient_points, and a single gradient call between two rounds changes nothing in the list.  The frame solves,
+ *     the point solves, the carried frame solve, the carried point list and wost_set_option leave the gradient list alone, and
+ *     the gradient list leaves all of them alone.  A refused bind leaves the old list as it was; wost_destroy frees it.
+ *   Arguments of a bind, checked in this order before the handle is read or a device is asked for: a null handle; n < 0; n > 0
+ *     with null points; seed_width <= 0; a negative seed; batch_walks < 2; round_stride < n; max_rounds < 1; seed_base +
+ *     (max_rounds - 1) * round_stride + n > 2^28; walk_seed_base + ((max_rounds - 1) * round_stride + n) * S > 2^28 (in 64 bits);
+ *     the two seed ranges overlapping; in the host form, the first non-finite point.  With the handle: S > width * height
+ *     (WOST_ERR_INVALID); a scene with a source term (WOST_ERR_UNSUPPORTED, as the single call answers).  A more / adaptive /
+ *     carried / restart call with no list bound is WOST_ERR_INVALID with a message that says so; a call that fails after device
+ *     work has begun drops the samples (not the list) and says so in wost_last_error.
+ * Not carried: the guided integrators; a list cannot be saved, and one list is not split into shards. */
+typedef struct wost_gradient_carried_out {   /* host pointers for the host forms, device pointers for the _dev forms; only grad is required */
+    float *grad;          /* n * DIM * 3, the layout of wost_gradient_out                                          */
+    float *grad_stderr;   /* n * DIM * 3 or NULL                                                                  */
+    float *field_rgb;     /* n * 3 or NULL: the mean of the point's batch means                                   */
+    float *radius;        /* n or NULL: the ball radius R_i                                                       */
+    int32_t *batches;     /* n or NULL: K_i                                                                       */
+} wost_gradient_carried_out;
+typedef struct wost_gradient_adaptive {
+    int32_t min_batches, max_batches;
+    float abs_tol, rel_tol;
+} wost_gradient_adaptive;
+int wost_gradient_points_carry(wost_handle h, const float *pts_xy, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                               int32_t seed_base, int32_t walk_seed_base, int32_t seed_width);
+int wost_gradient_points_carry_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t batch_walks, int32_t round_stride,
+                                   int32_t max_rounds, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width, void *stream);
+int wost_gradient_points_more(wost_handle h, const uint8_t *select, const wost_gradient_carried_out *out, wost_stats *stats);
+int wost_gradient_points_more_dev(wost_handle h, const uint8_t *select_dev, const wost_gradient_carried_out *out_dev, void *stream,
+                                  wost_stats *stats);
+int wost_gradient_points_carried(wost_handle h, const wost_gradient_carried_out *out);
+int wost_gradient_points_adaptive(wost_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out, wost_stats *stats);
+int wost_gradient_points_adaptive_dev(wost_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out_dev, void *stream,
+                                      wost_stats *stats);
+int wost_gradient_points_restart(wost_handle h);
+int wost_gradient_points_progress(wost_handle h, int32_t *n_points, int32_t *rounds_done);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -700,6 +777,21 @@ int wost3_solve_gradient_points(wost3_handle h, const float *pts_xyz, int32_t n,
                                 int32_t seed_width, const wost_gradient_out *out, wost_stats *stats);
 int wost3_solve_gradient_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t walk_seed_base,
                                     int32_t seed_width, const wost_gradient_out *out, void *stream, wost_stats *stats);
+/* The carried gradient list in 3-D: wost_gradient_points_carry & co. with the same rules in every clause (pts_xyz: n * 3 floats;
+ * DIM = 3; a batch is a row of wost3_solve_gradient_points). */
+int wost3_gradient_points_carry(wost3_handle h, const float *pts_xyz, int32_t n, int32_t batch_walks, int32_t round_stride, int32_t max_rounds,
+                                int32_t seed_base, int32_t walk_seed_base, int32_t seed_width);
+int wost3_gradient_points_carry_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t batch_walks, int32_t round_stride,
+                                    int32_t max_rounds, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width, void *stream);
+int wost3_gradient_points_more(wost3_handle h, const uint8_t *select, const wost_gradient_carried_out *out, wost_stats *stats);
+int wost3_gradient_points_more_dev(wost3_handle h, const uint8_t *select_dev, const wost_gradient_carried_out *out_dev, void *stream,
+                                   wost_stats *stats);
+int wost3_gradient_points_carried(wost3_handle h, const wost_gradient_carried_out *out);
+int wost3_gradient_points_adaptive(wost3_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out, wost_stats *stats);
+int wost3_gradient_points_adaptive_dev(wost3_handle h, const wost_gradient_adaptive *a, const wost_gradient_carried_out *out_dev, void *stream,
+                                       wost_stats *stats);
+int wost3_gradient_points_restart(wost3_handle h);
+int wost3_gradient_points_progress(wost3_handle h, int32_t *n_points, int32_t *rounds_done);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
