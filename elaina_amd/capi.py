@@ -192,27 +192,100 @@ SYNC_UNSUPPORTED = 2       # callback return value for an unknown op
 # wost_frame_fn: int (*)(void *user, int reason, int32_t sample_id, double elapsed_ms, const float *field_rgb)
 FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_double, C.POINTER(C.c_float))
 
-EXPORTS = [
-    "wost_create", "wost_solve", "wost_solve_sharded", "wost_solve_points", "wost_solve_points_dev",
-    "wost_solve_more", "wost_solve_more_sharded", "wost_solve_restart", "wost_solve_progress",
-    "wost_solve_more_where", "wost_solve_more_where_sharded", "wost_solve_carried", "wost_solve_adaptive", "wost_solve_adaptive_sharded", "wost_render_sdf", "wost_render_source", "wost_closest_point",
-    "wost_closest_silhouette", "wost_ray_intersect", "wost_set_option", "wost_last_launches", "wost_destroy",
-    "wost_vonmises_eval", "wost_vonmises_sample", "wost_vmm_pdf_sample", "wost_vmm_loss_gradients",
-    "wost_net_create", "wost_net_destroy", "wost_net_n_params", "wost_net_get_params",
-    "wost_net_set_params", "wost_net_set_gradient_buffer", "wost_net_inference", "wost_net_train_step", "wost_net_set_option",
-    "wost_guided_create", "wost_guided_set_sync", "wost_guided_set_frame_callback", "wost_guided_network", "wost_guided_scene", "wost_guided_query_network", "wost_guided_solve", "wost_guided_solve_sharded", "wost_guided_solve_points", "wost_guided_solve_points_dev", "wost_guided_train_set", "wost_guided_set_option", "wost_guided_destroy",
-    "wost3_create", "wost3_solve", "wost3_solve_sharded", "wost3_solve_points", "wost3_solve_points_dev",
-    "wost3_solve_more", "wost3_solve_more_sharded", "wost3_solve_restart", "wost3_solve_progress",
-    "wost3_solve_more_where", "wost3_solve_more_where_sharded", "wost3_solve_carried", "wost3_solve_adaptive", "wost3_solve_adaptive_sharded", "wost3_closest_point", "wost3_closest_silhouette", "wost3_ray_intersect", "wost3_mesh_build_check",
-    "wost3_render_sdf", "wost3_render_source", "wost3_destroy", "wost3_vmf_eval", "wost3_vmf_sample", "wost3_vmm_pdf_sample", "wost3_vmm_loss_gradients",
-    "wost3_net_create", "wost3_guided_create", "wost3_guided_destroy", "wost3_guided_network", "wost3_guided_solve", "wost3_guided_solve_sharded", "wost3_guided_solve_points", "wost3_guided_solve_points_dev",
-    "wost3_guided_query_network", "wost3_guided_train_set", "wost3_guided_scene",
-    "wost_last_error", "wost_version", "wost_mesh_build_check",
-] + [pre + "points_" + f for pre in ("wost_", "wost3_")
-     for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")
-     ] + [pre + "solve_gradient_points" + f for pre in ("wost_", "wost3_") for f in ("", "_dev")
-     ] + [pre + "gradient_points_" + f for pre in ("wost_", "wost3_")
-          for f in ("carry", "carry_dev", "more", "more_dev", "carried", "adaptive", "adaptive_dev", "restart", "progress")]
+# Every entry point of include/wost.h and its argument types, in one place: load() sets the prototypes from it and EXPORTS, the
+# symbols the library must have, is its key list.  _BOTH: entries that exist as wost_<name> and wost3_<name> with one signature.
+_pf, _pi, _pu8, _pu64, _pd = (C.POINTER(t) for t in (C.c_float, C.c_int32, C.c_uint8, C.c_uint64, C.c_double))
+_h, _dev, _i32, _st, _gst = C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Stats), C.POINTER(GuidedStats)      # _dev: a device array or a stream
+_gco = C.POINTER(GradientCarriedOut)
+_BOTH = {
+    "destroy": [_h],
+    "solve": [_h, _i32, _i32, _pf, _st],
+    "solve_sharded": [_h, _i32, _i32, _dev, _dev, _st],
+    "solve_points": [_h, _pf, _i32, _i32, _i32, _pf, _st],
+    "solve_points_dev": [_h, _dev, _i32, _i32, _i32, _dev, _dev, _st],
+    # the carried frame solve (wost_solve_more & co.)
+    "solve_more": [_h, _i32, _pf, _st],
+    "solve_more_sharded": [_h, _i32, _i32, _i32, _dev, _dev, _st],
+    "solve_restart": [_h],
+    "solve_progress": [_h, _pi],
+    "solve_more_where": [_h, _i32, _pu8, _pf, _st],
+    "solve_more_where_sharded": [_h, _i32, _i32, _i32, _dev, _dev, _dev, _st],
+    "solve_carried": [_h, _pi, _pi, _pf, _pf],
+    "solve_adaptive": [_h, C.POINTER(Adaptive), _pf, _pf, _pi, _st],
+    "solve_adaptive_sharded": [_h, _i32, _i32, C.POINTER(Adaptive), _dev, _dev, _st],
+    # the carried point list (wost_points_carry & co.)
+    "points_carry": [_h, _pf, _i32, _i32, _i32],
+    "points_carry_dev": [_h, _dev, _i32, _i32, _i32, _dev],
+    "points_more": [_h, _i32, _pu8, _pf, _st],
+    "points_more_dev": [_h, _i32, _dev, _dev, _dev, _st],
+    "points_carried": [_h, _pi, _pi, _pf, _pf],
+    "points_adaptive": [_h, C.POINTER(Adaptive), _pf, _pf, _pi, _st],
+    "points_adaptive_dev": [_h, C.POINTER(Adaptive), _dev, _dev, _st],
+    "points_restart": [_h],
+    "points_progress": [_h, _pi, _pi],
+    # the gradient at the caller's points (wost_solve_gradient_points & co.)
+    "solve_gradient_points": [_h, _pf, _i32, _i32, _i32, _i32, C.POINTER(GradientOut), _st],
+    "solve_gradient_points_dev": [_h, _dev, _i32, _i32, _i32, _i32, C.POINTER(GradientOut), _dev, _st],
+    # the carried gradient list (wost_gradient_points_carry & co.)
+    "gradient_points_carry": [_h, _pf, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "gradient_points_carry_dev": [_h, _dev, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dev],
+    "gradient_points_more": [_h, _pu8, _gco, _st],
+    "gradient_points_more_dev": [_h, _dev, _gco, _dev, _st],
+    "gradient_points_carried": [_h, _gco],
+    "gradient_points_adaptive": [_h, C.POINTER(GradientAdaptive), _gco, _st],
+    "gradient_points_adaptive_dev": [_h, C.POINTER(GradientAdaptive), _gco, _dev, _st],
+    "gradient_points_restart": [_h],
+    "gradient_points_progress": [_h, _pi, _pi],
+    # the batch queries
+    "render_sdf": [_h, C.c_int, _pf],
+    "render_source": [_h, _pf],
+    "closest_point": [_h, C.c_int, _pf, _i32, _pi, _pf, _pf, _pi],
+    "closest_silhouette": [_h, C.c_int, _pf, _pf, _i32, _pf],
+    "ray_intersect": [_h, C.c_int, _pf, _pf, _pf, _i32, _pi, _pf, _pi],
+    # the mixture, the network and the guided solves
+    "vmm_pdf_sample": [C.c_int, _pf, _pf, _pu64, _i32, _pf, _pf],
+    "vmm_loss_gradients": [C.c_int, _pf, _pf, _pf, _pf, _pu8, _pf, _i32, C.c_float, _pf, _pf],
+    "net_create": [C.c_int, C.POINTER(NetConfig), C.c_uint64, C.POINTER(_h)],
+    "guided_destroy": [_h],
+    "guided_network": [_h, C.POINTER(_h)],
+    "guided_scene": [_h, C.POINTER(_h)],
+    "guided_query_network": [_h, _pf, _i32, _pf],
+    "guided_solve": [_h, _pf, _gst],
+    "guided_solve_sharded": [_h, _i32, _i32, _dev, _gst],
+    "guided_solve_points": [_h, _pf, _i32, _i32, _i32, _i32, _pf, _gst],
+    "guided_solve_points_dev": [_h, _dev, _i32, _i32, _i32, _i32, _dev, _gst],
+    "guided_train_set": [_h, _i32, _pi, _pf, _pf, _pf, _pf, _pf, _pu8],
+}
+SIGNATURES = {pre + name: sig for pre in ("wost_", "wost3_") for name, sig in _BOTH.items()}
+SIGNATURES.update({
+    "wost_last_error": [], "wost_version": [],
+    "wost_create": [C.POINTER(SceneDesc), C.POINTER(Settings), C.c_int, C.POINTER(_h)],
+    "wost3_create": [C.POINTER(Scene3Desc), C.POINTER(Settings), C.c_int, C.POINTER(_h)],
+    "wost_mesh_build_check": [C.POINTER(MeshDesc), C.c_int, _i32, _pd, _pd, C.POINTER(C.c_int64)],
+    "wost3_mesh_build_check": [C.POINTER(Mesh3Desc), C.c_int, _i32, _pd, _pd, C.POINTER(C.c_int64)],
+    "wost_guided_create": [C.POINTER(SceneDesc), C.POINTER(GuidedSettings), C.POINTER(NetConfig), C.c_uint64, C.c_int, C.POINTER(_h)],
+    "wost3_guided_create": [C.POINTER(Scene3Desc), C.POINTER(Guided3Settings), C.POINTER(NetConfig), C.c_uint64, C.c_int, C.POINTER(_h)],
+    # 2-D alone
+    "wost_set_option": [_h, C.c_char_p, C.c_double],
+    "wost_last_launches": [_h, C.POINTER(LaunchInfo), _i32, _pi],
+    "wost_vonmises_eval": [C.c_int, _pf, _pf, _i32, _pf, _pf, _pf, _pf],
+    "wost_vonmises_sample": [C.c_int, _pf, _pu64, _i32, _i32, _pf],
+    "wost_net_destroy": [_h],
+    "wost_net_n_params": [_h, _pu64, _pu64],
+    "wost_net_get_params": [_h, C.c_int, _pf],
+    "wost_net_set_params": [_h, _pf],
+    "wost_net_set_gradient_buffer": [_h, _dev],
+    "wost_net_inference": [_h, _pf, _i32, _pf, C.c_int],
+    "wost_net_train_step": [_h, _pf, _pf, _i32, C.c_float, C.c_int],
+    "wost_net_set_option": [_h, C.c_char_p, C.c_double],
+    "wost_guided_set_sync": [_h, SYNC_FN, _h],
+    "wost_guided_set_frame_callback": [_h, FRAME_FN, _h, _i32, _i32, _i32],
+    "wost_guided_set_option": [_h, C.c_char_p, C.c_double],
+    # 3-D alone
+    "wost3_vmf_eval": [C.c_int, _pf, _pf, _i32, _pf],
+    "wost3_vmf_sample": [C.c_int, _pf, _pf, _pu64, _i32, _i32, _pf],
+})
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -239,117 +312,10 @@ def load():
             "libwost_hip.so is missing (%s): run `python -m elaina_amd.build`; "
             "this package has no CPU fallback" % path)
     L = C.CDLL(path)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    L.wost_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(Settings), C.c_int, C.POINTER(C.c_void_p)]
-    L.wost_solve.argtypes = [C.c_void_p, C.c_int32, C.c_int32, fp, C.POINTER(Stats)]
-    L.wost_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.wost_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(Stats)]
-    L.wost_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    for pre in ("wost_", "wost3_"):
-        getattr(L, pre + "solve_more").argtypes = [C.c_void_p, C.c_int32, fp, C.POINTER(Stats)]
-        getattr(L, pre + "solve_more_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "solve_restart").argtypes = [C.c_void_p]
-        getattr(L, pre + "solve_progress").argtypes = [C.c_void_p, ip]
-        getattr(L, pre + "solve_more_where").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), fp, C.POINTER(Stats)]
-        getattr(L, pre + "solve_more_where_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "solve_carried").argtypes = [C.c_void_p, ip, ip, fp, fp]
-        getattr(L, pre + "solve_adaptive").argtypes = [C.c_void_p, C.POINTER(Adaptive), fp, fp, ip, C.POINTER(Stats)]
-        getattr(L, pre + "solve_adaptive_sharded").argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        # the carried point list (wost_points_carry & co.)
-        getattr(L, pre + "points_carry").argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32]
-        getattr(L, pre + "points_carry_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-        getattr(L, pre + "points_more").argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint8), fp, C.POINTER(Stats)]
-        getattr(L, pre + "points_more_dev").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "points_carried").argtypes = [C.c_void_p, ip, ip, fp, fp]
-        getattr(L, pre + "points_adaptive").argtypes = [C.c_void_p, C.POINTER(Adaptive), fp, fp, ip, C.POINTER(Stats)]
-        getattr(L, pre + "points_adaptive_dev").argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "points_restart").argtypes = [C.c_void_p]
-        getattr(L, pre + "points_progress").argtypes = [C.c_void_p, ip, ip]
-        # the gradient at the caller's points (wost_solve_gradient_points & co.)
-        getattr(L, pre + "solve_gradient_points").argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GradientOut),
-                                                               C.POINTER(Stats)]
-        getattr(L, pre + "solve_gradient_points_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                                   C.POINTER(GradientOut), C.c_void_p, C.POINTER(Stats)]
-        # the carried gradient list (wost_gradient_points_carry & co.)
-        gco, i32 = C.POINTER(GradientCarriedOut), C.c_int32
-        getattr(L, pre + "gradient_points_carry").argtypes = [C.c_void_p, fp, i32, i32, i32, i32, i32, i32, i32]
-        getattr(L, pre + "gradient_points_carry_dev").argtypes = [C.c_void_p, C.c_void_p, i32, i32, i32, i32, i32, i32, i32, C.c_void_p]
-        getattr(L, pre + "gradient_points_more").argtypes = [C.c_void_p, C.POINTER(C.c_uint8), gco, C.POINTER(Stats)]
-        getattr(L, pre + "gradient_points_more_dev").argtypes = [C.c_void_p, C.c_void_p, gco, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "gradient_points_carried").argtypes = [C.c_void_p, gco]
-        getattr(L, pre + "gradient_points_adaptive").argtypes = [C.c_void_p, C.POINTER(GradientAdaptive), gco, C.POINTER(Stats)]
-        getattr(L, pre + "gradient_points_adaptive_dev").argtypes = [C.c_void_p, C.POINTER(GradientAdaptive), gco, C.c_void_p, C.POINTER(Stats)]
-        getattr(L, pre + "gradient_points_restart").argtypes = [C.c_void_p]
-        getattr(L, pre + "gradient_points_progress").argtypes = [C.c_void_p, ip, ip]
-    L.wost_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
-    L.wost_render_source.argtypes = [C.c_void_p, fp]
-    L.wost_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]
-    L.wost_closest_silhouette.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_int32, fp]
-    L.wost_ray_intersect.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, C.c_int32, ip, fp, ip]
-    L.wost_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
-    L.wost_last_launches.argtypes = [C.c_void_p, C.POINTER(LaunchInfo), C.c_int32, C.POINTER(C.c_int32)]
-    u64p = C.POINTER(C.c_uint64)
-    L.wost_vonmises_eval.argtypes = [C.c_int, fp, fp, C.c_int32, fp, fp, fp, fp]
-    L.wost_vonmises_sample.argtypes = [C.c_int, fp, u64p, C.c_int32, C.c_int32, fp]
-    L.wost_vmm_pdf_sample.argtypes = [C.c_int, fp, fp, u64p, C.c_int32, fp, fp]
-    L.wost_vmm_loss_gradients.argtypes = [C.c_int, fp, fp, fp, fp, C.POINTER(C.c_uint8), fp, C.c_int32, C.c_float, fp, fp]
-    L.wost_net_create.argtypes = [C.c_int, C.POINTER(NetConfig), C.c_uint64, C.POINTER(C.c_void_p)]
-    L.wost_net_destroy.argtypes = [C.c_void_p]
-    L.wost_net_n_params.argtypes = [C.c_void_p, u64p, u64p]
-    L.wost_net_get_params.argtypes = [C.c_void_p, C.c_int, fp]
-    L.wost_net_set_params.argtypes = [C.c_void_p, fp]
-    L.wost_net_inference.argtypes = [C.c_void_p, fp, C.c_int32, fp, C.c_int]
-    L.wost_net_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
-    L.wost_net_train_step.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_float, C.c_int]
-    L.wost_guided_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(GuidedSettings), C.POINTER(NetConfig), C.c_uint64,
-                                     C.c_int, C.POINTER(C.c_void_p)]
-    L.wost_guided_network.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.wost_guided_set_sync.argtypes = [C.c_void_p, SYNC_FN, C.c_void_p]
-    L.wost_guided_set_frame_callback.argtypes = [C.c_void_p, FRAME_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-    L.wost_net_set_gradient_buffer.argtypes = [C.c_void_p, C.c_void_p]
-    L.wost_guided_scene.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.wost_guided_query_network.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    L.wost_guided_solve.argtypes = [C.c_void_p, fp, C.POINTER(GuidedStats)]
-    L.wost_guided_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
-    L.wost_guided_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(GuidedStats)]
-    L.wost_guided_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
-    L.wost_guided_train_set.argtypes = [C.c_void_p, C.c_int32, ip, fp, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
-    L.wost_guided_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
-    L.wost_guided_destroy.argtypes = [C.c_void_p]
-    L.wost_destroy.argtypes = [C.c_void_p]
-    L.wost3_create.argtypes = [C.POINTER(Scene3Desc), C.POINTER(Settings), C.c_int, C.POINTER(C.c_void_p)]
-    L.wost3_solve.argtypes = [C.c_void_p, C.c_int32, C.c_int32, fp, C.POINTER(Stats)]
-    L.wost3_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.wost3_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(Stats)]
-    L.wost3_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.wost3_closest_point.argtypes = [C.c_void_p, C.c_int, fp, C.c_int32, ip, fp, fp, ip]
-    L.wost3_closest_silhouette.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_int32, fp]
-    L.wost3_ray_intersect.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, C.c_int32, ip, fp, ip]
-    L.wost3_mesh_build_check.argtypes = [C.POINTER(Mesh3Desc), C.c_int, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    L.wost_mesh_build_check.argtypes = [C.POINTER(MeshDesc), C.c_int, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    L.wost3_render_sdf.argtypes = [C.c_void_p, C.c_int, fp]
-    L.wost3_render_source.argtypes = [C.c_void_p, fp]
-    L.wost3_destroy.argtypes = [C.c_void_p]
-    L.wost3_vmf_eval.argtypes = [C.c_int, fp, fp, C.c_int32, fp]
-    L.wost3_vmf_sample.argtypes = [C.c_int, fp, fp, u64p, C.c_int32, C.c_int32, fp]
-    L.wost3_vmm_pdf_sample.argtypes = [C.c_int, fp, fp, u64p, C.c_int32, fp, fp]
-    L.wost3_vmm_loss_gradients.argtypes = [C.c_int, fp, fp, fp, fp, C.POINTER(C.c_ubyte), fp, C.c_int32, C.c_float, fp, fp]
-    L.wost3_net_create.argtypes = [C.c_int, C.POINTER(NetConfig), C.c_uint64, C.POINTER(C.c_void_p)]
-    L.wost3_guided_create.argtypes = [C.POINTER(Scene3Desc), C.POINTER(Guided3Settings), C.POINTER(NetConfig), C.c_uint64, C.c_int,
-                                      C.POINTER(C.c_void_p)]
-    L.wost3_guided_destroy.argtypes = [C.c_void_p]
-    L.wost3_guided_network.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.wost3_guided_scene.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.wost3_guided_solve.argtypes = [C.c_void_p, fp, C.POINTER(GuidedStats)]
-    L.wost3_guided_solve_sharded.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
-    L.wost3_guided_solve_points.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, C.POINTER(GuidedStats)]
-    L.wost3_guided_solve_points_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GuidedStats)]
-    L.wost3_guided_query_network.argtypes = [C.c_void_p, fp, C.c_int32, fp]
-    L.wost3_guided_train_set.argtypes = [C.c_void_p, C.c_int32, ip, fp, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
+    for name, argtypes in SIGNATURES.items():
+        getattr(L, name).argtypes = argtypes  # (fails loudly on a missing symbol)
     L.wost_last_error.restype = C.c_char_p
     L.wost_version.restype = C.c_char_p
-    for name in EXPORTS:
-        getattr(L, name)  # fail loudly on a missing symbol
     _lib = L
     return L
 

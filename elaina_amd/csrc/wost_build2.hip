@@ -2,7 +2,8 @@
 // reference builds its trees on the device: core/problem.cu:31-37, 48-54).  Same output as the host builder lbvh_build.cpp,
 // bit for bit -- segment records, Morton order, the perimeter-weighted (SAH) top-down assignment of the segments to the leaves
 // of the implicit 4-ary tree, oriented child boxes, normal cones, the compact scan copies -- with the host builder kept as the
-// checker (wost_mesh_build_check, tests/test_gpu_build2.py) and behind WOST_HOST_BUILD=1.
+// checker (wost_mesh_build_check, tests/test_gpu_build2.py) and behind WOST_HOST_BUILD=1.  Behind the builder: the upload of a
+// mesh into a handle by either builder (upload_mesh, upload_mesh_host, upload_run_boxes) and wost_mesh_build_check itself.
 //
 // How the two agree:
 //   * every stored floating-point number is a chain of correctly rounded operations executed the same way on both sides
@@ -33,6 +34,7 @@
 #include "wost_device.h"
 #include "wost_internal.h"
 #include "wost_build2.h"
+#include "wost_internal2.h"
 
 namespace wost {
 
@@ -760,4 +762,242 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     return WOST_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// the upload of a mesh into a handle, and the check of the device build against the host builder
+// ------------------------------------------------------------------------------------------
+// the host builder's tree (lbvh_build.cpp), uploaded array by array: the checker of the device build, small meshes,
+// WOST_HOST_BUILD=1 and the tree-quality knobs
+int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
+{
+    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
+    // developer knobs for tree-quality experiments (defaults: refined, minimal depth)
+    const char *e_refine = getenv("WOST_TREE_REFINE");
+    const char *e_extra = getenv("WOST_TREE_EXTRA_LEVELS");
+    const bool refine = e_refine ? atoi(e_refine) != 0 : true;
+    const int extra = e_extra ? std::max(0, std::min(3, atoi(e_extra))) : 0;
+    if (build_tree(d.n_verts, d.verts, d.n_segs, d.segs, d.colors, &s.host, refine, extra) != 0)
+        return set_error(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
+    const HostTree &t = s.host;
+    DevMesh &v = s.view;
+    v = DevMesh{};
+    v.n_segs = t.n_segs;
+    if (t.n_segs == 0) return WOST_OK;
+    v.n_sil = (int32_t)t.sil.size();
+    v.levels = t.levels;
+    {
+        // the boxes are padded by 2^-21 of the largest coordinate; the rounding of a box distance grows with the distance
+        // to the box (about 10^-7 of it): up to one and a half extents from the closest segment the padding covers it
+        float ext = 0.0f;
+        for (int i = 0; i < d.n_segs; ++i)
+            for (int e = 0; e < 2; ++e) {
+                const int32_t vi = d.segs[2 * i + e];
+                ext = std::max(ext, std::max(std::fabs(d.verts[2 * vi]), std::fabs(d.verts[2 * vi + 1])));
+            }
+        v.far2 = 2.25f * ext * ext;
+        v.huge2 = 4096.0f * ext * ext;       // 64 extents
+    }
+    v.first_leaf = t.first_leaf;
+    v.emissive = 0;
+    for (float c : t.flatCol)
+        if (c != 0.0f) v.emissive = 1;
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.nodes.data()), t.nodes.size() / 4, &v.nodes));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.segA.data()), t.segA.size() / 4, &v.segA));
+    WOST_TRY(upload(s.allocs, t.segInv.data(), t.segInv.size(), &v.segInv));
+    WOST_TRY(upload(s.allocs, t.segOrig.data(), t.segOrig.size(), &v.segOrig));
+    WOST_TRY(upload(s.allocs, t.segCol.data(), t.segCol.size(), &v.segCol));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevFlatSeg *>(t.flat.data()), t.flat.size(), &v.flat));
+    WOST_TRY(upload(s.allocs, t.flatCol.data(), t.flatCol.size(), &v.flatCol));
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevSilVertex *>(t.sil.data()), t.sil.size(), &v.sil));
+    {
+        // the normals of every vertex's two segments beside it: the flat silhouette test of a small boundary reads them with the vertex
+        std::vector<float> sn(t.sil.size() * 4, 0.0f);
+        for (size_t k = 0; k < t.sil.size(); ++k) {
+            const SilVertex &sv = t.sil[k];
+            if (sv.prev >= 0) { sn[4 * k] = t.flat[(size_t)sv.prev].nx; sn[4 * k + 1] = t.flat[(size_t)sv.prev].ny; }
+            if (sv.next >= 0) { sn[4 * k + 2] = t.flat[(size_t)sv.next].nx; sn[4 * k + 3] = t.flat[(size_t)sv.next].ny; }
+        }
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(sn.data()), t.sil.size(), &v.silN));
+    }
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.cones.data()), t.cones.size() / 4, &v.cones));
+    {
+        // closest_point_wave: the occupied slots, compact; the operands are those of the leaf-level node records
+        std::vector<float> box, hl;
+        std::vector<int32_t> id;
+        for (size_t k = 0; k < t.segOrig.size(); ++k) {
+            if (t.segOrig[k] == kFarIndex) continue;
+            const float *nd = &t.nodes[((size_t)t.first_leaf + k / 4) * WOST_NODE_FLOATS] + (k & 3);
+            box.insert(box.end(), {nd[0], nd[4], nd[8], nd[12]});
+            hl.push_back(nd[16]);
+            id.push_back((int32_t)k);
+            id.push_back(t.segOrig[k]);
+        }
+        while (hl.size() % 256) {
+            box.insert(box.end(), {1.0e18f, 1.0e18f, 1.0f, 0.0f});
+            hl.push_back(0.0f);
+            id.push_back(-1);
+            id.push_back(kFarIndex);
+        }
+        v.n_scan = (int32_t)hl.size();
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), hl.size(), &v.scanBox));
+        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.scanHl));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(id.data()), hl.size(), &v.scanId));
+    }
+    WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(t.segVerts.data()), t.segVerts.size() / 2, &v.segVerts));
+    if (v.emissive && t.n_segs > WOST_FLAT_MAX) return upload_run_boxes(t.flat, s);
+    return WOST_OK;
+}
+
+int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshStorage &s)
+{
+    DevMesh &v = s.view;
+    const int n_segs = (int)flat_recs.size();
+    // boxes over runs of consecutive original indices, for the index-ordered sampling of emissive Neumann meshes
+    // (sample_in_sphere_tree); padded like the tree's boxes, so that rounding never hides a segment the flat loop takes
+    {
+        float ext = 0.0f;
+        for (const FlatSeg &f : flat_recs) ext = std::max(ext, std::max(std::max(std::fabs(f.ax), std::fabs(f.ay)), std::max(std::fabs(f.ax + f.ex), std::fabs(f.ay + f.ey))));
+        const float pad = ext * 0x1p-18f + 1e-30f;
+        std::vector<float> ob;
+        int levels = 0;
+        size_t prev_off = 0, prev_n = 0;
+        for (int l = 0; l < 12; ++l) {
+            const size_t run = (size_t)4 << (2 * l), n_runs = ((size_t)n_segs + run - 1) / run;
+            v.obox_off[l] = (int32_t)(ob.size() / 4);
+            for (size_t r = 0; r < n_runs; ++r) {
+                float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+                if (l == 0) {
+                    for (size_t i = r * 4; i < std::min<size_t>(r * 4 + 4, (size_t)n_segs); ++i) {
+                        const FlatSeg &f = flat_recs[i];
+                        lo[0] = std::min(lo[0], std::min(f.ax, f.ax + f.ex)); hi[0] = std::max(hi[0], std::max(f.ax, f.ax + f.ex));
+                        lo[1] = std::min(lo[1], std::min(f.ay, f.ay + f.ey)); hi[1] = std::max(hi[1], std::max(f.ay, f.ay + f.ey));
+                    }
+                    lo[0] -= pad; lo[1] -= pad; hi[0] += pad; hi[1] += pad;
+                } else {
+                    for (size_t c = r * 4; c < std::min(r * 4 + 4, prev_n); ++c) {
+                        const float *b = &ob[(prev_off + c) * 4];
+                        lo[0] = std::min(lo[0], b[0]); lo[1] = std::min(lo[1], b[1]); hi[0] = std::max(hi[0], b[2]); hi[1] = std::max(hi[1], b[3]);
+                    }
+                }
+                ob.insert(ob.end(), {lo[0], lo[1], hi[0], hi[1]});
+            }
+            prev_off = (size_t)v.obox_off[l];
+            prev_n = n_runs;
+            levels = l + 1;
+            if (n_runs <= 1) break;
+        }
+        v.obox_levels = levels;
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(ob.data()), ob.size() / 4, &v.obox));
+        const size_t n4 = (flat_recs.size() + 3) / 4 * 4;
+        std::vector<float> lens(n4, 0.0f), hl(n4, 0.0f), box(n4 * 4, 1.0e18f);
+        for (size_t i = 0; i < flat_recs.size(); ++i) {
+            const FlatSeg &f = flat_recs[i];
+            lens[i] = f.len; hl[i] = f.hl;
+            box[4 * i] = f.cx; box[4 * i + 1] = f.cy; box[4 * i + 2] = f.ux; box[4 * i + 3] = f.uy;
+        }
+        WOST_TRY(upload(s.allocs, lens.data(), lens.size(), &v.lens));
+        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.sampHl));
+        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), n4, &v.sampBox));
+    }
+    return WOST_OK;
+}
+
+// Problem<2>::build_bvh: on the device (wost_build2.hip) for every mesh worth the launches; the host builder for the small ones
+// (a four-segment Neumann box is done before the first kernel would start), behind WOST_HOST_BUILD=1, and for the tree-quality
+// knobs.  Both give the same arrays bit for bit (wost_mesh_build_check, tests/test_gpu_build2.py).
+int upload_mesh(const wost_mesh_desc &d, DeviceMeshStorage &s)
+{
+    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
+    const char *e_host = getenv("WOST_HOST_BUILD");
+    const bool knobs = getenv("WOST_TREE_REFINE") || getenv("WOST_TREE_EXTRA_LEVELS");
+    int min_segs = 512;
+    if (const char *e = getenv("WOST_DEVICE_BUILD_MIN")) min_segs = std::max(1, atoi(e));
+    if ((e_host && atoi(e_host) != 0) || knobs || d.n_segs < min_segs) return upload_mesh_host(d, s);
+    DeviceTree2 t;
+    const int rc = build_tree_device(d, t);
+    if (rc != WOST_OK) return rc;
+    s.view = t.view;
+    if (t.alloc) s.allocs.push_back(t.alloc);
+    if (s.view.emissive && d.n_segs > WOST_FLAT_MAX) {
+        // (rare: an emissive boundary on the tree) the run boxes are built on the host from the flat records
+        std::vector<FlatSeg> flat_recs((size_t)d.n_segs);
+        WOST_TRY(hipMemcpy(flat_recs.data(), s.view.flat, flat_recs.size() * sizeof(FlatSeg), hipMemcpyDeviceToHost));
+        return upload_run_boxes(flat_recs, s);
+    }
+    return WOST_OK;
+}
+
+static_assert(sizeof(FlatSeg) == sizeof(DevFlatSeg), "flat segment layout");
+static_assert(sizeof(SilVertex) == sizeof(DevSilVertex), "silhouette vertex layout");
+
 }  // namespace wost
+
+using namespace wost;
+
+extern "C" {
+
+int wost_mesh_build_check(const wost_mesh_desc *mesh, int device, int32_t repeat, double *host_ms, double *device_ms, int64_t *mismatch)
+{
+    if (!mesh || !mismatch) return set_error(WOST_ERR_INVALID, "null argument");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
+    WOST_TRY(hipSetDevice(device));
+    if (mesh->n_segs < 0 || mesh->n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
+    struct Owned {
+        DeviceMeshStorage m;
+        ~Owned()
+        {
+            for (void *p : m.allocs) (void)hipFree(p);
+        }
+    };
+    using clock = std::chrono::steady_clock;
+    double best_host = 1e300, best_dev = 1e300;
+    Owned a, b;
+    for (int r = 0; r < std::max(1, repeat); ++r) {
+        Owned ha, hb;
+        WOST_TRY(hipDeviceSynchronize());
+        auto t0 = clock::now();
+        int rc = upload_mesh_host(*mesh, ha.m);
+        WOST_TRY(hipDeviceSynchronize());
+        auto t1 = clock::now();
+        if (rc != WOST_OK) return rc;
+        DeviceTree2 t;
+        rc = build_tree_device(*mesh, t);
+        if (t.alloc) hb.m.allocs.push_back(t.alloc);
+        hb.m.view = t.view;
+        WOST_TRY(hipDeviceSynchronize());
+        auto t2 = clock::now();
+        if (rc != WOST_OK) return rc;
+        best_host = std::min(best_host, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        best_dev = std::min(best_dev, std::chrono::duration<double, std::milli>(t2 - t1).count());
+        std::swap(a.m, ha.m);
+        std::swap(b.m, hb.m);
+    }
+    if (host_ms) *host_ms = best_host;
+    if (device_ms) *device_ms = best_dev;
+    const DevMesh &x = a.m.view, &y = b.m.view;
+    for (int i = 0; i < 16; ++i) mismatch[i] = 0;
+    const int64_t scalars = (x.n_segs != y.n_segs) + (x.n_sil != y.n_sil) + (x.levels != y.levels) + (x.first_leaf != y.first_leaf) + (x.emissive != y.emissive) +
+                            (std::memcmp(&x.far2, &y.far2, 4) != 0) + (std::memcmp(&x.huge2, &y.huge2, 4) != 0) + (x.n_scan != y.n_scan);
+    mismatch[14] = scalars;
+    if (x.n_segs == 0 || scalars) return WOST_OK;
+    const size_t cap = 3 * (size_t)x.first_leaf + 1, n_all = (size_t)x.first_leaf + cap, n_slots = cap * 4, n = (size_t)x.n_segs, nv = (size_t)x.n_sil;
+    int64_t *cmp = &mismatch[15];
+    mismatch[0] = differing_bytes(x.nodes, y.nodes, n_all * (WOST_NODE_FLOATS / 4), cmp);
+    mismatch[1] = differing_bytes(x.cones, y.cones, n_all * 5, cmp);
+    mismatch[2] = differing_bytes(x.segA, y.segA, n_slots, cmp);
+    mismatch[3] = differing_bytes(x.segInv, y.segInv, n_slots, cmp);
+    mismatch[4] = differing_bytes(x.segOrig, y.segOrig, n_slots, cmp);
+    mismatch[5] = differing_bytes(x.segCol, y.segCol, n_slots * 12, cmp);
+    mismatch[6] = differing_bytes(x.segVerts, y.segVerts, n_slots, cmp);
+    mismatch[7] = differing_bytes(x.flat, y.flat, n, cmp);
+    mismatch[8] = differing_bytes(x.flatCol, y.flatCol, n * 12, cmp);
+    mismatch[9] = differing_bytes(x.sil, y.sil, nv, cmp);
+    mismatch[10] = differing_bytes(x.silN, y.silN, nv, cmp);
+    mismatch[11] = differing_bytes(x.scanBox, y.scanBox, (size_t)x.n_scan, cmp);
+    mismatch[12] = differing_bytes(x.scanHl, y.scanHl, (size_t)x.n_scan, cmp);
+    mismatch[13] = differing_bytes(x.scanId, y.scanId, (size_t)x.n_scan, cmp);
+    return WOST_OK;
+}
+
+}  // extern "C"

@@ -960,23 +960,6 @@ int upload_mesh3(const wost3_mesh_desc &d, DeviceMesh3 &s)
 using namespace wost;
 
 // ---- developer / test entry: both builders on one mesh, every array of the two uploaded meshes compared byte for byte ------
-namespace {
-template <class T>
-int64_t differing_bytes(const T *a, const T *b, size_t count, int64_t *compared)
-{
-    if (count == 0) return 0;
-    const size_t bytes = count * sizeof(T);
-    if (!a || !b) return (a || b) ? (int64_t)bytes : 0;
-    std::vector<unsigned char> ha(bytes), hb(bytes);
-    if (hipMemcpy(ha.data(), a, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hb.data(), b, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return (int64_t)bytes;
-    int64_t diff = 0;
-    for (size_t i = 0; i < bytes; ++i) diff += ha[i] != hb[i];
-    *compared += (int64_t)bytes;
-    return diff;
-}
-}  // namespace
-
 int wost3_mesh_build_check(const wost3_mesh_desc *mesh, int device, int32_t repeat, double *host_ms, double *device_ms, int64_t *mismatch)
 {
     if (!mesh || !mismatch) return set_error(WOST_ERR_INVALID, "null argument");

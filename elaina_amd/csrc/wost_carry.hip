@@ -229,14 +229,6 @@ static int carry_drop(CarryState &s, hipStream_t stream, int rc)
     return set_error(rc, msg + " (the carried solve was dropped: spp_done is 0)");
 }
 
-static void add_stats(wost_stats &total, const wost_stats &st)
-{
-    total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
-    total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
-    total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
-    total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = st.reserved > total.reserved ? st.reserved : total.reserved;
-}
-
 static double ms_since(std::chrono::high_resolution_clock::time_point t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();

@@ -160,8 +160,7 @@ __global__ __launch_bounds__(256) void grad_prep3_kernel(GradPrepParams3 P)
 // the stack columns of a block of 256 threads for the deeper of the two trees
 static size_t prep_lds(int32_t levels_d, bool has_d, int32_t levels_n, bool has_n)
 {
-    const int lv = std::max(has_d ? levels_d : 1, has_n ? levels_n : 1);
-    return (size_t)(3 * lv + 1) * 256 * sizeof(uint32_t);
+    return stack_lds(std::max(has_d ? levels_d : 1, has_n ? levels_n : 1));
 }
 
 int grad_prep2(const DevMesh &dm, const DevMesh &nm, const GradPrep &p, hipStream_t stream)
@@ -319,11 +318,8 @@ int grad_solve_dev(const GradCall &c, const float *pts_dev, int32_t n, int32_t s
         float ms_front = 0.0f, ms_behind = 0.0f;
         WOST_TRY(hipEventElapsedTime(&ms_front, s.ev[0], s.ev[1]));
         WOST_TRY(hipEventElapsedTime(&ms_behind, s.ev[2], s.ev[3]));
-        total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
-        total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
-        total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
-        total.kernel_ms += st.kernel_ms + (double)ms_front + (double)ms_behind;
-        total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
+        add_stats(total, st);
+        total.kernel_ms += (double)ms_front + (double)ms_behind;
     }
     if (stats) {
         *stats = total;

@@ -257,14 +257,6 @@ int gradlist_bind(GradList &l, const GradCall &c, const float *pts, bool pts_on_
 }
 
 // ---- the calls ---------------------------------------------------------------------------------------------------------------
-static void add_stats(wost_stats &total, const wost_stats &st)
-{
-    total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
-    total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
-    total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
-    total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
-}
-
 // a call failed after device work had begun: some points' sums may be written and others' not -- the samples are gone
 static int gradlist_drop(GradList &l, hipStream_t stream, int rc)
 {

@@ -1,5 +1,9 @@
 // wost_hip.hip -- walk kernels and the C-ABI of libwost_hip.so (gfx950 / MI355X only).
 //
+// Holds: the 2-D walk, init and query kernels; the solve driver (run_solve) with its launch steps; what the 2-D context adds to
+// the shared bodies of the entry points (wost_uniform.h, wost_carry.h, wost_grad.h) and the entry points themselves, which
+// forward to those bodies; wost_set_option.  The context is in wost_internal2.h, the mesh upload in wost_build2.hip.
+//
 // Design (DESIGN.md has the long form):
 //   * one SoA walk-state queue; a queue slot is one PIXEL's walker, which carries its
 //     PCG32 state, position, partial solution and the temporal hint of the last closest
@@ -37,32 +41,12 @@
 #include "wost_order.h"
 #include "wost_device.h"
 #include "wost_internal.h"
-#include "wost_carry.h"
-#include "wost_grad.h"
+#include "wost_internal2.h"
 #include "wost_walk.h"
 #include "wost_quad.h"
 #include "wost_coop.h"
 
 namespace wost {
-
-// ------------------------------------------------------------------------------------------
-// queue layout
-// ------------------------------------------------------------------------------------------
-struct WalkQueue {
-    uint32_t *pix;     // global pixel id
-    float *x0, *y0;    // evaluation point of the pixel (start of every sample)
-    float *px, *py;    // current walk position
-    uint64_t *rng;     // PCG32 state (inc == 1 for every pixel: setSeed(.., seq 0))
-    uint32_t *meta;    // sample[0:20) | depth[20:30) | onNeumann[30]
-    float *nx, *ny;    // Neumann normal at the current point (valid when onNeumann)
-    int32_t *hint;     // slot of the closest Dirichlet segment of the previous step
-    float *thp;        // throughput (scalar: all three channels are always equal)
-    float *sr, *sg, *sb;  // running solution of the pixel
-    float *d0_d2;      // cached closest-point result of the evaluation point (depth 0 of
-    int32_t *d0_slot;  //   every sample starts at the same point)
-    float *est;        // written when a persistent launch hands a pixel over mid-way: walk steps the pixel is expected to need still
-                       //   (not part of a walker's state: no kernel loads it back; the host orders the next launch by it)
-};
 
 // Atomics on one cache line are served one by one by its L2 channel (about 10 ns each: the eight
 // counters of the 16 384 waves of a round cost over a millisecond), so the counters exist in
@@ -1214,258 +1198,9 @@ int set_error(int code, const std::string &msg)
     return code;
 }
 
-struct DeviceMeshStorage {
-    DevMesh view{};
-    std::vector<void *> allocs;
-    HostTree host;
-};
-
-
-// the run boxes over consecutive ORIGINAL indices and the sampler's compact copies (an emissive boundary on the tree only):
-// a function of the flat records alone
-static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshStorage &s);
-
-// the host builder's tree (lbvh_build.cpp), uploaded array by array: the checker of the device build, small meshes,
-// WOST_HOST_BUILD=1 and the tree-quality knobs
-static int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
-{
-    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
-    // developer knobs for tree-quality experiments (defaults: refined, minimal depth)
-    const char *e_refine = getenv("WOST_TREE_REFINE");
-    const char *e_extra = getenv("WOST_TREE_EXTRA_LEVELS");
-    const bool refine = e_refine ? atoi(e_refine) != 0 : true;
-    const int extra = e_extra ? std::max(0, std::min(3, atoi(e_extra))) : 0;
-    if (build_tree(d.n_verts, d.verts, d.n_segs, d.segs, d.colors, &s.host, refine, extra) != 0)
-        return set_error(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
-    const HostTree &t = s.host;
-    DevMesh &v = s.view;
-    v = DevMesh{};
-    v.n_segs = t.n_segs;
-    if (t.n_segs == 0) return WOST_OK;
-    v.n_sil = (int32_t)t.sil.size();
-    v.levels = t.levels;
-    {
-        // the boxes are padded by 2^-21 of the largest coordinate; the rounding of a box distance grows with the distance
-        // to the box (about 10^-7 of it): up to one and a half extents from the closest segment the padding covers it
-        float ext = 0.0f;
-        for (int i = 0; i < d.n_segs; ++i)
-            for (int e = 0; e < 2; ++e) {
-                const int32_t vi = d.segs[2 * i + e];
-                ext = std::max(ext, std::max(std::fabs(d.verts[2 * vi]), std::fabs(d.verts[2 * vi + 1])));
-            }
-        v.far2 = 2.25f * ext * ext;
-        v.huge2 = 4096.0f * ext * ext;       // 64 extents
-    }
-    v.first_leaf = t.first_leaf;
-    v.emissive = 0;
-    for (float c : t.flatCol)
-        if (c != 0.0f) v.emissive = 1;
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.nodes.data()), t.nodes.size() / 4, &v.nodes));
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.segA.data()), t.segA.size() / 4, &v.segA));
-    WOST_TRY(upload(s.allocs, t.segInv.data(), t.segInv.size(), &v.segInv));
-    WOST_TRY(upload(s.allocs, t.segOrig.data(), t.segOrig.size(), &v.segOrig));
-    WOST_TRY(upload(s.allocs, t.segCol.data(), t.segCol.size(), &v.segCol));
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevFlatSeg *>(t.flat.data()), t.flat.size(), &v.flat));
-    WOST_TRY(upload(s.allocs, t.flatCol.data(), t.flatCol.size(), &v.flatCol));
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const DevSilVertex *>(t.sil.data()), t.sil.size(), &v.sil));
-    {
-        // the normals of every vertex's two segments beside it: the flat silhouette test of a small boundary reads them with the vertex
-        std::vector<float> sn(t.sil.size() * 4, 0.0f);
-        for (size_t k = 0; k < t.sil.size(); ++k) {
-            const SilVertex &sv = t.sil[k];
-            if (sv.prev >= 0) { sn[4 * k] = t.flat[(size_t)sv.prev].nx; sn[4 * k + 1] = t.flat[(size_t)sv.prev].ny; }
-            if (sv.next >= 0) { sn[4 * k + 2] = t.flat[(size_t)sv.next].nx; sn[4 * k + 3] = t.flat[(size_t)sv.next].ny; }
-        }
-        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(sn.data()), t.sil.size(), &v.silN));
-    }
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(t.cones.data()), t.cones.size() / 4, &v.cones));
-    {
-        // closest_point_wave: the occupied slots, compact; the operands are those of the leaf-level node records
-        std::vector<float> box, hl;
-        std::vector<int32_t> id;
-        for (size_t k = 0; k < t.segOrig.size(); ++k) {
-            if (t.segOrig[k] == kFarIndex) continue;
-            const float *nd = &t.nodes[((size_t)t.first_leaf + k / 4) * WOST_NODE_FLOATS] + (k & 3);
-            box.insert(box.end(), {nd[0], nd[4], nd[8], nd[12]});
-            hl.push_back(nd[16]);
-            id.push_back((int32_t)k);
-            id.push_back(t.segOrig[k]);
-        }
-        while (hl.size() % 256) {
-            box.insert(box.end(), {1.0e18f, 1.0e18f, 1.0f, 0.0f});
-            hl.push_back(0.0f);
-            id.push_back(-1);
-            id.push_back(kFarIndex);
-        }
-        v.n_scan = (int32_t)hl.size();
-        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), hl.size(), &v.scanBox));
-        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.scanHl));
-        WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(id.data()), hl.size(), &v.scanId));
-    }
-    WOST_TRY(upload(s.allocs, reinterpret_cast<const int2 *>(t.segVerts.data()), t.segVerts.size() / 2, &v.segVerts));
-    if (v.emissive && t.n_segs > WOST_FLAT_MAX) return upload_run_boxes(t.flat, s);
-    return WOST_OK;
-}
-
-static int upload_run_boxes(const std::vector<FlatSeg> &flat_recs, DeviceMeshStorage &s)
-{
-    DevMesh &v = s.view;
-    const int n_segs = (int)flat_recs.size();
-    // boxes over runs of consecutive original indices, for the index-ordered sampling of emissive Neumann meshes
-    // (sample_in_sphere_tree); padded like the tree's boxes, so that rounding never hides a segment the flat loop takes
-    {
-        float ext = 0.0f;
-        for (const FlatSeg &f : flat_recs) ext = std::max(ext, std::max(std::max(std::fabs(f.ax), std::fabs(f.ay)), std::max(std::fabs(f.ax + f.ex), std::fabs(f.ay + f.ey))));
-        const float pad = ext * 0x1p-18f + 1e-30f;
-        std::vector<float> ob;
-        int levels = 0;
-        size_t prev_off = 0, prev_n = 0;
-        for (int l = 0; l < 12; ++l) {
-            const size_t run = (size_t)4 << (2 * l), n_runs = ((size_t)n_segs + run - 1) / run;
-            v.obox_off[l] = (int32_t)(ob.size() / 4);
-            for (size_t r = 0; r < n_runs; ++r) {
-                float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
-                if (l == 0) {
-                    for (size_t i = r * 4; i < std::min<size_t>(r * 4 + 4, (size_t)n_segs); ++i) {
-                        const FlatSeg &f = flat_recs[i];
-                        lo[0] = std::min(lo[0], std::min(f.ax, f.ax + f.ex)); hi[0] = std::max(hi[0], std::max(f.ax, f.ax + f.ex));
-                        lo[1] = std::min(lo[1], std::min(f.ay, f.ay + f.ey)); hi[1] = std::max(hi[1], std::max(f.ay, f.ay + f.ey));
-                    }
-                    lo[0] -= pad; lo[1] -= pad; hi[0] += pad; hi[1] += pad;
-                } else {
-                    for (size_t c = r * 4; c < std::min(r * 4 + 4, prev_n); ++c) {
-                        const float *b = &ob[(prev_off + c) * 4];
-                        lo[0] = std::min(lo[0], b[0]); lo[1] = std::min(lo[1], b[1]); hi[0] = std::max(hi[0], b[2]); hi[1] = std::max(hi[1], b[3]);
-                    }
-                }
-                ob.insert(ob.end(), {lo[0], lo[1], hi[0], hi[1]});
-            }
-            prev_off = (size_t)v.obox_off[l];
-            prev_n = n_runs;
-            levels = l + 1;
-            if (n_runs <= 1) break;
-        }
-        v.obox_levels = levels;
-        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(ob.data()), ob.size() / 4, &v.obox));
-        const size_t n4 = (flat_recs.size() + 3) / 4 * 4;
-        std::vector<float> lens(n4, 0.0f), hl(n4, 0.0f), box(n4 * 4, 1.0e18f);
-        for (size_t i = 0; i < flat_recs.size(); ++i) {
-            const FlatSeg &f = flat_recs[i];
-            lens[i] = f.len; hl[i] = f.hl;
-            box[4 * i] = f.cx; box[4 * i + 1] = f.cy; box[4 * i + 2] = f.ux; box[4 * i + 3] = f.uy;
-        }
-        WOST_TRY(upload(s.allocs, lens.data(), lens.size(), &v.lens));
-        WOST_TRY(upload(s.allocs, hl.data(), hl.size(), &v.sampHl));
-        WOST_TRY(upload(s.allocs, reinterpret_cast<const float4 *>(box.data()), n4, &v.sampBox));
-    }
-    return WOST_OK;
-}
-
-// Problem<2>::build_bvh: on the device (wost_build2.hip) for every mesh worth the launches; the host builder for the small ones
-// (a four-segment Neumann box is done before the first kernel would start), behind WOST_HOST_BUILD=1, and for the tree-quality
-// knobs.  Both give the same arrays bit for bit (wost_mesh_build_check, tests/test_gpu_build2.py).
-static int upload_mesh(const wost_mesh_desc &d, DeviceMeshStorage &s)
-{
-    if (d.n_segs < 0 || d.n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
-    const char *e_host = getenv("WOST_HOST_BUILD");
-    const bool knobs = getenv("WOST_TREE_REFINE") || getenv("WOST_TREE_EXTRA_LEVELS");
-    int min_segs = 512;
-    if (const char *e = getenv("WOST_DEVICE_BUILD_MIN")) min_segs = std::max(1, atoi(e));
-    if ((e_host && atoi(e_host) != 0) || knobs || d.n_segs < min_segs) return upload_mesh_host(d, s);
-    DeviceTree2 t;
-    const int rc = build_tree_device(d, t);
-    if (rc != WOST_OK) return rc;
-    s.view = t.view;
-    if (t.alloc) s.allocs.push_back(t.alloc);
-    if (s.view.emissive && d.n_segs > WOST_FLAT_MAX) {
-        // (rare: an emissive boundary on the tree) the run boxes are built on the host from the flat records
-        std::vector<FlatSeg> flat_recs((size_t)d.n_segs);
-        WOST_TRY(hipMemcpy(flat_recs.data(), s.view.flat, flat_recs.size() * sizeof(FlatSeg), hipMemcpyDeviceToHost));
-        return upload_run_boxes(flat_recs, s);
-    }
-    return WOST_OK;
-}
-
-static_assert(sizeof(FlatSeg) == sizeof(DevFlatSeg), "flat segment layout");
-static_assert(sizeof(SilVertex) == sizeof(DevSilVertex), "silhouette vertex layout");
-
 }  // namespace wost
 
 using namespace wost;
-
-struct wost_context {
-    int device = 0;
-    wost_settings settings{};
-    DevSettings dst{};
-    DevProbe probe{};
-    DeviceMeshStorage dm, nm;
-    uint8_t *mask = nullptr;
-    DevSource src{};                // rgb == nullptr: no source term
-    size_t n_pixels = 0;
-    // queues
-    void *queue_mem[2] = {nullptr, nullptr};
-    WalkQueue queue[2]{};
-    uint32_t *counts = nullptr;     // [2]
-    StatsDev *stats = nullptr;
-    float *field = nullptr;         // n_pixels * 3 (used by wost_solve)
-    uint32_t *host_count = nullptr; // pinned
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // options
-    int steps_per_round = 0;   // 0 = automatic (see run_solve)
-    int thin_waves = 1;        // spread the walkers of an under-full launch over more waves
-    int block_size = 256;
-    int wait_weight = 0;       // 0 = automatic: this and trav_burst per launch (set_schedule)
-    int trav_burst = 0;        // 0 = automatic
-    int time_kernels = 1;
-    int refill = -1;       // -1 = automatic (few samples per pixel), 0 = never, 1 = always
-    int persist = -1;      // many samples per pixel, more walkers than resident lanes: the first launch is persistent (lanes take pixels,
-                           //   longest expected chain first, until none is left; the rest of the solve runs in rounds): -1 = automatic, 0, 1
-    int persist_order = 1; // ... in the order of wost_order.h (0: queue order; comparison runs)
-    int few_order = 1;     // the one-launch path of few samples per pixel in that order too (config 2's frame at 1 / 2 / 4 spp: 2.64 -> 2.48, 4.09 -> 3.55, 6.79 -> 5.68 ms)
-    int dry_stop = 1;      // the persistent launch: once its input queue is dry every wave stops at its next look at the cursor (1), or only a
-                           //   wave that needs a refill does (0: the rule until this option existed; comparison runs)
-    int dry_cadence = 4;   // ... a wave looks again after dry_cadence walk steps of its busiest lane (a power of two), less often while the queue is far from dry
-    int chain_start = 1;   // the round and quad kernels: a lane whose walk is absorbed takes the depth-0 step of its pixel's next sample in the
-                           //   same step trip (1), or in the wave's next one (0: the rule until this option existed; comparison runs)
-    int resident_blocks = 0;  // blocks of a one-launch / persistent launch; 0 = as many as the chip holds (tests: a few blocks drain a small frame)
-    // what a persistent launch hands over (run_solve): the pixels expected to need `long_steps` walk steps or more run to their end at
-    // once, four lanes to a walker, on a stream of higher priority beside the rounds of the others (0 = none do); the first round
-    // takes the others in the order of their expected remainders (tail_sort), so that a wave's walkers finish together
-    int long_steps = 1024;
-    int long_cap = 32768;
-    int tail_sort = 1;
-    void *long_mem = nullptr;
-    WalkQueue long_queue{};
-    int long_thin = 2048;         // ... the first long_thin of them four to a wave, the others sixteen
-    // Their stream has the highest priority: they are the critical path of the solve's end, and the runtime keeps the hardware
-    // queues of a priority level apart from those of the others -- a stream of ordinary priority can land on the hardware queue
-    // of the caller's stream (four queues per level), and then the launch meant to run BESIDE the rounds runs behind them (seen
-    // in bench.py, which makes a second handle first: the solve waited 27 ms for it).
-    hipStream_t long_stream = nullptr;
-    hipEvent_t long_ev0 = nullptr, long_ev1 = nullptr;
-    WalkOrder order;
-    int quad = -1;         // four lanes per walker in under-filled launches: -1 = automatic, 0 = never, 1 = every ordinary round
-    double quad_fill = 1.0;   // automatic: when 4 x walkers <= quad_fill x resident lanes
-    int coop = 1;             // a Neumann mesh on the tree: its silhouette and ray queries by the wave as a whole (wost_coop.h); 0 = per lane
-    int pool_cap = 0;         // ... tasks per pool and wave; 0 = automatic: 128 per level of the Neumann tree (a deeper tree keeps more tasks in flight)
-    int ray_slot_trigger = 32;
-    uint32_t *cursor = nullptr;
-    hipStream_t far_stream = nullptr;          // the launches that take strayed walkers through the SLACK kernel (run_solve)
-    hipEvent_t far_ev0 = nullptr, far_ev1 = nullptr;
-    int n_cus = 256;
-    StatsDev *host_stats = nullptr;            // pinned: the counters as they stood after each launch (last_launches)
-    std::vector<wost_launch_info> last_launches;
-    uint64_t steps_before = 0;                 // a point solve in chunks: the walk steps of its earlier chunks (wost_launch_info::walk_steps_done)
-    // the carried frame solve (wost_solve_more & co., wost_carry.h)
-    wost::CarryState carry;
-    // ... and, beside it, the carried point list (wost_points_carry & co.)
-    wost::PointList list;
-    // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
-    wost::GradScratch grad;
-    // ... and the carried gradient list (wost_gradient_points_carry & co.), which shares it
-    wost::GradList glist;
-};
 
 namespace wost {
 SceneView scene_view(wost_handle h)
@@ -1514,18 +1249,12 @@ static void destroy_ctx(wost_context *c)
     (void)hipSetDevice(c->device);
     for (void *p : c->dm.allocs) (void)hipFree(p);
     for (void *p : c->nm.allocs) (void)hipFree(p);
-    if (c->mask) (void)hipFree(c->mask);
     if (c->src.rgb) (void)hipFree(const_cast<float *>(c->src.rgb));
     for (int i = 0; i < 2; ++i)
         if (c->queue_mem[i]) (void)hipFree(c->queue_mem[i]);
     if (c->counts) (void)hipFree(c->counts);
     if (c->stats) (void)hipFree(c->stats);
-    if (c->field) (void)hipFree(c->field);
     if (c->cursor) (void)hipFree(c->cursor);
-    carry_free(c->carry);
-    points_free(c->list);
-    grad_free(c->grad);
-    gradlist_free(c->glist);
     order_free(c->order);
     if (c->long_mem) (void)hipFree(c->long_mem);
     if (c->long_stream) (void)hipStreamDestroy(c->long_stream);
@@ -1536,28 +1265,65 @@ static void destroy_ctx(wost_context *c)
     if (c->far_ev1) (void)hipEventDestroy(c->far_ev1);
     if (c->host_count) (void)hipHostFree(c->host_count);
     if (c->host_stats) (void)hipHostFree(c->host_stats);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    destroy_base(c);
     delete c;
 }
 
-namespace {
-template <class T>
-int64_t differing_bytes2(const T *a, const T *b, size_t count, int64_t *compared)
+// What wost_create adds to the shared part (create_handle, wost_uniform.h): the probe, the meshes, the source grid, the queues
+// and counters of the rounds, the side streams and the order buffers.
+static int fill_ctx(wost_context *c, const wost_scene_desc &scene)
 {
-    if (count == 0) return 0;
-    const size_t bytes = count * sizeof(T);
-    if (!a || !b) return (a || b) ? (int64_t)bytes : 0;
-    std::vector<unsigned char> ha(bytes), hb(bytes);
-    if (hipMemcpy(ha.data(), a, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hb.data(), b, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        return (int64_t)bytes;
-    int64_t diff = 0;
-    for (size_t i = 0; i < bytes; ++i) diff += ha[i] != hb[i];
-    *compared += (int64_t)bytes;
-    return diff;
+    c->probe = DevProbe{scene.probe_scale, scene.probe_pos[0], scene.probe_pos[1], scene.probe_up[0], scene.probe_up[1]};
+    int rc = upload_mesh(scene.dirichlet, c->dm);
+    if (rc == WOST_OK) rc = upload_mesh(scene.neumann, c->nm);
+    if (rc == WOST_OK) rc = upload_mask(c, scene.mask);
+    if (rc != WOST_OK) return rc;
+    if (scene.source.nx > 0 && scene.source.ny > 0) {
+        const wost_source_desc &sd = scene.source;
+        if (!sd.rgb) return set_error(WOST_ERR_INVALID, "source grid without data");
+        const size_t bytes = (size_t)sd.nx * sd.ny * 3 * sizeof(float);
+        float *dev = nullptr;
+        WOST_TRY(hipMalloc((void **)&dev, bytes));
+        c->src = DevSource{dev, sd.nx, sd.ny, sd.index_scale[0], sd.index_scale[1], sd.index_offset[0], sd.index_offset[1],
+                           sd.intensity};
+        WOST_TRY(hipMemcpy(dev, sd.rgb, bytes, hipMemcpyHostToDevice));
+    }
+    const size_t qbytes = queue_bytes(c->n_pixels);
+    for (int i = 0; i < 2; ++i) {
+        WOST_TRY(hipMalloc(&c->queue_mem[i], qbytes));
+        carve_queue(c->queue_mem[i], c->n_pixels, c->queue[i]);
+    }
+    WOST_TRY(hipMalloc((void **)&c->counts, 12 * sizeof(uint32_t)));   // two queue counts, the far count and its input copy; [4..7]: the hand-over of a persistent launch
+    WOST_TRY(hipMalloc((void **)&c->stats, kStatCopies * sizeof(StatsDev)));
+    WOST_TRY(hipMalloc((void **)&c->cursor, sizeof(uint32_t)));
+    WOST_TRY(hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    WOST_TRY(hipHostMalloc((void **)&c->host_count, 8 * sizeof(uint32_t)));
+    WOST_TRY(hipHostMalloc((void **)&c->host_stats, kStatCopies * sizeof(StatsDev)));
+    if ((rc = create_frame(c)) != WOST_OK) return rc;
+    WOST_TRY(hipStreamCreateWithFlags(&c->far_stream, hipStreamNonBlocking));
+    WOST_TRY(hipEventCreateWithFlags(&c->far_ev0, hipEventDisableTiming));
+    WOST_TRY(hipEventCreateWithFlags(&c->far_ev1, hipEventDisableTiming));
+    {
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+        WOST_TRY(hipStreamCreateWithPriority(&c->long_stream, hipStreamNonBlocking, greatest));
+    }
+    WOST_TRY(hipEventCreateWithFlags(&c->long_ev0, hipEventDisableTiming));
+    WOST_TRY(hipEventCreateWithFlags(&c->long_ev1, hipEventDisableTiming));
+    {
+        // the order of a persistent / one-launch solve: its buffers and the first use of its sort kernels (their code objects load
+        // then: 2.5 ms) belong here, beside the tree builds, not inside the first solve -- time-to-1spp of a fresh handle
+        WOST_TRY((hipError_t)order_alloc(c->order, c->n_pixels));
+        const uint32_t n_warm = (uint32_t)std::min<size_t>(c->n_pixels, 1024);
+        const uint32_t *unused = nullptr;
+        WOST_TRY(hipMemsetAsync(c->queue[0].d0_d2, 0, n_warm * sizeof(float), c->stream));
+        WOST_TRY(hipMemsetAsync(c->queue[0].est, 0, n_warm * sizeof(float), c->stream));
+        WOST_TRY((hipError_t)order_by_distance(c->order, c->queue[0].d0_d2, n_warm, c->stream, &unused));
+        WOST_TRY((hipError_t)order_by_estimate(c->order, c->queue[0].est, n_warm, c->stream, &unused));
+        WOST_TRY(hipStreamSynchronize(c->stream));
+    }
+    return WOST_OK;
 }
-}  // namespace
 
 extern "C" {
 
@@ -1565,167 +1331,11 @@ extern "C" {
 // 0.3: the carried point list (wost_points_carry & co., wost3_points_carry & co.)
 const char *wost_version(void) { return "wost-hip 0.3 (gfx950)"; }
 
-
-int wost_mesh_build_check(const wost_mesh_desc *mesh, int device, int32_t repeat, double *host_ms, double *device_ms, int64_t *mismatch)
-{
-    if (!mesh || !mismatch) return set_error(WOST_ERR_INVALID, "null argument");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    WOST_TRY(hipSetDevice(device));
-    if (mesh->n_segs < 0 || mesh->n_verts < 0) return set_error(WOST_ERR_INVALID, "negative mesh size");
-    struct Owned {
-        DeviceMeshStorage m;
-        ~Owned()
-        {
-            for (void *p : m.allocs) (void)hipFree(p);
-        }
-    };
-    using clock = std::chrono::steady_clock;
-    double best_host = 1e300, best_dev = 1e300;
-    Owned a, b;
-    for (int r = 0; r < std::max(1, repeat); ++r) {
-        Owned ha, hb;
-        WOST_TRY(hipDeviceSynchronize());
-        auto t0 = clock::now();
-        int rc = upload_mesh_host(*mesh, ha.m);
-        WOST_TRY(hipDeviceSynchronize());
-        auto t1 = clock::now();
-        if (rc != WOST_OK) return rc;
-        DeviceTree2 t;
-        rc = build_tree_device(*mesh, t);
-        if (t.alloc) hb.m.allocs.push_back(t.alloc);
-        hb.m.view = t.view;
-        WOST_TRY(hipDeviceSynchronize());
-        auto t2 = clock::now();
-        if (rc != WOST_OK) return rc;
-        best_host = std::min(best_host, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        best_dev = std::min(best_dev, std::chrono::duration<double, std::milli>(t2 - t1).count());
-        std::swap(a.m, ha.m);
-        std::swap(b.m, hb.m);
-    }
-    if (host_ms) *host_ms = best_host;
-    if (device_ms) *device_ms = best_dev;
-    const DevMesh &x = a.m.view, &y = b.m.view;
-    for (int i = 0; i < 16; ++i) mismatch[i] = 0;
-    const int64_t scalars = (x.n_segs != y.n_segs) + (x.n_sil != y.n_sil) + (x.levels != y.levels) + (x.first_leaf != y.first_leaf) + (x.emissive != y.emissive) +
-                            (std::memcmp(&x.far2, &y.far2, 4) != 0) + (std::memcmp(&x.huge2, &y.huge2, 4) != 0) + (x.n_scan != y.n_scan);
-    mismatch[14] = scalars;
-    if (x.n_segs == 0 || scalars) return WOST_OK;
-    const size_t cap = 3 * (size_t)x.first_leaf + 1, n_all = (size_t)x.first_leaf + cap, n_slots = cap * 4, n = (size_t)x.n_segs, nv = (size_t)x.n_sil;
-    int64_t *cmp = &mismatch[15];
-    mismatch[0] = differing_bytes2(x.nodes, y.nodes, n_all * (WOST_NODE_FLOATS / 4), cmp);
-    mismatch[1] = differing_bytes2(x.cones, y.cones, n_all * 5, cmp);
-    mismatch[2] = differing_bytes2(x.segA, y.segA, n_slots, cmp);
-    mismatch[3] = differing_bytes2(x.segInv, y.segInv, n_slots, cmp);
-    mismatch[4] = differing_bytes2(x.segOrig, y.segOrig, n_slots, cmp);
-    mismatch[5] = differing_bytes2(x.segCol, y.segCol, n_slots * 12, cmp);
-    mismatch[6] = differing_bytes2(x.segVerts, y.segVerts, n_slots, cmp);
-    mismatch[7] = differing_bytes2(x.flat, y.flat, n, cmp);
-    mismatch[8] = differing_bytes2(x.flatCol, y.flatCol, n * 12, cmp);
-    mismatch[9] = differing_bytes2(x.sil, y.sil, nv, cmp);
-    mismatch[10] = differing_bytes2(x.silN, y.silN, nv, cmp);
-    mismatch[11] = differing_bytes2(x.scanBox, y.scanBox, (size_t)x.n_scan, cmp);
-    mismatch[12] = differing_bytes2(x.scanHl, y.scanHl, (size_t)x.n_scan, cmp);
-    mismatch[13] = differing_bytes2(x.scanId, y.scanId, (size_t)x.n_scan, cmp);
-    return WOST_OK;
-}
-
 const char *wost_last_error(void) { return g_last_error.c_str(); }
 
 int wost_create(const wost_scene_desc *scene, const wost_settings *settings, int device, wost_handle *out)
 {
-    if (!scene || !settings || !out) return set_error(WOST_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (settings->width <= 0 || settings->height <= 0 || settings->spp < 0 || settings->max_depth <= 0)
-        return set_error(WOST_ERR_INVALID, "bad settings");
-    if (settings->spp >= (1 << 20) || settings->max_depth >= (1 << 10))
-        return set_error(WOST_ERR_UNSUPPORTED, "spp must be < 2^20 and max_depth < 2^10");
-    if ((int64_t)settings->width * settings->height > (1 << 28))
-        return set_error(WOST_ERR_UNSUPPORTED, "frame too large");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    WOST_TRY(hipSetDevice(device));
-    wost_context *c = new (std::nothrow) wost_context();
-    if (!c) return set_error(WOST_ERR_NOMEM, "out of host memory");
-    c->device = device;
-    c->settings = *settings;
-    c->dst = DevSettings{settings->width, settings->height, settings->spp, settings->max_depth, settings->eps_shell,
-                         scene->dirichlet_intensity, scene->neumann_intensity};
-    c->probe = DevProbe{scene->probe_scale, scene->probe_pos[0], scene->probe_pos[1], scene->probe_up[0],
-                        scene->probe_up[1]};
-    c->n_pixels = (size_t)settings->width * settings->height;
-    int rc = upload_mesh(scene->dirichlet, c->dm);
-    if (rc == WOST_OK) rc = upload_mesh(scene->neumann, c->nm);
-    auto bail = [&](int code) {
-        destroy_ctx(c);
-        return code;
-    };
-    if (rc != WOST_OK) return bail(rc);
-#define HIP_TRY_C(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return bail(hip_failed(#expr, e_));                                        \
-    } while (0)
-    if (scene->mask) {
-        HIP_TRY_C(hipMalloc((void **)&c->mask, c->n_pixels));
-        HIP_TRY_C(hipMemcpy(c->mask, scene->mask, c->n_pixels, hipMemcpyHostToDevice));
-    }
-    if (scene->source.nx > 0 && scene->source.ny > 0) {
-        const wost_source_desc &sd = scene->source;
-        if (!sd.rgb) {
-            set_error(WOST_ERR_INVALID, "source grid without data");
-            return bail(WOST_ERR_INVALID);
-        }
-        const size_t bytes = (size_t)sd.nx * sd.ny * 3 * sizeof(float);
-        float *dev = nullptr;
-        HIP_TRY_C(hipMalloc((void **)&dev, bytes));
-        c->src = DevSource{dev, sd.nx, sd.ny, sd.index_scale[0], sd.index_scale[1], sd.index_offset[0], sd.index_offset[1],
-                           sd.intensity};
-        HIP_TRY_C(hipMemcpy(dev, sd.rgb, bytes, hipMemcpyHostToDevice));
-    }
-    const size_t qbytes = queue_bytes(c->n_pixels);
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY_C(hipMalloc(&c->queue_mem[i], qbytes));
-        carve_queue(c->queue_mem[i], c->n_pixels, c->queue[i]);
-    }
-    HIP_TRY_C(hipMalloc((void **)&c->counts, 12 * sizeof(uint32_t)));   // two queue counts, the far count and its input copy; [4..7]: the hand-over of a persistent launch
-    HIP_TRY_C(hipMalloc((void **)&c->stats, kStatCopies * sizeof(StatsDev)));
-    HIP_TRY_C(hipMalloc((void **)&c->cursor, sizeof(uint32_t)));
-    HIP_TRY_C(hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIP_TRY_C(hipMalloc((void **)&c->field, c->n_pixels * 3 * sizeof(float)));
-    HIP_TRY_C(hipHostMalloc((void **)&c->host_count, 8 * sizeof(uint32_t)));
-    HIP_TRY_C(hipHostMalloc((void **)&c->host_stats, kStatCopies * sizeof(StatsDev)));
-    HIP_TRY_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_TRY_C(hipStreamCreateWithFlags(&c->far_stream, hipStreamNonBlocking));
-    HIP_TRY_C(hipEventCreateWithFlags(&c->far_ev0, hipEventDisableTiming));
-    HIP_TRY_C(hipEventCreateWithFlags(&c->far_ev1, hipEventDisableTiming));
-    {
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        HIP_TRY_C(hipStreamCreateWithPriority(&c->long_stream, hipStreamNonBlocking, greatest));
-    }
-    HIP_TRY_C(hipEventCreateWithFlags(&c->long_ev0, hipEventDisableTiming));
-    HIP_TRY_C(hipEventCreateWithFlags(&c->long_ev1, hipEventDisableTiming));
-    HIP_TRY_C(hipEventCreate(&c->ev0));
-    HIP_TRY_C(hipEventCreate(&c->ev1));
-    {
-        // the order of a persistent / one-launch solve: its buffers and the first use of its sort kernels (their code objects load
-        // then: 2.5 ms) belong here, beside the tree builds, not inside the first solve -- time-to-1spp of a fresh handle
-        HIP_TRY_C((hipError_t)order_alloc(c->order, c->n_pixels));
-        const uint32_t n_warm = (uint32_t)std::min<size_t>(c->n_pixels, 1024);
-        const uint32_t *unused = nullptr;
-        HIP_TRY_C(hipMemsetAsync(c->queue[0].d0_d2, 0, n_warm * sizeof(float), c->stream));
-        HIP_TRY_C(hipMemsetAsync(c->queue[0].est, 0, n_warm * sizeof(float), c->stream));
-        HIP_TRY_C((hipError_t)order_by_distance(c->order, c->queue[0].d0_d2, n_warm, c->stream, &unused));
-        HIP_TRY_C((hipError_t)order_by_estimate(c->order, c->queue[0].est, n_warm, c->stream, &unused));
-        HIP_TRY_C(hipStreamSynchronize(c->stream));
-    }
-#undef HIP_TRY_C
-    *out = c;
-    return WOST_OK;
+    return create_handle(scene, settings, device, out, true, destroy_ctx, fill_ctx);
 }
 
 int wost_destroy(wost_handle h)
@@ -2287,12 +1897,48 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
     return WOST_OK;
 }
 
-static DeviceMeshStorage *pick_mesh(wost_handle h, int which)
+// ---- the frame and point solves (the bodies of the entry points: UniformCalls, wost_uniform.h) ----
+static int frame_solve(wost_context *c, int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, float *field_dev,
+                       int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
-    if (which == WOST_MESH_DIRICHLET) return &h->dm;
-    if (which == WOST_MESH_NEUMANN) return &h->nm;
-    return nullptr;
+    return run_solve(c, frame_step(pixel_begin, pixel_end, shard_index, shard_count), field_dev, field_base, stream, stats);
 }
+
+// A point list of n points in chunks of at most n_pixels points -- what the handle's queues, order buffers and out_capacity hold --
+// each a pass of the driver on `fs` with its first and n set; a walker's pix is its point's index in the list, so every chunk
+// writes the one field.  The stats are the sum of the chunks.  steps_before, the walk steps of the earlier chunks: a point solve
+// sets it, a call on the carried list (fs.carry_more > 0), whose second walk counts on from its first, adds to it and appends
+// to last_launches from its second chunk on.
+static int solve_point_chunks(wost_context *c, FirstStep fs, int32_t n, float *field_dev, hipStream_t stream, wost_stats *stats)
+{
+    const auto t0 = HostClock::now();
+    wost_stats total{};
+    const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
+    for (fs.first = 0; fs.first < n; fs.first += cap) {
+        fs.n = std::min(cap, n - fs.first);
+        wost_stats st{};
+        const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
+        if (rc != WOST_OK) return rc;
+        add_stats(total, st);
+        if (fs.carry_more > 0) {
+            c->steps_before += st.walk_steps;
+            fs.carry_append = true;
+        } else {
+            c->steps_before = total.walk_steps;
+        }
+    }
+    stamp_solve_ms(&total, t0);
+    if (stats) *stats = total;
+    return WOST_OK;
+}
+
+static int point_solve(wost_context *c, const float *pts_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_dev, hipStream_t stream,
+                       wost_stats *stats)
+{
+    return solve_point_chunks(c, FirstStep{0, 0, 0, 1, pts_dev, 0, 0, seed_base, seed_width, 0, 0, nullptr, false}, n, field_dev, stream, stats);
+}
+
+static const UniformCalls<wost_context> kUniform{2, frame_solve, point_solve};
 
 // ---- the continued frame solve (the drivers: wost_carry.hip; the bodies of the entry points: CarryCalls, wost_carry.h) ----
 // a walk of the carried solve: a pass of the solve driver on the selected pixels (the 2-D walkers are queued by init_kernel from
@@ -2321,26 +1967,10 @@ static CarryWalk points_walk(PointListCtx<wost_context> *x, int32_t, int32_t)
     wost_context *c = x->h;
     return [c](int32_t more_spp, const uint8_t *sel, const int32_t *, uint32_t, float *field_dev, hipStream_t stream, wost_stats *stats) {
         const PointList &l = c->list;
-        const auto t0 = std::chrono::high_resolution_clock::now();
-        bool append = l.carry.walks > 0;
+        const bool append = l.carry.walks > 0;
         if (!append) c->steps_before = 0;
-        wost_stats total{};
-        const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
-        for (int32_t first = 0; first < l.n; first += cap) {
-            const FirstStep fs{0, 0, 0, 1, l.pts, first, std::min(cap, l.n - first), l.seed_base, l.seed_width, l.carry.done, more_spp, sel, append};
-            wost_stats st{};
-            const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
-            if (rc != WOST_OK) return rc;
-            total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
-            total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
-            total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
-            total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
-            c->steps_before += st.walk_steps;
-            append = true;
-        }
-        total.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-        if (stats) *stats = total;
-        return WOST_OK;
+        return solve_point_chunks(c, FirstStep{0, 0, 0, 1, l.pts, 0, 0, l.seed_base, l.seed_width, l.carry.done, more_spp, sel, append}, l.n, field_dev,
+                                  stream, stats);
     };
 }
 
@@ -2361,6 +1991,43 @@ static GradCall grad_call(wost_context *c)
 
 // ---- the carried gradient list (wost_gradient_points_carry & co.; the bodies of the entry points: GradListCalls, wost_grad.h) ----
 static const GradListCalls<wost_context> kGradList{grad_call, 2};
+
+// ---- the launches of the batch queries (their bodies: query_*, wost_uniform.h).  The closest-point and the distance kernel
+// take the stride of the stack columns; render_sdf renders into the handle's field buffer (n_pixels floats fit) and tells its
+// kernel which mesh it is ----
+namespace {
+struct Query2 {
+    static constexpr int dim = 2, uv = 1, bs = 256;
+    static int32_t count(const DevMesh &m) { return m.n_segs; }
+    static dim3 grid(int n) { return dim3((n + bs - 1) / bs); }
+    static void closest_point(wost_context *h, const DevMesh &m, size_t lds, const float *pts, int n, int32_t *idx, float *dist, float *uv, int32_t *side)
+    {
+        hipLaunchKernelGGL(closest_point_kernel, grid(n), dim3(bs), lds, h->stream, m, pts, n, idx, dist, uv, side, bs);
+    }
+    static void silhouette(wost_context *h, const DevMesh &m, size_t lds, const float *pts, const float *rmax, int n, float *out)
+    {
+        hipLaunchKernelGGL(silhouette_kernel, grid(n), dim3(bs), lds, h->stream, m, pts, rmax, n, out);
+    }
+    static void ray(wost_context *h, const DevMesh &m, size_t lds, const float *o, const float *d, const float *tmax, int n, int32_t *hit, float *t,
+                    int32_t *idx)
+    {
+        hipLaunchKernelGGL(ray_kernel, grid(n), dim3(bs), lds, h->stream, m, o, d, tmax, n, hit, t, idx);
+    }
+    static hipError_t sdf_out(wost_context *h, Batch &, int, float **out)
+    {
+        *out = h->field;
+        return hipSuccess;
+    }
+    static void sdf(wost_context *h, const DevMesh &m, int which_mesh, size_t lds, int n, float *out)
+    {
+        hipLaunchKernelGGL(sdf_kernel, grid(n), dim3(bs), lds, h->stream, m, h->probe, h->settings.width, h->settings.height, which_mesh, out, bs);
+    }
+    static void source(wost_context *h, int n, float *out)
+    {
+        hipLaunchKernelGGL(source_kernel, grid(n), dim3(bs), 0, h->stream, h->src, h->probe, h->settings.width, h->settings.height, out);
+    }
+};
+}  // namespace
 
 extern "C" {
 
@@ -2405,58 +2072,12 @@ int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done) { 
 
 int wost_solve(wost_handle h, int32_t pixel_begin, int32_t pixel_end, float *field_rgb, wost_stats *stats)
 {
-    if (!h || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    if (pixel_begin < 0 || pixel_end > (int64_t)h->n_pixels || pixel_begin > pixel_end)
-        return set_error(WOST_ERR_INVALID, "pixel range outside the frame");
-    const auto t0 = HostClock::now();
-    const size_t n = (size_t)(pixel_end - pixel_begin);
-    if (n == 0) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return WOST_OK;
-    }
-    WOST_TRY(hipSetDevice(h->device));
-    WOST_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
-    int rc = run_solve(h, frame_step(pixel_begin, pixel_end, 0, 1), h->field, pixel_begin, h->stream, stats);
-    if (rc != WOST_OK) return rc;
-    WOST_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    WOST_TRY(hipStreamSynchronize(h->stream));
-    stamp_solve_ms(stats, t0);
-    return WOST_OK;
+    return kUniform.solve(h, pixel_begin, pixel_end, field_rgb, stats);
 }
 
-int wost_solve_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, void *stream,
-                       wost_stats *stats)
+int wost_solve_sharded(wost_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, void *stream, wost_stats *stats)
 {
-    if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
-    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count)
-        return set_error(WOST_ERR_INVALID, "bad shard");
-    // NULL is the legacy default stream, which is also torch's default stream
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return run_solve(h, frame_step(0, (int32_t)h->n_pixels, shard_index, shard_count), field_rgb_dev, 0, s, stats);
-}
-
-// The point solve on device arrays: chunks of at most n_pixels points -- what the handle's queues, order buffers and out_capacity
-// hold -- each a pass of the driver; a walker's pix is its point's index in the call, so every chunk writes the call's field.
-static int solve_points_dev(wost_context *c, const float *pts_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_dev,
-                            hipStream_t stream, wost_stats *stats)
-{
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    wost_stats total{};
-    const int32_t cap = (int32_t)std::min<size_t>(c->n_pixels, (size_t)1 << 28);
-    for (int32_t first = 0; first < n; first += cap) {
-        const FirstStep fs{0, 0, 0, 1, pts_dev, first, std::min(cap, n - first), seed_base, seed_width, 0, 0, nullptr, false};
-        wost_stats st{};
-        const int rc = run_solve(c, fs, field_dev, 0, stream, &st);
-        if (rc != WOST_OK) return rc;
-        total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
-        total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
-        total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
-        total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
-        c->steps_before = total.walk_steps;
-    }
-    total.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    if (stats) *stats = total;
-    return WOST_OK;
+    return kUniform.solve_sharded(h, shard_index, shard_count, field_rgb_dev, stream, stats);
 }
 
 int wost_solve_more_where(wost_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
@@ -2504,35 +2125,12 @@ int wost_solve_progress(wost_handle h, int32_t *spp_done) { return kCarry.progre
 int wost_solve_points_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
                           void *stream, wost_stats *stats)
 {
-    const int rc = check_point_solve(h, pts_xy_dev, field_rgb_dev, n, seed_base, seed_width);
-    if (rc != WOST_OK) return rc;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0) return WOST_OK;
-    return solve_points_dev(h, pts_xy_dev, n, seed_base, seed_width, field_rgb_dev, reinterpret_cast<hipStream_t>(stream), stats);
+    return kUniform.solve_points_dev(h, pts_xy_dev, n, seed_base, seed_width, field_rgb_dev, stream, stats);
 }
 
 int wost_solve_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb, wost_stats *stats)
 {
-    int rc = check_point_solve(h, pts_xy, field_rgb, n, seed_base, seed_width);
-    if (rc == WOST_OK) rc = check_points_finite(pts_xy, n, 2);
-    if (rc != WOST_OK) return rc;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0) return WOST_OK;
-    const auto t0 = HostClock::now();
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_field;
-    WOST_TRY(b.in(pts_xy, (size_t)n * 2, &d_pts));
-    WOST_TRY(b.out(&d_field, (size_t)n * 3));
-    WOST_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
-    rc = solve_points_dev(h, d_pts, n, seed_base, seed_width, d_field, h->stream, stats);
-    if (rc != WOST_OK) {
-        (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
-        return rc;
-    }
-    WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
-    if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
-    return rc;
+    return kUniform.solve_points(h, pts_xy, n, seed_base, seed_width, field_rgb, stats);
 }
 
 int wost_solve_gradient_points(wost_handle h, const float *pts_xy, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
@@ -2594,117 +2192,26 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
     return WOST_OK;
 }
 
-int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist)
-{
-    if (!h || !out_dist) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    WOST_TRY(hipSetDevice(h->device));
-    const int bs = 256;
-    const int levels = m->view.n_segs > 0 ? m->view.levels : 1;
-    const size_t lds = (size_t)(3 * levels + 1) * bs * sizeof(uint32_t);
-    const int n = (int)h->n_pixels;
-    float *d_out = h->field;  // reuse: n_pixels floats fit in the field buffer
-    hipLaunchKernelGGL(sdf_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, h->probe,
-                       h->settings.width, h->settings.height, which_mesh, d_out, bs);
-    WOST_TRY(hipGetLastError());
-    Batch b{h->stream};
-    WOST_TRY(b.fetch(out_dist, d_out, (size_t)n));
-    return b.finish();
-}
+int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist) { return query_render_sdf<Query2>(h, which_mesh, out_dist); }
 
-int wost_render_source(wost_handle h, float *out_rgb)
-{
-    if (!h || !out_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    WOST_TRY(hipSetDevice(h->device));
-    const int n = (int)h->n_pixels;
-    Batch b{h->stream};
-    float *d = nullptr;
-    WOST_TRY(b.out(&d, (size_t)n * 3));
-    hipLaunchKernelGGL(source_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->src, h->probe, h->settings.width,
-                       h->settings.height, d);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_rgb, d, (size_t)n * 3));
-    return b.finish();
-}
+int wost_render_source(wost_handle h, float *out_rgb) { return query_render_source<Query2>(h, out_rgb); }
 
 int wost_closest_point(wost_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
                        float *out_uv, int32_t *out_side)
 {
-    if (!h || !pts || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m || m->view.n_segs == 0) return set_error(WOST_ERR_INVALID, "mesh is empty or unknown");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_dist, *d_uv;
-    int32_t *d_idx, *d_side;
-    WOST_TRY(b.in(pts, (size_t)n * 2, &d_pts));
-    WOST_TRY(b.out(&d_dist, n));
-    WOST_TRY(b.out(&d_uv, n));
-    WOST_TRY(b.out(&d_idx, n));
-    WOST_TRY(b.out(&d_side, n));
-    const int bs = 256;
-    const size_t lds = (size_t)(3 * m->view.levels + 1) * bs * sizeof(uint32_t);
-    hipLaunchKernelGGL(closest_point_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, n,
-                       d_idx, d_dist, d_uv, d_side, bs);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_idx, d_idx, n));
-    WOST_TRY(b.fetch(out_dist, d_dist, n));
-    WOST_TRY(b.fetch(out_uv, d_uv, n));
-    WOST_TRY(b.fetch(out_side, d_side, n));
-    return b.finish();
+    return query_closest_point<Query2>(h, which_mesh, pts, n, out_idx, out_dist, out_uv, out_side);
 }
 
 int wost_closest_silhouette(wost_handle h, int which_mesh, const float *pts, const float *rmax, int32_t n,
                             float *out_dist)
 {
-    if (!h || !pts || !out_dist || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_rmax = nullptr, *d_out;
-    WOST_TRY(b.in(pts, (size_t)n * 2, &d_pts));
-    WOST_TRY(b.out(&d_out, n));
-    if (rmax) WOST_TRY(b.in(rmax, n, &d_rmax));
-    const int bs = 256;
-    const size_t lds = (size_t)(3 * (m->view.n_segs > 0 ? m->view.levels : 1) + 1) * bs * sizeof(uint32_t);
-    hipLaunchKernelGGL(silhouette_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, d_rmax, n,
-                       d_out);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_dist, d_out, n));
-    return b.finish();
+    return query_closest_silhouette<Query2>(h, which_mesh, pts, rmax, n, out_dist);
 }
 
 int wost_ray_intersect(wost_handle h, int which_mesh, const float *origins, const float *dirs, const float *tmax,
                        int32_t n, int32_t *out_hit, float *out_t, int32_t *out_idx)
 {
-    if (!h || !origins || !dirs || !tmax || !out_hit || !out_t || !out_idx || n < 0)
-        return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMeshStorage *m = pick_mesh(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_o, *d_d, *d_tm, *d_t;
-    int32_t *d_hit, *d_idx;
-    WOST_TRY(b.in(origins, (size_t)n * 2, &d_o));
-    WOST_TRY(b.in(dirs, (size_t)n * 2, &d_d));
-    WOST_TRY(b.in(tmax, n, &d_tm));
-    WOST_TRY(b.out(&d_t, n));
-    WOST_TRY(b.out(&d_hit, n));
-    WOST_TRY(b.out(&d_idx, n));
-    const int bs = 256;
-    const size_t lds = (size_t)(3 * (m->view.n_segs > 0 ? m->view.levels : 1) + 1) * bs * sizeof(uint32_t);
-    hipLaunchKernelGGL(ray_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit,
-                       d_t, d_idx);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_hit, d_hit, n));
-    WOST_TRY(b.fetch(out_t, d_t, n));
-    WOST_TRY(b.fetch(out_idx, d_idx, n));
-    return b.finish();
+    return query_ray_intersect<Query2>(h, which_mesh, origins, dirs, tmax, n, out_hit, out_t, out_idx);
 }
 
 }  // extern "C"

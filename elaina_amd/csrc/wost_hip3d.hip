@@ -1,5 +1,9 @@
 // wost_hip3d.hip -- the 3-D uniform Walk-on-Stars path on MI355X, gfx950 only.
 //
+// Holds: the 3-D walk and query kernels; the solve driver (run_solve3) and its plan; what the 3-D context adds to the shared
+// bodies of the entry points (wost_uniform.h, wost_carry.h, wost_grad.h) and the wost3_ entry points themselves, which forward
+// to those bodies.  The context is in wost_internal3.h, the mesh upload in wost_build3.hip.
+//
 // UniformIntegrator<3> of the reference: the DIM == 3 branches of integrator/uniform/integrator.cu
 // (:128-211 separateEvaluationPoint with triangles and barycentric uv :150-168, :224-231
 // handleBoundary, :336-444 sampleNeumann with three draws, :465-525 oneStepWalk), EvaluationGrid<3>
@@ -735,18 +739,10 @@ static void destroy3(wost3_context *c)
     (void)hipSetDevice(c->device);
     for (void *p : c->dm.allocs) (void)hipFree(p);
     for (void *p : c->nm.allocs) (void)hipFree(p);
-    if (c->mask) (void)hipFree(c->mask);
     if (c->src.rgb) (void)hipFree(const_cast<float *>(c->src.rgb));
-    if (c->field) (void)hipFree(c->field);
     if (c->stats) (void)hipFree(c->stats);
     if (c->cursor) (void)hipFree(c->cursor);
-    carry_free(c->carry);
-    points_free(c->list);
-    grad_free(c->grad);
-    gradlist_free(c->glist);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    destroy_base(c);
     delete c;
 }
 
@@ -884,10 +880,20 @@ static int run_solve3(wost3_context *c, const FirstStep3 &fs, float *field_dev, 
     return WOST_OK;
 }
 
-static DeviceMesh3 *pick3(wost3_handle h, int which)
+// ---- the frame and point solves (the bodies of the entry points: UniformCalls, wost_uniform.h) ----
+static int frame_solve3(wost3_context *c, int32_t pixel_begin, int32_t pixel_end, int32_t shard_index, int32_t shard_count, float *field_dev,
+                        int32_t field_base, hipStream_t stream, wost_stats *stats)
 {
-    return which == WOST_MESH_DIRICHLET ? &h->dm : which == WOST_MESH_NEUMANN ? &h->nm : nullptr;
+    return run_solve3(c, FirstStep3{pixel_begin, pixel_end, shard_index, shard_count, nullptr, 0, 0}, field_dev, field_base, stream, stats);
 }
+// (one launch, however long the list)
+static int point_solve3(wost3_context *c, const float *pts_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_dev, hipStream_t stream,
+                        wost_stats *stats)
+{
+    return run_solve3(c, FirstStep3{0, n, 0, 1, pts_dev, seed_base, seed_width}, field_dev, 0, stream, stats);
+}
+
+static const UniformCalls<wost3_context> kUniform3{3, frame_solve3, point_solve3};
 
 // ---- the continued frame solve (wost_solve_more & co. in 3-D: the same drivers, wost_carry.hip, and the same bodies of the
 // entry points, CarryCalls of wost_carry.h) ----
@@ -938,6 +944,67 @@ static GradCall grad_call3(wost3_context *c)
 // ---- the carried gradient list (wost3_gradient_points_carry & co.; the bodies of the entry points: GradListCalls, wost_grad.h) ----
 static const GradListCalls<wost3_context> kGradList3{grad_call3, 3};
 
+// ---- what wost3_create adds to the shared part (create_handle, wost_uniform.h): the probe, the meshes, the source grid and the
+// counters of the one launch ----
+static int fill3(wost3_context *c, const wost3_scene_desc &scene)
+{
+    c->probe.scale = scene.probe_scale;
+    for (int k = 0; k < 3; ++k) { c->probe.pos[k] = scene.probe_pos[k]; c->probe.up[k] = scene.probe_up[k]; c->probe.right[k] = scene.probe_right[k]; }
+    int rc = upload_mesh3(scene.dirichlet, c->dm);
+    if (rc == WOST_OK) rc = upload_mesh3(scene.neumann, c->nm);
+    if (rc == WOST_OK) rc = upload_mask(c, scene.mask);
+    if (rc != WOST_OK) return rc;
+    if (scene.source.nx > 0) {
+        const wost3_source_desc &sd = scene.source;
+        if (sd.ny <= 0 || sd.nz <= 0 || !sd.rgb) return set_error(WOST_ERR_INVALID, "source grid: bad size or null samples");
+        const size_t bytes = (size_t)sd.nx * sd.ny * sd.nz * 3 * sizeof(float);
+        float *d = nullptr;
+        WOST_TRY(hipMalloc((void **)&d, bytes));
+        c->src = DevSource3{d, sd.nx, sd.ny, sd.nz, sd.index_scale[0], sd.index_scale[1], sd.index_scale[2], sd.index_offset[0],
+                            sd.index_offset[1], sd.index_offset[2], sd.intensity};
+        WOST_TRY(hipMemcpy(d, sd.rgb, bytes, hipMemcpyHostToDevice));
+    }
+    if ((rc = create_frame(c)) != WOST_OK) return rc;
+    WOST_TRY(hipMalloc((void **)&c->stats, kStat3Copies * sizeof(Stats3Dev)));
+    WOST_TRY(hipMalloc((void **)&c->cursor, sizeof(uint32_t)));
+    return WOST_OK;
+}
+
+// ---- the launches of the batch queries (their bodies: query_*, wost_uniform.h).  The silhouette and ray queries of a Neumann
+// mesh above the flat limit descend its tree (NTREE); render_sdf tells the kernel which of the two distances it renders ----
+namespace {
+struct Query3 {
+    static constexpr int dim = 3, uv = 2;
+    static int32_t count(const DevMesh3 &m) { return m.n_tris; }
+    static dim3 grid(int n) { return dim3((n + 255) / 256); }
+    static void closest_point(wost3_context *h, const DevMesh3 &m, size_t lds, const float *pts, int n, int32_t *idx, float *dist, float *uv, int32_t *side)
+    {
+        hipLaunchKernelGGL(closest_point3_kernel, grid(n), dim3(256), lds, h->stream, m, pts, n, idx, dist, uv, side);
+    }
+    static void silhouette(wost3_context *h, const DevMesh3 &m, size_t lds, const float *pts, const float *rmax, int n, float *out)
+    {
+        if (m.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((silhouette3_kernel<true>), grid(n), dim3(256), lds, h->stream, m, pts, rmax, n, out);
+        else hipLaunchKernelGGL((silhouette3_kernel<false>), grid(n), dim3(256), lds, h->stream, m, pts, rmax, n, out);
+    }
+    static void ray(wost3_context *h, const DevMesh3 &m, size_t lds, const float *o, const float *d, const float *tmax, int n, int32_t *hit, float *t,
+                    int32_t *idx)
+    {
+        if (m.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((ray3_kernel<true>), grid(n), dim3(256), lds, h->stream, m, o, d, tmax, n, hit, t, idx);
+        else hipLaunchKernelGGL((ray3_kernel<false>), grid(n), dim3(256), lds, h->stream, m, o, d, tmax, n, hit, t, idx);
+    }
+    static hipError_t sdf_out(wost3_context *, Batch &b, int n, float **out) { return b.out(out, n); }
+    static void sdf(wost3_context *h, const DevMesh3 &m, int which_mesh, size_t lds, int n, float *out)
+    {
+        hipLaunchKernelGGL(render3_sdf_kernel, grid(n), dim3(256), lds, h->stream, m, h->probe, h->settings.width, h->settings.height,
+                           which_mesh == WOST_MESH_NEUMANN ? 1 : 0, out);
+    }
+    static void source(wost3_context *h, int n, float *out)
+    {
+        hipLaunchKernelGGL(render3_source_kernel, grid(n), dim3(256), 0, h->stream, h->src, h->probe, h->settings.width, h->settings.height, out);
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int wost3_points_carry(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width)
@@ -981,57 +1048,7 @@ int wost3_points_progress(wost3_handle h, int32_t *n_points, int32_t *spp_done) 
 
 int wost3_create(const wost3_scene_desc *scene, const wost_settings *settings, int device, wost3_handle *out)
 {
-    if (!scene || !settings || !out) return set_error(WOST_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (settings->width <= 0 || settings->height <= 0 || settings->spp < 0 || settings->max_depth <= 0)
-        return set_error(WOST_ERR_INVALID, "bad settings");
-    if ((int64_t)settings->width * settings->height > (1 << 28)) return set_error(WOST_ERR_UNSUPPORTED, "frame too large");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return set_error(WOST_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return set_error(WOST_ERR_INVALID, "device index out of range");
-    WOST_TRY(hipSetDevice(device));
-    wost3_context *c = new (std::nothrow) wost3_context();
-    if (!c) return set_error(WOST_ERR_NOMEM, "out of host memory");
-    c->device = device;
-    c->settings = *settings;
-    c->dst = DevSettings{settings->width, settings->height, settings->spp, settings->max_depth, settings->eps_shell,
-                         scene->dirichlet_intensity, scene->neumann_intensity};
-    c->probe.scale = scene->probe_scale;
-    for (int k = 0; k < 3; ++k) { c->probe.pos[k] = scene->probe_pos[k]; c->probe.up[k] = scene->probe_up[k]; c->probe.right[k] = scene->probe_right[k]; }
-    c->n_pixels = (size_t)settings->width * settings->height;
-    int rc = upload_mesh3(scene->dirichlet, c->dm);
-    if (rc == WOST_OK) rc = upload_mesh3(scene->neumann, c->nm);
-    hipError_t e = hipSuccess;
-    if (rc == WOST_OK && scene->mask) {
-        e = hipMalloc((void **)&c->mask, c->n_pixels);
-        if (e == hipSuccess) e = hipMemcpy(c->mask, scene->mask, c->n_pixels, hipMemcpyHostToDevice);
-    }
-    if (rc == WOST_OK && e == hipSuccess && scene->source.nx > 0) {
-        const wost3_source_desc &sd = scene->source;
-        if (sd.ny <= 0 || sd.nz <= 0 || !sd.rgb) rc = set_error(WOST_ERR_INVALID, "source grid: bad size or null samples");
-        else {
-            const size_t bytes = (size_t)sd.nx * sd.ny * sd.nz * 3 * sizeof(float);
-            float *d = nullptr;
-            e = hipMalloc((void **)&d, bytes);
-            if (e == hipSuccess) e = hipMemcpy(d, sd.rgb, bytes, hipMemcpyHostToDevice);
-            c->src = DevSource3{d, sd.nx, sd.ny, sd.nz, sd.index_scale[0], sd.index_scale[1], sd.index_scale[2], sd.index_offset[0],
-                                sd.index_offset[1], sd.index_offset[2], sd.intensity};
-        }
-    }
-    if (rc == WOST_OK && e == hipSuccess) e = hipMalloc((void **)&c->field, c->n_pixels * 3 * sizeof(float));
-    if (rc == WOST_OK && e == hipSuccess) e = hipMalloc((void **)&c->stats, kStat3Copies * sizeof(Stats3Dev));
-    if (rc == WOST_OK && e == hipSuccess) e = hipMalloc((void **)&c->cursor, sizeof(uint32_t));
-    if (rc == WOST_OK && e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (rc == WOST_OK && e == hipSuccess) e = hipEventCreate(&c->ev0);
-    if (rc == WOST_OK && e == hipSuccess) e = hipEventCreate(&c->ev1);
-    if (rc == WOST_OK && e != hipSuccess) rc = set_error(WOST_ERR_DEVICE, std::string("wost3_create: ") + hipGetErrorString(e));
-    if (rc != WOST_OK) {
-        destroy3(c);
-        return rc;
-    }
-    *out = c;
-    return WOST_OK;
+    return create_handle(scene, settings, device, out, false, destroy3, fill3);
 }
 
 int wost3_destroy(wost3_handle h)
@@ -1042,30 +1059,12 @@ int wost3_destroy(wost3_handle h)
 
 int wost3_solve(wost3_handle h, int32_t pixel_begin, int32_t pixel_end, float *field_rgb, wost_stats *stats)
 {
-    if (!h || !field_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    if (pixel_begin < 0 || pixel_end > (int64_t)h->n_pixels || pixel_begin > pixel_end)
-        return set_error(WOST_ERR_INVALID, "pixel range outside the frame");
-    const auto t0 = HostClock::now();
-    const size_t n = (size_t)(pixel_end - pixel_begin);
-    if (n == 0) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return WOST_OK;
-    }
-    WOST_TRY(hipSetDevice(h->device));
-    WOST_TRY(hipMemsetAsync(h->field, 0, n * 3 * sizeof(float), h->stream));
-    const int rc = run_solve3(h, FirstStep3{pixel_begin, pixel_end, 0, 1, nullptr, 0, 0}, h->field, pixel_begin, h->stream, stats);
-    if (rc != WOST_OK) return rc;
-    WOST_TRY(hipMemcpyAsync(field_rgb, h->field, n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    WOST_TRY(hipStreamSynchronize(h->stream));
-    stamp_solve_ms(stats, t0);
-    return WOST_OK;
+    return kUniform3.solve(h, pixel_begin, pixel_end, field_rgb, stats);
 }
 
 int wost3_solve_sharded(wost3_handle h, int32_t shard_index, int32_t shard_count, float *field_rgb_dev, void *stream, wost_stats *stats)
 {
-    if (!h || !field_rgb_dev) return set_error(WOST_ERR_INVALID, "null argument");
-    if (shard_count <= 0 || shard_index < 0 || shard_index >= shard_count) return set_error(WOST_ERR_INVALID, "bad shard");
-    return run_solve3(h, FirstStep3{0, (int32_t)h->n_pixels, shard_index, shard_count, nullptr, 0, 0}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+    return kUniform3.solve_sharded(h, shard_index, shard_count, field_rgb_dev, stream, stats);
 }
 
 int wost3_solve_more_where(wost3_handle h, int32_t more_spp, const uint8_t *select, float *field_rgb, wost_stats *stats)
@@ -1113,35 +1112,12 @@ int wost3_solve_progress(wost3_handle h, int32_t *spp_done) { return kCarry3.pro
 int wost3_solve_points_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb_dev,
                            void *stream, wost_stats *stats)
 {
-    const int rc = check_point_solve(h, pts_xyz_dev, field_rgb_dev, n, seed_base, seed_width);
-    if (rc != WOST_OK) return rc;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0) return WOST_OK;
-    return run_solve3(h, FirstStep3{0, n, 0, 1, pts_xyz_dev, seed_base, seed_width}, field_rgb_dev, 0, reinterpret_cast<hipStream_t>(stream), stats);
+    return kUniform3.solve_points_dev(h, pts_xyz_dev, n, seed_base, seed_width, field_rgb_dev, stream, stats);
 }
 
 int wost3_solve_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t seed_width, float *field_rgb, wost_stats *stats)
 {
-    int rc = check_point_solve(h, pts_xyz, field_rgb, n, seed_base, seed_width);
-    if (rc == WOST_OK) rc = check_points_finite(pts_xyz, n, 3);
-    if (rc != WOST_OK) return rc;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0) return WOST_OK;
-    const auto t0 = HostClock::now();
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_field;
-    WOST_TRY(b.in(pts_xyz, (size_t)n * 3, &d_pts));
-    WOST_TRY(b.out(&d_field, (size_t)n * 3));
-    WOST_TRY(hipMemsetAsync(d_field, 0, (size_t)n * 3 * sizeof(float), h->stream));
-    rc = run_solve3(h, FirstStep3{0, n, 0, 1, d_pts, seed_base, seed_width}, d_field, 0, h->stream, stats);
-    if (rc != WOST_OK) {
-        (void)hipStreamSynchronize(h->stream);      // (the scratch arrays are freed on return)
-        return rc;
-    }
-    WOST_TRY(b.fetch(field_rgb, d_field, (size_t)n * 3));
-    if ((rc = b.finish()) == WOST_OK) stamp_solve_ms(stats, t0);
-    return rc;
+    return kUniform3.solve_points(h, pts_xyz, n, seed_base, seed_width, field_rgb, stats);
 }
 
 int wost3_solve_gradient_points(wost3_handle h, const float *pts_xyz, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
@@ -1198,103 +1174,22 @@ int wost3_gradient_points_progress(wost3_handle h, int32_t *n_points, int32_t *r
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist, float *out_uv,
                         int32_t *out_side)
 {
-    if (!h || !pts || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMesh3 *m = pick3(h, which_mesh);
-    if (!m || m->view.n_tris == 0) return set_error(WOST_ERR_INVALID, "mesh is empty or unknown");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_dist, *d_uv;
-    int32_t *d_idx, *d_side;
-    WOST_TRY(b.in(pts, (size_t)n * 3, &d_pts)); WOST_TRY(b.out(&d_dist, n)); WOST_TRY(b.out(&d_uv, (size_t)n * 2));
-    WOST_TRY(b.out(&d_idx, n)); WOST_TRY(b.out(&d_side, n));
-    const int bs = 256;
-    const size_t lds = (size_t)(3 * m->view.levels + 1) * bs * sizeof(uint32_t);
-    hipLaunchKernelGGL(closest_point3_kernel, dim3((n + bs - 1) / bs), dim3(bs), lds, h->stream, m->view, d_pts, n, d_idx, d_dist, d_uv, d_side);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_idx, d_idx, n));
-    WOST_TRY(b.fetch(out_dist, d_dist, n));
-    WOST_TRY(b.fetch(out_uv, d_uv, (size_t)n * 2));
-    WOST_TRY(b.fetch(out_side, d_side, n));
-    return b.finish();
+    return query_closest_point<Query3>(h, which_mesh, pts, n, out_idx, out_dist, out_uv, out_side);
 }
 
 int wost3_closest_silhouette(wost3_handle h, int which_mesh, const float *pts, const float *rmax, int32_t n, float *out_dist)
 {
-    if (!h || !pts || !out_dist || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMesh3 *m = pick3(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_pts, *d_rmax = nullptr, *d_out;
-    WOST_TRY(b.in(pts, (size_t)n * 3, &d_pts)); WOST_TRY(b.out(&d_out, n));
-    if (rmax) WOST_TRY(b.in(rmax, n, &d_rmax));
-    {
-        const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
-        if (m->view.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((silhouette3_kernel<true>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_pts, d_rmax, n, d_out);
-        else hipLaunchKernelGGL((silhouette3_kernel<false>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_pts, d_rmax, n, d_out);
-    }
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_dist, d_out, n));
-    return b.finish();
+    return query_closest_silhouette<Query3>(h, which_mesh, pts, rmax, n, out_dist);
 }
 
-int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist)
-{
-    if (!h || !out_dist) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMesh3 *m = pick3(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    WOST_TRY(hipSetDevice(h->device));
-    const int n = (int)h->n_pixels;
-    Batch b{h->stream};
-    float *d_out;
-    WOST_TRY(b.out(&d_out, n));
-    const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
-    hipLaunchKernelGGL(render3_sdf_kernel, dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, h->probe, h->settings.width, h->settings.height,
-                       which_mesh == WOST_MESH_NEUMANN ? 1 : 0, d_out);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_dist, d_out, n));
-    return b.finish();
-}
+int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist) { return query_render_sdf<Query3>(h, which_mesh, out_dist); }
 
-int wost3_render_source(wost3_handle h, float *out_rgb)
-{
-    if (!h || !out_rgb) return set_error(WOST_ERR_INVALID, "null argument");
-    WOST_TRY(hipSetDevice(h->device));
-    const int n = (int)h->n_pixels;
-    Batch b{h->stream};
-    float *d_out;
-    WOST_TRY(b.out(&d_out, (size_t)n * 3));
-    hipLaunchKernelGGL(render3_source_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->src, h->probe, h->settings.width, h->settings.height, d_out);
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_rgb, d_out, (size_t)n * 3));
-    return b.finish();
-}
+int wost3_render_source(wost3_handle h, float *out_rgb) { return query_render_source<Query3>(h, out_rgb); }
 
 int wost3_ray_intersect(wost3_handle h, int which_mesh, const float *origins, const float *dirs, const float *tmax, int32_t n,
                         int32_t *out_hit, float *out_t, int32_t *out_idx)
 {
-    if (!h || !origins || !dirs || !tmax || !out_hit || !out_t || !out_idx || n < 0) return set_error(WOST_ERR_INVALID, "null argument");
-    DeviceMesh3 *m = pick3(h, which_mesh);
-    if (!m) return set_error(WOST_ERR_INVALID, "unknown mesh selector");
-    if (n == 0) return WOST_OK;
-    WOST_TRY(hipSetDevice(h->device));
-    Batch b{h->stream};
-    float *d_o, *d_d, *d_tm, *d_t;
-    int32_t *d_hit, *d_idx;
-    WOST_TRY(b.in(origins, (size_t)n * 3, &d_o)); WOST_TRY(b.in(dirs, (size_t)n * 3, &d_d)); WOST_TRY(b.in(tmax, n, &d_tm));
-    WOST_TRY(b.out(&d_t, n)); WOST_TRY(b.out(&d_hit, n)); WOST_TRY(b.out(&d_idx, n));
-    {
-        const size_t lds = (size_t)(3 * (m->view.n_tris > 0 ? m->view.levels : 1) + 1) * 256 * sizeof(uint32_t);
-        if (m->view.n_tris > WOST3_FLAT_MAX) hipLaunchKernelGGL((ray3_kernel<true>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit, d_t, d_idx);
-        else hipLaunchKernelGGL((ray3_kernel<false>), dim3((n + 255) / 256), dim3(256), lds, h->stream, m->view, d_o, d_d, d_tm, n, d_hit, d_t, d_idx);
-    }
-    WOST_TRY(hipGetLastError());
-    WOST_TRY(b.fetch(out_hit, d_hit, n));
-    WOST_TRY(b.fetch(out_t, d_t, n));
-    WOST_TRY(b.fetch(out_idx, d_idx, n));
-    return b.finish();
+    return query_ray_intersect<Query3>(h, which_mesh, origins, dirs, tmax, n, out_hit, out_t, out_idx);
 }
 
 }  // extern "C"

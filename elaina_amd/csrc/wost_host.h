@@ -1,5 +1,6 @@
 // wost_host.h -- the host-side helpers every translation unit of libwost_hip.so shares (host code only, not part of the
-// C-ABI): the error macro, device scratch, uploads, environment switches and the skeleton of a batch entry point.
+// C-ABI): the error macro, device scratch, uploads, environment switches, the LDS of a query kernel's stack columns, the sum of two
+// wost_stats, the byte comparison of the mesh build checks and the skeleton of a batch entry point.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +66,42 @@ inline void stamp_solve_ms(wost_stats *stats, HostClock::time_point t0)
 {
     if (stats) stats->solve_ms = std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
 }
+
+// (hidden: the dynamic symbol table of the library stays the C-ABI and what it held before; nothing here joins it)
+#pragma GCC visibility push(hidden)
+
+// LDS bytes of the traversal stacks of a 256-lane block of a query kernel over a tree of `levels` levels: a column of
+// 3 * levels + 1 entries per lane (pushes on the inner levels, at most 3 each; the Neumann tree queries push up to 4 and pop 1)
+inline size_t stack_lds(int levels) { return (size_t)(3 * levels + 1) * 256 * sizeof(uint32_t); }
+
+// the counters and kernel times of `st` added to `total`, for a call that makes several passes of a solve driver (reserved, the
+// deepest stack, is a maximum; solve_ms is the whole call's and left to the caller)
+inline void add_stats(wost_stats &total, const wost_stats &st)
+{
+    total.walk_steps += st.walk_steps; total.walks_started += st.walks_started; total.walks_absorbed += st.walks_absorbed;
+    total.walks_truncated += st.walks_truncated; total.neumann_hits += st.neumann_hits; total.inner_visits += st.inner_visits;
+    total.leaf_visits += st.leaf_visits; total.trav_trips += st.trav_trips; total.step_trips += st.step_trips;
+    total.kernel_ms += st.kernel_ms; total.kernel_launches += st.kernel_launches; total.reserved = std::max(total.reserved, st.reserved);
+}
+
+// the mesh build checks: the bytes in which two device arrays of `count` elements differ (all of them when one is missing or a
+// copy fails); *compared grows by the bytes looked at
+template <class T>
+int64_t differing_bytes(const T *a, const T *b, size_t count, int64_t *compared)
+{
+    if (count == 0) return 0;
+    const size_t bytes = count * sizeof(T);
+    if (!a || !b) return (a || b) ? (int64_t)bytes : 0;
+    std::vector<unsigned char> ha(bytes), hb(bytes);
+    if (hipMemcpy(ha.data(), a, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hb.data(), b, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return (int64_t)bytes;
+    int64_t diff = 0;
+    for (size_t i = 0; i < bytes; ++i) diff += ha[i] != hb[i];
+    *compared += (int64_t)bytes;
+    return diff;
+}
+
+#pragma GCC visibility pop
 
 }  // namespace wost
 

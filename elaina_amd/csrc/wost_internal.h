@@ -33,7 +33,7 @@ inline int check_points_finite(const float *pts, int32_t n, int dim)
     return WOST_OK;
 }
 
-// What the guided integrator needs from a wost_context (wost_hip.hip): the uploaded scene.
+// What the guided integrator needs from a wost_context (wost_internal2.h): the uploaded scene.
 struct SceneView {
     int device;
     DevMesh dm, nm;

@@ -12,8 +12,7 @@
 #include "../../include/wost.h"
 #include "wost_device3.h"
 #include "wost_internal.h"
-#include "wost_carry.h"
-#include "wost_grad.h"
+#include "wost_uniform.h"
 
 namespace wost {
 
@@ -40,30 +39,15 @@ inline size_t pool3_lds_bytes(int waves, int pool_cap) { return (size_t)waves * 
 
 }  // namespace wost
 
-// (the handle type of the C-ABI lives outside the namespace; its members are the namespace's)
-struct wost3_context {
-    int device = 0;
-    wost_settings settings{};
-    wost::DevSettings dst{};
+// (the handle type of the C-ABI lives outside the namespace; its members are the namespace's.  device, settings, dst, mask, n_pixels,
+// field, stream, the events and the carried states: HandleBase, wost_uniform.h)
+struct wost3_context : wost::HandleBase {
     wost::DevProbe3 probe{};
     wost::DeviceMesh3 dm, nm;
-    uint8_t *mask = nullptr;
     wost::DevSource3 src{};          // rgb owned by the context
-    size_t n_pixels = 0;
-    float *field = nullptr;
     wost::Stats3Dev *stats = nullptr;
     uint32_t *cursor = nullptr;
     int wait_weight = 32, trav_burst = 3;   // a sweep over both constants: a leaf visit (four exact triangle distances) is dear, steps are served early
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the carried frame solve (wost3_solve_more & co., wost_carry.h)
-    wost::CarryState carry;
-    // ... and, beside it, the carried point list (wost3_points_carry & co.)
-    wost::PointList list;
-    // the scratch of the gradient calls (wost3_solve_gradient_points & co., wost_grad.h)
-    wost::GradScratch grad;
-    // ... and the carried gradient list (wost3_gradient_points_carry & co.), which shares it
-    wost::GradList glist;
 };
 
 namespace wost {
