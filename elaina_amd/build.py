@@ -86,13 +86,20 @@ def _library_flags():
     return [f for f in HIPCC_FLAGS if f != "-shared"] + os.environ.get("WOST_HIPCC_DEFS", "").split()
 
 
-PROBE_SRC = os.path.join(_HERE, "..", "tests", "probe", "wost_probe.hip")
+PROBE_DIR = os.path.join(_HERE, "..", "tests", "probe")
+PROBE_SRC = os.path.join(PROBE_DIR, "wost_probe.hip")
+# (object, source) of the probe library: its own two units, and the product's csrc/wost_order.hip compiled a second time -- the
+# order probe runs the product's key kernels and sort, it restates none of them
+PROBE_UNITS = [("wost_probe.o", PROBE_SRC),
+               ("wost_order_probe.o", os.path.join(PROBE_DIR, "wost_order_probe.hip")),
+               ("probe_wost_order.o", os.path.join(CSRC, "wost_order.hip"))]
 PROBE_PATH = os.path.join(LIB_DIR, "libwost_probe.so")
 
 
 def build_probe(force=False, verbose=False):
-    """libwost_probe.so (test infrastructure, tests/probe/wost_probe.hip): one elementwise kernel over the inline math functions
-    of csrc/, compiled with exactly the flags of the product's units -- it tests what those flags make of the headers -- and
+    """libwost_probe.so (test infrastructure, tests/probe/): one elementwise kernel over the inline math functions of csrc/
+    (wost_probe.hip) and a driver of the walk orders (wost_order_probe.hip, linked with csrc/wost_order.hip), every unit
+    compiled with exactly the flags of the product's units -- it tests what those flags make of the product's code -- and
     rebuilt when the unit, a header of csrc/ or the flags change."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
@@ -103,16 +110,24 @@ def build_probe(force=False, verbose=False):
         same_flags = open(stamp).read().strip() == flag_id
     except OSError:
         same_flags = False
-    obj = os.path.join(OBJ_DIR, "wost_probe.o")
-    if force or not same_flags or _stale(obj, [PROBE_SRC] + headers):
-        cmd = [_hipcc()] + flags + ["-c", PROBE_SRC, "-o", obj]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+    jobs, objs = [], []
+    for name, src in PROBE_UNITS:
+        obj = os.path.join(OBJ_DIR, name)
+        objs.append(obj)
+        if force or not same_flags or _stale(obj, [src] + headers):
+            cmd = [_hipcc()] + flags + ["-c", src, "-o", obj]
+            if verbose:
+                print(" ".join(cmd))
+            jobs.append((cmd, subprocess.Popen(cmd)))
+    # (as in build_library: every compiler is waited for before a failure is reported)
+    failed = [(cmd, p.returncode) for cmd, p in jobs if p.wait() != 0]
+    if failed:
+        raise subprocess.CalledProcessError(failed[0][1], failed[0][0])
+    if jobs or not same_flags:
         with open(stamp, "w") as f:
             f.write(flag_id + "\n")
-    if force or _stale(PROBE_PATH, [obj]):
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", obj, "-o", PROBE_PATH]
+    if force or jobs or _stale(PROBE_PATH, objs):
+        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", PROBE_PATH]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

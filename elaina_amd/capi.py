@@ -181,8 +181,8 @@ class LaunchInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-LAUNCH_ROUND, LAUNCH_QUAD, LAUNCH_ONE, LAUNCH_PERSISTENT, LAUNCH_WAIT = 0, 1, 2, 3, 4
-LAUNCH_NAMES = {0: "round", 1: "quad round", 2: "one launch", 3: "persistent", 4: "wait"}
+LAUNCH_ROUND, LAUNCH_QUAD, LAUNCH_ONE, LAUNCH_PERSISTENT, LAUNCH_WAIT, LAUNCH_BESIDE = 0, 1, 2, 3, 4, 5
+LAUNCH_NAMES = {0: "round", 1: "quad round", 2: "one launch", 3: "persistent", 4: "wait", 5: "beside only"}
 
 
 # wost_sync_fn (include/wost.h): int (*)(void *user, int op, void *data, uint64_t count)

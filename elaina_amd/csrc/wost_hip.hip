@@ -1376,7 +1376,9 @@ int wost_set_option(wost_handle h, const char *key, double value)
     } else if (k == "few_order") {
         h->few_order = value != 0;
     } else if (k == "long_steps") {
-        if (value < 0 || value > 65528 || ((int)value & 7)) return set_error(WOST_ERR_INVALID, "long_steps must be a multiple of 8 in 0..65528 (0 = no pixel runs beside the rounds)");
+        // (the bound: above it the order by estimate no longer puts the long remainders first, wost_order.h)
+        static_assert(kOrderMaxThreshold == 32760, "the bound is part of the option's text");
+        if (value < 0 || value > kOrderMaxThreshold || ((int)value & 7)) return set_error(WOST_ERR_INVALID, "long_steps must be a multiple of 8 in 0..32760 (0 = no pixel runs beside the rounds)");
         h->long_steps = (int)value;
     } else if (k == "long_cap") {
         if (value < 1 || value > (1 << 20)) return set_error(WOST_ERR_INVALID, "long_cap must be in 1..2^20");
@@ -1555,6 +1557,10 @@ struct Pass {
     unsigned grid;
     RoundParams rp;
 };
+// walkers a pass started on the side streams (long remainders, strayed walkers), and whether it started anything at all: the
+// passes wost_last_launches lists are the passes wost_stats.kernel_launches counts
+static uint32_t pass_beside(const Pass &p) { return p.n_active - p.n_round + p.far + p.beside_far; }
+static bool pass_launched(const Pass &p) { return p.n_round > 0 || pass_beside(p) > 0; }
 
 // The hand-over after a persistent launch: it left one partly solved pixel per lane, each with an estimate of the walk steps it
 // still needs (config 2: 387 000 pixels, 12 % of the solve's steps; half of them need 650 steps more, a few thousand over 1 500),
@@ -1636,7 +1642,7 @@ static int launch_strayed(wost_context *c, const LaunchGeometry &g, hipStream_t 
     launch_walk(g, WOST_LAUNCH_ROUND, true, (unsigned)((((uint64_t)p.far << fp.lane_shift) + g.bs - 1) / g.bs), c->far_stream, fp);
     WOST_TRY(hipGetLastError());
     WOST_TRY(hipEventRecord(c->far_ev1, c->far_stream));
-    // (not counted in `launches`: kernel_ms / kernel_launches stays the average duration of the ordinary launches)
+    // (not a launch of its own in `launches`: kernel_launches counts passes, and a pass is counted once whatever it started)
     return WOST_OK;
 }
 
@@ -1731,7 +1737,9 @@ static int finish_pass(wost_context *c, hipStream_t stream, const Pass &p, uint3
     float ms = 0.0f;
     WOST_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     kernel_ms += ms;
-    wost_launch_info li{p.kind, p.n_round, p.n_active - p.n_round + p.far + p.beside_far, p.n_round > 0 ? p.grid : 0u, ms, 0};
+    if (!pass_launched(p)) return WOST_OK;
+    // (a pass whose walkers all went to the side streams has no ordinary launch: WOST_LAUNCH_BESIDE)
+    wost_launch_info li{p.n_round > 0 ? p.kind : (int)WOST_LAUNCH_BESIDE, p.n_round, pass_beside(p), p.n_round > 0 ? p.grid : 0u, ms, 0};
     li.walk_steps_done = c->steps_before;
     for (int k = 0; k < kStatCopies; ++k) li.walk_steps_done += c->host_stats[k].steps;
     c->last_launches.push_back(li);
@@ -1827,7 +1835,7 @@ static int run_solve(wost_context *c, const FirstStep &fs, float *field_dev, int
         if (rc == WOST_OK) rc = finish_pass(c, stream, p, launches, kernel_ms);
         if (rc != WOST_OK) return rc;
         handed_over = p.kind == WOST_LAUNCH_PERSISTENT;
-        if (p.n_round > 0) ++launches;
+        if (pass_launched(p)) ++launches;
         pending_far = c->host_count[2];
         n_active = c->host_count[0];
         cur = nxt;

@@ -31,7 +31,11 @@ int order_by_distance(WalkOrder &o, const float *d0_d2, uint32_t n, hipStream_t 
 
 // order[k] = queue slot of the walker with the k-th largest `est` (expected walk steps left, written by a persistent launch when
 // it hands its pixels over): keys are est / 8 clamped to 12 bits, descending and stable.  An estimate of at least T (a multiple
-// of 8) sorts before every estimate below T: the first `count(est >= T)` entries are exactly those walkers.
+// of 8 in 8 .. kOrderMaxThreshold) sorts before every estimate below T: the first `count(est >= T)` entries are exactly those
+// walkers.  The bound is where the key saturates: every estimate of 32760 or more has the key 4095, so above it the prefix may
+// hold an estimate in [32760, T) in place of a longer one ([32760, 40000, 32767, 65528] at T = 32768).  run_solve's hand_over
+// takes the walkers for the launch beside the rounds from that prefix, so wost_set_option("long_steps") accepts no larger T.
+constexpr int kOrderMaxThreshold = 32760;
 int order_by_estimate(WalkOrder &o, const float *est, uint32_t n, hipStream_t stream, const uint32_t **order_out);
 
 }  // namespace wost

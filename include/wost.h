@@ -666,15 +666,20 @@ enum {
     WOST_LAUNCH_ONE = 2,         /* few samples per pixel: resident lanes drain the queue, the whole solve in one launch   */
     WOST_LAUNCH_PERSISTENT = 3,  /* many samples per pixel: resident lanes take whole pixels, longest expected chain first,
                                     until none is unread; what they hold then goes to rounds                              */
-    WOST_LAUNCH_WAIT = 4         /* no launch: the time the solve waited at its end for what ran beside the rounds         */
+    WOST_LAUNCH_WAIT = 4,        /* no launch: the time the solve waited at its end for what ran beside the rounds         */
+    WOST_LAUNCH_BESIDE = 5       /* a pass without an ordinary launch: every walker it had started on the other streams
+                                    (walkers = 0, grid = 0, walkers_beside > 0)                                            */
 };
+/* Every record but WOST_LAUNCH_WAIT is one pass of the solve, and wost_stats.kernel_launches counts those passes: a record of kind
+ * ROUND, QUAD, ONE or PERSISTENT has walkers > 0 and grid > 0. */
 int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, int32_t *count);
 
 /* Tuning knobs ("steps_per_round", "block_size", "refill", "thin_waves", ...; scheduling only,
  * never the result); unknown keys -> WOST_ERR_INVALID.
  * "persist" (-1 automatic / 0 / 1): the persistent first launch of a solve with many samples per pixel and more walkers than
  * resident lanes (WOST_LAUNCH_PERSISTENT); "persist_order" 0: in queue order instead of longest-first; "long_steps" (a multiple
- * of 8, default 1024; 0 = none): pixels that launch hands over with at least that many walk steps expected still run to their
+ * of 8 in 0..32760, default 1024; 0 = none; larger values are refused: the order by estimate tells no estimates apart beyond
+ * 32760): pixels that launch hands over with at least that many walk steps expected still run to their
  * end beside the rounds of the others, the first "long_thin" (2048) of them four to a wave, at most "long_cap" (32768);
  * "tail_sort" (1): the first round after it takes its walkers in the order of their expected remainders; "few_order" (1): the
  * one-launch path of few samples per pixel takes the pixels longest-first too; "resident_blocks": workgroups of those launches

@@ -23,6 +23,12 @@ def load():
         _lib = C.CDLL(b.PROBE_PATH)
         _lib.wost_probe_run.restype = C.c_int
         _lib.wost_probe_run.argtypes = [C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.wost_order_probe_open.restype = C.c_int
+        _lib.wost_order_probe_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+        _lib.wost_order_probe_run.restype = C.c_int
+        _lib.wost_order_probe_run.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+        _lib.wost_order_probe_close.restype = C.c_int
+        _lib.wost_order_probe_close.argtypes = [C.c_void_p]
     return _lib
 
 
@@ -33,6 +39,51 @@ def device_probe(fn, x, device=0):
     if rc != 0:
         raise RuntimeError("wost_probe_run(%s): hipError_t %d" % (fn, rc))
     return out
+
+
+ORDER_SENTINEL = 0xFFFFFFFF
+HIP_SUCCESS, HIP_ERROR_INVALID_VALUE = 0, 1
+
+
+class WalkOrderProbe:
+    """one WalkOrder of the product (csrc/wost_order.h) for `cap` walkers, through tests/probe/wost_order_probe.hip: the scratch
+    is sized once and serves every run, as a handle's does"""
+
+    BY_DISTANCE, BY_ESTIMATE = 0, 1
+
+    def __init__(self, cap, device=0):
+        self.lib, self.cap, self._h = load(), int(cap), C.c_void_p()
+        rc = self.lib.wost_order_probe_open(device, self.cap, C.byref(self._h))
+        if rc != 0:
+            raise RuntimeError("wost_order_probe_open(%d): hipError_t %d" % (self.cap, rc))
+
+    def run(self, which, keys):
+        """order_by_distance / order_by_estimate on a float32 array -> (what the function returned, all cap entries of the buffer
+        *order_out points into, all cap entries of the other value buffer); both buffers held ORDER_SENTINEL before the run"""
+        keys = np.ascontiguousarray(keys, dtype=np.float32)
+        rc = C.c_int32(-1)
+        out, other = np.zeros(self.cap, np.uint32), np.zeros(self.cap, np.uint32)
+        e = self.lib.wost_order_probe_run(self._h, which, keys.ctypes.data, len(keys), C.byref(rc), out.ctypes.data, other.ctypes.data)
+        if e != 0:
+            raise RuntimeError("wost_order_probe_run: error %d of the probe's own calls" % e)
+        return rc.value, out, other
+
+    def by_distance(self, d2):
+        return self.run(self.BY_DISTANCE, d2)
+
+    def by_estimate(self, est):
+        return self.run(self.BY_ESTIMATE, est)
+
+    def close(self):
+        if self._h:
+            self.lib.wost_order_probe_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- building blocks ------------------------------------------------------------------------------------------------------

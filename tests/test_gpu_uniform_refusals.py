@@ -103,6 +103,41 @@ def test_solve_sharded_refuses_a_null_field(dim):
     assert dim.error() == "null argument"
 
 
+def test_set_option_refuses_long_steps_beyond_the_order_by_estimate():
+    """long_steps is the threshold hand_over reads off the order by estimate, whose key saturates at 32760 (wost_order.h): the
+    option takes the multiples of 8 up to there and refuses 32768 and 65528, which it once took.  A refusal leaves the handle's
+    setting as it was -- seen in what the next solve sends beside its rounds: with long_steps 8 some of the pixels a persistent
+    launch hands over, with 0 (or any value no estimate of this frame reaches) none."""
+    from elaina_amd import UniformIntegrator, UniformIntegratorSettings, capi
+    it = UniformIntegrator(box_problem(), UniformIntegratorSettings((32, 32), 8, 16, 1e-3))
+    lib = capi.load()
+    for k, v in {"persist": 1, "resident_blocks": 1, "block_size": 64}.items():
+        it.set_option(k, v)
+
+    def beside():
+        it.solve()
+        ll = it.last_launches()
+        assert ll[0]["kind"] == capi.LAUNCH_PERSISTENT and len(ll) >= 2
+        return ll[1]["walkers_beside"], any(l["kind"] == capi.LAUNCH_WAIT for l in ll)
+
+    def refused(value):
+        assert lib.wost_set_option(it._handle, b"long_steps", float(value)) == WOST_ERR_INVALID
+        assert lib.wost_last_error().decode() == "long_steps must be a multiple of 8 in 0..32760 (0 = no pixel runs beside the rounds)"
+
+    assert lib.wost_set_option(it._handle, b"long_steps", 32760.0) == WOST_OK
+    assert beside() == (0, False)
+    assert lib.wost_set_option(it._handle, b"long_steps", 8.0) == WOST_OK
+    for value in (32768, 65528, 32764, -8):
+        refused(value)
+    n, waited = beside()
+    assert n > 0 and waited
+    assert lib.wost_set_option(it._handle, b"long_steps", 0.0) == WOST_OK
+    for value in (32768, 65528):
+        refused(value)
+    assert beside() == (0, False)
+    it.close()
+
+
 def test_create_refuses_a_source_grid_without_samples(dim):
     """2-D: a grid with both sizes positive needs its samples.  3-D: a grid with nx > 0 needs the other two sizes and its samples."""
     from elaina_amd import capi
