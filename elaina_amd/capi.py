@@ -282,6 +282,7 @@ SIGNATURES.update({
     "wost_guided_set_frame_callback": [_h, FRAME_FN, _h, _i32, _i32, _i32],
     "wost_guided_set_option": [_h, C.c_char_p, C.c_double],
     # 3-D alone
+    "wost3_set_option": [_h, C.c_char_p, C.c_double],
     "wost3_vmf_eval": [C.c_int, _pf, _pf, _i32, _pf],
     "wost3_vmf_sample": [C.c_int, _pf, _pf, _pu64, _i32, _i32, _pf],
 })

@@ -15,21 +15,29 @@
 namespace wost {
 
 struct DevMesh3;      // wost_device3.h
+struct DevSource3;
 
 // the first ball stays clear of the Neumann boundary: R = min(dD, kGradNeumannShrink * dN).  Exact in binary; a design constant
 constexpr float kGradNeumannShrink = 0.875f;
 
 // The scratch of a handle's gradient calls, sized by the handle (n_pixels walks, what one point step takes), allocated on the
 // first call and freed with the handle: per walk its first point and direction (dim floats each) and its result (RGB), per
-// point of a block its radius; two pairs of events around the two kernels of a block.
+// point of a block its radius; two pairs of events around the two kernels of a block.  A second allocation, made on the first
+// call that takes in-ball samples (a scene with a source term and the handle's "grad_source" on) and on no other: per sample
+// its direction, its two weights and the odd and even part of the source at its pair of points -- dim + 8 arrays of n_pixels
+// floats (kBall*), so that the samples of a block lie side by side in each.
 struct GradScratch {
     void *mem = nullptr;
     float *first = nullptr, *dirs = nullptr, *w = nullptr, *radius = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float *ball = nullptr;
+    size_t ball_stride = 0;      // n_pixels
 };
 void grad_free(GradScratch &s);
 // the scratch allocated (the first call of a handle) for blocks of a frame of n_pixels
 int grad_ready(GradScratch &s, size_t n_pixels, int dim);
+// ... and its in-ball part (the first call of a handle that takes in-ball samples)
+int grad_ball_ready(GradScratch &s, size_t n_pixels, int dim);
 
 // ---- what the kernel behind the walks and the accumulate step of the carried list share -------------------------------------
 // a point is degenerate -- its walks start at the point itself, its gradient is NaN -- when R is not finite or within the shell
@@ -65,6 +73,33 @@ __device__ __forceinline__ void grad_point_sums(const float *w, const float *d, 
 template <int DIM>
 __device__ __forceinline__ double grad_scale(float R, int S) { return (double)DIM / ((double)R * ((double)S - 1.0)); }
 
+// The in-ball samples of a block as grad_ball_kernel leaves them (include/wost.h "In-ball samples"): array a of sample t at
+// ball[a * stride + t], t = j * S + s for sample s of point j of the block.  The arrays: the direction m (DIM), then
+enum { kBallWg = 0, kBallWu = 1, kBallDs = 2, kBallMs = 5, kBallArrays = 8 };      // ... these, behind the DIM of m
+// The pass over a point's S in-ball samples by the lanes of one wave (all of them call; `ball` points at the point's sample 0):
+//   a_kc = sum_s wg_s m_sk ds_sc   and   u_c = sum_s wu_s ms_sc,   in fp64, the same on every lane.
+// A point that took no samples has zeros there and gets zeros here.
+template <int DIM>
+__device__ __forceinline__ void grad_ball_sums(const float *ball, size_t stride, int S, int lane, double (&a)[DIM * 3], double (&u)[3])
+{
+    const float *wg = ball + (DIM + kBallWg) * stride, *wu = ball + (DIM + kBallWu) * stride;
+    const float *ds = ball + (DIM + kBallDs) * stride, *ms = ball + (DIM + kBallMs) * stride;
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) a[e] = 0.0;
+    for (int c = 0; c < 3; ++c) u[c] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) a[e] += (double)wg[s] * (double)ball[(e / 3) * stride + s] * (double)ds[(e % 3) * stride + s];
+        for (int c = 0; c < 3; ++c) u[c] += (double)wu[s] * (double)ms[c * stride + s];
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) a[e] = wave_sum(a[e]);
+    for (int c = 0; c < 3; ++c) u[c] = wave_sum(u[c]);
+}
+// T_kc = (R / S) a_kc joins the walk part of grad, U_c = (R^2 / S) u_c the mean, before the one rounding to fp32
+__device__ __forceinline__ double ball_grad_term(float R, int S, double a) { return (double)R / (double)S * a; }
+__device__ __forceinline__ double ball_field_term(float R, int S, double u) { return (double)R * (double)R / (double)S * u; }
+
 // The kernel in front of the walks, for `count` points of the caller's list from point `first` on, `spp` walks each: point j of
 // the block draws its directions from the stream of pixel seed_base + first + j of a frame seed_width wide.  All pointers on
 // the device; radius, dirs and first_pts are the block's (indexed from 0).  sel (a round of the carried gradient list; nullptr:
@@ -80,22 +115,47 @@ struct GradPrep {
 int grad_prep2(const DevMesh &dm, const DevMesh &nm, const GradPrep &p, hipStream_t stream);
 int grad_prep3(const DevMesh3 &dm, const DevMesh3 &nm, const GradPrep &p, hipStream_t stream);
 
-// What the driver reads of a context, and what a dimension adds: its kernel in front (grad_prep2 / grad_prep3 on its meshes) and
-// its point step -- one sample at each of the n_walks device points, walk w on the stream of pixel seed_base + w, into w_rgb.
+// The kernel between the one in front and the walks, on a scene with a source term when the handle's "grad_source" is on: for
+// the same `count` points, `spp` in-ball samples each from the same streams, behind the direction draws.  It reads the block's
+// radii (a point whose radius is degenerate -- an unselected or a non-finite point's is NaN -- takes no samples and draws
+// none: zeros) and writes the block's part of the in-ball arrays (GradScratch::ball, stride floats apart).
+struct GradBall {
+    const float *pts;
+    int32_t first, count, spp, seed_base, seed_width;
+    float eps;
+    const float *radius;
+    float *ball;
+    size_t stride;
+};
+int grad_ball2(const DevSource &src, const GradBall &p, hipStream_t stream);
+int grad_ball3(const DevSource3 &src, const GradBall &p, hipStream_t stream);
+
+// What the driver reads of a context, and what a dimension adds: its kernel in front (grad_prep2 / grad_prep3 on its meshes),
+// its point step -- one sample at each of the n_walks device points, walk w on the stream of pixel seed_base + w, into w_rgb --
+// and the in-ball kernel on its source grid (grad_ball2 / grad_ball3).  source_term: the handle's option "grad_source"; a scene
+// with a source term is refused without it and takes in-ball samples with it (in_ball).
 struct GradCall {
     const char *prefix;
     int dim, device;
     int32_t spp;
     size_t n_pixels;
     float eps;
-    bool has_source;
+    bool has_source, source_term;
     hipStream_t stream;      // the handle's own: where a host call runs
     GradScratch *scratch;
     std::function<int(const GradPrep &, hipStream_t)> prep;
     std::function<int(const float *first_pts, int32_t n_walks, int32_t seed_base, int32_t seed_width, float *w_rgb, hipStream_t stream,
                       wost_stats *stats)>
         walk;
+    std::function<int(const GradBall &, hipStream_t)> ball;
+    bool in_ball() const { return has_source && source_term; }
 };
+// the block's in-ball samples behind the kernel in front (the scratch has its in-ball part): sel as in GradPrep, through the radii
+int grad_ball_block(const GradCall &c, const float *pts, int32_t first, int32_t count, int32_t spp, int32_t seed_base, int32_t seed_width,
+                    hipStream_t stream);
+
+// the option "grad_source" of a handle (wost_set_option, wost3_set_option): exactly 0 or 1
+int grad_source_option(double value, bool *option);
 
 // the argument rules that need no look at the handle (include/wost.h), in the order of the header
 int grad_check(const void *h, const float *pts, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
@@ -143,6 +203,7 @@ struct GradList {
     int32_t n = 0, S = 0, round_stride = 0, max_rounds = 0, seed_base = 0, walk_seed_base = 0, seed_width = 1;
     int32_t per_block = 0, n_blocks = 0, rounds = 0;
     bool stale = false;                          // restarted: K and the sums are zeroed before their next use
+    bool in_ball = false;                        // GradCall::in_ball() at the bind: every round takes in-ball samples, or none does
 };
 void gradlist_free(GradList &l);
 void gradlist_restart(GradList &l);

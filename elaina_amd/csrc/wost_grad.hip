@@ -13,6 +13,7 @@
 
 #include "wost_device3.h"
 #include "wost_grad.h"
+#include "wost_walk.h"
 
 namespace wost {
 
@@ -181,10 +182,117 @@ int grad_prep3(const DevMesh3 &dm, const DevMesh3 &nm, const GradPrep &p, hipStr
     return WOST_OK;
 }
 
+// ---- the in-ball kernel --------------------------------------------------------------------------------------------------------
+// the source at a point, intensity included, by the walk step's own functions
+__device__ __forceinline__ void ball_source(const DevSource &src, const float (&y)[2], float (&f)[3]) { source_eval(src, y[0], y[1], f[0], f[1], f[2]); }
+__device__ __forceinline__ void ball_source(const DevSource3 &src, const float (&y)[3], float (&f)[3]) { source3_eval(src, v3(y[0], y[1], y[2]), f); }
+
+template <class SRC>
+struct GradBallParams {
+    SRC src;
+    GradBall p;
+};
+
+// Thread t takes in-ball sample s = t % spp of point j = t / spp of the block.  It jumps to its place in the stream of pixel
+// seed_base + first + j -- behind the spp direction draws of the kernel in front, DIM - 1 floats each, and the s samples before
+// its own, DIM floats each --, draws a direction m as that kernel does and rho, and evaluates the source at the pair
+// x +- rho R m: every operation a single fp32 one in the order of include/wost.h ("In-ball samples"), no fused multiply-add.
+// A point whose radius is degenerate (NaN for an unselected and for a non-finite point) draws nothing: zeros.
+template <int DIM, class SRC>
+__global__ __launch_bounds__(256) void grad_ball_kernel(GradBallParams<SRC> P)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)P.p.count * P.p.spp) return;
+    const int j = (int)(t / P.p.spp), s = (int)(t % P.p.spp);
+    float *out = P.p.ball + t;
+    const size_t stride = P.p.stride;
+    const float R = P.p.radius[j];
+    float m[DIM], wg = 0.0f, wu = 0.0f, ds[3] = {0.0f, 0.0f, 0.0f}, ms[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) m[k] = 0.0f;
+    if (!ball_degenerate(R, P.p.eps)) {
+        Pcg rng{0, 1};
+        pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
+        pcg_advance(rng, (int64_t)(DIM - 1) * P.p.spp + (int64_t)DIM * s);
+        float c, sn;
+        if (DIM == 2) {
+            sincos_2pi(pcg_next_float(rng), c, sn);
+            m[0] = c; m[1] = sn;
+        } else {
+            const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
+            sincos_2pi(u2, c, sn);
+            const float z = 1 - 2 * u1, r = sqrtf(1 - z * z);
+            m[0] = r * c; m[1] = r * sn; m[DIM - 1] = z;
+        }
+        const float rho = pcg_next_float(rng);
+        const float r = rho * R;
+        float yp[DIM], ym[DIM], fp[3], fm[3];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+            const float x = P.p.pts[(size_t)DIM * (size_t)(P.p.first + j) + k], p = r * m[k];
+            yp[k] = x + p;
+            ym[k] = x - p;
+        }
+        ball_source(P.src, yp, fp);
+        ball_source(P.src, ym, fm);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            ds[ch] = 0.5f * (fp[ch] - fm[ch]);
+            ms[ch] = 0.5f * (fp[ch] + fm[ch]);
+        }
+        if (DIM == 2) {
+            wg = 1.0f - rho * rho;
+            wu = rho > 0.0f ? -(rho * det_logf(rho)) : 0.0f;
+        } else {
+            wg = 1.0f - (rho * rho) * rho;
+            wu = rho - rho * rho;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) out[k * stride] = m[k];
+    out[(DIM + kBallWg) * stride] = wg;
+    out[(DIM + kBallWu) * stride] = wu;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        out[(DIM + kBallDs + ch) * stride] = ds[ch];
+        out[(DIM + kBallMs + ch) * stride] = ms[ch];
+    }
+}
+
+template <int DIM, class SRC>
+static int grad_ball_launch(const SRC &src, const GradBall &p, hipStream_t stream)
+{
+    const GradBallParams<SRC> P{src, p};
+    const int64_t threads = (int64_t)p.count * p.spp;
+    hipLaunchKernelGGL((grad_ball_kernel<DIM, SRC>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+int grad_ball2(const DevSource &src, const GradBall &p, hipStream_t stream) { return grad_ball_launch<2>(src, p, stream); }
+int grad_ball3(const DevSource3 &src, const GradBall &p, hipStream_t stream) { return grad_ball_launch<3>(src, p, stream); }
+
+int grad_ball_block(const GradCall &c, const float *pts, int32_t first, int32_t count, int32_t spp, int32_t seed_base, int32_t seed_width,
+                    hipStream_t stream)
+{
+    const GradScratch &s = *c.scratch;
+    return c.ball(GradBall{pts, first, count, spp, seed_base, seed_width, c.eps, s.radius, s.ball, s.ball_stride}, stream);
+}
+
+int grad_source_option(double value, bool *option)
+{
+    if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "grad_source must be 0 or 1");
+    *option = value == 1;
+    return WOST_OK;
+}
+
 // ---- the kernel behind ---------------------------------------------------------------------------------------------------------
 struct GradReduceParams {
     // the block: count points of spp walks each -- results (RGB), directions and first points per walk, radii per point
     const float *w, *dirs, *first_pts, *radius;
+    // ... and with in-ball samples (nullptr: none) their arrays, ball_stride floats apart
+    const float *ball;
+    size_t ball_stride;
     int32_t first, count, spp;
     float eps;
     // the call's outputs, indexed by the point's index in the call; nullptr: not wanted (grad always is)
@@ -197,6 +305,9 @@ struct GradReduceParams {
 // The sums run in fp64 and the results are rounded once.  The control variate subtracts numbers of the size of u and leaves
 // differences of the size of R |grad u|: a mean rounded to fp32 would sit in t_s with |u| / (R |grad u|) ulps, and the standard
 // error of a point close to the boundary would lose that factor of its precision.
+// With in-ball samples (include/wost.h "The gradient on a scene with a source term"): a_s = wg_s m_sk ds_sc,
+//   T_kc = (R / S) sum_s a_s,   seT_kc = R sqrt(sum_s (a_s - mean a)^2 / (S - 1) / S),   U_c = (R^2 / S) sum_s wu_s ms_sc,
+//   grad = walk part + T,   stderr = sqrt(walk part^2 + seT^2),   field = mean + U,   each still rounded once.
 template <int DIM>
 __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
 {
@@ -222,15 +333,39 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
     for (int e = 0; e < DIM * 3; ++e) v[e] = wave_sum(v[e]);
     const float R = P.radius[j];
     const bool degenerate = ball_degenerate(R, P.eps);
+    double a[DIM * 3], u[3], va[DIM * 3];
+    if (P.ball) {      // (the whole grid: P is uniform)
+        const float *b = P.ball + (size_t)j * S;
+        const size_t stride = P.ball_stride;
+        grad_ball_sums<DIM>(b, stride, S, lane, a, u);
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) va[e] = 0.0;
+        for (int s = lane; s < S; s += 64) {
+#pragma unroll
+            for (int e = 0; e < DIM * 3; ++e) {
+                const double dev = (double)b[(DIM + kBallWg) * stride + s] * (double)b[(e / 3) * stride + s] * (double)b[(DIM + kBallDs + e % 3) * stride + s] -
+                                   a[e] / dS;
+                va[e] += dev * dev;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) va[e] = wave_sum(va[e]);
+    }
     if (lane == 0) {
         const double scale = grad_scale<DIM>(R, S), scale_se = (double)DIM / (double)R;
 #pragma unroll
         for (int e = 0; e < DIM * 3; ++e) {
-            P.grad[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
-            if (P.grad_stderr) P.grad_stderr[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)(scale_se * sqrt(v[e] / (dS - 1.0) / dS));
+            double g = scale * t[e], se = scale_se * sqrt(v[e] / (dS - 1.0) / dS);
+            if (P.ball) {
+                const double se_t = (double)R * sqrt(va[e] / (dS - 1.0) / dS);
+                g += ball_grad_term(R, S, a[e]);
+                se = sqrt(se * se + se_t * se_t);
+            }
+            P.grad[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)g;
+            if (P.grad_stderr) P.grad_stderr[(size_t)(DIM * 3) * i + e] = degenerate ? WOST_NAN : (float)se;
         }
         if (P.field)
-            for (int c = 0; c < 3; ++c) P.field[3 * i + c] = (float)mean[c];
+            for (int c = 0; c < 3; ++c) P.field[3 * i + c] = (float)(P.ball && !degenerate ? mean[c] + ball_field_term(R, S, u[c]) : mean[c]);
         if (P.radius_out) P.radius_out[i] = R;
     }
     if (P.first_out)
@@ -241,6 +376,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
 void grad_free(GradScratch &s)
 {
     if (s.mem) (void)hipFree(s.mem);
+    if (s.ball) (void)hipFree(s.ball);
     for (hipEvent_t e : s.ev)
         if (e) (void)hipEventDestroy(e);
     s = GradScratch{};
@@ -260,6 +396,14 @@ int grad_ready(GradScratch &s, size_t n_pixels, int dim)
     return WOST_OK;
 }
 
+int grad_ball_ready(GradScratch &s, size_t n_pixels, int dim)
+{
+    if (s.ball) return WOST_OK;
+    WOST_TRY(hipMalloc((void **)&s.ball, n_pixels * (size_t)(dim + kBallArrays) * sizeof(float)));
+    s.ball_stride = n_pixels;
+    return WOST_OK;
+}
+
 int grad_check(const void *h, const float *pts, int32_t n, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
                const wost_gradient_out *out)
 {
@@ -275,7 +419,7 @@ int grad_check(const void *h, const float *pts, int32_t n, int32_t seed_base, in
 int grad_check_handle(const GradCall &c, int32_t n, int32_t seed_base, int32_t walk_seed_base)
 {
     const std::string name = std::string(c.prefix) + "solve_gradient_points: ";
-    if (c.has_source)
+    if (c.has_source && !c.source_term)
         return set_error(WOST_ERR_UNSUPPORTED, name + "a scene with a source term is not covered (the in-ball term of the gradient is not built)");
     const int64_t S = c.spp, walks = S * (int64_t)n;
     if (S < 2) return set_error(WOST_ERR_INVALID, name + "the handle's spp is " + std::to_string(S) + ", the estimator needs spp >= 2 walks per point");
@@ -297,6 +441,7 @@ int grad_solve_dev(const GradCall &c, const float *pts_dev, int32_t n, int32_t s
     WOST_TRY(hipSetDevice(c.device));
     GradScratch &s = *c.scratch;
     int rc = grad_ready(s, c.n_pixels, c.dim);
+    if (rc == WOST_OK && c.in_ball()) rc = grad_ball_ready(s, c.n_pixels, c.dim);
     if (rc != WOST_OK) return rc;
     const int32_t S = c.spp, per_block = (int32_t)(c.n_pixels / (size_t)S);
     wost_stats total{};
@@ -304,11 +449,13 @@ int grad_solve_dev(const GradCall &c, const float *pts_dev, int32_t n, int32_t s
         const int32_t m = std::min(per_block, n - a), walks = m * S;
         WOST_TRY(hipEventRecord(s.ev[0], stream));
         if ((rc = c.prep(GradPrep{pts_dev, a, m, S, seed_base, seed_width, c.eps, s.radius, s.dirs, s.first}, stream)) != WOST_OK) return rc;
+        if (c.in_ball() && (rc = grad_ball_block(c, pts_dev, a, m, S, seed_base, seed_width, stream)) != WOST_OK) return rc;
         WOST_TRY(hipEventRecord(s.ev[1], stream));
         WOST_TRY(hipMemsetAsync(s.w, 0, (size_t)walks * 3 * sizeof(float), stream));
         wost_stats st{};
         if ((rc = c.walk(s.first, walks, walk_seed_base + a * S, seed_width, s.w, stream, &st)) != WOST_OK) return rc;
-        const GradReduceParams rp{s.w, s.dirs, s.first, s.radius, a, m, S, c.eps, out.grad, out.grad_stderr, out.field_rgb, out.radius, out.first_pts};
+        const GradReduceParams rp{s.w, s.dirs, s.first, s.radius, c.in_ball() ? s.ball : nullptr, s.ball_stride, a, m, S, c.eps,
+                                  out.grad, out.grad_stderr, out.field_rgb, out.radius, out.first_pts};
         WOST_TRY(hipEventRecord(s.ev[2], stream));
         if (c.dim == 2) hipLaunchKernelGGL(grad_reduce_kernel<2>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, rp);
         else hipLaunchKernelGGL(grad_reduce_kernel<3>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, rp);

@@ -29,14 +29,17 @@ __global__ __launch_bounds__(256) void gradlist_walkable_kernel(const float *rad
 struct GradAccumParams {
     // the block: count points of spp walks each from point `first` of the list on -- results and directions per walk, radii per point
     const float *w, *dirs, *radius;
+    const float *ball;         // the in-ball samples of a list bound to take them (nullptr: none), ball_stride floats apart
+    size_t ball_stride;
     const uint8_t *sel;        // over the list: the points this round walks
     int32_t first, count, spp;
     int32_t *K;
     double *G, *Q, *F;
 };
 
-// One wave per point of the block; a selected point's batch is reduced as grad_reduce_kernel reduces it (grad_point_sums), so
-// its fp32 gradient and mean have the bits of the single call, and lane 0 adds them to the point's sums.
+// One wave per point of the block; a selected point's batch is reduced as grad_reduce_kernel reduces it (grad_point_sums and,
+// with in-ball samples, grad_ball_sums), so its fp32 gradient and mean have the bits of the single call, and lane 0 adds them
+// to the point's sums.
 template <int DIM>
 __global__ __launch_bounds__(256) void gradlist_accumulate_kernel(GradAccumParams P)
 {
@@ -48,15 +51,20 @@ __global__ __launch_bounds__(256) void gradlist_accumulate_kernel(GradAccumParam
     const int S = P.spp;
     double mean[3], t[DIM * 3];
     grad_point_sums<DIM>(P.w + 3 * (size_t)j * S, P.dirs + DIM * (size_t)j * S, S, lane, mean, t);
+    double a[DIM * 3], u[3];
+    if (P.ball) grad_ball_sums<DIM>(P.ball + (size_t)j * S, P.ball_stride, S, lane, a, u);      // (the whole grid: P is uniform)
     if (lane != 0) return;
-    const double scale = grad_scale<DIM>(P.radius[j], S);
+    const float R = P.radius[j];
+    const double scale = grad_scale<DIM>(R, S);
 #pragma unroll
     for (int e = 0; e < DIM * 3; ++e) {
-        const double g = (double)(float)(scale * t[e]);
+        double g = scale * t[e];
+        if (P.ball) g += ball_grad_term(R, S, a[e]);
+        g = (double)(float)g;
         P.G[(size_t)(DIM * 3) * i + e] += g;
         P.Q[(size_t)(DIM * 3) * i + e] += g * g;
     }
-    for (int c = 0; c < 3; ++c) P.F[3 * i + c] += (double)(float)mean[c];
+    for (int c = 0; c < 3; ++c) P.F[3 * i + c] += (double)(float)(P.ball ? mean[c] + ball_field_term(R, S, u[c]) : mean[c]);
     P.K[i] += 1;
 }
 
@@ -217,7 +225,7 @@ int gradlist_bind(GradList &l, const GradCall &c, const float *pts, bool pts_on_
     if ((uint64_t)batch_walks > (uint64_t)c.n_pixels)
         return set_error(WOST_ERR_INVALID, name + "batch_walks (" + std::to_string(batch_walks) + ") exceeds n_pixels (" + std::to_string(c.n_pixels) +
                                                "): a point's walks must fit one point step");
-    if (c.has_source)
+    if (c.has_source && !c.source_term)
         return set_error(WOST_ERR_UNSUPPORTED, name + "a scene with a source term is not covered (the in-ball term of the gradient is not built)");
     WOST_TRY(hipSetDevice(c.device));
     // the new list first, whole; the old one goes only when the new one stands
@@ -227,6 +235,7 @@ int gradlist_bind(GradList &l, const GradCall &c, const float *pts, bool pts_on_
     fresh.per_block = (int32_t)std::min<size_t>(c.n_pixels / (size_t)batch_walks, (size_t)INT32_MAX);
     fresh.n_blocks = (n + fresh.per_block - 1) / fresh.per_block;
     fresh.stale = true;
+    fresh.in_ball = c.in_ball();
     void *mem = nullptr;
     WOST_TRY(hipMalloc(&mem, gradlist_carve(fresh, nullptr)));
     fresh.mem = mem;
@@ -319,11 +328,12 @@ static int gradlist_round(GradList &l, const GradCall &c, const std::vector<uint
         int rc;
         WOST_TRY(hipEventRecord(s.ev[0], stream));
         if ((rc = c.prep(GradPrep{l.pts, a, m, S, l.seed_base + at, l.seed_width, c.eps, s.radius, s.dirs, s.first, l.sel}, stream)) != WOST_OK) return rc;
+        if (l.in_ball && (rc = grad_ball_block(c, l.pts, a, m, S, l.seed_base + at, l.seed_width, stream)) != WOST_OK) return rc;
         WOST_TRY(hipEventRecord(s.ev[1], stream));
         WOST_TRY(hipMemsetAsync(s.w, 0, (size_t)walks * 3 * sizeof(float), stream));
         wost_stats st{};
         if ((rc = c.walk(s.first, walks, l.walk_seed_base + (at + a) * S, l.seed_width, s.w, stream, &st)) != WOST_OK) return rc;
-        const GradAccumParams ap{s.w, s.dirs, s.radius, l.sel, a, m, S, l.K, l.G, l.Q, l.F};
+        const GradAccumParams ap{s.w, s.dirs, s.radius, l.in_ball ? s.ball : nullptr, s.ball_stride, l.sel, a, m, S, l.K, l.G, l.Q, l.F};
         WOST_TRY(hipEventRecord(s.ev[2], stream));
         if (c.dim == 2) hipLaunchKernelGGL(gradlist_accumulate_kernel<2>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, ap);
         else hipLaunchKernelGGL(gradlist_accumulate_kernel<3>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, ap);
@@ -357,7 +367,8 @@ static int fetch_outputs(const GradList &l, const wost_gradient_carried_out &out
 static int gradlist_begin(GradList &l, const GradCall &c, hipStream_t stream)
 {
     WOST_TRY(hipSetDevice(c.device));
-    const int rc = grad_ready(*c.scratch, c.n_pixels, c.dim);
+    int rc = grad_ready(*c.scratch, c.n_pixels, c.dim);
+    if (rc == WOST_OK && l.in_ball) rc = grad_ball_ready(*c.scratch, c.n_pixels, c.dim);
     return rc != WOST_OK ? rc : gradlist_ready(l, stream);
 }
 

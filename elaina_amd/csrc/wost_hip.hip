@@ -1421,6 +1421,8 @@ int wost_set_option(wost_handle h, const char *key, double value)
         h->thin_waves = value != 0;
     } else if (k == "time_kernels") {
         h->time_kernels = value != 0;
+    } else if (k == "grad_source") {
+        return grad_source_option(value, &h->grad_source);
     } else {
         return set_error(WOST_ERR_INVALID, "unknown option: " + k);
     }
@@ -1985,15 +1987,18 @@ static CarryWalk points_walk(PointListCtx<wost_context> *x, int32_t, int32_t)
 static const PointCalls<wost_context> kPoints{{"wost_points_", points_walk, [](PointListCtx<wost_context> *x) { x->h->last_launches.clear(); }}, 2};
 
 // ---- the gradient at the caller's points (the driver and its kernels: wost_grad.hip; the body of the entry points: grad_entry) ----
-// what the 2-D context adds: the kernel in front on its meshes, and a point step of one sample per walk on the handle's queues
+// what the 2-D context adds: the kernel in front on its meshes, a point step of one sample per walk on the handle's queues, and
+// the in-ball kernel on its source grid
 static GradCall grad_call(wost_context *c)
 {
-    GradCall g{"wost_", 2, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->stream, &c->grad, nullptr, nullptr};
+    GradCall g{"wost_", 2, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->grad_source, c->stream, &c->grad, nullptr, nullptr,
+               nullptr};
     g.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep2(c->dm.view, c->nm.view, p, stream); };
     g.walk = [c](const float *first_pts, int32_t n_walks, int32_t seed_base, int32_t seed_width, float *w_rgb, hipStream_t stream, wost_stats *stats) {
         const FirstStep fs{0, 0, 0, 1, first_pts, 0, n_walks, seed_base, seed_width, 0, 0, nullptr, false, 1};
         return run_solve(c, fs, w_rgb, 0, stream, stats);
     };
+    g.ball = [c](const GradBall &p, hipStream_t stream) { return grad_ball2(c->src, p, stream); };
     return g;
 }
 

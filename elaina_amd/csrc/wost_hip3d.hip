@@ -928,16 +928,19 @@ static CarryWalk points_walk3(PointListCtx<wost3_context> *x, int32_t, int32_t)
 static const PointCalls<wost3_context> kPoints3{{"wost3_points_", points_walk3, nullptr}, 3};
 
 // ---- the gradient at the caller's points (the driver and its kernels: wost_grad.hip; the body of the entry points: grad_entry) ----
-// what the 3-D context adds: the kernel in front on its meshes, and a point step of one sample per walk
+// what the 3-D context adds: the kernel in front on its meshes, a point step of one sample per walk, and the in-ball kernel on
+// its source grid
 static GradCall grad_call3(wost3_context *c)
 {
-    GradCall g{"wost3_", 3, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->stream, &c->grad, nullptr, nullptr};
+    GradCall g{"wost3_", 3, c->device, c->dst.spp, c->n_pixels, c->dst.eps, c->src.rgb != nullptr, c->grad_source, c->stream, &c->grad, nullptr, nullptr,
+               nullptr};
     g.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep3(c->dm.view, c->nm.view, p, stream); };
     g.walk = [c](const float *first_pts, int32_t n_walks, int32_t seed_base, int32_t seed_width, float *w_rgb, hipStream_t stream, wost_stats *stats) {
         FirstStep3 fs{0, n_walks, 0, 1, first_pts, seed_base, seed_width};
         fs.spp = 1;
         return run_solve3(c, fs, w_rgb, 0, stream, stats);
     };
+    g.ball = [c](const GradBall &p, hipStream_t stream) { return grad_ball3(c->src, p, stream); };
     return g;
 }
 
@@ -1055,6 +1058,14 @@ int wost3_destroy(wost3_handle h)
 {
     destroy3(h);
     return WOST_OK;
+}
+
+int wost3_set_option(wost3_handle h, const char *key, double value)
+{
+    if (!h || !key) return set_error(WOST_ERR_INVALID, "null argument");
+    const std::string k(key);
+    if (k == "grad_source") return grad_source_option(value, &h->grad_source);
+    return set_error(WOST_ERR_INVALID, "unknown option: " + k);
 }
 
 int wost3_solve(wost3_handle h, int32_t pixel_begin, int32_t pixel_end, float *field_rgb, wost_stats *stats)

@@ -33,6 +33,7 @@ struct HandleBase {
     PointList list;                 // ... and, beside it, the carried point list (wost_points_carry & co.)
     GradScratch grad;               // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
     GradList glist;                 // ... and the carried gradient list (wost_gradient_points_carry & co.), which shares it
+    bool grad_source = false;       // the option "grad_source": the gradient calls take a scene with a source term (GradCall)
 };
 
 // (hidden: the dynamic symbol table of the library stays the C-ABI and what it held before; nothing here joins it)

@@ -98,6 +98,10 @@ class UniformIntegrator3(UniformCalls):
         self.n_pixels = w * h
         self.solution, self.last_stats = None, None
 
+    def set_option(self, key, value):
+        """wost3_set_option: "grad_source" 1 lets the gradient calls take a scene with a source term (0, the default: refused)"""
+        _check(self.lib.wost3_set_option(self._handle, key.encode(), float(value)), "wost3_set_option")
+
     def render_sdf(self, which=0):
         """renderDirichletSDF (which = 0) / renderSilhouetteSDF (which = 1): one distance per pixel of the frame"""
         out = np.zeros(self.n_pixels, dtype=np.float32)

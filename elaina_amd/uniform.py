@@ -78,7 +78,9 @@ class UniformCalls:
         seed_base + n, right behind the directions') in a frame seed_width wide (default: the frame's width).  Returns a dict of
         float32 arrays: "grad" (n, dim, 3) = d u_c / d x_k, and what `want` names of "stderr" (n, dim, 3), "field" (n, 3) the
         mean of the point's walks, "radius" (n,) and "first_pts" (n, spp, dim) -- the last sized by `spp` (default: the spp the
-        integrator was made with; pass it after set_option("spp", ...))"""
+        integrator was made with; pass it after set_option("spp", ...)).  A scene with a source term is refused unless
+        set_option("grad_source", 1) was called on the integrator: then grad and stderr include the in-ball term of the
+        gradient, from spp more samples per point, and "field" the in-ball term of u"""
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
         n, S = len(p), int(self.settings.samplesPerPixel if spp is None else spp)
         unknown = set(want) - set(self.GRADIENT_OUTPUTS)
@@ -117,7 +119,9 @@ class UniformCalls:
         pixel seed_base + r * round_stride + i and walks on the streams of pixels walk_seed_base + (r * round_stride + i) *
         batch_walks + s.  round_stride defaults to n, walk_seed_base to just behind the direction seeds of the last of the
         max_rounds rounds.  A rank that holds points [a, b) of a longer list binds them with seed_base + a, walk_seed_base + a *
-        batch_walks and the round_stride of the whole list.  The list replaces the one bound before; an empty list releases it."""
+        batch_walks and the round_stride of the whole list.  The list replaces the one bound before; an empty list releases it.
+        On a scene with a source term the bind needs set_option("grad_source", 1), as solve_gradient_points does; the list keeps
+        the option's value of the bind for all its rounds."""
         fn, name = self._fn("gradient_points_carry")
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
         _check(fn(self._handle, _fp(p), *self._gradient_carry_args(len(p), batch_walks, round_stride, max_rounds, seed_base, walk_seed_base, seed_width)),

@@ -284,7 +284,8 @@ int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done);
  *     cuts a list at point a moves seed_base by a and walk_seed_base by a * S and gets the same bits.  wost_stats sums the blocks
  *     (walks_started is n * S for finite points; kernel_ms includes the two kernels around the walks); wost_last_launches
  *     describes the walks of the LAST block only.
- *   - Not covered: a scene with a source term (the in-ball term of the gradient is not built): WOST_ERR_UNSUPPORTED.  Neumann
+ *   - Not covered by default: a scene with a source term (the in-ball term of the gradient is not built into the default
+ *     estimator): WOST_ERR_UNSUPPORTED, unless the handle's option "grad_source" is 1 (below).  Neumann
  *     data needs nothing extra.  The frame's mask does not apply.  The carried frame solve, the carried point list and the options
  *     of the handle are left alone.
  *   Arguments, checked in this order before the handle is read or a device is asked for: null h / pts / out / out->grad; n < 0;
@@ -294,7 +295,42 @@ int wost_points_progress(wost_handle h, int32_t *n_points, int32_t *spp_done);
  *     n * S): WOST_ERR_INVALID, the message names the quantity.  A refused call writes no output.
  * wost_solve_gradient_points: host arrays.  wost_solve_gradient_points_dev: DEVICE arrays in pts and out, the caller's stream as
  * in wost_solve_points_dev; the call returns after the stream work has completed; a point with a non-finite coordinate is never
- * walked, all its outputs are NaN. */
+ * walked, all its outputs are NaN.
+ *
+ * The gradient on a scene with a source term (DESIGN 4.3f "The in-ball term").  For laplace(u) = -f in the ball B(x, R)
+ *     grad u(x) = (d / R) E[ n u(x + R n) ] + int_B grad_x G(x, y) f(y) dy,     u(x) = E[ u(x + R n) ] + int_B G(x, y) f(y) dy
+ * with grad_x G = (y - x) / (2 pi) (1 / r^2 - 1 / R^2), G = ln(R / r) / (2 pi) in 2-D and grad_x G = (y - x) / (4 pi) (1 / r^3 -
+ * 1 / R^3), G = (1 / r - 1 / R) / (4 pi) in 3-D.  The option "grad_source" of the handle (wost_set_option, wost3_set_option;
+ * exactly 0, the default, or 1 -- anything else is WOST_ERR_INVALID naming the key) adds the two integrals: with 0 a scene with
+ * a source term is refused as above, with 1 it is taken.  On a scene without a source term the option changes nothing: every
+ * output keeps its bits, nothing extra is drawn, allocated or launched.  The carried gradient list records the option when it
+ * is bound, and every later round uses the recorded value.  Option 1, a scene with a source term, a non-degenerate finite
+ * selected point i with radius R, S walks:
+ *   1. Walks.  Radius, directions, first points, walks and the walk part of the reduction are exactly those above: the first S
+ *     (2-D) or 2 S (3-D) draws of the stream of pixel seed_base + i are unchanged, and so are first_pts.
+ *   2. In-ball samples.  S of them, drawn from the SAME stream AFTER the direction draws.  Sample s takes, in this order, a
+ *     direction m (2-D: one float through sincos_2pi; 3-D: u1, u2 formed into m exactly as a walk's direction n above), then one
+ *     float rho in [0, 1).  Then, every line a single fp32 operation in the written order (no fused multiply-add: numpy float32
+ *     reproduces the bits):
+ *         r = rho * R;   p_k = r * m_k;   yp_k = x_k + p_k,  ym_k = x_k - p_k
+ *         fp = source(yp), fm = source(ym)      (the walk step's bilinear / trilinear grid sample, intensity included)
+ *         ds_c = 0.5f * (fp_c - fm_c),   ms_c = 0.5f * (fp_c + fm_c)
+ *         wg = 1 - rho * rho  (2-D),  1 - (rho * rho) * rho  (3-D)
+ *         wu = rho > 0 ? -(rho * logf(rho)) : 0  (2-D, the deterministic logf of the walk step),  rho - rho * rho  (3-D)
+ *     The antithetic pair yp, ym is the analogue of the sample-mean control variate: the constant part of f drops out of the
+ *     gradient term exactly.
+ *   3. Reduction, in fp64 from those fp32 values as the walk part, rounded once:  a_s,kc = wg_s m_sk ds_sc,
+ *         T_kc = (R / S) sum_s a_s,kc          seT_kc = R sqrt( sum_s (a_s - mean a)^2 / (S - 1) / S )
+ *         U_c = (R^2 / S) sum_s wu_s ms_sc
+ *         grad = (float)(grad_walk + T)     grad_stderr = (float)sqrt(se_walk^2 + seT^2)     field_rgb = (float)(mean + U)
+ *     The two parts use disjoint draws, so their variances add; field_rgb stays an estimate of u(x).
+ *   4. Excluded points.  A degenerate point takes no in-ball samples and draws none: grad and grad_stderr are NaN and field_rgb
+ *     is its mean (its walks start at x and already carry the source).  An unselected point and a point with a non-finite
+ *     coordinate behave as above.
+ *   5. Cuts and carried lists.  A cut list gives the same bits as before: per-point outputs depend only on the point's own
+ *     streams.  In a carried list a batch of round r is still row i of the single call at the round's seeds, bit for bit, in-ball
+ *     term included; the state (G, Q, F of rounded batch results) and the adaptive rule are unchanged.
+ *   6. Statistics.  walks_started and the other counters do not change; kernel_ms includes the in-ball kernel. */
 typedef struct wost_gradient_out {   /* host pointers for the host form, device pointers for the _dev form; only grad is required */
     float *grad;          /* n * DIM * 3: grad[(i*DIM + k)*3 + c] = d u_c / d x_k at point i                      */
     float *grad_stderr;   /* n * DIM * 3 or NULL: the standard error of each entry                                */
@@ -691,7 +727,9 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
  * takes together for a Neumann mesh on the tree.
  * "spp" changes samplesPerPixel of an existing handle (a pixel's first k samples do not depend on
  * the total, so solving with spp = k reproduces the state of a longer solve after k samples: the
- * host mirror uses this for saveSppMetrics frames). */
+ * host mirror uses this for saveSppMetrics frames).
+ * "grad_source" (exactly 0, the default, or 1) is no tuning knob: 1 lets the gradient calls take a scene with a source term
+ * ("The gradient on a scene with a source term" above). */
 int wost_set_option(wost_handle h, const char *key, double value);
 
 int wost_destroy(wost_handle h);
@@ -837,6 +875,9 @@ int wost3_vmm_loss_gradients(int device, const float *raw, const float *dir, con
  * out_rgb width*height*3 floats (zeros without a source term) */
 int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist);
 int wost3_render_source(wost3_handle h, float *out_rgb);
+/* The options of a 3-D handle, as wost_set_option: "grad_source" (0 / 1, the rules of wost_set_option's) is the only key; any other
+ * is WOST_ERR_INVALID "unknown option: KEY", a null handle or key WOST_ERR_INVALID "null argument". */
+int wost3_set_option(wost3_handle h, const char *key, double value);
 int wost3_destroy(wost3_handle h);
 
 /* ---- 3-D: GuidedIntegrator<3> (SURVEY.md 8a rows a21-a27 with DIM == 3) -----------------------------------------------
