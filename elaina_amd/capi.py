@@ -100,6 +100,11 @@ class GradientAdaptive(C.Structure):
     _fields_ = [("min_batches", C.c_int32), ("max_batches", C.c_int32), ("abs_tol", C.c_float), ("rel_tol", C.c_float)]
 
 
+class ExitRecords(C.Structure):
+    """wost_exit_records: host arrays of n * S entries (uv: n * S * (DIM - 1), base_rgb: n * S * 3); any may be NULL"""
+    _fields_ = [("prim", C.c_void_p), ("uv", C.c_void_p), ("side", C.c_void_p), ("thp", C.c_void_p), ("base_rgb", C.c_void_p)]
+
+
 class Mesh3Desc(C.Structure):
     """wost3_mesh_desc (include/wost.h)"""
     _fields_ = [("n_verts", C.c_int32), ("n_tris", C.c_int32), ("verts", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_int32)),
@@ -236,6 +241,15 @@ _BOTH = {
     "gradient_points_adaptive_dev": [_h, C.POINTER(GradientAdaptive), _gco, _dev, _st],
     "gradient_points_restart": [_h],
     "gradient_points_progress": [_h, _pi, _pi],
+    # the exit list (wost_exits_walk & co.)
+    "exits_walk": [_h, _pf, _i32, _i32, _i32, _i32, _st],
+    "exits_walk_dev": [_h, _dev, _i32, _i32, _i32, _i32, _dev, _st],
+    "exits_records": [_h, C.POINTER(ExitRecords)],
+    "exits_apply": [_h, _pf, _i32, _pf, _pf],
+    "exits_apply_dev": [_h, _dev, _i32, _dev, _dev, _dev],
+    "exits_adjoint": [_h, _pf, _i32, _pf],
+    "exits_adjoint_dev": [_h, _dev, _i32, _dev, _dev],
+    "exits_progress": [_h, _pi, _pi],
     # the batch queries
     "render_sdf": [_h, C.c_int, _pf],
     "render_source": [_h, _pf],

@@ -1,0 +1,138 @@
+// wost_exits.h -- the exit list of a handle (wost_exits_walk & co., include/wost.h "Exit lists"), shared by the 2-D
+// and the 3-D context: per walk the record of where it left the domain -- the absorbing primitive, its projection ratio and
+// side, the throughput and what the source and Neumann samples had added -- so that the solution for any Dirichlet data is one
+// multiply-add per walk (apply) and its derivative with respect to that data a scatter over the same records (adjoint).  A
+// dimension adds the kernel that walks (appended to wost_hip.hip / wost_hip3d.hip, on their unchanged step functions); the
+// list, the two kernels behind it and the bodies of the entry points are here and in wost_exits.hip.  Not part of the C-ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <functional>
+
+#include "../../include/wost.h"
+#include "wost_internal.h"
+
+namespace wost {
+
+// The records on the device, one array per field (a wave's lanes write neighbouring walks: coalesced), walk (i, s) at i * S + s:
+// 6 + DIM arrays of `stride` four-byte entries in one allocation -- prim, slot, side, thp, DIM - 1 of uv, three of base.  slot is
+// the primitive's place in the tree's leaf order, where the mesh tables list its vertices; prim its index in the caller's array.
+// (One pointer and the stride, not an address per array: the walk kernels hold what they are given in scalar registers to
+// their end, and they are short of those.)
+struct ExitRecords {
+    int32_t *mem = nullptr;
+    size_t stride = 0;
+    __host__ __device__ int32_t *prim() const { return mem; }
+    __host__ __device__ int32_t *slot() const { return mem + stride; }
+    __host__ __device__ int32_t *side() const { return mem + 2 * stride; }
+    __host__ __device__ float *thp() const { return reinterpret_cast<float *>(mem + 3 * stride); }
+    __host__ __device__ float *uv(int k) const { return reinterpret_cast<float *>(mem + (4 + (size_t)k) * stride); }
+    __host__ __device__ float *base(int dim, int c) const { return reinterpret_cast<float *>(mem + (3 + (size_t)dim + (size_t)c) * stride); }
+};
+
+// What a handle carries beside the carried frame solve, the carried point list and the gradient list: one allocation.
+struct ExitList {
+    void *mem = nullptr;
+    ExitRecords rec;
+    int dim = 0;
+    int32_t n = 0, S = 0;
+};
+void exits_free(ExitList &l);
+
+// One launch of a dimension's walk kernel: the `count` walks from walk `first_walk` of the list on, one lane each.  Walk w
+// belongs to point w / S of pts and runs on the stream of pixel walk_seed_base + w of a frame seed_width wide.  counters: five
+// 64-bit sums on the device (steps, started, absorbed, truncated, Neumann hits), added to.
+struct ExitWalk {
+    const float *pts;
+    int32_t first_walk, count, S, walk_seed_base, seed_width;
+    ExitRecords rec;
+    unsigned long long *counters;
+};
+
+// What the driver reads of a context, and what a dimension adds: its walk kernel with the template flags of its point solve.
+// verts: the mesh table of the vertex ids of the primitive in a slot (DIM per slot), n_verts the Dirichlet mesh's vertices
+// (0: the scene has no Dirichlet mesh).
+struct ExitCall {
+    const char *prefix;
+    int dim, device;
+    size_t n_pixels;
+    hipStream_t stream;      // the handle's own: where a host call runs
+    ExitList *list;
+    const int32_t *verts;
+    int32_t n_verts;
+    float dirichlet_intensity;
+    std::function<int(const ExitWalk &, hipStream_t)> walk;
+};
+
+// the argument rules that need no look at the handle (include/wost.h), in the order of the header
+int exits_check_walk(const void *h, const float *pts, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width);
+int exits_check_apply(const void *h, const void *in, int32_t K, const void *out, const char *in_name, const char *out_name);
+// the walk after them (n > 0): the new list, which replaces the old one when it stands whole
+int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+               hipStream_t stream, wost_stats *stats);
+int exits_records(const ExitCall &c, const wost_exit_records &out);
+int exits_apply(const ExitCall &c, const float *colors, int32_t K, float *field, float *stderr_rgb, bool on_host, hipStream_t stream);
+int exits_adjoint(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
+
+// the bodies of the entry points, written once: H is the context (device, stream, exits), `call` what a dimension adds
+template <class H>
+struct ExitCalls {
+    ExitCall (*call)(H *);
+    int dim;
+
+    static int bound(const H *h)
+    {
+        if (h->exits.n <= 0) return set_error(WOST_ERR_INVALID, "no exit list is bound to the handle (exits_walk binds one)");
+        return WOST_OK;
+    }
+    // host points travel on the handle's stream, device points on the caller's
+    int walk(H *h, const float *pts, bool pts_on_host, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width, void *stream,
+             wost_stats *stats) const
+    {
+        int rc = exits_check_walk(h, pts, n, walks, walk_seed_base, seed_width);
+        if (rc == WOST_OK && pts_on_host) rc = check_points_finite(pts, n, dim);
+        if (rc != WOST_OK) return rc;
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        if (n == 0) {
+            if (h->exits.mem) {
+                WOST_TRY(hipSetDevice(h->device));
+                exits_free(h->exits);
+            }
+            return WOST_OK;
+        }
+        return exits_walk(call(h), pts, pts_on_host, n, walks, walk_seed_base, seed_width,
+                          pts_on_host ? h->stream : reinterpret_cast<hipStream_t>(stream), stats);
+    }
+    int records(H *h, const wost_exit_records *out) const
+    {
+        if (!h || !out) return set_error(WOST_ERR_INVALID, "null argument");
+        const int rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return exits_records(call(h), *out);
+    }
+    int apply(H *h, const float *colors, int32_t K, float *field, float *stderr_rgb, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, colors, K, field, "colors", "field_rgb");
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return exits_apply(call(h), colors, K, field, stderr_rgb, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int adjoint(H *h, const float *dfield, int32_t K, float *dcolors, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, dfield, K, dcolors, "dfield", "dcolors");
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        return exits_adjoint(call(h), dfield, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int progress(H *h, int32_t *n_points, int32_t *walks) const
+    {
+        if (!h || !n_points || !walks) return set_error(WOST_ERR_INVALID, "null argument");
+        *n_points = h->exits.n;
+        *walks = h->exits.S;
+        return WOST_OK;
+    }
+};
+
+}  // namespace wost

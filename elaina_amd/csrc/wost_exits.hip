@@ -1,0 +1,416 @@
+// wost_exits.hip -- the exit list of a handle (wost_exits.h; include/wost.h "Exit lists"): the two kernels behind
+// the walks -- apply, one wave per point over its records for K sets of Dirichlet colours, and the adjoint, a scatter of fp64
+// atomic adds over the same records -- and the driver: the list in chunks of n_pixels walks, the records into host arrays, the
+// host and device forms of apply and adjoint.  Cold path beside the walk kernels, which do not know of it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "wost_exits.h"
+#include "wost_grad.h"
+
+namespace wost {
+
+#define WOST_NAN __int_as_float(0x7fc00000)
+
+// ---- one record against one set of colours ----------------------------------------------------------------------------------
+// A record as a lane holds it: slot < 0 is a walk that was not absorbed (W = base).
+template <int DIM>
+struct ExitRec {
+    int32_t slot, side;
+    float uv[DIM - 1], thp, base[3];
+    int32_t v[DIM];
+};
+
+template <int DIM>
+__device__ __forceinline__ ExitRec<DIM> exit_load(const ExitRecords &r, const int32_t *verts, size_t w)
+{
+    ExitRec<DIM> e;
+    e.slot = r.slot()[w];
+    e.side = r.side()[w];
+#pragma unroll
+    for (int k = 0; k < DIM - 1; ++k) e.uv[k] = r.uv(k)[w];
+    e.thp = r.thp()[w];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e.base[c] = r.base(DIM, c)[w];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) e.v[k] = e.slot >= 0 ? verts[(size_t)DIM * e.slot + k] : 0;
+    return e;
+}
+
+// the weights of the primitive's vertices, with the operations of surface_color (1 - uv, uv) and surface_color3 (1 - u - v, u, v)
+template <int DIM>
+__device__ __forceinline__ void exit_weights(const ExitRec<DIM> &e, float (&wgt)[DIM])
+{
+    if (DIM == 2) {
+        wgt[0] = 1 - e.uv[0];
+        wgt[1] = e.uv[0];
+    } else {
+        wgt[0] = 1 - e.uv[0] - e.uv[DIM - 2];
+        wgt[1] = e.uv[0];
+        wgt[DIM - 1] = e.uv[DIM - 2];
+    }
+}
+
+// W of the walk for one set of colours (n_verts * 6), channel by channel: the colour of surface_color / surface_color3, times
+// the intensity, times the throughput, plus base -- every line one fp32 operation, as the walk step has them
+template <int DIM>
+__device__ __forceinline__ void exit_value(const ExitRec<DIM> &e, const float *colors, float intensity, float (&W)[3])
+{
+    if (e.slot < 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W[c] = e.base[c];
+        return;
+    }
+    float wgt[DIM];
+    exit_weights<DIM>(e, wgt);
+    const int off = (e.side >= 0) ? 0 : 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = colors[6 * (size_t)e.v[0] + off + c], b = colors[6 * (size_t)e.v[1] + off + c];
+        float col;
+        if (DIM == 2) {
+            col = a * wgt[0] + b * wgt[1];
+        } else {
+            const float cc = colors[6 * (size_t)e.v[DIM - 1] + off + c];
+            col = (a * wgt[0] + b * wgt[1]) + cc * wgt[DIM - 1];
+        }
+        col *= intensity;
+        col *= e.thp;
+        W[c] = col + e.base[c];
+    }
+}
+
+// ---- apply ------------------------------------------------------------------------------------------------------------------
+struct ExitApplyParams {
+    ExitRecords rec;
+    const int32_t *verts;
+    const float *colors;     // K sets of n_verts * 6
+    int32_t n, S, K, n_verts;
+    float intensity;
+    float *field, *se;       // K * n * 3 each; se may be nullptr
+};
+
+// One wave per point, its lanes over the point's S walks, per set two passes in fp64 over the fp32 W (the mean, the two-pass
+// variance), rounded once.  A lane keeps the record of its first walk in registers for all K sets -- with S <= 64 every record
+// is read once --; the walks beyond the first 64 of a point are read again per set (from the cache: a point's records are
+// S * 36 bytes).
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_apply_kernel(ExitApplyParams P)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= P.n) return;      // (the whole wave)
+    const int S = P.S;
+    const size_t w0 = (size_t)i * S;
+    ExitRec<DIM> first{};
+    first.slot = -1;
+    if (lane < S) first = exit_load<DIM>(P.rec, P.verts, w0 + lane);
+    const double dS = (double)S;
+    for (int k = 0; k < P.K; ++k) {
+        const float *colors = P.colors + (size_t)k * P.n_verts * 6;
+        double mean[3] = {0.0, 0.0, 0.0}, var[3] = {0.0, 0.0, 0.0};
+        for (int s = lane; s < S; s += 64) {
+            float W[3];
+            exit_value<DIM>(s == lane ? first : exit_load<DIM>(P.rec, P.verts, w0 + s), colors, P.intensity, W);
+            for (int c = 0; c < 3; ++c) mean[c] += (double)W[c];
+        }
+        for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
+        if (P.se) {
+            for (int s = lane; s < S; s += 64) {
+                float W[3];
+                exit_value<DIM>(s == lane ? first : exit_load<DIM>(P.rec, P.verts, w0 + s), colors, P.intensity, W);
+                for (int c = 0; c < 3; ++c) {
+                    const double dev = (double)W[c] - mean[c];
+                    var[c] += dev * dev;
+                }
+            }
+            for (int c = 0; c < 3; ++c) var[c] = wave_sum(var[c]);
+        }
+        if (lane == 0) {
+            const size_t o = ((size_t)k * P.n + i) * 3;
+            for (int c = 0; c < 3; ++c) {
+                P.field[o + c] = (float)mean[c];
+                if (P.se) P.se[o + c] = S > 1 ? (float)sqrt(var[c] / (dS - 1.0) / dS) : __builtin_inff();
+            }
+        }
+    }
+}
+
+// ---- adjoint ----------------------------------------------------------------------------------------------------------------
+struct ExitAdjointParams {
+    ExitRecords rec;
+    const int32_t *verts;
+    const float *dfield;     // K * n * 3
+    int32_t n, S, K, n_verts;
+    float intensity;
+    double *acc;             // K * n_verts * 6, zeroed
+};
+
+// One lane per walk.  An absorbed walk (i, s) adds, per set, channel and vertex of its primitive, the term
+// (dfield[k][i][c] / S) * intensity * thp * w_v -- fp64 from the fp32 operands, multiplied in this order -- to the entry of that
+// vertex and side, by an fp64 atomic add: the order of the sum is the arrival order.
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_adjoint_kernel(ExitAdjointParams P)
+{
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= (size_t)P.n * P.S) return;
+    const ExitRec<DIM> e = exit_load<DIM>(P.rec, P.verts, w);
+    if (e.slot < 0) return;
+    float wgt[DIM];
+    exit_weights<DIM>(e, wgt);
+    const int off = (e.side >= 0) ? 0 : 3;
+    const size_t i = w / (size_t)P.S;
+    for (int k = 0; k < P.K; ++k) {
+        double *acc = P.acc + (size_t)k * P.n_verts * 6;
+        for (int c = 0; c < 3; ++c) {
+            const double g = (double)P.dfield[((size_t)k * P.n + i) * 3 + c] / (double)P.S * (double)P.intensity * (double)e.thp;
+#pragma unroll
+            for (int v = 0; v < DIM; ++v) atomicAdd(acc + 6 * (size_t)e.v[v] + off + c, g * (double)wgt[v]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void exits_round_kernel(const double *acc, float *out, size_t count)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < count) out[j] = (float)acc[j];
+}
+
+// ---- the driver -------------------------------------------------------------------------------------------------------------
+void exits_free(ExitList &l)
+{
+    if (l.mem) (void)hipFree(l.mem);
+    l = ExitList{};
+}
+
+// a device allocation that may fail for want of memory: WOST_ERR_NOMEM then, WOST_ERR_DEVICE for anything else
+static int exits_alloc(void **p, size_t bytes, const char *what)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return set_error(WOST_ERR_NOMEM, std::string("out of device memory for ") + what + " (" + std::to_string(bytes) + " bytes)");
+    }
+    WOST_TRY_AS("hipMalloc", e);
+    return WOST_OK;
+}
+
+// a device array of `count` floats that the batch of a host call owns (never empty: a scene without a Dirichlet mesh has no colours)
+static int exits_stage(Batch &b, float **dev, size_t count, const char *what)
+{
+    void *p = nullptr;
+    const int rc = exits_alloc(&p, count * sizeof(float) + 16, what);
+    if (rc != WOST_OK) return rc;
+    b.scratch.ptrs.push_back(p);
+    *dev = static_cast<float *>(p);
+    return WOST_OK;
+}
+
+// the arrays of a list of N walks, carved from one allocation: prim, slot, side, thp, DIM - 1 of uv and three of base, four
+// bytes an entry
+static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S)
+{
+    const size_t N = (size_t)n * S;
+    const int rc = exits_alloc(&l.mem, N * (size_t)(6 + dim) * 4, "the exit list");
+    if (rc != WOST_OK) return rc;
+    l.rec = ExitRecords{static_cast<int32_t *>(l.mem), N};
+    l.dim = dim; l.n = n; l.S = S;
+    return WOST_OK;
+}
+
+int exits_check_walk(const void *h, const float *pts, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    if (n < 0) return set_error(WOST_ERR_INVALID, "negative number of points");
+    if (n > 0 && !pts) return set_error(WOST_ERR_INVALID, "null argument");
+    if (walks < 1) return set_error(WOST_ERR_INVALID, "walks must be at least 1");
+    if (seed_width <= 0) return set_error(WOST_ERR_INVALID, "seed_width must be positive");
+    if (walk_seed_base < 0) return set_error(WOST_ERR_INVALID, "walk_seed_base must be >= 0");
+    const int64_t end = (int64_t)walk_seed_base + (int64_t)n * walks;
+    if (end > ((int64_t)1 << 28))
+        return set_error(WOST_ERR_INVALID, "walk_seed_base + n * walks (" + std::to_string(end) + ") must be at most 2^28");
+    return WOST_OK;
+}
+
+int exits_check_apply(const void *h, const void *in, int32_t K, const void *out, const char *in_name, const char *out_name)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    if (!in) return set_error(WOST_ERR_INVALID, std::string("null argument: ") + in_name);
+    if (!out) return set_error(WOST_ERR_INVALID, std::string("null argument: ") + out_name);
+    if (K < 1) return set_error(WOST_ERR_INVALID, "K must be at least 1");
+    return WOST_OK;
+}
+
+namespace {
+// two events of a call, destroyed on every return path
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+// the new list of a walk until it stands whole: freed on every other return path
+struct ListGuard {
+    ExitList l;
+    ~ListGuard() { exits_free(l); }
+};
+}  // namespace
+
+int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+               hipStream_t stream, wost_stats *stats)
+{
+    const auto t0 = HostClock::now();
+    WOST_TRY(hipSetDevice(c.device));
+    ListGuard fresh;
+    int rc = exits_carve(fresh.l, c.dim, n, walks);
+    if (rc != WOST_OK) return rc;
+    Scratch scratch;
+    void *d_pts = nullptr, *d_counters = nullptr;
+    if ((rc = exits_alloc(&d_counters, 5 * sizeof(unsigned long long), "the counters of the walk")) != WOST_OK) return rc;
+    scratch.ptrs.push_back(d_counters);
+    if (pts_on_host) {
+        const size_t bytes = (size_t)n * c.dim * sizeof(float);
+        if ((rc = exits_alloc(&d_pts, bytes, "the points")) != WOST_OK) return rc;
+        scratch.ptrs.push_back(d_pts);
+        WOST_TRY(hipMemcpyAsync(d_pts, pts, bytes, hipMemcpyHostToDevice, stream));
+    }
+    EventPair ev;
+    WOST_TRY(hipEventCreate(&ev.a));
+    WOST_TRY(hipEventCreate(&ev.b));
+    WOST_TRY(hipMemsetAsync(d_counters, 0, 5 * sizeof(unsigned long long), stream));
+    WOST_TRY(hipEventRecord(ev.a, stream));
+    const int64_t N = (int64_t)n * walks, cap = (int64_t)std::min<size_t>(c.n_pixels, (size_t)1 << 28);
+    uint32_t launches = 0;
+    for (int64_t a = 0; a < N; a += cap, ++launches) {
+        const ExitWalk w{pts_on_host ? static_cast<const float *>(d_pts) : pts, (int32_t)a, (int32_t)std::min(cap, N - a), walks, walk_seed_base, seed_width,
+                         fresh.l.rec, static_cast<unsigned long long *>(d_counters)};
+        if ((rc = c.walk(w, stream)) != WOST_OK) {
+            (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+            return rc;
+        }
+    }
+    WOST_TRY(hipEventRecord(ev.b, stream));
+    unsigned long long counters[5] = {0, 0, 0, 0, 0};
+    WOST_TRY(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, stream));
+    WOST_TRY(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    WOST_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    exits_free(*c.list);
+    *c.list = fresh.l;
+    fresh.l = ExitList{};
+    if (stats) {
+        stats->walk_steps = counters[0]; stats->walks_started = counters[1]; stats->walks_absorbed = counters[2];
+        stats->walks_truncated = counters[3]; stats->neumann_hits = counters[4];
+        stats->kernel_ms = ms;
+        stats->kernel_launches = launches;
+        stamp_solve_ms(stats, t0);
+    }
+    return WOST_OK;
+}
+
+int exits_records(const ExitCall &c, const wost_exit_records &out)
+{
+    WOST_TRY(hipSetDevice(c.device));
+    const ExitList &l = *c.list;
+    const size_t N = (size_t)l.n * l.S, uvs = (size_t)l.dim - 1;
+    // uv and base are interleaved per walk for the caller: fetched array by array and woven on the host
+    std::vector<float> uv(out.uv ? N * uvs : 0), base(out.base_rgb ? N * 3 : 0);
+    if (out.prim) WOST_TRY(hipMemcpyAsync(out.prim, l.rec.prim(), N * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out.side) WOST_TRY(hipMemcpyAsync(out.side, l.rec.side(), N * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out.thp) WOST_TRY(hipMemcpyAsync(out.thp, l.rec.thp(), N * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out.uv) WOST_TRY(hipMemcpyAsync(uv.data(), l.rec.uv(0), N * uvs * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out.base_rgb) WOST_TRY(hipMemcpyAsync(base.data(), l.rec.base(l.dim, 0), N * 3 * 4, hipMemcpyDeviceToHost, c.stream));
+    WOST_TRY(hipStreamSynchronize(c.stream));
+    if (out.uv)
+        for (size_t w = 0; w < N; ++w)
+            for (size_t k = 0; k < uvs; ++k) out.uv[w * uvs + k] = uv[k * N + w];
+    if (out.base_rgb)
+        for (size_t w = 0; w < N; ++w)
+            for (size_t k = 0; k < 3; ++k) out.base_rgb[w * 3 + k] = base[k * N + w];
+    return WOST_OK;
+}
+
+static int exits_apply_dev(const ExitCall &c, const float *colors, int32_t K, float *field, float *se, hipStream_t stream)
+{
+    const ExitList &l = *c.list;
+    const ExitApplyParams P{l.rec, c.verts, colors, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, field, se};
+    const dim3 grid((unsigned)((l.n + 3) / 4));
+    if (c.dim == 2) hipLaunchKernelGGL(exits_apply_kernel<2>, grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(exits_apply_kernel<3>, grid, dim3(256), 0, stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+int exits_apply(const ExitCall &c, const float *colors, int32_t K, float *field, float *stderr_rgb, bool on_host, hipStream_t stream)
+{
+    WOST_TRY(hipSetDevice(c.device));
+    const size_t n_colors = (size_t)K * c.n_verts * 6, n_field = (size_t)K * c.list->n * 3;
+    if (!on_host) {
+        const int rc = exits_apply_dev(c, colors, K, field, stderr_rgb, stream);
+        if (rc != WOST_OK) return rc;
+        WOST_TRY(hipStreamSynchronize(stream));
+        return WOST_OK;
+    }
+    Batch b{stream};
+    float *d_colors = nullptr, *d_field = nullptr, *d_se = nullptr;
+    int rc = exits_stage(b, &d_colors, n_colors, "the colours");
+    if (rc == WOST_OK) rc = exits_stage(b, &d_field, n_field, "the field");
+    if (rc == WOST_OK && stderr_rgb) rc = exits_stage(b, &d_se, n_field, "the standard errors");
+    if (rc != WOST_OK) return rc;
+    WOST_TRY(hipMemcpyAsync(d_colors, colors, n_colors * sizeof(float), hipMemcpyHostToDevice, stream));
+    rc = exits_apply_dev(c, d_colors, K, d_field, d_se, stream);
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    WOST_TRY(b.fetch(field, d_field, n_field));
+    WOST_TRY(b.fetch(stderr_rgb, d_se, n_field));
+    return b.finish();
+}
+
+int exits_adjoint(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream)
+{
+    if (c.n_verts <= 0)
+        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_adjoint: the scene has no Dirichlet mesh, so there are no colours to differentiate by");
+    WOST_TRY(hipSetDevice(c.device));
+    const ExitList &l = *c.list;
+    const size_t n_colors = (size_t)K * c.n_verts * 6, n_field = (size_t)K * l.n * 3, N = (size_t)l.n * l.S;
+    Batch b{stream};
+    void *acc = nullptr;
+    int rc = exits_alloc(&acc, n_colors * sizeof(double), "the fp64 sums of the adjoint");
+    if (rc != WOST_OK) return rc;
+    b.scratch.ptrs.push_back(acc);
+    const float *d_dfield = dfield;
+    float *d_out = dcolors;
+    if (on_host) {
+        float *in = nullptr;
+        if ((rc = exits_stage(b, &in, n_field, "dfield")) != WOST_OK || (rc = exits_stage(b, &d_out, n_colors, "dcolors")) != WOST_OK) return rc;
+        WOST_TRY(hipMemcpyAsync(in, dfield, n_field * sizeof(float), hipMemcpyHostToDevice, stream));
+        d_dfield = in;
+    }
+    WOST_TRY(hipMemsetAsync(acc, 0, n_colors * sizeof(double), stream));
+    const ExitAdjointParams P{l.rec, c.verts, d_dfield, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, static_cast<double *>(acc)};
+    const dim3 grid((unsigned)((N + 255) / 256));
+    if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_kernel<2>, grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(exits_adjoint_kernel<3>, grid, dim3(256), 0, stream, P);
+    rc = hipGetLastError() == hipSuccess ? WOST_OK : set_error(WOST_ERR_DEVICE, "the adjoint kernel could not be launched");
+    if (rc == WOST_OK) {
+        hipLaunchKernelGGL(exits_round_kernel, dim3((unsigned)((n_colors + 255) / 256)), dim3(256), 0, stream, static_cast<const double *>(acc), d_out, n_colors);
+        if (hipGetLastError() != hipSuccess) rc = set_error(WOST_ERR_DEVICE, "the rounding kernel of the adjoint could not be launched");
+    }
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    if (on_host) WOST_TRY(b.fetch(dcolors, d_out, n_colors));
+    return b.finish();
+}
+
+}  // namespace wost

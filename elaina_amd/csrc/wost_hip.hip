@@ -1278,6 +1278,7 @@ static int fill_ctx(wost_context *c, const wost_scene_desc &scene)
     if (rc == WOST_OK) rc = upload_mesh(scene.neumann, c->nm);
     if (rc == WOST_OK) rc = upload_mask(c, scene.mask);
     if (rc != WOST_OK) return rc;
+    c->dirichlet_verts = scene.dirichlet.n_segs > 0 ? scene.dirichlet.n_verts : 0;
     if (scene.source.nx > 0 && scene.source.ny > 0) {
         const wost_source_desc &sd = scene.source;
         if (!sd.rgb) return set_error(WOST_ERR_INVALID, "source grid without data");
@@ -2226,5 +2227,199 @@ int wost_ray_intersect(wost_handle h, int which_mesh, const float *origins, cons
 {
     return query_ray_intersect<Query2>(h, which_mesh, origins, dirs, tmax, n, out_hit, out_t, out_idx);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// the exit list (wost_exits_walk & co.; the list, apply and adjoint: wost_exits.hip; the bodies of the entry points: ExitCalls)
+// ------------------------------------------------------------------------------------------
+namespace wost {
+
+struct ExitWalkParams {
+    DevMesh dm, nm;
+    DevSettings st;      // (spp: 1)
+    DevSource src;
+    ExitWalk w;
+    int32_t stack_stride;
+};
+
+// One lane per walk, in lock step to the walk's end: the depth-0 query as init_points_kernel makes it (the far-point scan
+// included), every later query seeded with the lane's hint as the round kernels seed it -- the plain visits within dm.far2, the
+// slack ones beyond, the scan by the wave beyond dm.huge2 --, and between two queries the unchanged step_finish with the flags
+// of the handle's point solve, not chained.  So walk w takes the steps of wost_solve_points of one sample at its point on the
+// stream of pixel walk_seed_base + w, bit for bit; the lane keeps the throughput and the sums as they stood before each step,
+// and when the step absorbs -- L.hint the slot, L.px, L.py still the absorbed position -- it forms uv and side again with the
+// step's own expressions and writes the record.  Cold path beside the scheduled kernels: no queue, no rounds.
+template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE>
+__global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
+{
+    extern __shared__ uint32_t lds_stack[];
+    uint32_t *stack = lds_stack + threadIdx.x;
+    const LdsColumn stk{stack, (uint32_t)P.stack_stride};
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool owned = t < P.w.count;
+    const int32_t w = P.w.first_walk + (owned ? t : 0);
+    const bool has_d = P.dm.n_segs > 0;
+    float x0 = 0, y0 = 0;
+    if (owned) {
+        const size_t i = (size_t)(w / P.w.S);
+        x0 = P.w.pts[2 * i];
+        y0 = P.w.pts[2 * i + 1];
+    }
+    const bool finite = isfinite(x0) && isfinite(y0);
+    bool alive = owned && finite;
+    Lane L{};
+    L.rng = Pcg{0, 1};
+    Closest cp{WOST_INF, -1};
+    bool huge = false;
+    if (alive) {
+        pcg_seed_pixel(L.rng, P.w.walk_seed_base + w, P.w.seed_width);
+        if (has_d) {
+            cp = slot_candidate(P.dm, 0, x0, y0);
+            huge = cp.d2 > P.dm.huge2;
+            if (!huge) cp = closest_point(P.dm, x0, y0, cp, stack, P.stack_stride);
+        }
+    }
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_point_wave(P.dm, __shfl(x0, src), __shfl(y0, src));
+        if ((int)(threadIdx.x & 63) == src) cp = r;
+        hb &= hb - 1;
+    }
+    L.x0 = x0; L.y0 = y0; L.px = x0; L.py = y0;
+    L.hint = cp.slot;
+    L.thp = 1.0f;
+    L.d0_d2 = cp.d2; L.d0_slot = cp.slot;
+    // the record: a walk that is not absorbed keeps slot -1 and its final sums, a point that is not finite NaN
+    int32_t slot = -1, side = 0;
+    float uv = finite ? 0.0f : __int_as_float(0x7fc00000), thp = uv, br = uv, bg = uv, bb = uv;
+    uint32_t c_steps = 0, c_absorbed = 0, c_truncated = 0, c_nhits = 0;
+    const uint32_t c_started = alive ? 1u : 0u;
+    while (__ballot(alive)) {
+        if (alive) {
+            thp = L.thp; br = L.sr; bg = L.sg; bb = L.sb;
+            ++c_steps;
+            const uint32_t status = step_finish<NEUMANN_EMISSIVE, NEUMANN_TREE, SOURCE>(P.dm, P.nm, P.st, L, cp, stk, P.src, false);
+            c_absorbed += (status >> 1) & 1u;
+            c_truncated += (status >> 2) & 1u;
+            c_nhits += (status >> 3) & 1u;
+            if (status & STEP_ABSORBED) {
+                slot = L.hint;
+                const float4 a = P.dm.segA[slot];
+                const float inv = P.dm.segInv[slot];
+                const float wx = L.px - a.x, wy = L.py - a.y;
+                uv = dot2(wx, wy, a.z, a.w) * inv;
+                const float cr = cross2(a.z, a.w, wx, wy);
+                side = (0.0f < cr) - (cr < 0.0f);
+            } else if (status & STEP_ENDED) {
+                thp = L.thp; br = L.sr; bg = L.sg; bb = L.sb;
+            }
+            if (status & STEP_ENDED) alive = false;
+        }
+        huge = false;
+        if (alive && has_d) {
+            cp = slot_candidate(P.dm, L.hint, L.px, L.py);
+            if (cp.d2 > P.dm.huge2) {
+                huge = true;
+            } else {
+                Trav T = trav_begin(cp);
+                if (cp.d2 > P.dm.far2) {
+                    while (trav_visit<true>(P.dm, L.px, L.py, T, stk)) {
+                    }
+                } else {
+                    while (trav_visit<false>(P.dm, L.px, L.py, T, stk)) {
+                    }
+                }
+                cp = T.best;
+            }
+        }
+        hb = __ballot(huge);
+        while (hb) {
+            const int src = __builtin_ctzll(hb);
+            const Closest r = closest_point_wave(P.dm, __shfl(L.px, src), __shfl(L.py, src));
+            if ((int)(threadIdx.x & 63) == src) cp = r;
+            hb &= hb - 1;
+        }
+    }
+    if (owned) {
+        const ExitRecords &R = P.w.rec;
+        R.prim()[w] = slot >= 0 ? P.dm.segOrig[slot] : -1;
+        R.slot()[w] = slot;
+        R.side()[w] = side;
+        R.uv(0)[w] = uv;
+        R.thp()[w] = thp;
+        R.base(2, 0)[w] = br; R.base(2, 1)[w] = bg; R.base(2, 2)[w] = bb;
+    }
+    uint32_t v[5] = {c_steps, c_started, c_absorbed, c_truncated, c_nhits};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        uint32_t x = v[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+        if ((threadIdx.x & 63) == 0 && x) atomicAdd(P.w.counters + k, (unsigned long long)x);
+    }
+}
+
+}  // namespace wost
+
+// what the 2-D context adds: the walk kernel on its meshes and source, with the flags of its point solve (launch_walk)
+static ExitCall exit_call(wost_context *c)
+{
+    ExitCall e{"wost_", 2, c->device, c->n_pixels, c->stream, &c->exits, reinterpret_cast<const int32_t *>(c->dm.view.segVerts), c->dirichlet_verts,
+               c->dst.dirichlet_intensity, nullptr};
+    e.walk = [c](const ExitWalk &w, hipStream_t stream) {
+        const LaunchGeometry g = launch_geometry(c);
+        ExitWalkParams P{c->dm.view, c->nm.view, c->dst, c->src, w, 256};
+        P.st.spp = 1;
+        const dim3 grid((unsigned)((w.count + 255) / 256));
+        const size_t lds = (size_t)g.stack_depth * 256 * sizeof(uint32_t);
+        auto launch = [&](auto E, auto T, auto S) {
+            hipLaunchKernelGGL((exits2_kernel<decltype(E)::value, decltype(T)::value, decltype(S)::value>), grid, dim3(256), lds, stream, P);
+        };
+        auto with_src = [&](auto E, auto T) { g.has_src ? launch(E, T, std::true_type{}) : launch(E, T, std::false_type{}); };
+        auto with_tree = [&](auto E) { g.ntree ? with_src(E, std::true_type{}) : with_src(E, std::false_type{}); };
+        g.emissive ? with_tree(std::true_type{}) : with_tree(std::false_type{});
+        WOST_TRY(hipGetLastError());
+        return WOST_OK;
+    };
+    return e;
+}
+
+static const ExitCalls<wost_context> kExits{exit_call, 2};
+
+extern "C" {
+
+int wost_exits_walk(wost_handle h, const float *pts_xy, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width, wost_stats *stats)
+{
+    return kExits.walk(h, pts_xy, true, n, walks, walk_seed_base, seed_width, nullptr, stats);
+}
+
+int wost_exits_walk_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width, void *stream,
+                        wost_stats *stats)
+{
+    return kExits.walk(h, pts_xy_dev, false, n, walks, walk_seed_base, seed_width, stream, stats);
+}
+
+int wost_exits_records(wost_handle h, const wost_exit_records *out) { return kExits.records(h, out); }
+
+int wost_exits_apply(wost_handle h, const float *colors, int32_t K, float *field_rgb, float *stderr_rgb)
+{
+    return kExits.apply(h, colors, K, field_rgb, stderr_rgb, true, nullptr);
+}
+
+int wost_exits_apply_dev(wost_handle h, const float *colors_dev, int32_t K, float *field_rgb_dev, float *stderr_rgb_dev, void *stream)
+{
+    return kExits.apply(h, colors_dev, K, field_rgb_dev, stderr_rgb_dev, false, stream);
+}
+
+int wost_exits_adjoint(wost_handle h, const float *dfield, int32_t K, float *dcolors) { return kExits.adjoint(h, dfield, K, dcolors, true, nullptr); }
+
+int wost_exits_adjoint_dev(wost_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits.adjoint(h, dfield_dev, K, dcolors_dev, false, stream);
+}
+
+int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks) { return kExits.progress(h, n_points, walks); }
 
 }  // extern "C"

@@ -957,6 +957,7 @@ static int fill3(wost3_context *c, const wost3_scene_desc &scene)
     if (rc == WOST_OK) rc = upload_mesh3(scene.neumann, c->nm);
     if (rc == WOST_OK) rc = upload_mask(c, scene.mask);
     if (rc != WOST_OK) return rc;
+    c->dirichlet_verts = scene.dirichlet.n_tris > 0 ? scene.dirichlet.n_verts : 0;
     if (scene.source.nx > 0) {
         const wost3_source_desc &sd = scene.source;
         if (sd.ny <= 0 || sd.nz <= 0 || !sd.rgb) return set_error(WOST_ERR_INVALID, "source grid: bad size or null samples");
@@ -1202,5 +1203,206 @@ int wost3_ray_intersect(wost3_handle h, int which_mesh, const float *origins, co
 {
     return query_ray_intersect<Query3>(h, which_mesh, origins, dirs, tmax, n, out_hit, out_t, out_idx);
 }
+
+}  // extern "C"
+
+// ---- the exit list (wost3_exits_walk & co.; the list, apply and adjoint: wost_exits.hip; the bodies of the entry points: ExitCalls) ----
+namespace wost {
+
+struct ExitWalk3Params {
+    Walk3Params P;       // the scene and the settings as step3 reads them (spp: 1); nothing of the frame, the queue or the carry
+    ExitWalk w;
+};
+
+// One lane per walk, in lock step to the walk's end, as exits2_kernel: the depth-0 query without a hint -- the scan by the wave
+// where the boxes of the root's children all lie beyond dm.huge2, the descent otherwise (depth0_distance3 of the gradient's
+// kernel in front makes the same choice; both answers are exact, lowest original index among equal distances) --, every later
+// query seeded with the lane's hint as walk3_kernel's begin_step seeds it, and between two queries the unchanged step3 with the
+// flags of the handle's point solve.  When step3_a absorbs (the lane's absorbed count moves; L.hint is the slot, L.p still the
+// absorbed position) the lane forms side, u and v again with the step's own expressions and writes the record.
+// (One wave per SIMD asked for, as walk3_kernel: the instantiations take 114 to 133 registers.  The cap of 100 scalar registers:
+// with the default of 102 the instantiation with every flag set keeps a private segment of 36 bytes per lane for scalar spills
+// that end up in register lanes -- never addressed, but reserved per lane at launch; under the cap every instantiation reports
+// none, for 4 to 37 more scalar spills to lanes.)
+template <bool EMISSIVE, bool SOURCE, bool NTREE>
+__global__ __launch_bounds__(kWalk3Threads, 1) __attribute__((amdgpu_num_sgpr(100))) void exits3_kernel(ExitWalk3Params X)
+{
+    extern __shared__ uint32_t lds_stack[];
+    const LdsColumn stk(lds_stack + threadIdx.x, blockDim.x);
+    const Walk3Params &P = X.P;
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool owned = t < X.w.count;
+    const int32_t w = X.w.first_walk + (owned ? t : 0);
+    const bool has_d = P.dm.n_tris > 0;
+    V3 q = v3(0.0f, 0.0f, 0.0f);
+    if (owned) q = ld3(X.w.pts + 3 * (size_t)(w / X.w.S));
+    const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    bool alive = owned && finite;
+    Lane3 L{};
+    L.rng = Pcg{0, 1};
+    if (alive) pcg_seed_pixel(L.rng, X.w.walk_seed_base + w, X.w.seed_width);
+    L.p_eval = q; L.p = q;
+    L.thp = 1.0f;
+    L.hint = L.hint0 = -1;
+    L.c_started = alive ? 1u : 0u;
+    // the record: a walk that is not absorbed keeps slot -1 and its final sums, a point that is not finite NaN
+    int32_t slot = -1, side = 0;
+    float u = finite ? 0.0f : __int_as_float(0x7fc00000), v = u, thp = u, base[3] = {u, u, u};
+    // ---- the closest Dirichlet triangle of the evaluation point: no hint ----
+    Trav T = trav_begin(Closest{WOST_INF, -1});
+    bool huge = false;
+    if (alive && has_d) {
+        const float4 LX = P.dm.nodes[0], LY = P.dm.nodes[1], LZ = P.dm.nodes[2], HX = P.dm.nodes[3], HY = P.dm.nodes[4], HZ = P.dm.nodes[5];
+        const float d0 = aabb_d2(LX.x, LY.x, LZ.x, HX.x, HY.x, HZ.x, q), d1 = aabb_d2(LX.y, LY.y, LZ.y, HX.y, HY.y, HZ.y, q);
+        const float d2 = aabb_d2(LX.z, LY.z, LZ.z, HX.z, HY.z, HZ.z, q), d3 = aabb_d2(LX.w, LY.w, LZ.w, HX.w, HY.w, HZ.w, q);
+        huge = fminf(fminf(d0, d1), fminf(d2, d3)) > P.dm.huge2;
+        if (!huge) {
+            while (trav_visit3(P.dm, q, T, stk)) {
+            }
+        }
+    }
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_triangle_wave(P.dm, v3(__shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src)));
+        if (lane == src) T.best = r;
+        hb &= hb - 1;
+    }
+    while (__ballot(alive)) {
+        // ---- the step ----
+        if (alive) {
+            thp = L.thp;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) base[k] = L.sol[k];
+            ++L.c_steps;
+            const uint32_t absorbed_before = L.c_absorbed;
+            bool ended = step3<EMISSIVE, SOURCE, NTREE>(P, L, T.best, stk);
+            if (L.c_absorbed != absorbed_before) {
+                slot = L.hint;
+                const float4 a = P.dm.tri[3 * (size_t)slot], b = P.dm.tri[3 * (size_t)slot + 1], c = P.dm.tri[3 * (size_t)slot + 2];
+                const V3 p0 = v3(a.x, a.y, a.z), e0 = v3(b.x, b.y, b.z) - p0, e1 = v3(c.x, c.y, c.z) - p0;
+                side = tri_side(p0, cross3(e0, e1), L.p);
+                tri_uv(p0, e0, e1, L.p, u, v);
+            } else {
+                if (!ended) {
+                    ++L.depth;
+                    if (L.depth == P.st.max_depth) {
+                        ++L.c_truncated;
+                        ended = true;
+                    }
+                }
+                if (ended) {
+                    thp = L.thp;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) base[k] = L.sol[k];
+                }
+            }
+            if (ended) alive = false;
+        }
+        // ---- the closest Dirichlet triangle of the next point, seeded with the hint as begin_step seeds it ----
+        T = trav_begin(Closest{WOST_INF, -1});
+        huge = false;
+        if (alive && has_d) {
+            if (L.hint >= 0 && P.dm.triOrig[L.hint] != WOST_FAR_INDEX) {
+                const float4 a = P.dm.tri[3 * (size_t)L.hint], b = P.dm.tri[3 * (size_t)L.hint + 1], c = P.dm.tri[3 * (size_t)L.hint + 2];
+                T.best = Closest{tri_d2(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), L.p), L.hint};
+                T.best_orig = P.dm.triOrig[L.hint];
+                huge = T.best.d2 > P.dm.huge2;
+            }
+            if (!huge) {
+                while (trav_visit3(P.dm, L.p, T, stk)) {
+                }
+            }
+        }
+        hb = __ballot(huge);
+        while (hb) {
+            const int src = __builtin_ctzll(hb);
+            const Closest r = closest_triangle_wave(P.dm, v3(__shfl(L.p.x, src), __shfl(L.p.y, src), __shfl(L.p.z, src)));
+            if (lane == src) T.best = r;
+            hb &= hb - 1;
+        }
+    }
+    if (owned) {
+        const ExitRecords &R = X.w.rec;
+        R.prim()[w] = slot >= 0 ? P.dm.triOrig[slot] : -1;
+        R.slot()[w] = slot;
+        R.side()[w] = side;
+        R.uv(0)[w] = u; R.uv(1)[w] = v;
+        R.thp()[w] = thp;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) R.base(3, k)[w] = base[k];
+    }
+    uint32_t cnt[5] = {L.c_steps, L.c_started, L.c_absorbed, L.c_truncated, L.c_nhits};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        uint32_t x = cnt[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+        if (lane == 0 && x) atomicAdd(X.w.counters + k, (unsigned long long)x);
+    }
+}
+
+}  // namespace wost
+
+// what the 3-D context adds: the walk kernel on its meshes and source, with the flags of its point solve (walk3_plan)
+static ExitCall exit_call3(wost3_context *c)
+{
+    ExitCall e{"wost3_", 3, c->device, c->n_pixels, c->stream, &c->exits, c->dm.view.triVerts, c->dirichlet_verts, c->dst.dirichlet_intensity, nullptr};
+    e.walk = [c](const ExitWalk &w, hipStream_t stream) {
+        const Walk3Plan pl = walk3_plan(c, w.count);
+        ExitWalk3Params X{};
+        X.P.dm = c->dm.view; X.P.nm = c->nm.view; X.P.st = c->dst; X.P.src = c->src;
+        X.P.st.spp = 1;
+        X.w = w;
+        const dim3 grid((unsigned)((w.count + kWalk3Threads - 1) / kWalk3Threads));
+        const size_t lds = (size_t)pl.stack_words * sizeof(uint32_t);
+        auto launch = [&](auto E, auto S, auto T) {
+            hipLaunchKernelGGL((exits3_kernel<decltype(E)::value, decltype(S)::value, decltype(T)::value>), grid, dim3(kWalk3Threads), lds, stream, X);
+        };
+        auto with_tree = [&](auto E, auto S) { pl.ntree ? launch(E, S, std::true_type{}) : launch(E, S, std::false_type{}); };
+        auto with_src = [&](auto E) { pl.source ? with_tree(E, std::true_type{}) : with_tree(E, std::false_type{}); };
+        pl.emissive ? with_src(std::true_type{}) : with_src(std::false_type{});
+        WOST_TRY(hipGetLastError());
+        return WOST_OK;
+    };
+    return e;
+}
+
+static const ExitCalls<wost3_context> kExits3{exit_call3, 3};
+
+extern "C" {
+
+int wost3_exits_walk(wost3_handle h, const float *pts_xyz, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width, wost_stats *stats)
+{
+    return kExits3.walk(h, pts_xyz, true, n, walks, walk_seed_base, seed_width, nullptr, stats);
+}
+
+int wost3_exits_walk_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width, void *stream,
+                         wost_stats *stats)
+{
+    return kExits3.walk(h, pts_xyz_dev, false, n, walks, walk_seed_base, seed_width, stream, stats);
+}
+
+int wost3_exits_records(wost3_handle h, const wost_exit_records *out) { return kExits3.records(h, out); }
+
+int wost3_exits_apply(wost3_handle h, const float *colors, int32_t K, float *field_rgb, float *stderr_rgb)
+{
+    return kExits3.apply(h, colors, K, field_rgb, stderr_rgb, true, nullptr);
+}
+
+int wost3_exits_apply_dev(wost3_handle h, const float *colors_dev, int32_t K, float *field_rgb_dev, float *stderr_rgb_dev, void *stream)
+{
+    return kExits3.apply(h, colors_dev, K, field_rgb_dev, stderr_rgb_dev, false, stream);
+}
+
+int wost3_exits_adjoint(wost3_handle h, const float *dfield, int32_t K, float *dcolors) { return kExits3.adjoint(h, dfield, K, dcolors, true, nullptr); }
+
+int wost3_exits_adjoint_dev(wost3_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits3.adjoint(h, dfield_dev, K, dcolors_dev, false, stream);
+}
+
+int wost3_exits_progress(wost3_handle h, int32_t *n_points, int32_t *walks) { return kExits3.progress(h, n_points, walks); }
 
 }  // extern "C"

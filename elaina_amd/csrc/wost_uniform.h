@@ -14,6 +14,7 @@
 #include "wost_internal.h"
 #include "wost_carry.h"
 #include "wost_grad.h"
+#include "wost_exits.h"
 
 namespace wost {
 
@@ -34,6 +35,8 @@ struct HandleBase {
     GradScratch grad;               // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
     GradList glist;                 // ... and the carried gradient list (wost_gradient_points_carry & co.), which shares it
     bool grad_source = false;       // the option "grad_source": the gradient calls take a scene with a source term (GradCall)
+    ExitList exits;                 // the exit list (wost_exits_walk & co., wost_exits.h), beside the three carried states
+    int32_t dirichlet_verts = 0;    // ... and the vertices of the Dirichlet mesh, which size a set of its colours (0: no such mesh)
 };
 
 // (hidden: the dynamic symbol table of the library stays the C-ABI and what it held before; nothing here joins it)
@@ -48,6 +51,7 @@ inline void destroy_base(HandleBase *c)
     points_free(c->list);
     grad_free(c->grad);
     gradlist_free(c->glist);
+    exits_free(c->exits);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);

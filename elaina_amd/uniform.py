@@ -210,6 +210,87 @@ class UniformCalls:
         fn, name = self._fn("gradient_points_restart")
         _check(fn(self._handle), name)
 
+    # -- the exit list (wost_exits_walk & co.) ----------------------------------------------------
+    def exits_walk(self, points, walks, walk_seed_base=0, seed_width=None):
+        """walk `walks` walks at each of the points ([n, dim] floats) once and keep one exit record per walk on the integrator
+        (wost_exits_walk; include/wost.h "Exit lists"): walk (i, s) is solve_points of one sample at point i on the stream of
+        pixel walk_seed_base + i * walks + s in a frame seed_width wide (default: the frame's width).  The list replaces the one
+        bound before; an empty list releases it.  exits_apply then gives the solution for any Dirichlet colours, exits_adjoint
+        its derivative with respect to them.  Returns the stats as a dict"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        return self._dev_solve("exits_walk", _fp(p), len(p), int(walks), int(walk_seed_base), self._seed_width(seed_width))
+
+    def exits_walk_dev(self, points_ptr, n, walks, stream_ptr=None, walk_seed_base=0, seed_width=None):
+        """the same from a device pointer (int) to n * dim floats on the caller's stream; a point with a non-finite coordinate
+        is never walked and its field is NaN.  Returns the stats as a dict"""
+        return self._dev_solve("exits_walk_dev", C.c_void_p(points_ptr), int(n), int(walks), int(walk_seed_base), self._seed_width(seed_width),
+                               C.c_void_p(stream_ptr or 0))
+
+    @property
+    def exits_done(self):
+        """(points of the bound exit list, walks per point); (0, 0): none is bound"""
+        fn, name = self._fn("exits_progress")
+        n, S = C.c_int32(0), C.c_int32(0)
+        _check(fn(self._handle, C.byref(n), C.byref(S)), name)
+        return n.value, S.value
+
+    def exits_records(self):
+        """the records of the list: {"prim" (n, S) int32: the absorbing segment / triangle by its index in the caller's array,
+        -1 for a walk that was not absorbed; "uv" (n, S, dim - 1); "side" (n, S) int32; "thp" (n, S); "base" (n, S, 3)}"""
+        fn, name = self._fn("exits_records")
+        n, S = self.exits_done
+        m = max(n * S, 1)      # (with no list bound the call says so; its pointers are still real ones)
+        out = {"prim": np.zeros(m, np.int32), "uv": np.zeros(m * (self._dim - 1), np.float32), "side": np.zeros(m, np.int32),
+               "thp": np.zeros(m, np.float32), "base": np.zeros(m * 3, np.float32)}
+        rec = capi.ExitRecords(*[out[k].ctypes.data for k in ("prim", "uv", "side", "thp", "base")])
+        _check(fn(self._handle, C.byref(rec)), name)
+        shapes = {"prim": (n, S), "uv": (n, S, self._dim - 1), "side": (n, S), "thp": (n, S), "base": (n, S, 3)}
+        return {k: v[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k, v in out.items()}
+
+    def _exit_verts(self):
+        """the vertices of the Dirichlet mesh, which size a set of colours (0: the scene has no such mesh)"""
+        prims = getattr(self.problem, "d_segs" if self._dim == 2 else "d_tris", None)
+        return 0 if self.problem.d_verts is None or prims is None or len(prims) == 0 else len(self.problem.d_verts)
+
+    def _exit_sets(self, a, rows, cols):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != (rows, cols) or len(a) < 1:
+            raise ValueError("expected [K, %d, %d] floats, got %s" % (rows, cols, a.shape))
+        return a
+
+    def exits_apply(self, colors, want_stderr=False):
+        """the field of the listed points for K sets of Dirichlet colours ([K, n_verts, 6] floats, each in the layout of the
+        problem's d_colors; [n_verts, 6] is one set) -> (K, n, 3) float32, or with want_stderr (field, stderr), both (K, n, 3)"""
+        fn, name = self._fn("exits_apply")
+        c = self._exit_sets(colors, self._exit_verts(), 6)
+        K, n = len(c), self.exits_done[0]
+        field = np.zeros((K, n, 3), np.float32)
+        se = np.zeros((K, n, 3), np.float32) if want_stderr else None
+        _check(fn(self._handle, _fp(c), K, _fp(field), _fp(se) if want_stderr else None), name)
+        return (field, se) if want_stderr else field
+
+    def exits_apply_dev(self, colors_ptr, K, field_ptr, stream_ptr=None, stderr_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n_verts * 6 floats of colours, K * n * 3 of field and,
+        where given, of stderr"""
+        fn, name = self._fn("exits_apply_dev")
+        _check(fn(self._handle, C.c_void_p(colors_ptr), int(K), C.c_void_p(field_ptr), C.c_void_p(stderr_ptr or 0), C.c_void_p(stream_ptr or 0)), name)
+
+    def exits_adjoint(self, dfield):
+        """the transposed map of exits_apply: dfield ([K, n, 3] floats; [n, 3] is one set) -> the derivative of sum(field *
+        dfield) by the colours, (K, n_verts, 6) float32"""
+        fn, name = self._fn("exits_adjoint")
+        d = self._exit_sets(dfield, self.exits_done[0], 3)
+        out = np.zeros((len(d), self._exit_verts(), 6), np.float32)
+        _check(fn(self._handle, _fp(d), len(d), _fp(out)), name)
+        return out
+
+    def exits_adjoint_dev(self, dfield_ptr, K, dcolors_ptr, stream_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n * 3 floats in, K * n_verts * 6 floats out"""
+        fn, name = self._fn("exits_adjoint_dev")
+        _check(fn(self._handle, C.c_void_p(dfield_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
+
     # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
     def solve_more(self, more_spp):
         """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at

@@ -420,6 +420,81 @@ int wost_gradient_points_adaptive_dev(wost_handle h, const wost_gradient_adaptiv
 int wost_gradient_points_restart(wost_handle h);
 int wost_gradient_points_progress(wost_handle h, int32_t *n_points, int32_t *rounds_done);
 
+/* Exit lists: walk once, then the solution for any Dirichlet data and its derivative by that data.  A walk reads
+ * no Dirichlet colour before the step that absorbs it, and that step adds  colour * dirichlet_intensity * thp  to the walk's
+ * sum: everything else -- the path, the throughput thp, what the source and the Neumann samples added -- depends on the geometry,
+ * the Neumann data, the source and the two intensities, which stay the handle's.  wost_exits_walk walks S = walks walks at each
+ * of n points of the caller (pts_xy: n * 2 floats) and keeps one record per walk; the list belongs to the handle.  The reference
+ * has no counterpart.
+ *   Walks.  Walk (i, s) is wost_solve_points of ONE sample at point i on the stream of pixel walk_seed_base + i * S + s in a
+ *     frame seed_width wide, with the handle's max_depth, eps_shell, meshes, source and intensities -- the walk convention of
+ *     wost_solve_gradient_points.  The handle's spp setting is neither read nor changed.  The list is walked in launches of
+ *     width * height walks, so S is not bound by the frame; a list cut at point a and walked with walk_seed_base + a * S gives
+ *     the same records.  wost_stats: the five counters as that point solve counts them (walks_started is n * S for finite
+ *     points), kernel_ms the launches' device time, kernel_launches their number; the other counters are zero.
+ *     wost_last_launches is left as it was.
+ *   Records, per walk, entry i * S + s:
+ *       prim      the absorbing segment by its index in the caller's segs array; -1 for a walk that was not absorbed -- truncated
+ *                 at max_depth, escaped (no boundary within reach), or a scene without a Dirichlet mesh
+ *       uv        the fp32 projection ratio of the absorbing step, the same bits; side: its side (-1, 0, +1), the same bits
+ *       thp       the throughput at absorption
+ *       base_rgb  the walk's three sums just before the Dirichlet term is added; for a walk that was not absorbed, its final sums
+ *     A walk that was not absorbed has uv = 0, side = 0 and its final thp.  A point with a non-finite coordinate (only the _dev
+ *     form lets one in) is never walked: prim = -1, uv, thp and base_rgb NaN.
+ *   Apply.  K >= 1 sets of per-vertex colours in the layout of wost_mesh_desc.colors (colors: K * n_verts * 6 floats, n_verts the
+ *     Dirichlet mesh's).  Per walk, set k and channel c, with v0, v1 the vertices of segment prim and off = 0 for side >= 0, else
+ *     3, every line a single fp32 operation (no fused multiply-add: numpy float32 reproduces the bits):
+ *         col = colors[k][v0][off + c] * (1 - uv) + colors[k][v1][off + c] * uv
+ *         col = col * dirichlet_intensity;   col = col * thp;   W = col + base_c
+ *     and W = base_c for a walk that was not absorbed: with the handle's own colours W is the result of that walk's point solve,
+ *     bit for bit.  Per point, in fp64 from the fp32 W, rounded once:
+ *         field_rgb[k][i][c] = (float)(sum_s W / S)
+ *         stderr_rgb[k][i][c] = (float)sqrt( sum_s (W - mean)^2 / (S - 1) / S ),   +inf when S = 1        (stderr_rgb may be NULL)
+ *     The fp64 sums are taken in an order of the library's choice.
+ *   Adjoint.  field is linear in colors; given dfield (K * n * 3) the transposed map into dcolors (K * n_verts * 6):
+ *         dcolors[k][v][off + c] = sum over the absorbed walks (i, s) with v a vertex of their segment, on that side, of
+ *                                  (dfield[k][i][c] / S) * dirichlet_intensity * thp * w_v
+ *     w_v = 1 - uv for v0 and uv for v1, formed in fp32 as apply forms them; every factor is promoted to fp64, the products are
+ *     taken from left to right and summed in fp64, and the sum is rounded to fp32 once.  A vertex no walk exits at gets exactly
+ *     0.  The summation order is the library's (atomic adds) and may differ from run to run: an entry of M terms is within
+ *     M * 2^-52 * sum |terms| + 2^-24 |value| of the exact sum of those terms.  A scene without a Dirichlet mesh has no colours
+ *     to differentiate by: WOST_ERR_UNSUPPORTED.
+ *   - wost_exits_walk: host points; a non-finite coordinate is refused.  wost_exits_walk_dev: DEVICE points and the caller's
+ *     stream (NULL = default stream); both return when the list stands.  n == 0 (pts may be NULL) releases the list.  A new walk
+ *     replaces the list only once it stands whole; a call that is refused or fails leaves the old list as it was and writes
+ *     nothing; an allocation that fails is WOST_ERR_NOMEM.  wost_destroy frees the list.
+ *   - wost_exits_records: the records into host arrays of n * S entries (uv: n * S * (DIM - 1), base_rgb: n * S * 3); any
+ *     pointer of wost_exit_records may be NULL.
+ *   - wost_exits_apply, wost_exits_adjoint: host arrays.  wost_exits_apply_dev, wost_exits_adjoint_dev: DEVICE arrays, the work
+ *     runs on the caller's stream and is complete when the call returns.
+ *   - wost_exits_progress: the points of the list and S (0, 0: none is bound).
+ *   One exit list per handle, beside the carried frame solve, the carried point list and the gradient list: the frame solves, the
+ *     point solves, the carried solves, the gradient calls and wost_set_option leave the list alone, and the list leaves all of
+ *     them alone.  No mesh table of the handle is written: the colours are arguments.
+ *   Arguments of a walk, checked in this order before the handle is read or a device is asked for: a null handle; n < 0, or n > 0
+ *     with null points; walks < 1; seed_width <= 0; walk_seed_base < 0; walk_seed_base + n * walks > 2^28 (in 64 bits); in the
+ *     host form, the first non-finite point (the message names its index).  Of apply and adjoint: a null handle, a null array,
+ *     K < 1, no list bound -- each WOST_ERR_INVALID with a message that says so.
+ * Not built: adding walks to a list, shards of one list, saving a list, the guided integrators, the C++ host mirror, and Neumann
+ * or source data as variables. */
+typedef struct wost_exit_records {   /* host arrays; any may be NULL */
+    int32_t *prim;        /* n * S                                                                                 */
+    float *uv;            /* n * S * (DIM - 1): in 3-D u and v of walk w at 2 w, 2 w + 1                           */
+    int32_t *side;        /* n * S                                                                                 */
+    float *thp;           /* n * S                                                                                 */
+    float *base_rgb;      /* n * S * 3                                                                             */
+} wost_exit_records;
+int wost_exits_walk(wost_handle h, const float *pts_xy, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+                    wost_stats *stats);
+int wost_exits_walk_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+                        void *stream, wost_stats *stats);
+int wost_exits_records(wost_handle h, const wost_exit_records *out);
+int wost_exits_apply(wost_handle h, const float *colors, int32_t K, float *field_rgb, float *stderr_rgb);
+int wost_exits_apply_dev(wost_handle h, const float *colors_dev, int32_t K, float *field_rgb_dev, float *stderr_rgb_dev, void *stream);
+int wost_exits_adjoint(wost_handle h, const float *dfield, int32_t K, float *dcolors);
+int wost_exits_adjoint_dev(wost_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
+int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -835,6 +910,19 @@ int wost3_gradient_points_adaptive_dev(wost3_handle h, const wost_gradient_adapt
                                        wost_stats *stats);
 int wost3_gradient_points_restart(wost3_handle h);
 int wost3_gradient_points_progress(wost3_handle h, int32_t *n_points, int32_t *rounds_done);
+/* Exit lists in 3-D: wost_exits_walk & co. with the same rules in every clause (pts_xyz: n * 3 floats; DIM = 3: prim is the index
+ * of the absorbing triangle in the caller's triangle array, uv holds u and v of a walk side by side, the weights of the
+ * triangle's three vertices are 1 - u - v, u, v; colours in the layout of wost3_mesh_desc.colors). */
+int wost3_exits_walk(wost3_handle h, const float *pts_xyz, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+                     wost_stats *stats);
+int wost3_exits_walk_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+                         void *stream, wost_stats *stats);
+int wost3_exits_records(wost3_handle h, const wost_exit_records *out);
+int wost3_exits_apply(wost3_handle h, const float *colors, int32_t K, float *field_rgb, float *stderr_rgb);
+int wost3_exits_apply_dev(wost3_handle h, const float *colors_dev, int32_t K, float *field_rgb_dev, float *stderr_rgb_dev, void *stream);
+int wost3_exits_adjoint(wost3_handle h, const float *dfield, int32_t K, float *dcolors);
+int wost3_exits_adjoint_dev(wost3_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
+int wost3_exits_progress(wost3_handle h, int32_t *n_points, int32_t *walks);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
