@@ -749,6 +749,8 @@ int build_tree_device(const wost_mesh_desc &d, DeviceTree2 &out_tree)
     WOST_BUILD_TRY(hipMemcpy(&hm, meta, sizeof(hm), hipMemcpyDeviceToHost));         // the one wait of the build
     if (hm.bad) return set_error(WOST_ERR_INVALID, "mesh: segment index out of range or null arrays");
     const float ext = std::max(std::max(std::fabs(b2_dec(hm.lo[0])), std::fabs(b2_dec(hm.hi[0]))), std::max(std::fabs(b2_dec(hm.lo[1])), std::fabs(b2_dec(hm.hi[1]))));
+    // (the walk kernels visit the root without the leaf-level part, trav_visit_root: it must have nodes below it)
+    if (S.levels < 1) return set_error(WOST_ERR_UNSUPPORTED, "tree build: a tree without a level below its root");
     v.n_sil = nv; v.levels = S.levels; v.first_leaf = S.first_leaf; v.emissive = hm.emissive;
     v.far2 = 2.25f * ext * ext;
     v.huge2 = 4096.0f * ext * ext;
@@ -783,6 +785,8 @@ int upload_mesh_host(const wost_mesh_desc &d, DeviceMeshStorage &s)
     v.n_segs = t.n_segs;
     if (t.n_segs == 0) return WOST_OK;
     v.n_sil = (int32_t)t.sil.size();
+    // (the walk kernels visit the root without the leaf-level part, trav_visit_root: it must have nodes below it)
+    if (t.levels < 1) return set_error(WOST_ERR_UNSUPPORTED, "tree build: a tree without a level below its root");
     v.levels = t.levels;
     {
         // the boxes are padded by 2^-21 of the largest coordinate; the rounding of a box distance grows with the distance

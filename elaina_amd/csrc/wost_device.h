@@ -50,7 +50,7 @@ struct DevMesh {
     const int2 *segVerts;    // [slots] vertex ids of the slot's segment
     int32_t n_segs;
     int32_t n_sil;
-    int32_t levels;
+    int32_t levels;          // >= 1 whenever n_segs > 0: the root (level 0) is never the leaf level (checked where a tree is uploaded)
     int32_t first_leaf;
     int32_t emissive;        // any non-zero colour
     float far2;              // squared distance from the mesh beyond which box pruning needs the relative slack (trav_visit<true>)
@@ -333,18 +333,21 @@ __device__ __forceinline__ void trav_leaf_ties(const DevMesh &m, Trav &T, int sl
 // escaped walkers 50 scene sizes away).  Within DevMesh::far2 of the mesh the padding covers the rounding and the plain
 // form is exact; it is the one the walk kernels run in their lane machines, where a single extra live register costs a
 // quarter of the throughput; a query that starts beyond far2 is answered by closest_point_far instead.
-template <bool SLACK = false, class STK = LdsColumn>
-__device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy, Trav &T, const STK &stk)
+// trav_node is that visit with the node's six rows handed in: one code path measures, sorts and pushes the children, whoever
+// fetched them.  ROOT = true is the visit of node (0, 0) of a query that has just begun (trav_begin: nothing on the stack):
+// level, position and stack pointer are constants, and the leaf-level part is left out -- the root is never the leaf level
+// (DevMesh::levels >= 1), so no segment is measured, best stays what it was and segOrig is never read.  With every child pruned
+// the stack is still empty, which is what trav_pop answers with "complete" without changing T: the root form returns false there.
+template <bool SLACK, bool ROOT, class STK>
+__device__ __forceinline__ bool trav_node(const DevMesh &m, const float4 CX, const float4 CY, const float4 UX, const float4 UY,
+                                          const float4 HL, const float4 HW, float qx, float qy, Trav &T, const STK &stk)
 {
-    const uint32_t g = level_first(T.level) + (uint32_t)T.pos;
-    // 96-byte nodes; the byte offset stays below 4 GiB
-    const float4 *nd = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(m.nodes) + __umul24(g, 4u * WOST_NODE_FLOATS));
-    const float4 CX = nd[0], CY = nd[1], UX = nd[2], UY = nd[3], HL = nd[4], HW = nd[5];
+    const int level = ROOT ? 0 : T.level, pos = ROOT ? 0 : T.pos;
     // plain scalar fp32: on gfx950 a packed v_pk_fma_f32 costs two v_fma_f32 (tools/micro/op_rate.hip,
     // profiles/r02_micro_*), has no |x| source modifier and needs hazard nops; the scalar form
     // spends 12 instructions per child with the absolute values folded into the subtractions
     const float bd = T.best.d2;
-    const bool at_leaf = T.level == m.levels;
+    const bool at_leaf = ROOT ? false : level == m.levels;
     const float shrink = (SLACK && !at_leaf) ? kBoxShrink : 1.0f;
     const float d0 = SLACK ? obb_d2(CX.x, CY.x, UX.x, UY.x, HL.x, HW.x, qx, qy) * shrink : obb_d2(CX.x, CY.x, UX.x, UY.x, HL.x, HW.x, qx, qy);
     const float d1 = SLACK ? obb_d2(CX.y, CY.y, UX.y, UY.y, HL.y, HW.y, qx, qy) * shrink : obb_d2(CX.y, CY.y, UX.y, UY.y, HL.y, HW.y, qx, qy);
@@ -361,6 +364,7 @@ __device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy,
 #ifdef WOST_EXP_LOADS
     {   // sensitivity experiment (developer builds only): a second, unrelated node fetched per visit
         const uint32_t nn = level_first(m.levels + 1);
+        const uint32_t g = level_first(level) + (uint32_t)pos;
         uint32_t g2 = g + (nn >> 1);
         g2 = g2 >= nn ? g2 - nn : g2;
         const float4 *n2 = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(m.nodes) + __umul24(g2, 4u * WOST_NODE_FLOATS));
@@ -370,10 +374,10 @@ __device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy,
 #endif
     // ---- last level: the children are segments, the distances are exact.  Branch-free in
     // the common case (one strict winner); exact ties take the rare path.
-    {
+    if (!ROOT) {
         const float mn = fminf(fminf(d0, d1), fminf(d2, d3));
         const int n_eq = (d0 == mn) + (d1 == mn) + (d2 == mn) + (d3 == mn);
-        const int slot = 4 * T.pos + ((d0 == mn) ? 0 : (d1 == mn) ? 1 : (d2 == mn) ? 2 : 3);
+        const int slot = 4 * pos + ((d0 == mn) ? 0 : (d1 == mn) ? 1 : (d2 == mn) ? 2 : 3);
         const bool clean = (n_eq == 1);
         const bool win = at_leaf && clean && mn < bd;
         // same segment as the current best (the temporal hint met again) needs nothing
@@ -381,13 +385,13 @@ __device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy,
         T.best.d2 = win ? mn : T.best.d2;
         T.best.slot = win ? slot : T.best.slot;
         T.best_orig = win ? -1 : T.best_orig;
-        if (tie) trav_leaf_ties(m, T, 4 * T.pos, d0, d1, d2, d3);
+        if (tie) trav_leaf_ties(m, T, 4 * pos, d0, d1, d2, d3);
     }
     // ---- inner level: near-first order.  The (non-negative) distance orders as an integer;
     // level and child index ride in the low mantissa bits, so five integer compare-exchanges
     // sort the candidates.  Lanes at the last level simply have no valid key.
     {
-        const uint32_t tag = (uint32_t)(T.level + 1) << 2;
+        const uint32_t tag = (uint32_t)(level + 1) << 2;
         const bool inner = !at_leaf;
         uint32_t k0 = (inner && d0 <= bd) ? ((__float_as_uint(d0) & ~0x3Fu) | tag | 0u) : 0xffffffffu;
         uint32_t k1 = (inner && d1 <= bd) ? ((__float_as_uint(d1) & ~0x3Fu) | tag | 1u) : 0xffffffffu;
@@ -401,7 +405,7 @@ __device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy,
         // branch-free pushes: sorted keys keep the invalid ones (0xffffffff) last, i.e. first
         // in far-to-near push order; an invalid key is written but the pointer does not move,
         // so the next write lands on top of it (the column has three words of slack)
-        int sp = T.sp;
+        int sp = ROOT ? 0 : T.sp;
         stk.put(sp, k3);
         sp += (k3 != 0xffffffffu) ? 1 : 0;
         stk.put(sp, k2);
@@ -410,11 +414,34 @@ __device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy,
         sp += (k1 != 0xffffffffu) ? 1 : 0;
         T.sp = sp;
         const bool descend = k0 != 0xffffffffu;
-        T.pos = descend ? 4 * T.pos + (int)(k0 & 3u) : T.pos;
-        T.level = descend ? T.level + 1 : T.level;
-        if (descend) return true;
+        T.pos = descend ? 4 * pos + (int)(k0 & 3u) : pos;
+        T.level = descend ? level + 1 : level;
+        if (ROOT || descend) return descend;
     }
     return trav_pop(T, stk);
+}
+
+template <bool SLACK = false, class STK = LdsColumn>
+__device__ __forceinline__ bool trav_visit(const DevMesh &m, float qx, float qy, Trav &T, const STK &stk)
+{
+    const uint32_t g = level_first(T.level) + (uint32_t)T.pos;
+    // 96-byte nodes; the byte offset stays below 4 GiB
+    const float4 *nd = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(m.nodes) + __umul24(g, 4u * WOST_NODE_FLOATS));
+    return trav_node<SLACK, false>(m, nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], qx, qy, T, stk);
+}
+
+// The first visit of a query, made where the query begins (T = trav_begin(...), the step phase of the walk kernels) and not in
+// its first traversal burst: every query starts at node 0, whose 96 bytes are one address for all the lanes of all the waves,
+// so its six rows come through the scalar path -- no vector-memory instruction, and the query's chain of dependent node fetches
+// is one link shorter.  Same arithmetic, same keys, same pushes and the same T as trav_visit<SLACK> leaves after a trav_begin.
+// UNI as in table_load: true in the kernels that store inside their scheduler loop, where the plain read would be a per-lane load.
+template <bool SLACK, bool UNI, class STK>
+__device__ __forceinline__ bool trav_visit_root(const DevMesh &m, float qx, float qy, Trav &T, const STK &stk)
+{
+    const float4 *nd = table_base<UNI>(m.nodes);
+    const float4 CX = table_load<UNI>(nd + 0), CY = table_load<UNI>(nd + 1), UX = table_load<UNI>(nd + 2);
+    const float4 UY = table_load<UNI>(nd + 3), HL = table_load<UNI>(nd + 4), HW = table_load<UNI>(nd + 5);
+    return trav_node<SLACK, true>(m, CX, CY, UX, UY, HL, HW, qx, qy, T, stk);
 }
 
 __device__ __forceinline__ Closest closest_point(const DevMesh &m, float qx, float qy, Closest seed,

@@ -109,6 +109,9 @@ struct RoundParams {
     // the chained start (wost_set_option "chain_start"): a lane whose walk is absorbed takes the depth-0 step of its pixel's
     // next sample in the same step trip (step_finish); 0 = that step waits for the wave's next step trip
     int32_t chain;
+    // the root visit at query start (wost_set_option "root_visit"): a lane that begins a closest-point query visits the tree's
+    // root in the same step trip, its rows fetched on the scalar path (trav_visit_root); 0 = in its first traversal burst
+    int32_t root_visit;
 };
 
 struct InitParams {
@@ -814,6 +817,16 @@ __device__ __forceinline__ void walk_round_body(const RoundParams &P)
                             // SLACK: a query from so far away that every segment of the mesh ties within rounding is answered
                             // by the whole wave at the end of this trip
                             mode = (SLACK && T.best.d2 > P.dm.huge2) ? MODE_HUGE : MODE_TRAV;
+                            // every query starts at the root, one address for the whole chip: visited here, from the scalar
+                            // cache, not as the first gather of the lane's first burst.  (UNI as for the flat tables: the refilling
+                            // kernels store inside this loop, and with a Neumann mesh on the tree the compiler proves nothing
+                            // either -- the plain read was six per-lane loads there; the others issue scalar loads by themselves.)
+                            if (P.root_visit && mode == MODE_TRAV) {
+                                S.visits++;
+                                WOST_TRACK_VISIT_PRE();
+                                if (!trav_visit_root<SLACK, REFILL || NEUMANN_TREE>(P.dm, L.px, L.py, T, stk)) mode = MODE_WAIT;
+                                WOST_TRACK_VISIT_POST();
+                            }
                         }
                     }
                 } else {
@@ -1401,6 +1414,9 @@ int wost_set_option(wost_handle h, const char *key, double value)
     } else if (k == "chain_start") {
         if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "chain_start must be 0 or 1");
         h->chain_start = (int)value;
+    } else if (k == "root_visit") {
+        if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "root_visit must be 0 or 1");
+        h->root_visit = (int)value;
     } else if (k == "resident_blocks") {
         if (value < 0 || value > 65535) return set_error(WOST_ERR_INVALID, "resident_blocks must be in 0..65535 (0 = what the chip holds)");
         h->resident_blocks = (int)value;
@@ -1507,6 +1523,7 @@ static RoundParams base_params(const wost_context *c, const LaunchGeometry &g, f
     rp.steps_per_round = c->steps_per_round > 0 ? c->steps_per_round : 256;
     rp.stack_stride = g.bs;
     rp.chain = c->chain_start;
+    rp.root_visit = c->root_visit;
     set_schedule(c, g.ntree, false, rp);
     rp.coop = g.coop; rp.pool_cap = g.pool_cap; rp.pool_offset = (int32_t)(g.lds / sizeof(uint32_t)); rp.ray_slot_trigger = c->ray_slot_trigger;
     return rp;

@@ -72,6 +72,8 @@ struct wost_context : wost::HandleBase {
     int dry_cadence = 4;   // ... a wave looks again after dry_cadence walk steps of its busiest lane (a power of two), less often while the queue is far from dry
     int chain_start = 1;   // the round and quad kernels: a lane whose walk is absorbed takes the depth-0 step of its pixel's next sample in the
                            //   same step trip (1), or in the wave's next one (0: the rule until this option existed; comparison runs)
+    int root_visit = 1;    // the round kernels: a lane that begins a closest-point query visits the tree's root in the same step trip, its
+                           //   rows read on the scalar path (1), or in its first traversal burst (0: the rule until this option existed; comparison runs)
     int resident_blocks = 0;  // blocks of a one-launch / persistent launch; 0 = as many as the chip holds (tests: a few blocks drain a small frame)
     // what a persistent launch hands over (run_solve): the pixels expected to need `long_steps` walk steps or more run to their end at
     // once, four lanes to a walker, on a stream of higher priority beside the rounds of the others (0 = none do); the first round

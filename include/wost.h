@@ -800,6 +800,9 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
  * "chain_start" (1): a lane whose walk is absorbed takes the first step of its pixel's next sample, whose closest point is cached,
  * in the same pass over the step code (0: in the wave's next one).  The 2-D uniform walk kernels only, and not the steps a wave
  * takes together for a Neumann mesh on the tree.
+ * "root_visit" (1): a lane of the 2-D round kernels that begins a closest-point query visits the root of the Dirichlet tree in
+ * the same pass over the step code, the root's record read once per wave (0: in its first traversal burst, as a per-lane fetch).
+ * The result and every counter but trav_trips are the same either way.
  * "spp" changes samplesPerPixel of an existing handle (a pixel's first k samples do not depend on
  * the total, so solving with spp = k reproduces the state of a longer solve after k samples: the
  * host mirror uses this for saveSppMetrics frames).
