@@ -105,6 +105,11 @@ class ExitRecords(C.Structure):
     _fields_ = [("prim", C.c_void_p), ("uv", C.c_void_p), ("side", C.c_void_p), ("thp", C.c_void_p), ("base_rgb", C.c_void_p)]
 
 
+class ExitGradientRecords(C.Structure):
+    """wost_exit_gradient_records: host arrays of n (radius) and n * S * DIM (dirs, first_pts) floats; any may be NULL"""
+    _fields_ = [("radius", C.c_void_p), ("dirs", C.c_void_p), ("first_pts", C.c_void_p)]
+
+
 class Mesh3Desc(C.Structure):
     """wost3_mesh_desc (include/wost.h)"""
     _fields_ = [("n_verts", C.c_int32), ("n_tris", C.c_int32), ("verts", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_int32)),
@@ -250,6 +255,14 @@ _BOTH = {
     "exits_adjoint": [_h, _pf, _i32, _pf],
     "exits_adjoint_dev": [_h, _dev, _i32, _dev, _dev],
     "exits_progress": [_h, _pi, _pi],
+    # the exit list of the gradient (wost_exits_walk_gradient & co.)
+    "exits_walk_gradient": [_h, _pf, _i32, _i32, _i32, _i32, _i32, _st],
+    "exits_walk_gradient_dev": [_h, _dev, _i32, _i32, _i32, _i32, _i32, _dev, _st],
+    "exits_gradient_records": [_h, C.POINTER(ExitGradientRecords)],
+    "exits_apply_gradient": [_h, _pf, _i32, _pf, _pf, _pf],
+    "exits_apply_gradient_dev": [_h, _dev, _i32, _dev, _dev, _dev, _dev],
+    "exits_adjoint_gradient": [_h, _pf, _i32, _pf],
+    "exits_adjoint_gradient_dev": [_h, _dev, _i32, _dev, _dev],
     # the batch queries
     "render_sdf": [_h, C.c_int, _pf],
     "render_source": [_h, _pf],

@@ -3,7 +3,10 @@
 // side, the throughput and what the source and Neumann samples had added -- so that the solution for any Dirichlet data is one
 // multiply-add per walk (apply) and its derivative with respect to that data a scatter over the same records (adjoint).  A
 // dimension adds the kernel that walks (appended to wost_hip.hip / wost_hip3d.hip, on their unchanged step functions); the
-// list, the two kernels behind it and the bodies of the entry points are here and in wost_exits.hip.  Not part of the C-ABI.
+// list, the two kernels behind it and the bodies of the entry points are here and in wost_exits.hip.  The list of the gradient
+// (wost_exits_walk_gradient & co., "Exit lists of the gradient") is the same list walked from the first points of
+// the gradient's estimator (wost_grad.h) and kept with their directions and radii: grad u for any Dirichlet data and the
+// transpose of that map are two more kernels over the same records.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +15,7 @@
 #include <functional>
 
 #include "../../include/wost.h"
+#include "wost_grad.h"
 #include "wost_internal.h"
 
 namespace wost {
@@ -32,12 +36,16 @@ struct ExitRecords {
     __host__ __device__ float *base(int dim, int c) const { return reinterpret_cast<float *>(mem + (3 + (size_t)dim + (size_t)c) * stride); }
 };
 
-// What a handle carries beside the carried frame solve, the carried point list and the gradient list: one allocation.
+// What a handle carries beside the carried frame solve, the carried point list and the gradient list: one allocation.  A list
+// of the gradient (wost_exits_walk_gradient) has three more arrays in it, behind the records: per point the radius
+// of its first ball, per walk its direction and its first point, dim floats each, interleaved per walk as GradPrep writes them
+// -- 4 * (6 + 3 dim) bytes per walk and 4 per point in all.  A plain list has none of them (dirs == nullptr).
 struct ExitList {
     void *mem = nullptr;
     ExitRecords rec;
     int dim = 0;
     int32_t n = 0, S = 0;
+    float *radius = nullptr, *dirs = nullptr, *first = nullptr;
 };
 void exits_free(ExitList &l);
 
@@ -64,6 +72,11 @@ struct ExitCall {
     int32_t n_verts;
     float dirichlet_intensity;
     std::function<int(const ExitWalk &, hipStream_t)> walk;
+    // ... and for a list of the gradient: the kernel in front (grad_prep2 / grad_prep3 on the context's meshes), the shell, and
+    // whether the scene has a source term (refused: the in-ball term is not carried in the list)
+    std::function<int(const GradPrep &, hipStream_t)> prep;
+    float eps = 0.0f;
+    bool has_source = false;
 };
 
 // the argument rules that need no look at the handle (include/wost.h), in the order of the header
@@ -75,6 +88,22 @@ int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n,
 int exits_records(const ExitCall &c, const wost_exit_records &out);
 int exits_apply(const ExitCall &c, const float *colors, int32_t K, float *field, float *stderr_rgb, bool on_host, hipStream_t stream);
 int exits_adjoint(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
+
+// ---- the list of the gradient (include/wost.h "Exit lists of the gradient") ----
+// the seeds of a walk of the gradient: where the directions are drawn, where the walks run
+struct ExitSeeds {
+    int32_t seed_base, walk_seed_base, seed_width;
+};
+// the argument rules that need no look at the handle, in the order of the header
+int exits_check_walk_gradient(const void *h, const float *pts, int32_t n, int32_t walks, const ExitSeeds &seeds);
+// the walk after them (n > 0): the rule that needs the handle, then the kernel in front straight into the new list and the walks
+// from its first points, one each
+int exits_walk_gradient(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, hipStream_t stream,
+                        wost_stats *stats);
+int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &out);
+// grad is required, se and field may be nullptr
+int exits_apply_gradient(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, bool on_host, hipStream_t stream);
+int exits_adjoint_gradient(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
 
 // the bodies of the entry points, written once: H is the context (device, stream, exits), `call` what a dimension adds
 template <class H>
@@ -125,6 +154,51 @@ struct ExitCalls {
         if (rc == WOST_OK) rc = bound(h);
         if (rc != WOST_OK) return rc;
         return exits_adjoint(call(h), dfield, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    // ---- the list of the gradient ----
+    static int bound_gradient(const H *h)
+    {
+        const int rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        if (!h->exits.dirs)
+            return set_error(WOST_ERR_INVALID, "the exit list bound to the handle has no directions (wost_exits_walk_gradient binds one that has)");
+        return WOST_OK;
+    }
+    int walk_gradient(H *h, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, void *stream, wost_stats *stats) const
+    {
+        int rc = exits_check_walk_gradient(h, pts, n, walks, seeds);
+        if (rc == WOST_OK && pts_on_host) rc = check_points_finite(pts, n, dim);
+        if (rc != WOST_OK) return rc;
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        if (n == 0) {
+            if (h->exits.mem) {
+                WOST_TRY(hipSetDevice(h->device));
+                exits_free(h->exits);
+            }
+            return WOST_OK;
+        }
+        return exits_walk_gradient(call(h), pts, pts_on_host, n, walks, seeds, pts_on_host ? h->stream : reinterpret_cast<hipStream_t>(stream), stats);
+    }
+    int gradient_records(H *h, const wost_exit_gradient_records *out) const
+    {
+        if (!h || !out) return set_error(WOST_ERR_INVALID, "null argument");
+        const int rc = bound_gradient(h);
+        if (rc != WOST_OK) return rc;
+        return exits_gradient_records(call(h), *out);
+    }
+    int apply_gradient(H *h, const float *colors, int32_t K, float *grad, float *se, float *field, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, colors, K, grad, "colors", "grad");
+        if (rc == WOST_OK) rc = bound_gradient(h);
+        if (rc != WOST_OK) return rc;
+        return exits_apply_gradient(call(h), colors, K, grad, se, field, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int adjoint_gradient(H *h, const float *dgrad, int32_t K, float *dcolors, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, dgrad, K, dcolors, "dgrad", "dcolors");
+        if (rc == WOST_OK) rc = bound_gradient(h);
+        if (rc != WOST_OK) return rc;
+        return exits_adjoint_gradient(call(h), dgrad, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
     }
     int progress(H *h, int32_t *n_points, int32_t *walks) const
     {

@@ -1,7 +1,10 @@
 // wost_exits.hip -- the exit list of a handle (wost_exits.h; include/wost.h "Exit lists"): the two kernels behind
 // the walks -- apply, one wave per point over its records for K sets of Dirichlet colours, and the adjoint, a scatter of fp64
 // atomic adds over the same records -- and the driver: the list in chunks of n_pixels walks, the records into host arrays, the
-// host and device forms of apply and adjoint.  Cold path beside the walk kernels, which do not know of it.
+// host and device forms of apply and adjoint.  Cold path beside the walk kernels, which do not know of it.  And the list of the
+// gradient (include/wost.h "Exit lists of the gradient"): the same list walked from the first points of the
+// gradient's estimator, kept with their directions and radii, and the two kernels that are its hot path -- grad u, its standard
+// error and the mean for K sets of colours, one wave per point, and the transpose of that map.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -181,6 +184,137 @@ __global__ __launch_bounds__(256) void exits_round_kernel(const double *acc, flo
     if (j < count) out[j] = (float)acc[j];
 }
 
+// ---- the list of the gradient: apply -----------------------------------------------------------------------------------------
+struct ExitApplyGradParams {
+    ExitRecords rec;
+    const int32_t *verts;
+    const float *colors;             // K sets of n_verts * 6
+    const float *radius, *dirs;      // the list's: n, and DIM per walk
+    int32_t n, S, K, n_verts;
+    float intensity, eps;
+    float *grad, *se, *field;        // K * n * DIM * 3, the same, K * n * 3; se and field may be nullptr
+};
+
+// One wave per point, its lanes over the point's S walks, per set the three passes of grad_reduce_kernel (the mean, the
+// estimate, its two-pass variance) in fp64 over W as exit_value forms it, through the loader forms of grad_point_sums: the same
+// operations on the same numbers in the same order (s = lane, lane + 64, ..., then the butterfly), so with the handle's own
+// colours the bits of wost_solve_gradient_points.  A lane keeps the record, the weights' operands and the direction of its first
+// walk in registers for all K sets and that walk's W for the three passes of a set: with S <= 64 every record and direction is
+// read once, and W is formed once per set.  The walks beyond the first 64 of a point are read again per pass (from the cache).
+// W never passes through memory.  Lane 0 writes the DIM * 3 + DIM * 3 + 3 results of a set.
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_apply_gradient_kernel(ExitApplyGradParams P)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= P.n) return;      // (the whole wave)
+    const int S = P.S;
+    const size_t w0 = (size_t)i * S;
+    ExitRec<DIM> first{};
+    first.slot = -1;
+    float n0[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) n0[a] = 0.0f;
+    if (lane < S) {
+        first = exit_load<DIM>(P.rec, P.verts, w0 + lane);
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) n0[a] = P.dirs[DIM * (w0 + lane) + a];
+    }
+    const float R = P.radius[i];
+    const bool degenerate = ball_degenerate(R, P.eps);
+    const double dS = (double)S;
+    for (int k = 0; k < P.K; ++k) {
+        const float *colors = P.colors + (size_t)k * P.n_verts * 6;
+        float W0[3];
+        exit_value<DIM>(first, colors, P.intensity, W0);
+        const auto load = [&](int s, float (&W)[3], float (&n)[DIM]) {
+            if (s == lane) {
+                for (int c = 0; c < 3; ++c) W[c] = W0[c];
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) n[a] = n0[a];
+            } else {
+                exit_value<DIM>(exit_load<DIM>(P.rec, P.verts, w0 + s), colors, P.intensity, W);
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) n[a] = P.dirs[DIM * (w0 + s) + a];
+            }
+        };
+        double mean[3], t[DIM * 3], v[DIM * 3];
+        grad_point_sums_from<DIM>(load, S, lane, mean, t);
+        if (P.se) grad_point_variance_from<DIM>(load, S, lane, mean, t, v);      // (the whole grid: P is uniform)
+        if (lane == 0) {
+            const size_t o = (size_t)k * P.n + i;
+            const double scale = grad_scale<DIM>(R, S), scale_se = (double)DIM / (double)R;
+#pragma unroll
+            for (int e = 0; e < DIM * 3; ++e) {
+                P.grad[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
+                if (P.se) P.se[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale_se * sqrt(v[e] / (dS - 1.0) / dS));
+            }
+            if (P.field)
+                for (int c = 0; c < 3; ++c) P.field[3 * o + c] = (float)mean[c];
+        }
+    }
+}
+
+// ---- the list of the gradient: adjoint ---------------------------------------------------------------------------------------
+struct ExitAdjointGradParams {
+    ExitRecords rec;
+    const int32_t *verts;
+    const float *dgrad;              // K * n * DIM * 3
+    const float *radius, *dirs;
+    int32_t n, S, K, n_verts;
+    float intensity, eps;
+    double *acc;                     // K * n_verts * 6, zeroed
+};
+
+// One wave per point: its walks share R, nbar and the rows of dgrad.  nbar_a = sum_s n_sa / S by one wave_sum per axis; then
+// the lanes run over the walks, and an absorbed walk adds, per set, channel and vertex of its primitive, the term
+//   q * intensity * thp * w_v,   q = sum_a dgrad[k][i][a][c] * (DIM / (R (S - 1))) * (n_sa - nbar_a)
+// -- fp64 from the fp32 operands, multiplied in this order -- to the entry of that vertex and side, by an fp64 atomic add.  A
+// degenerate point (a point that is not finite has a NaN radius) adds nothing and its dgrad is not read.
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_adjoint_gradient_kernel(ExitAdjointGradParams P)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i >= P.n) return;      // (the whole wave)
+    const float R = P.radius[i];
+    if (ball_degenerate(R, P.eps)) return;      // (the whole wave)
+    const int S = P.S;
+    const size_t w0 = (size_t)i * S;
+    double nbar[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) nbar[a] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) nbar[a] += (double)P.dirs[DIM * (w0 + s) + a];
+    }
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) nbar[a] = wave_sum(nbar[a]) / (double)S;
+    const double scale = grad_scale<DIM>(R, S);
+    for (int s = lane; s < S; s += 64) {
+        const ExitRec<DIM> e = exit_load<DIM>(P.rec, P.verts, w0 + s);
+        if (e.slot < 0) continue;
+        float wgt[DIM];
+        exit_weights<DIM>(e, wgt);
+        const int off = (e.side >= 0) ? 0 : 3;
+        double cen[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) cen[a] = (double)P.dirs[DIM * (w0 + s) + a] - nbar[a];
+        for (int k = 0; k < P.K; ++k) {
+            double *acc = P.acc + (size_t)k * P.n_verts * 6;
+            const float *dg = P.dgrad + ((size_t)k * P.n + i) * (DIM * 3);
+            for (int c = 0; c < 3; ++c) {
+                double q = (double)dg[c] * scale * cen[0];
+#pragma unroll
+                for (int a = 1; a < DIM; ++a) q += (double)dg[3 * a + c] * scale * cen[a];
+                const double g = q * (double)P.intensity * (double)e.thp;
+#pragma unroll
+                for (int v = 0; v < DIM; ++v) atomicAdd(acc + 6 * (size_t)e.v[v] + off + c, g * (double)wgt[v]);
+            }
+        }
+    }
+}
+
 // ---- the driver -------------------------------------------------------------------------------------------------------------
 void exits_free(ExitList &l)
 {
@@ -212,14 +346,19 @@ static int exits_stage(Batch &b, float **dev, size_t count, const char *what)
 }
 
 // the arrays of a list of N walks, carved from one allocation: prim, slot, side, thp, DIM - 1 of uv and three of base, four
-// bytes an entry
-static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S)
+// bytes an entry -- and behind them, for a list of the gradient, the radii (n), the directions and the first points (dim * N each)
+static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S, bool gradient)
 {
-    const size_t N = (size_t)n * S;
-    const int rc = exits_alloc(&l.mem, N * (size_t)(6 + dim) * 4, "the exit list");
+    const size_t N = (size_t)n * S, records = N * (size_t)(6 + dim);
+    const int rc = exits_alloc(&l.mem, (records + (gradient ? (size_t)n + 2 * (size_t)dim * N : 0)) * 4, "the exit list");
     if (rc != WOST_OK) return rc;
     l.rec = ExitRecords{static_cast<int32_t *>(l.mem), N};
     l.dim = dim; l.n = n; l.S = S;
+    if (gradient) {
+        l.radius = static_cast<float *>(l.mem) + records;
+        l.dirs = l.radius + n;
+        l.first = l.dirs + (size_t)dim * N;
+    }
     return WOST_OK;
 }
 
@@ -234,6 +373,24 @@ int exits_check_walk(const void *h, const float *pts, int32_t n, int32_t walks, 
     const int64_t end = (int64_t)walk_seed_base + (int64_t)n * walks;
     if (end > ((int64_t)1 << 28))
         return set_error(WOST_ERR_INVALID, "walk_seed_base + n * walks (" + std::to_string(end) + ") must be at most 2^28");
+    return WOST_OK;
+}
+
+int exits_check_walk_gradient(const void *h, const float *pts, int32_t n, int32_t walks, const ExitSeeds &seeds)
+{
+    if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+    if (n < 0) return set_error(WOST_ERR_INVALID, "negative number of points");
+    if (n > 0 && !pts) return set_error(WOST_ERR_INVALID, "null argument");
+    if (walks < 2) return set_error(WOST_ERR_INVALID, "walks must be at least 2: the estimator needs two walks per point");
+    if (seeds.seed_width <= 0) return set_error(WOST_ERR_INVALID, "seed_width must be positive");
+    if (seeds.seed_base < 0 || seeds.walk_seed_base < 0) return set_error(WOST_ERR_INVALID, "seed_base and walk_seed_base must be >= 0");
+    if ((int64_t)seeds.seed_base + n > ((int64_t)1 << 28)) return set_error(WOST_ERR_INVALID, "seed_base + n must be at most 2^28");
+    const int64_t end = (int64_t)seeds.walk_seed_base + (int64_t)n * walks;
+    if (end > ((int64_t)1 << 28))
+        return set_error(WOST_ERR_INVALID, "walk_seed_base + n * walks (" + std::to_string(end) + ") must be at most 2^28");
+    if ((int64_t)seeds.seed_base < end && (int64_t)seeds.walk_seed_base < (int64_t)seeds.seed_base + n)
+        return set_error(WOST_ERR_INVALID, "the seeds of the directions [seed_base, seed_base + n) overlap those of the walks [walk_seed_base, "
+                                           "walk_seed_base + n * walks)");
     return WOST_OK;
 }
 
@@ -263,13 +420,18 @@ struct ListGuard {
 };
 }  // namespace
 
-int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
-               hipStream_t stream, wost_stats *stats)
+// The walk of a plain list (gradient == false: seeds.seed_base is not read) and of a list of the gradient.  The latter runs the
+// kernel in front first, in launches of at most n_pixels points, straight into the new list's radii, directions and first
+// points (GradPrep's pointers are the launch's own: offset per launch); then its walks are those of a plain list of the n * S
+// first points with one walk each -- walk w reads point w, seeds pixel walk_seed_base + w and writes record w.
+static int exits_walk_list(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, bool gradient,
+                           hipStream_t stream, wost_stats *stats)
 {
+    const int32_t walk_seed_base = seeds.walk_seed_base, seed_width = seeds.seed_width;
     const auto t0 = HostClock::now();
     WOST_TRY(hipSetDevice(c.device));
     ListGuard fresh;
-    int rc = exits_carve(fresh.l, c.dim, n, walks);
+    int rc = exits_carve(fresh.l, c.dim, n, walks, gradient);
     if (rc != WOST_OK) return rc;
     Scratch scratch;
     void *d_pts = nullptr, *d_counters = nullptr;
@@ -288,8 +450,24 @@ int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n,
     WOST_TRY(hipEventRecord(ev.a, stream));
     const int64_t N = (int64_t)n * walks, cap = (int64_t)std::min<size_t>(c.n_pixels, (size_t)1 << 28);
     uint32_t launches = 0;
+    const float *walk_pts = pts_on_host ? static_cast<const float *>(d_pts) : pts;
+    int32_t per_point = walks;
+    if (gradient) {
+        const ExitList &l = fresh.l;
+        for (int64_t a = 0; a < n; a += cap, ++launches) {
+            const size_t at = (size_t)c.dim * (size_t)a * (size_t)walks;
+            const GradPrep p{walk_pts, (int32_t)a, (int32_t)std::min<int64_t>(cap, n - a), walks, seeds.seed_base, seed_width, c.eps,
+                             l.radius + a, l.dirs + at, l.first + at};
+            if ((rc = c.prep(p, stream)) != WOST_OK) {
+                (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+                return rc;
+            }
+        }
+        walk_pts = l.first;
+        per_point = 1;
+    }
     for (int64_t a = 0; a < N; a += cap, ++launches) {
-        const ExitWalk w{pts_on_host ? static_cast<const float *>(d_pts) : pts, (int32_t)a, (int32_t)std::min(cap, N - a), walks, walk_seed_base, seed_width,
+        const ExitWalk w{walk_pts, (int32_t)a, (int32_t)std::min(cap, N - a), per_point, walk_seed_base, seed_width,
                          fresh.l.rec, static_cast<unsigned long long *>(d_counters)};
         if ((rc = c.walk(w, stream)) != WOST_OK) {
             (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
@@ -313,6 +491,130 @@ int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n,
         stamp_solve_ms(stats, t0);
     }
     return WOST_OK;
+}
+
+int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, int32_t walk_seed_base, int32_t seed_width,
+               hipStream_t stream, wost_stats *stats)
+{
+    return exits_walk_list(c, pts, pts_on_host, n, walks, ExitSeeds{0, walk_seed_base, seed_width}, false, stream, stats);
+}
+
+int exits_walk_gradient(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, hipStream_t stream,
+                        wost_stats *stats)
+{
+    if (c.has_source)
+        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_walk_gradient: a scene with a source term is not covered (the in-ball term of "
+                                                                        "the gradient does not depend on the Dirichlet data and is not carried in the list)");
+    return exits_walk_list(c, pts, pts_on_host, n, walks, seeds, true, stream, stats);
+}
+
+int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &out)
+{
+    WOST_TRY(hipSetDevice(c.device));
+    const ExitList &l = *c.list;
+    const size_t n = (size_t)l.n, per_point = (size_t)l.S * (size_t)l.dim;
+    // a point that is not finite has a NaN radius (and no other has); the kernel in front drew its directions all the same
+    std::vector<float> radius(out.dirs ? n : 0);
+    if (out.radius) WOST_TRY(hipMemcpyAsync(out.radius, l.radius, n * 4, hipMemcpyDeviceToHost, c.stream));
+    if (out.dirs) {
+        WOST_TRY(hipMemcpyAsync(radius.data(), l.radius, n * 4, hipMemcpyDeviceToHost, c.stream));
+        WOST_TRY(hipMemcpyAsync(out.dirs, l.dirs, n * per_point * 4, hipMemcpyDeviceToHost, c.stream));
+    }
+    if (out.first_pts) WOST_TRY(hipMemcpyAsync(out.first_pts, l.first, n * per_point * 4, hipMemcpyDeviceToHost, c.stream));
+    WOST_TRY(hipStreamSynchronize(c.stream));
+    if (out.dirs)
+        for (size_t i = 0; i < n; ++i)
+            if (std::isnan(radius[i])) std::fill(out.dirs + i * per_point, out.dirs + (i + 1) * per_point, std::nanf(""));
+    return WOST_OK;
+}
+
+static int exits_apply_gradient_dev(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, hipStream_t stream)
+{
+    const ExitList &l = *c.list;
+    const ExitApplyGradParams P{l.rec, c.verts, colors, l.radius, l.dirs, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, c.eps, grad, se, field};
+    const dim3 grid((unsigned)((l.n + 3) / 4));
+    if (c.dim == 2) hipLaunchKernelGGL(exits_apply_gradient_kernel<2>, grid, dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(exits_apply_gradient_kernel<3>, grid, dim3(256), 0, stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
+}
+
+int exits_apply_gradient(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, bool on_host, hipStream_t stream)
+{
+    WOST_TRY(hipSetDevice(c.device));
+    const size_t n_colors = (size_t)K * c.n_verts * 6, n_field = (size_t)K * c.list->n * 3, n_grad = n_field * (size_t)c.dim;
+    if (!on_host) {
+        const int rc = exits_apply_gradient_dev(c, colors, K, grad, se, field, stream);
+        if (rc != WOST_OK) return rc;
+        WOST_TRY(hipStreamSynchronize(stream));
+        return WOST_OK;
+    }
+    Batch b{stream};
+    float *d_colors = nullptr, *d_grad = nullptr, *d_se = nullptr, *d_field = nullptr;
+    int rc = exits_stage(b, &d_colors, n_colors, "the colours");
+    if (rc == WOST_OK) rc = exits_stage(b, &d_grad, n_grad, "the gradient");
+    if (rc == WOST_OK && se) rc = exits_stage(b, &d_se, n_grad, "the standard errors");
+    if (rc == WOST_OK && field) rc = exits_stage(b, &d_field, n_field, "the field");
+    if (rc != WOST_OK) return rc;
+    WOST_TRY(hipMemcpyAsync(d_colors, colors, n_colors * sizeof(float), hipMemcpyHostToDevice, stream));
+    rc = exits_apply_gradient_dev(c, d_colors, K, d_grad, d_se, d_field, stream);
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    WOST_TRY(b.fetch(grad, d_grad, n_grad));
+    WOST_TRY(b.fetch(se, d_se, n_grad));
+    WOST_TRY(b.fetch(field, d_field, n_field));
+    return b.finish();
+}
+
+// the frame both adjoints share: the zeroed fp64 sums, the input and the output staged for a host call, `launch` (the scatter
+// into acc from the input on the device), the rounding kernel, the fetch
+static int exits_adjoint_run(const ExitCall &c, const char *name, const float *in, size_t n_in, const char *in_name, int32_t K, float *dcolors, bool on_host,
+                             hipStream_t stream, const std::function<void(const float *d_in, double *acc)> &launch)
+{
+    if (c.n_verts <= 0)
+        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + name + ": the scene has no Dirichlet mesh, so there are no colours to differentiate by");
+    WOST_TRY(hipSetDevice(c.device));
+    const size_t n_colors = (size_t)K * c.n_verts * 6;
+    Batch b{stream};
+    void *acc = nullptr;
+    int rc = exits_alloc(&acc, n_colors * sizeof(double), "the fp64 sums of the adjoint");
+    if (rc != WOST_OK) return rc;
+    b.scratch.ptrs.push_back(acc);
+    const float *d_in = in;
+    float *d_out = dcolors;
+    if (on_host) {
+        float *staged = nullptr;
+        if ((rc = exits_stage(b, &staged, n_in, in_name)) != WOST_OK || (rc = exits_stage(b, &d_out, n_colors, "dcolors")) != WOST_OK) return rc;
+        WOST_TRY(hipMemcpyAsync(staged, in, n_in * sizeof(float), hipMemcpyHostToDevice, stream));
+        d_in = staged;
+    }
+    WOST_TRY(hipMemsetAsync(acc, 0, n_colors * sizeof(double), stream));
+    launch(d_in, static_cast<double *>(acc));
+    rc = hipGetLastError() == hipSuccess ? WOST_OK : set_error(WOST_ERR_DEVICE, "the adjoint kernel could not be launched");
+    if (rc == WOST_OK) {
+        hipLaunchKernelGGL(exits_round_kernel, dim3((unsigned)((n_colors + 255) / 256)), dim3(256), 0, stream, static_cast<const double *>(acc), d_out, n_colors);
+        if (hipGetLastError() != hipSuccess) rc = set_error(WOST_ERR_DEVICE, "the rounding kernel of the adjoint could not be launched");
+    }
+    if (rc != WOST_OK) {
+        (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+        return rc;
+    }
+    if (on_host) WOST_TRY(b.fetch(dcolors, d_out, n_colors));
+    return b.finish();
+}
+
+int exits_adjoint_gradient(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream)
+{
+    const ExitList &l = *c.list;
+    return exits_adjoint_run(c, "exits_adjoint_gradient", dgrad, (size_t)K * l.n * 3 * (size_t)c.dim, "dgrad", K, dcolors, on_host, stream,
+                             [&](const float *d_dgrad, double *acc) {
+                                 const ExitAdjointGradParams P{l.rec, c.verts, d_dgrad, l.radius, l.dirs, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, c.eps, acc};
+                                 const dim3 grid((unsigned)((l.n + 3) / 4));
+                                 if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_gradient_kernel<2>, grid, dim3(256), 0, stream, P);
+                                 else hipLaunchKernelGGL(exits_adjoint_gradient_kernel<3>, grid, dim3(256), 0, stream, P);
+                             });
 }
 
 int exits_records(const ExitCall &c, const wost_exit_records &out)
@@ -377,40 +679,13 @@ int exits_apply(const ExitCall &c, const float *colors, int32_t K, float *field,
 
 int exits_adjoint(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream)
 {
-    if (c.n_verts <= 0)
-        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_adjoint: the scene has no Dirichlet mesh, so there are no colours to differentiate by");
-    WOST_TRY(hipSetDevice(c.device));
     const ExitList &l = *c.list;
-    const size_t n_colors = (size_t)K * c.n_verts * 6, n_field = (size_t)K * l.n * 3, N = (size_t)l.n * l.S;
-    Batch b{stream};
-    void *acc = nullptr;
-    int rc = exits_alloc(&acc, n_colors * sizeof(double), "the fp64 sums of the adjoint");
-    if (rc != WOST_OK) return rc;
-    b.scratch.ptrs.push_back(acc);
-    const float *d_dfield = dfield;
-    float *d_out = dcolors;
-    if (on_host) {
-        float *in = nullptr;
-        if ((rc = exits_stage(b, &in, n_field, "dfield")) != WOST_OK || (rc = exits_stage(b, &d_out, n_colors, "dcolors")) != WOST_OK) return rc;
-        WOST_TRY(hipMemcpyAsync(in, dfield, n_field * sizeof(float), hipMemcpyHostToDevice, stream));
-        d_dfield = in;
-    }
-    WOST_TRY(hipMemsetAsync(acc, 0, n_colors * sizeof(double), stream));
-    const ExitAdjointParams P{l.rec, c.verts, d_dfield, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, static_cast<double *>(acc)};
-    const dim3 grid((unsigned)((N + 255) / 256));
-    if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_kernel<2>, grid, dim3(256), 0, stream, P);
-    else hipLaunchKernelGGL(exits_adjoint_kernel<3>, grid, dim3(256), 0, stream, P);
-    rc = hipGetLastError() == hipSuccess ? WOST_OK : set_error(WOST_ERR_DEVICE, "the adjoint kernel could not be launched");
-    if (rc == WOST_OK) {
-        hipLaunchKernelGGL(exits_round_kernel, dim3((unsigned)((n_colors + 255) / 256)), dim3(256), 0, stream, static_cast<const double *>(acc), d_out, n_colors);
-        if (hipGetLastError() != hipSuccess) rc = set_error(WOST_ERR_DEVICE, "the rounding kernel of the adjoint could not be launched");
-    }
-    if (rc != WOST_OK) {
-        (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
-        return rc;
-    }
-    if (on_host) WOST_TRY(b.fetch(dcolors, d_out, n_colors));
-    return b.finish();
+    return exits_adjoint_run(c, "exits_adjoint", dfield, (size_t)K * l.n * 3, "dfield", K, dcolors, on_host, stream, [&](const float *d_dfield, double *acc) {
+        const ExitAdjointParams P{l.rec, c.verts, d_dfield, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, acc};
+        const dim3 grid((unsigned)(((size_t)l.n * l.S + 255) / 256));
+        if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_kernel<2>, grid, dim3(256), 0, stream, P);
+        else hipLaunchKernelGGL(exits_adjoint_kernel<3>, grid, dim3(256), 0, stream, P);
+    });
 }
 
 }  // namespace wost

@@ -69,6 +69,50 @@ __device__ __forceinline__ void grad_point_sums(const float *w, const float *d, 
 #pragma unroll
     for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
 }
+// The same two passes where no array holds the walks' results (the exit list of the gradient, wost_exits.hip): load(s, W, n)
+// gives the result and the direction of walk s of the point.  The same operations in the same order, so the same bits; and
+// the third pass of grad_reduce_kernel beside them,  v_kc = sum_s (n_sk (W_sc - mean_c) - t_kc / S)^2.
+template <int DIM, class LOAD>
+__device__ __forceinline__ void grad_point_sums_from(const LOAD &load, int S, int lane, double (&mean)[3], double (&t)[DIM * 3])
+{
+    const double dS = (double)S;
+    for (int c = 0; c < 3; ++c) mean[c] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+        float W[3], n[DIM];
+        load(s, W, n);
+        for (int c = 0; c < 3; ++c) mean[c] += (double)W[c];
+    }
+    for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+        float W[3], n[DIM];
+        load(s, W, n);
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) t[e] += (double)n[e / 3] * ((double)W[e % 3] - mean[e % 3]);
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
+}
+template <int DIM, class LOAD>
+__device__ __forceinline__ void grad_point_variance_from(const LOAD &load, int S, int lane, const double (&mean)[3], const double (&t)[DIM * 3],
+                                                         double (&v)[DIM * 3])
+{
+    const double dS = (double)S;
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) v[e] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+        float W[3], n[DIM];
+        load(s, W, n);
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) {
+            const double dev = (double)n[e / 3] * ((double)W[e % 3] - mean[e % 3]) - t[e] / dS;
+            v[e] += dev * dev;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) v[e] = wave_sum(v[e]);
+}
 // grad_kc = grad_scale * t_kc, rounded to fp32 once
 template <int DIM>
 __device__ __forceinline__ double grad_scale(float R, int S) { return (double)DIM / ((double)R * ((double)S - 1.0)); }

@@ -2400,6 +2400,9 @@ static ExitCall exit_call(wost_context *c)
         WOST_TRY(hipGetLastError());
         return WOST_OK;
     };
+    e.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep2(c->dm.view, c->nm.view, p, stream); };
+    e.eps = c->dst.eps;
+    e.has_source = c->src.rgb != nullptr;
     return e;
 }
 
@@ -2438,5 +2441,40 @@ int wost_exits_adjoint_dev(wost_handle h, const float *dfield_dev, int32_t K, fl
 }
 
 int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks) { return kExits.progress(h, n_points, walks); }
+
+int wost_exits_walk_gradient(wost_handle h, const float *pts_xy, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base, int32_t seed_width,
+                             wost_stats *stats)
+{
+    return kExits.walk_gradient(h, pts_xy, true, n, walks, ExitSeeds{seed_base, walk_seed_base, seed_width}, nullptr, stats);
+}
+
+int wost_exits_walk_gradient_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base,
+                                 int32_t seed_width, void *stream, wost_stats *stats)
+{
+    return kExits.walk_gradient(h, pts_xy_dev, false, n, walks, ExitSeeds{seed_base, walk_seed_base, seed_width}, stream, stats);
+}
+
+int wost_exits_gradient_records(wost_handle h, const wost_exit_gradient_records *out) { return kExits.gradient_records(h, out); }
+
+int wost_exits_apply_gradient(wost_handle h, const float *colors, int32_t K, float *grad, float *grad_stderr, float *field_rgb)
+{
+    return kExits.apply_gradient(h, colors, K, grad, grad_stderr, field_rgb, true, nullptr);
+}
+
+int wost_exits_apply_gradient_dev(wost_handle h, const float *colors_dev, int32_t K, float *grad_dev, float *grad_stderr_dev, float *field_rgb_dev,
+                                  void *stream)
+{
+    return kExits.apply_gradient(h, colors_dev, K, grad_dev, grad_stderr_dev, field_rgb_dev, false, stream);
+}
+
+int wost_exits_adjoint_gradient(wost_handle h, const float *dgrad, int32_t K, float *dcolors)
+{
+    return kExits.adjoint_gradient(h, dgrad, K, dcolors, true, nullptr);
+}
+
+int wost_exits_adjoint_gradient_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits.adjoint_gradient(h, dgrad_dev, K, dcolors_dev, false, stream);
+}
 
 }  // extern "C"

@@ -291,6 +291,76 @@ class UniformCalls:
         fn, name = self._fn("exits_adjoint_dev")
         _check(fn(self._handle, C.c_void_p(dfield_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
 
+    # -- the exit list of the gradient (wost_exits_walk_gradient & co.) ---------------------------
+    def exits_walk_gradient(self, points, walks, seed_base=0, walk_seed_base=None, seed_width=None):
+        """bind the exit list of the gradient's first points (wost_exits_walk_gradient; include/wost.h "Exit lists of the
+        gradient"): radius, directions and first points of the points ([n, dim] floats) as solve_gradient_points(points,
+        seed_base, walk_seed_base, seed_width, spp=walks) has them, and one exit record per walk from a first point, walk (i, s)
+        on the stream of pixel walk_seed_base + i * walks + s (default: seed_base + n, right behind the directions').  The list
+        replaces the one bound before, plain or not; an empty list releases it.  exits_apply_gradient then gives grad u for any
+        Dirichlet colours, exits_adjoint_gradient its derivative with respect to them; exits_apply and exits_adjoint see the
+        mean of the walks from the first points.  Returns the stats as a dict"""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, self._dim)
+        return self._dev_solve("exits_walk_gradient", _fp(p), len(p), int(walks), *self._gradient_seeds(len(p), seed_base, walk_seed_base, seed_width))
+
+    def exits_walk_gradient_dev(self, points_ptr, n, walks, stream_ptr=None, seed_base=0, walk_seed_base=None, seed_width=None):
+        """the same from a device pointer (int) to n * dim floats on the caller's stream; a point with a non-finite coordinate
+        is never walked and answers NaN.  Returns the stats as a dict"""
+        return self._dev_solve("exits_walk_gradient_dev", C.c_void_p(points_ptr), int(n), int(walks),
+                               *self._gradient_seeds(int(n), seed_base, walk_seed_base, seed_width), C.c_void_p(stream_ptr or 0))
+
+    def exits_gradient_records(self):
+        """the gradient part of the list: {"radius" (n,), "dirs" (n, S, dim), "first_pts" (n, S, dim)}, float32"""
+        fn, name = self._fn("exits_gradient_records")
+        n, S = self.exits_done
+        m = max(n * S, 1)      # (with no list bound the call says so; its pointers are still real ones)
+        out = {"radius": np.zeros(max(n, 1), np.float32), "dirs": np.zeros(m * self._dim, np.float32), "first_pts": np.zeros(m * self._dim, np.float32)}
+        rec = capi.ExitGradientRecords(*[out[k].ctypes.data for k in ("radius", "dirs", "first_pts")])
+        _check(fn(self._handle, C.byref(rec)), name)
+        return {"radius": out["radius"][:n], "dirs": out["dirs"][:n * S * self._dim].reshape(n, S, self._dim),
+                "first_pts": out["first_pts"][:n * S * self._dim].reshape(n, S, self._dim)}
+
+    def exits_apply_gradient(self, colors, want=("stderr", "field")):
+        """grad u at the listed points for K sets of Dirichlet colours ([K, n_verts, 6] floats; [n_verts, 6] is one set) -> a dict
+        of float32 arrays: "grad" (K, n, dim, 3) and what `want` names of "stderr" (K, n, dim, 3) and "field" (K, n, 3), the
+        mean of a point's walks.  With the colours the integrator was made with: solve_gradient_points' outputs, bit for bit"""
+        fn, name = self._fn("exits_apply_gradient")
+        unknown = set(want) - {"stderr", "field"}
+        if unknown:
+            raise ValueError("unknown outputs %s (known: stderr, field)" % sorted(unknown))
+        c = self._exit_sets(colors, self._exit_verts(), 6)
+        K, n = len(c), self.exits_done[0]
+        shapes = {"grad": (K, n, self._dim, 3), "stderr": (K, n, self._dim, 3), "field": (K, n, 3)}
+        out = {k: np.zeros(shapes[k], np.float32) for k in shapes if k == "grad" or k in want}
+        _check(fn(self._handle, _fp(c), K, _fp(out["grad"]), *[_fp(out[k]) if k in out else None for k in ("stderr", "field")]), name)
+        return out
+
+    def exits_apply_gradient_dev(self, colors_ptr, K, grad_ptr, stream_ptr=None, stderr_ptr=None, field_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n_verts * 6 floats of colours, K * n * dim * 3 of grad
+        and, where given, of stderr, K * n * 3 of field"""
+        fn, name = self._fn("exits_apply_gradient_dev")
+        _check(fn(self._handle, C.c_void_p(colors_ptr), int(K), C.c_void_p(grad_ptr), C.c_void_p(stderr_ptr or 0), C.c_void_p(field_ptr or 0),
+                  C.c_void_p(stream_ptr or 0)), name)
+
+    def exits_adjoint_gradient(self, dgrad):
+        """the transposed map of exits_apply_gradient's grad: dgrad ([K, n, dim, 3] floats; [n, dim, 3] is one set) -> the
+        derivative of sum(grad * dgrad) by the colours, (K, n_verts, 6) float32"""
+        fn, name = self._fn("exits_adjoint_gradient")
+        n = self.exits_done[0]
+        d = np.ascontiguousarray(dgrad, dtype=np.float32)
+        if d.ndim == 3:
+            d = d[None]
+        if d.ndim != 4 or d.shape[1:] != (n, self._dim, 3) or len(d) < 1:
+            raise ValueError("expected [K, %d, %d, 3] floats, got %s" % (n, self._dim, d.shape))
+        out = np.zeros((len(d), self._exit_verts(), 6), np.float32)
+        _check(fn(self._handle, _fp(d), len(d), _fp(out)), name)
+        return out
+
+    def exits_adjoint_gradient_dev(self, dgrad_ptr, K, dcolors_ptr, stream_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n * dim * 3 floats in, K * n_verts * 6 floats out"""
+        fn, name = self._fn("exits_adjoint_gradient_dev")
+        _check(fn(self._handle, C.c_void_p(dgrad_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
+
     # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
     def solve_more(self, more_spp):
         """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at

@@ -495,6 +495,77 @@ int wost_exits_adjoint(wost_handle h, const float *dfield, int32_t K, float *dco
 int wost_exits_adjoint_dev(wost_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
 int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks);
 
+/* Exit lists of the gradient: the exit list of the FIRST POINTS of wost_solve_gradient_points, kept with the
+ * directions and the radii, so that grad u, its standard error and the mean at the caller's points follow for any Dirichlet data
+ * without another walk, and so does the derivative of that gradient by the data.  The estimator is linear in the walks' results,
+ *     grad_kc = d / (R (S - 1)) sum_s n_sk (W_sc - mean_c)  =  d / (R (S - 1)) sum_s (n_sk - nbar_k) W_sc,
+ * and every W_s is base + colour * dirichlet_intensity * thp of that walk's exit record.  The reference has no counterpart.
+ *   1. The list.  wost_exits_walk_gradient binds THE exit list of the handle (there is one): n points, S = walks walks each.  It
+ *     replaces a plain list, and a plain wost_exits_walk replaces it.  Radius, directions and first points are those of
+ *     wost_solve_gradient_points(pts, n, seed_base, walk_seed_base, seed_width) on a handle with spp = S, items 1-3 of its
+ *     contract, bit for bit (the same kernel in front).  Walk (i, s) is an exit-list walk that starts at the first point y_is on
+ *     the stream of pixel walk_seed_base + i * S + s: its record is what wost_exits_walk records for a point at y_is with walks = 1
+ *     on that pixel.  The handle's spp setting is neither read nor changed, and S is not bound by the frame.  A degenerate point
+ *     (R <= eps_shell or R not finite) has y = x, as in the single call.  A point with a non-finite coordinate (only the _dev
+ *     form lets one in) is never walked: its radius, directions and first points are NaN (wost_exits_gradient_records), its
+ *     records those of such a point in a plain list.  wost_exits_records, wost_exits_apply, wost_exits_adjoint and
+ *     wost_exits_progress work on such a list as on any other: the field they see is the mean of the walks from the first points.
+ *     A list cut at point a and walked with seed_base + a and walk_seed_base + a * S gives the same rows.
+ *   2. Apply.  K >= 1 sets of colours as wost_exits_apply takes them.  Per walk W is formed exactly as there (the same fp32
+ *     operations).  Per point and set field_rgb, grad and grad_stderr follow item 4 of the gradient's contract: the sums run in
+ *     fp64 from the fp32 W and directions, each result is rounded to fp32 once, the variance is the two-pass one.  A degenerate
+ *     point gets NaN grad and grad_stderr and still its mean.  WITH THE HANDLE'S OWN COLOURS THE THREE OUTPUTS ARE THOSE OF
+ *     wost_solve_gradient_points AT spp = S, BIT FOR BIT, and with any other colours those of a handle created with them.
+ *     Layouts: grad, grad_stderr: K * n * DIM * 3, entry [k][i][axis][c] as in wost_gradient_out; field_rgb: K * n * 3.
+ *   3. Adjoint.  grad is affine in colors; given dgrad (K * n * DIM * 3) the transposed map of its linear part into dcolors
+ *     (K * n_verts * 6):
+ *         dcolors[k][v][off + c] = sum over the absorbed walks (i, s) of non-degenerate points with v a vertex of their
+ *                                  primitive, on that side, of   q * dirichlet_intensity * thp * w_v
+ *         q = sum_axis dgrad[k][i][axis][c] * (DIM / (R_i (S - 1))) * (n_s,axis - nbar_i,axis),     nbar_i = sum_s n_s / S
+ *     w_v is formed in fp32 as apply forms it; every factor is promoted to fp64, summed in fp64 and the sum is rounded to fp32
+ *     once.  A vertex no walk exits at gets exactly 0; degenerate and non-finite points add nothing, and their dgrad is not read.
+ *     The summation order is the library's (atomic adds, and the order of the nbar sum) and may differ from run to run: an entry
+ *     of M terms is within (M + S + 12) * 2^-52 * sum 2 |a| + 2^-24 |value| of the exact sum, a the term without its direction
+ *     factor.  A scene without a Dirichlet mesh: WOST_ERR_UNSUPPORTED.  The derivative of field_rgb is wost_exits_adjoint on the
+ *     same list.
+ *   - wost_exits_walk_gradient: host points; a non-finite coordinate is refused.  wost_exits_walk_gradient_dev: DEVICE points and
+ *     the caller's stream (NULL = default stream); both return when the list stands.  n == 0 (pts may be NULL) releases the list.
+ *     A call that is refused or fails leaves the old list as it was; an allocation that fails is WOST_ERR_NOMEM.  The list costs
+ *     4 * (6 + 3 * DIM) bytes per walk and 4 per point.
+ *   - wost_exits_gradient_records: radius, directions and first points into host arrays; any pointer may be NULL.
+ *   - wost_exits_apply_gradient, wost_exits_adjoint_gradient: host arrays; grad_stderr and field_rgb may be NULL.  The _dev
+ *     forms: DEVICE arrays, the work runs on the caller's stream and is complete when the call returns.
+ *   - wost_stats of the walk: the five counters as the plain exit walk counts them; kernel_ms includes the kernels in front;
+ *     kernel_launches = ceil(n / (width * height)) + ceil(n * S / (width * height)): the kernels in front run in launches of at
+ *     most width * height points, then the walks as in wost_exits_walk.  wost_last_launches is left as it was.
+ *   The carried frame solve, the carried point list, the gradient list, wost_solve_gradient_points (which keeps its own scratch)
+ *     and wost_set_option neither touch the list nor are touched by it.
+ *   Arguments of a walk, checked in this order before the handle is read or a device is asked for: a null handle; n < 0, or n > 0
+ *     with null points; walks < 2; seed_width <= 0; a negative seed; seed_base + n > 2^28; walk_seed_base + n * walks > 2^28 (in
+ *     64 bits); [seed_base, seed_base + n) overlapping [walk_seed_base, walk_seed_base + n * walks); in the host form, the first
+ *     non-finite point.  With the handle: a scene with a source term is WOST_ERR_UNSUPPORTED whatever the option "grad_source"
+ *     says (the in-ball term does not depend on the Dirichlet data and is not carried in the list).  Of apply and adjoint: a null
+ *     handle, a null required array, K < 1, no list bound, a bound list without directions (WOST_ERR_INVALID; the message names
+ *     wost_exits_walk_gradient) -- which wost_exits_gradient_records answers on a plain list too.
+ * Not built: the in-ball term and scenes with a source term, adding walks to a list, shards of one list, saving a list, the
+ * carried gradient list on top of exit lists, the guided integrators, the C++ host mirror, and Neumann or source data as
+ * variables. */
+typedef struct wost_exit_gradient_records {   /* host arrays; any may be NULL */
+    float *radius;        /* n                                                                                     */
+    float *dirs;          /* n * S * DIM: the direction of walk w at w * DIM                                       */
+    float *first_pts;     /* n * S * DIM: where walk w started                                                     */
+} wost_exit_gradient_records;
+int wost_exits_walk_gradient(wost_handle h, const float *pts_xy, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base,
+                             int32_t seed_width, wost_stats *stats);
+int wost_exits_walk_gradient_dev(wost_handle h, const float *pts_xy_dev, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base,
+                                 int32_t seed_width, void *stream, wost_stats *stats);
+int wost_exits_gradient_records(wost_handle h, const wost_exit_gradient_records *out);
+int wost_exits_apply_gradient(wost_handle h, const float *colors, int32_t K, float *grad, float *grad_stderr, float *field_rgb);
+int wost_exits_apply_gradient_dev(wost_handle h, const float *colors_dev, int32_t K, float *grad_dev, float *grad_stderr_dev,
+                                  float *field_rgb_dev, void *stream);
+int wost_exits_adjoint_gradient(wost_handle h, const float *dgrad, int32_t K, float *dcolors);
+int wost_exits_adjoint_gradient_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -926,6 +997,18 @@ int wost3_exits_apply_dev(wost3_handle h, const float *colors_dev, int32_t K, fl
 int wost3_exits_adjoint(wost3_handle h, const float *dfield, int32_t K, float *dcolors);
 int wost3_exits_adjoint_dev(wost3_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
 int wost3_exits_progress(wost3_handle h, int32_t *n_points, int32_t *walks);
+/* Exit lists of the gradient in 3-D: wost_exits_walk_gradient & co. with the same rules in every clause (DIM = 3: two draws per
+ * direction as in wost3_solve_gradient_points; grad, grad_stderr and dgrad hold K * n * 3 * 3 floats). */
+int wost3_exits_walk_gradient(wost3_handle h, const float *pts_xyz, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base,
+                              int32_t seed_width, wost_stats *stats);
+int wost3_exits_walk_gradient_dev(wost3_handle h, const float *pts_xyz_dev, int32_t n, int32_t walks, int32_t seed_base, int32_t walk_seed_base,
+                                  int32_t seed_width, void *stream, wost_stats *stats);
+int wost3_exits_gradient_records(wost3_handle h, const wost_exit_gradient_records *out);
+int wost3_exits_apply_gradient(wost3_handle h, const float *colors, int32_t K, float *grad, float *grad_stderr, float *field_rgb);
+int wost3_exits_apply_gradient_dev(wost3_handle h, const float *colors_dev, int32_t K, float *grad_dev, float *grad_stderr_dev,
+                                   float *field_rgb_dev, void *stream);
+int wost3_exits_adjoint_gradient(wost3_handle h, const float *dgrad, int32_t K, float *dcolors);
+int wost3_exits_adjoint_gradient_dev(wost3_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
