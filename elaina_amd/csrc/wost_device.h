@@ -501,6 +501,47 @@ __device__ __forceinline__ Closest closest_point_wave(const DevMesh &m, float qx
     return Closest{bd, bs};
 }
 
+// The scan for every lane of the wave with `huge` (all lanes call; x, y the lane's own point): one closest_point_wave per such
+// lane, its answer into that lane's c.  The loop behind the lock-step queries of the cold-path kernels.
+__device__ __forceinline__ void closest_point_scan_huge(const DevMesh &m, float x, float y, bool huge, Closest &c)
+{
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_point_wave(m, __shfl(x, src), __shfl(y, src));
+        if ((int)(threadIdx.x & 63) == src) c = r;
+        hb &= hb - 1;
+    }
+}
+
+// The closest segment as wost_closest_point answers it, at any distance from the mesh, for every lane with `active` (all lanes
+// of the wave call): the descent seeded with slot 0, or -- beyond huge2, where the descent opens every box -- the scan by the
+// wave: the same candidates and the same tie rule, hence the same bits.  An inactive lane or an empty mesh: {+inf, -1}.
+// The one depth-0 query of the point solve's init, the gradient's kernel in front and the exit walk.
+__device__ __forceinline__ Closest closest_point_lockstep(const DevMesh &m, float x, float y, bool active, uint32_t *stack, int stride)
+{
+    Closest c{WOST_INF, -1};
+    bool huge = false;
+    if (active && m.n_segs > 0) {
+        c = slot_candidate(m, 0, x, y);
+        huge = c.d2 > m.huge2;
+        if (!huge) c = closest_point(m, x, y, c, stack, stride);
+    }
+    closest_point_scan_huge(m, x, y, huge, c);
+    return c;
+}
+
+// checkPointSide / computeProjectionRatio of (x, y) on the segment in `slot`, as wost_closest_point reports them
+__device__ __forceinline__ void segment_uv_side(const DevMesh &m, int32_t slot, float x, float y, float &uv, int32_t &side)
+{
+    const float4 a = m.segA[slot];
+    const float inv = m.segInv[slot];
+    const float wx = x - a.x, wy = y - a.y;
+    const float cr = cross2(a.z, a.w, wx, wy);
+    uv = dot2(wx, wy, a.z, a.w) * inv;
+    side = (0.0f < cr) - (cr < 0.0f);
+}
+
 // the operands of seg_d2 from a record of a flat table: (cx, cy, ux, uy) in one load, hl in a second, nothing else of the 64 bytes
 template <bool UNI>
 __device__ __forceinline__ float flat_seg_d2(const DevFlatSeg *s, float qx, float qy)

@@ -240,6 +240,54 @@ __device__ __forceinline__ void tri_uv(V3 p0, V3 e0, V3 e1, V3 q, float &u, floa
     u = __builtin_fmaf(d11, d20, -(d01 * d21)) / denom;
     v = __builtin_fmaf(d00, d21, -(d01 * d20)) / denom;
 }
+// ... of q on the triangle in `slot`, as wost3_closest_point reports them
+__device__ __forceinline__ void triangle_uv_side(const DevMesh3 &m, int32_t slot, V3 q, float &u, float &v, int32_t &side)
+{
+    const float4 a = m.tri[3 * (size_t)slot], b = m.tri[3 * (size_t)slot + 1], c = m.tri[3 * (size_t)slot + 2];
+    const V3 p0 = v3(a.x, a.y, a.z), e0 = v3(b.x, b.y, b.z) - p0, e1 = v3(c.x, c.y, c.z) - p0;
+    side = tri_side(p0, cross3(e0, e1), q);
+    tri_uv(p0, e0, e1, q, u, v);
+}
+
+// ---- the lock-step query of the cold-path kernels, safe at any distance from the mesh ----
+// The mesh lies beyond huge2 of q when the boxes of the root's four children all do: a box is never farther than its triangles.
+__device__ __forceinline__ bool root_beyond_huge3(const DevMesh3 &m, V3 q)
+{
+    const float4 LX = m.nodes[0], LY = m.nodes[1], LZ = m.nodes[2], HX = m.nodes[3], HY = m.nodes[4], HZ = m.nodes[5];
+    const float d0 = aabb_d2(LX.x, LY.x, LZ.x, HX.x, HY.x, HZ.x, q), d1 = aabb_d2(LX.y, LY.y, LZ.y, HX.y, HY.y, HZ.y, q);
+    const float d2 = aabb_d2(LX.z, LY.z, LZ.z, HX.z, HY.z, HZ.z, q), d3 = aabb_d2(LX.w, LY.w, LZ.w, HX.w, HY.w, HZ.w, q);
+    return fminf(fminf(d0, d1), fminf(d2, d3)) > m.huge2;
+}
+
+// The scan for every lane of the wave with `huge` (all lanes call; q the lane's own point): one closest_triangle_wave per such
+// lane, its answer into that lane's c.
+__device__ __forceinline__ void closest_triangle_scan_huge(const DevMesh3 &m, V3 q, bool huge, Closest &c)
+{
+    unsigned long long hb = __ballot(huge);
+    while (hb) {
+        const int src = __builtin_ctzll(hb);
+        const Closest r = closest_triangle_wave(m, v3(__shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src)));
+        if ((int)(threadIdx.x & 63) == src) c = r;
+        hb &= hb - 1;
+    }
+}
+
+// The closest triangle as wost3_closest_point answers it (the descent without a hint), at any distance from the mesh, for
+// every lane with `active` (all lanes of the wave call): beyond huge2 the scan by the wave, which gives the bits of the descent
+// -- both are exact, lowest original index among equal distances.  An inactive lane or an empty mesh: {+inf, -1}.
+// The query of the gradient's kernel in front, its only caller: exits3_kernel takes the same steps at depth 0 written out
+// (wost_hip3d.hip says why), so there the agreement is the tests', not the compiler's.
+__device__ __forceinline__ Closest closest_triangle_lockstep(const DevMesh3 &m, V3 q, bool active, const LdsColumn &stk)
+{
+    Closest c{WOST_INF, -1};
+    bool huge = false;
+    if (active && m.n_tris > 0) {
+        huge = root_beyond_huge3(m, q);
+        if (!huge) c = closest_triangle(m, q, -1, stk);
+    }
+    closest_triangle_scan_huge(m, q, huge, c);
+    return c;
+}
 // computeSurfaceColor<3> + barycentric_interpolate: (a w + b u) + c v
 __device__ __forceinline__ void surface_color3(const float *colors, int i0, int i1, int i2, int side, float u, float v, float out[3])
 {

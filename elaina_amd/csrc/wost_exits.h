@@ -58,6 +58,19 @@ struct ExitWalk {
     ExitRecords rec;
     unsigned long long *counters;
 };
+// the close of a walk kernel (all lanes of the wave call): the lanes' five counts summed over the wave, one add per non-zero sum
+__device__ __forceinline__ void wave_add_counters(unsigned long long *counters, uint32_t steps, uint32_t started, uint32_t absorbed, uint32_t truncated,
+                                                  uint32_t nhits)
+{
+    const uint32_t v[5] = {steps, started, absorbed, truncated, nhits};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        uint32_t x = v[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+        if ((threadIdx.x & 63) == 0 && x) atomicAdd(counters + k, (unsigned long long)x);
+    }
+}
 
 // What the driver reads of a context, and what a dimension adds: its walk kernel with the template flags of its point solve.
 // verts: the mesh table of the vertex ids of the primitive in a slot (DIM per slot), n_verts the Dirichlet mesh's vertices

@@ -196,9 +196,8 @@ struct ExitApplyGradParams {
 };
 
 // One wave per point, its lanes over the point's S walks, per set the three passes of grad_reduce_kernel (the mean, the
-// estimate, its two-pass variance) in fp64 over W as exit_value forms it, through the loader forms of grad_point_sums: the same
-// operations on the same numbers in the same order (s = lane, lane + 64, ..., then the butterfly), so with the handle's own
-// colours the bits of wost_solve_gradient_points.  A lane keeps the record, the weights' operands and the direction of its first
+// estimate, its two-pass variance) in fp64 over W as exit_value forms it: the same functions (grad_point_sums_from,
+// grad_point_variance_from) with another loader, so with the handle's own colours the bits of wost_solve_gradient_points.  A lane keeps the record, the weights' operands and the direction of its first
 // walk in registers for all K sets and that walk's W for the three passes of a set: with S <= 64 every record and direction is
 // read once, and W is formed once per set.  The walks beyond the first 64 of a point are read again per pass (from the cache).
 // W never passes through memory.  Lane 0 writes the DIM * 3 + DIM * 3 + 3 results of a set.

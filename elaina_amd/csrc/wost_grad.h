@@ -50,28 +50,11 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// The first two passes over a point's S walks by the lanes of one wave (all of them call): w their results (RGB), d their
-// directions;  mean_c = sum_s W_sc / S  and  t_kc = sum_s n_sk (W_sc - mean_c), in fp64, the same on every lane.
-template <int DIM>
-__device__ __forceinline__ void grad_point_sums(const float *w, const float *d, int S, int lane, double (&mean)[3], double (&t)[DIM * 3])
-{
-    const double dS = (double)S;
-    for (int c = 0; c < 3; ++c) mean[c] = 0.0;
-    for (int s = lane; s < S; s += 64)
-        for (int c = 0; c < 3; ++c) mean[c] += (double)w[3 * s + c];
-    for (int c = 0; c < 3; ++c) mean[c] = wave_sum(mean[c]) / dS;
-#pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) t[e] = 0.0;
-    for (int s = lane; s < S; s += 64) {
-#pragma unroll
-        for (int e = 0; e < DIM * 3; ++e) t[e] += (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]);
-    }
-#pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
-}
-// The same two passes where no array holds the walks' results (the exit list of the gradient, wost_exits.hip): load(s, W, n)
-// gives the result and the direction of walk s of the point.  The same operations in the same order, so the same bits; and
-// the third pass of grad_reduce_kernel beside them,  v_kc = sum_s (n_sk (W_sc - mean_c) - t_kc / S)^2.
+// The first two passes over a point's S walks by the lanes of one wave (all of them call): load(s, W, n) gives the result W
+// (RGB) and the direction n of walk s of the point;  mean_c = sum_s W_sc / S  and  t_kc = sum_s n_sk (W_sc - mean_c), in fp64,
+// the same on every lane.  Every kernel that reduces a point's walks -- grad_reduce_kernel, gradlist_accumulate_kernel,
+// exits_apply_gradient_kernel -- goes through these passes and the third one below, so they agree bit for bit: a lane adds its
+// walks s = lane, lane + 64, ... in that order, then the butterfly of wave_sum.
 template <int DIM, class LOAD>
 __device__ __forceinline__ void grad_point_sums_from(const LOAD &load, int S, int lane, double (&mean)[3], double (&t)[DIM * 3])
 {
@@ -94,6 +77,7 @@ __device__ __forceinline__ void grad_point_sums_from(const LOAD &load, int S, in
 #pragma unroll
     for (int e = 0; e < DIM * 3; ++e) t[e] = wave_sum(t[e]);
 }
+// the third pass,  v_kc = sum_s (n_sk (W_sc - mean_c) - t_kc / S)^2
 template <int DIM, class LOAD>
 __device__ __forceinline__ void grad_point_variance_from(const LOAD &load, int S, int lane, const double (&mean)[3], const double (&t)[DIM * 3],
                                                          double (&v)[DIM * 3])
@@ -113,6 +97,16 @@ __device__ __forceinline__ void grad_point_variance_from(const LOAD &load, int S
 #pragma unroll
     for (int e = 0; e < DIM * 3; ++e) v[e] = wave_sum(v[e]);
 }
+// the loader of walks held in arrays: w their results (RGB), d their directions (DIM each), both interleaved per walk
+template <int DIM>
+struct GradWalkArrays {
+    const float *w, *d;
+    __device__ __forceinline__ void operator()(int s, float (&W)[3], float (&n)[DIM]) const
+    {
+        for (int c = 0; c < 3; ++c) W[c] = w[3 * s + c];
+        for (int k = 0; k < DIM; ++k) n[k] = d[DIM * s + k];
+    }
+};
 // grad_kc = grad_scale * t_kc, rounded to fp32 once
 template <int DIM>
 __device__ __forceinline__ double grad_scale(float R, int S) { return (double)DIM / ((double)R * ((double)S - 1.0)); }
@@ -139,6 +133,24 @@ __device__ __forceinline__ void grad_ball_sums(const float *ball, size_t stride,
 #pragma unroll
     for (int e = 0; e < DIM * 3; ++e) a[e] = wave_sum(a[e]);
     for (int c = 0; c < 3; ++c) u[c] = wave_sum(u[c]);
+}
+// ... and the second pass over them,  va_kc = sum_s (wg_s m_sk ds_sc - a_kc / S)^2
+template <int DIM>
+__device__ __forceinline__ void grad_ball_variance(const float *ball, size_t stride, int S, int lane, const double (&a)[DIM * 3], double (&va)[DIM * 3])
+{
+    const double dS = (double)S;
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) va[e] = 0.0;
+    for (int s = lane; s < S; s += 64) {
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) {
+            const double dev = (double)ball[(DIM + kBallWg) * stride + s] * (double)ball[(e / 3) * stride + s] * (double)ball[(DIM + kBallDs + e % 3) * stride + s] -
+                               a[e] / dS;
+            va[e] += dev * dev;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < DIM * 3; ++e) va[e] = wave_sum(va[e]);
 }
 // T_kc = (R / S) a_kc joins the walk part of grad, U_c = (R^2 / S) u_c the mean, before the one rounding to fp32
 __device__ __forceinline__ double ball_grad_term(float R, int S, double a) { return (double)R / (double)S * a; }

@@ -19,87 +19,72 @@ namespace wost {
 
 #define WOST_NAN __int_as_float(0x7fc00000)
 
-// ---- the kernels in front ----------------------------------------------------------------------------------------------------
-// The distance of a point to a mesh as wost_closest_point answers it, for every lane with `active` (all lanes of the wave must
-// call): the descent seeded with slot 0, or -- beyond huge2, where the descent opens every box -- the scan by the wave, through
-// the ballot loop of init_points_kernel: the same candidates and tie rule, hence the same bits.  An empty mesh: +inf.
-__device__ __forceinline__ float depth0_distance(const DevMesh &m, float x, float y, bool active, uint32_t *stack, int stride)
-{
-    if (m.n_segs <= 0) return WOST_INF;
-    Closest c{WOST_INF, -1};
-    bool huge = false;
-    if (active) {
-        c = slot_candidate(m, 0, x, y);
-        huge = c.d2 > m.huge2;
-        if (!huge) c = closest_point(m, x, y, c, stack, stride);
-    }
-    unsigned long long hb = __ballot(huge);
-    while (hb) {
-        const int src = __builtin_ctzll(hb);
-        const Closest r = closest_point_wave(m, __shfl(x, src), __shfl(y, src));
-        if ((int)(threadIdx.x & 63) == src) c = r;
-        hb &= hb - 1;
-    }
-    return sqrtf(c.d2);
-}
+// ---- the kernel in front ------------------------------------------------------------------------------------------------------
+constexpr int kPrepThreads = 256;
 
-// ... and in 3-D, as wost3_closest_point answers it (the descent without a hint).  The mesh is beyond huge2 when the boxes of
-// the root's four children all are: a box is never farther than its triangles, and the scan gives the bits of the descent.
-__device__ __forceinline__ float depth0_distance3(const DevMesh3 &m, V3 q, bool active, const LdsColumn &stk)
+// What a dimension adds to the kernel in front and the in-ball kernel.  The distance of a point to a mesh as wost_closest_point /
+// wost3_closest_point answers it, at any distance from the mesh (closest_point_lockstep, closest_triangle_lockstep: all lanes
+// of the wave call; an empty mesh: +inf); col is the thread's stack column in a block of kPrepThreads.
+__device__ __forceinline__ float mesh_distance(const DevMesh &m, const float (&x)[2], bool active, uint32_t *col)
 {
-    if (m.n_tris <= 0) return WOST_INF;
-    Closest c{WOST_INF, -1};
-    bool huge = false;
-    if (active) {
-        const float4 LX = m.nodes[0], LY = m.nodes[1], LZ = m.nodes[2], HX = m.nodes[3], HY = m.nodes[4], HZ = m.nodes[5];
-        const float d0 = aabb_d2(LX.x, LY.x, LZ.x, HX.x, HY.x, HZ.x, q), d1 = aabb_d2(LX.y, LY.y, LZ.y, HX.y, HY.y, HZ.y, q);
-        const float d2 = aabb_d2(LX.z, LY.z, LZ.z, HX.z, HY.z, HZ.z, q), d3 = aabb_d2(LX.w, LY.w, LZ.w, HX.w, HY.w, HZ.w, q);
-        huge = fminf(fminf(d0, d1), fminf(d2, d3)) > m.huge2;
-        if (!huge) c = closest_triangle(m, q, -1, stk);
+    return sqrtf(closest_point_lockstep(m, x[0], x[1], active, col, kPrepThreads).d2);
+}
+__device__ __forceinline__ float mesh_distance(const DevMesh3 &m, const float (&x)[3], bool active, uint32_t *col)
+{
+    return sqrtf(closest_triangle_lockstep(m, v3(x[0], x[1], x[2]), active, LdsColumn(col, kPrepThreads)).d2);
+}
+// A uniform direction from the stream: in 2-D one draw, (cos, sin) of sincos_2pi(u); in 3-D two, u1 then u2, the walk's own
+// uniform direction (step3_b0).
+template <int DIM>
+__device__ __forceinline__ void draw_direction(Pcg &rng, float (&n)[DIM])
+{
+    float c, sn;
+    if (DIM == 2) {
+        sincos_2pi(pcg_next_float(rng), c, sn);
+        n[0] = c; n[1] = sn;
+    } else {
+        const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
+        sincos_2pi(u2, c, sn);
+        const float z = 1 - 2 * u1, r = sqrtf(1 - z * z);
+        n[0] = r * c; n[1] = r * sn; n[DIM - 1] = z;
     }
-    unsigned long long hb = __ballot(huge);
-    while (hb) {
-        const int src = __builtin_ctzll(hb);
-        const Closest r = closest_triangle_wave(m, v3(__shfl(q.x, src), __shfl(q.y, src), __shfl(q.z, src)));
-        if ((int)(threadIdx.x & 63) == src) c = r;
-        hb &= hb - 1;
-    }
-    return sqrtf(c.d2);
 }
 
 // R = min(dD, 0.875 dN) (degenerate or not: ball_degenerate, wost_grad.h)
 __device__ __forceinline__ float ball_radius(float dD, float dN) { return fminf(dD, kGradNeumannShrink * dN); }
 
-struct GradPrepParams2 {
-    DevMesh dm, nm;
+template <class MESH>
+struct GradPrepParams {
+    MESH dm, nm;
     GradPrep p;
-    int32_t stack_stride;
 };
 
 // Thread j takes point first + j of the call: its radius, then spp draws from the stream of pixel seed_base + first + j --
-// walk s of the point gets the direction (cos, sin) of sincos_2pi(u) and the first point fmaf(R, n, x).  A point with a
+// walk s of the point gets the direction n of draw_direction and the first point fmaf(R, n, x) (madd3 in 3-D).  A point with a
 // non-finite coordinate makes no query; its radius and first points are NaN, so the point step never queues its walks.  The
 // same holds for a point that the map of a carried list's round (GradPrep::sel) leaves out; it draws nothing either.
-__global__ __launch_bounds__(256) void grad_prep2_kernel(GradPrepParams2 P)
+template <int DIM, class MESH>
+__global__ __launch_bounds__(kPrepThreads) void grad_prep_kernel(GradPrepParams<MESH> P)
 {
     extern __shared__ uint32_t lds_stack[];
-    uint32_t *stack = lds_stack + threadIdx.x;
+    uint32_t *col = lds_stack + threadIdx.x;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const bool owned = j < P.p.count;
-    float x = 0.0f, y = 0.0f;
-    if (owned) {
-        x = P.p.pts[2 * (size_t)(P.p.first + j)];
-        y = P.p.pts[2 * (size_t)(P.p.first + j) + 1];
+    float x[DIM];
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+        x[k] = owned ? P.p.pts[DIM * (size_t)(P.p.first + j) + k] : 0.0f;
+        finite = finite && isfinite(x[k]);
     }
     const bool chosen = owned && (P.p.sel == nullptr || P.p.sel[P.p.first + j] != 0);
-    const bool finite = isfinite(x) && isfinite(y);
-    const float dD = depth0_distance(P.dm, x, y, chosen && finite, stack, P.stack_stride);
-    const float dN = depth0_distance(P.nm, x, y, chosen && finite, stack, P.stack_stride);
+    const float dD = mesh_distance(P.dm, x, chosen && finite, col);
+    const float dN = mesh_distance(P.nm, x, chosen && finite, col);
     if (!owned) return;
-    float *dirs = P.p.dirs + 2 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 2 * (size_t)j * P.p.spp;
+    float *dirs = P.p.dirs + DIM * (size_t)j * P.p.spp, *fp = P.p.first_pts + DIM * (size_t)j * P.p.spp;
     if (!chosen) {
         P.p.radius[j] = WOST_NAN;
-        for (int s = 0; s < 2 * P.p.spp; ++s) fp[s] = WOST_NAN;
+        for (int s = 0; s < DIM * P.p.spp; ++s) fp[s] = WOST_NAN;
         return;
     }
     const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
@@ -108,78 +93,38 @@ __global__ __launch_bounds__(256) void grad_prep2_kernel(GradPrepParams2 P)
     Pcg rng{0, 1};
     pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
     for (int s = 0; s < P.p.spp; ++s) {
-        float c, sn;
-        sincos_2pi(pcg_next_float(rng), c, sn);
-        dirs[2 * s] = c; dirs[2 * s + 1] = sn;
-        fp[2 * s] = !finite ? WOST_NAN : degenerate ? x : __builtin_fmaf(R, c, x);
-        fp[2 * s + 1] = !finite ? WOST_NAN : degenerate ? y : __builtin_fmaf(R, sn, y);
+        float n[DIM];
+        draw_direction<DIM>(rng, n);
+        float f[DIM];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) f[k] = !finite ? WOST_NAN : degenerate ? x[k] : __builtin_fmaf(R, n[k], x[k]);
+        // (the direction whole, then the first point whole: stores to the two arrays in turn are not merged into wide ones)
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) dirs[DIM * s + k] = n[k];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) fp[DIM * s + k] = f[k];
     }
 }
 
-struct GradPrepParams3 {
-    DevMesh3 dm, nm;
-    GradPrep p;
-};
-
-// The same in 3-D: two draws per walk, the walk's own uniform direction (step3_b0)
-__global__ __launch_bounds__(256) void grad_prep3_kernel(GradPrepParams3 P)
+// the launch, with the stack columns of a block for the deeper of the two trees (levels of an empty mesh: 1)
+template <int DIM, class MESH>
+static int grad_prep_launch(const MESH &dm, int32_t levels_d, const MESH &nm, int32_t levels_n, const GradPrep &p, hipStream_t stream)
 {
-    extern __shared__ uint32_t lds_stack[];
-    const LdsColumn stk(lds_stack + threadIdx.x, blockDim.x);
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool owned = j < P.p.count;
-    V3 q = v3(0.0f, 0.0f, 0.0f);
-    if (owned) q = ld3(P.p.pts + 3 * (size_t)(P.p.first + j));
-    const bool chosen = owned && (P.p.sel == nullptr || P.p.sel[P.p.first + j] != 0);
-    const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
-    const float dD = depth0_distance3(P.dm, q, chosen && finite, stk);
-    const float dN = depth0_distance3(P.nm, q, chosen && finite, stk);
-    if (!owned) return;
-    float *dirs = P.p.dirs + 3 * (size_t)j * P.p.spp, *fp = P.p.first_pts + 3 * (size_t)j * P.p.spp;
-    if (!chosen) {
-        P.p.radius[j] = WOST_NAN;
-        for (int s = 0; s < 3 * P.p.spp; ++s) fp[s] = WOST_NAN;
-        return;
-    }
-    const float R = finite ? ball_radius(dD, dN) : WOST_NAN;
-    const bool degenerate = ball_degenerate(R, P.p.eps);
-    P.p.radius[j] = R;
-    Pcg rng{0, 1};
-    pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
-    for (int s = 0; s < P.p.spp; ++s) {
-        const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
-        float c, sn;
-        sincos_2pi(u2, c, sn);
-        const float z = 1 - 2 * u1, r = sqrtf(1 - z * z);
-        const V3 n = v3(r * c, r * sn, z);
-        const V3 f = !finite ? v3(WOST_NAN, WOST_NAN, WOST_NAN) : degenerate ? q : madd3(q, R, n);
-        dirs[3 * s] = n.x; dirs[3 * s + 1] = n.y; dirs[3 * s + 2] = n.z;
-        fp[3 * s] = f.x; fp[3 * s + 1] = f.y; fp[3 * s + 2] = f.z;
-    }
-}
-
-// the stack columns of a block of 256 threads for the deeper of the two trees
-static size_t prep_lds(int32_t levels_d, bool has_d, int32_t levels_n, bool has_n)
-{
-    return stack_lds(std::max(has_d ? levels_d : 1, has_n ? levels_n : 1));
+    const GradPrepParams<MESH> P{dm, nm, p};
+    hipLaunchKernelGGL((grad_prep_kernel<DIM, MESH>), dim3((unsigned)((p.count + kPrepThreads - 1) / kPrepThreads)), dim3(kPrepThreads),
+                       stack_lds(std::max(levels_d, levels_n)), stream, P);
+    WOST_TRY(hipGetLastError());
+    return WOST_OK;
 }
 
 int grad_prep2(const DevMesh &dm, const DevMesh &nm, const GradPrep &p, hipStream_t stream)
 {
-    const GradPrepParams2 P{dm, nm, p, 256};
-    hipLaunchKernelGGL(grad_prep2_kernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), prep_lds(dm.levels, dm.n_segs > 0, nm.levels, nm.n_segs > 0),
-                       stream, P);
-    WOST_TRY(hipGetLastError());
-    return WOST_OK;
+    return grad_prep_launch<2>(dm, dm.n_segs > 0 ? dm.levels : 1, nm, nm.n_segs > 0 ? nm.levels : 1, p, stream);
 }
 
 int grad_prep3(const DevMesh3 &dm, const DevMesh3 &nm, const GradPrep &p, hipStream_t stream)
 {
-    const GradPrepParams3 P{dm, nm, p};
-    hipLaunchKernelGGL(grad_prep3_kernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), prep_lds(dm.levels, dm.n_tris > 0, nm.levels, nm.n_tris > 0),
-                       stream, P);
-    WOST_TRY(hipGetLastError());
-    return WOST_OK;
+    return grad_prep_launch<3>(dm, dm.n_tris > 0 ? dm.levels : 1, nm, nm.n_tris > 0 ? nm.levels : 1, p, stream);
 }
 
 // ---- the in-ball kernel --------------------------------------------------------------------------------------------------------
@@ -195,7 +140,7 @@ struct GradBallParams {
 
 // Thread t takes in-ball sample s = t % spp of point j = t / spp of the block.  It jumps to its place in the stream of pixel
 // seed_base + first + j -- behind the spp direction draws of the kernel in front, DIM - 1 floats each, and the s samples before
-// its own, DIM floats each --, draws a direction m as that kernel does and rho, and evaluates the source at the pair
+// its own, DIM floats each --, draws a direction m by that kernel's draw_direction and rho, and evaluates the source at the pair
 // x +- rho R m: every operation a single fp32 one in the order of include/wost.h ("In-ball samples"), no fused multiply-add.
 // A point whose radius is degenerate (NaN for an unselected and for a non-finite point) draws nothing: zeros.
 template <int DIM, class SRC>
@@ -214,16 +159,7 @@ __global__ __launch_bounds__(256) void grad_ball_kernel(GradBallParams<SRC> P)
         Pcg rng{0, 1};
         pcg_seed_pixel(rng, P.p.seed_base + P.p.first + j, P.p.seed_width);
         pcg_advance(rng, (int64_t)(DIM - 1) * P.p.spp + (int64_t)DIM * s);
-        float c, sn;
-        if (DIM == 2) {
-            sincos_2pi(pcg_next_float(rng), c, sn);
-            m[0] = c; m[1] = sn;
-        } else {
-            const float u1 = pcg_next_float(rng), u2 = pcg_next_float(rng);
-            sincos_2pi(u2, c, sn);
-            const float z = 1 - 2 * u1, r = sqrtf(1 - z * z);
-            m[0] = r * c; m[1] = r * sn; m[DIM - 1] = z;
-        }
+        draw_direction<DIM>(rng, m);
         const float rho = pcg_next_float(rng);
         const float r = rho * R;
         float yp[DIM], ym[DIM], fp[3], fm[3];
@@ -299,7 +235,8 @@ struct GradReduceParams {
     float *grad, *grad_stderr, *field, *radius_out, *first_out;
 };
 
-// One wave per point, its lanes over the point's walks, three passes (the mean, the estimate, its two-pass variance):
+// One wave per point, its lanes over the point's walks, three passes (the mean, the estimate, its two-pass variance:
+// grad_point_sums_from, grad_point_variance_from; with in-ball samples grad_ball_sums, grad_ball_variance -- wost_grad.h):
 //   mean_c = sum_s W_sc / S,   t_s = n_sk (W_sc - mean_c),   grad_kc = DIM / (R (S - 1)) sum_s t_s,
 //   stderr_kc = DIM / R sqrt(sum_s (t_s - mean t)^2 / (S - 1) / S);   a degenerate point: NaN, NaN and its mean.
 // The sums run in fp64 and the results are rounded once.  The control variate subtracts numbers of the size of u and leaves
@@ -316,40 +253,17 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceParams P)
     if (j >= P.count) return;      // (the whole wave)
     const int S = P.spp;
     const size_t i = (size_t)P.first + (size_t)j;
-    const float *w = P.w + 3 * (size_t)j * S, *d = P.dirs + DIM * (size_t)j * S;
+    const GradWalkArrays<DIM> load{P.w + 3 * (size_t)j * S, P.dirs + DIM * (size_t)j * S};
     const double dS = (double)S;
     double mean[3], t[DIM * 3], v[DIM * 3];
-    grad_point_sums<DIM>(w, d, S, lane, mean, t);
-#pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) v[e] = 0.0;
-    for (int s = lane; s < S; s += 64) {
-#pragma unroll
-        for (int e = 0; e < DIM * 3; ++e) {
-            const double dev = (double)d[DIM * s + e / 3] * ((double)w[3 * s + e % 3] - mean[e % 3]) - t[e] / dS;
-            v[e] += dev * dev;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < DIM * 3; ++e) v[e] = wave_sum(v[e]);
+    grad_point_sums_from<DIM>(load, S, lane, mean, t);
+    grad_point_variance_from<DIM>(load, S, lane, mean, t, v);
     const float R = P.radius[j];
     const bool degenerate = ball_degenerate(R, P.eps);
     double a[DIM * 3], u[3], va[DIM * 3];
     if (P.ball) {      // (the whole grid: P is uniform)
-        const float *b = P.ball + (size_t)j * S;
-        const size_t stride = P.ball_stride;
-        grad_ball_sums<DIM>(b, stride, S, lane, a, u);
-#pragma unroll
-        for (int e = 0; e < DIM * 3; ++e) va[e] = 0.0;
-        for (int s = lane; s < S; s += 64) {
-#pragma unroll
-            for (int e = 0; e < DIM * 3; ++e) {
-                const double dev = (double)b[(DIM + kBallWg) * stride + s] * (double)b[(e / 3) * stride + s] * (double)b[(DIM + kBallDs + e % 3) * stride + s] -
-                                   a[e] / dS;
-                va[e] += dev * dev;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < DIM * 3; ++e) va[e] = wave_sum(va[e]);
+        grad_ball_sums<DIM>(P.ball + (size_t)j * S, P.ball_stride, S, lane, a, u);
+        grad_ball_variance<DIM>(P.ball + (size_t)j * S, P.ball_stride, S, lane, a, va);
     }
     if (lane == 0) {
         const double scale = grad_scale<DIM>(R, S), scale_se = (double)DIM / (double)R;

@@ -37,9 +37,9 @@ struct GradAccumParams {
     double *G, *Q, *F;
 };
 
-// One wave per point of the block; a selected point's batch is reduced as grad_reduce_kernel reduces it (grad_point_sums and,
-// with in-ball samples, grad_ball_sums), so its fp32 gradient and mean have the bits of the single call, and lane 0 adds them
-// to the point's sums.
+// One wave per point of the block; a selected point's batch is reduced by the passes of grad_reduce_kernel (grad_point_sums_from
+// over GradWalkArrays and, with in-ball samples, grad_ball_sums), so its fp32 gradient and mean have the bits of the single
+// call, and lane 0 adds them to the point's sums.
 template <int DIM>
 __global__ __launch_bounds__(256) void gradlist_accumulate_kernel(GradAccumParams P)
 {
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void gradlist_accumulate_kernel(GradAccumParam
     if (P.sel[i] == 0) return;     // (the whole wave)
     const int S = P.spp;
     double mean[3], t[DIM * 3];
-    grad_point_sums<DIM>(P.w + 3 * (size_t)j * S, P.dirs + DIM * (size_t)j * S, S, lane, mean, t);
+    grad_point_sums_from<DIM>(GradWalkArrays<DIM>{P.w + 3 * (size_t)j * S, P.dirs + DIM * (size_t)j * S}, S, lane, mean, t);
     double a[DIM * 3], u[3];
     if (P.ball) grad_ball_sums<DIM>(P.ball + (size_t)j * S, P.ball_stride, S, lane, a, u);      // (the whole grid: P is uniform)
     if (lane != 0) return;

@@ -218,10 +218,10 @@ struct InitPointsParams {
 };
 
 // Thread t takes point i = first + t of the call: the stream of pixel seed_base + i in a
-// frame seed_width wide, pix = i, the rest as init_kernel writes it.  A point with a non-finite coordinate is never queued -- no walker may carry a NaN into a persistent launch -- and
-// its field entry is NaN.  A caller's point can lie thousands of extents from the mesh, where the descent opens every box
-// (closest_point_wave): beyond dm.huge2 the depth-0 query is that scan, through the ballot loop of the SLACK walk kernels --
-// the same candidates and the same tie rule as the descent, hence the same bits.
+// frame seed_width wide, pix = i, the rest as init_kernel writes it (the record is written out in both: a shared function
+// changes init_kernel's code, EXPERIMENTS 51).  A point with a non-finite coordinate is never queued -- no walker may carry a
+// NaN into a persistent launch -- and its field entry is NaN.  A caller's point can lie thousands of extents from the mesh,
+// where the descent opens every box: the depth-0 query is closest_point_lockstep, which scans by the wave beyond dm.huge2.
 __global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
 {
     extern __shared__ uint32_t lds_stack[];
@@ -242,23 +242,8 @@ __global__ __launch_bounds__(256) void init_points_kernel(InitPointsParams P)
         f[0] = z; f[1] = z; f[2] = z;
     }
     Pcg rng{0, 1};
-    Closest c0{WOST_INF, -1};
-    bool huge = false;
-    if (active) {
-        pcg_seed_pixel(rng, P.seed_base + pid, P.seed_width);
-        if (P.dm.n_segs > 0) {
-            c0 = slot_candidate(P.dm, 0, x0, y0);
-            huge = c0.d2 > P.dm.huge2;
-            if (!huge) c0 = closest_point(P.dm, x0, y0, c0, stack, P.stack_stride);
-        }
-    }
-    unsigned long long hb = __ballot(huge);
-    while (hb) {
-        const int src = __builtin_ctzll(hb);
-        const Closest r = closest_point_wave(P.dm, __shfl(x0, src), __shfl(y0, src));
-        if ((int)(threadIdx.x & 63) == src) c0 = r;
-        hb &= hb - 1;
-    }
+    if (active) pcg_seed_pixel(rng, P.seed_base + pid, P.seed_width);
+    const Closest c0 = closest_point_lockstep(P.dm, x0, y0, active, stack, P.stack_stride);
     float sr = 0.0f, sg = 0.0f, sb = 0.0f;
     if (active && P.carry_n != nullptr && P.carry_n[pid] > 0u) {
         rng.state = P.carry_rng[pid];
@@ -1129,14 +1114,13 @@ __global__ __launch_bounds__(256) void closest_point_kernel(DevMesh m, const flo
     if (i >= n) return;
     const float qx = pts[2 * i], qy = pts[2 * i + 1];
     const Closest c = closest_point(m, qx, qy, slot_candidate(m, 0, qx, qy), stack, stack_stride);
-    const float4 a = m.segA[c.slot];
-    const float inv = m.segInv[c.slot];
-    const float wx = qx - a.x, wy = qy - a.y;
-    const float cr = cross2(a.z, a.w, wx, wy);
+    float uv;
+    int32_t side;
+    segment_uv_side(m, c.slot, qx, qy, uv, side);
     if (out_idx) out_idx[i] = m.segOrig[c.slot];
     if (out_dist) out_dist[i] = sqrtf(c.d2);
-    if (out_uv) out_uv[i] = dot2(wx, wy, a.z, a.w) * inv;
-    if (out_side) out_side[i] = (0.0f < cr) - (cr < 0.0f);
+    if (out_uv) out_uv[i] = uv;
+    if (out_side) out_side[i] = side;
 }
 
 __global__ __launch_bounds__(256) void sdf_kernel(DevMesh m, DevProbe probe, int width, int height, int which,
@@ -2260,13 +2244,14 @@ struct ExitWalkParams {
     int32_t stack_stride;
 };
 
-// One lane per walk, in lock step to the walk's end: the depth-0 query as init_points_kernel makes it (the far-point scan
-// included), every later query seeded with the lane's hint as the round kernels seed it -- the plain visits within dm.far2, the
-// slack ones beyond, the scan by the wave beyond dm.huge2 --, and between two queries the unchanged step_finish with the flags
+// One lane per walk, in lock step to the walk's end: the depth-0 query of init_points_kernel (closest_point_lockstep, the
+// far-point scan included), every later query seeded with the lane's hint as the round kernels seed it -- the plain visits
+// within dm.far2, the slack ones beyond, the scan by the wave beyond dm.huge2 (closest_point_scan_huge) --, and between two
+// queries the unchanged step_finish with the flags
 // of the handle's point solve, not chained.  So walk w takes the steps of wost_solve_points of one sample at its point on the
 // stream of pixel walk_seed_base + w, bit for bit; the lane keeps the throughput and the sums as they stood before each step,
-// and when the step absorbs -- L.hint the slot, L.px, L.py still the absorbed position -- it forms uv and side again with the
-// step's own expressions and writes the record.  Cold path beside the scheduled kernels: no queue, no rounds.
+// and when the step absorbs -- L.hint the slot, L.px, L.py still the absorbed position -- it forms uv and side as the batch
+// query reports them (segment_uv_side) and writes the record.  Cold path beside the scheduled kernels: no queue, no rounds.
 template <bool NEUMANN_EMISSIVE, bool NEUMANN_TREE, bool SOURCE>
 __global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
 {
@@ -2287,23 +2272,8 @@ __global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
     bool alive = owned && finite;
     Lane L{};
     L.rng = Pcg{0, 1};
-    Closest cp{WOST_INF, -1};
-    bool huge = false;
-    if (alive) {
-        pcg_seed_pixel(L.rng, P.w.walk_seed_base + w, P.w.seed_width);
-        if (has_d) {
-            cp = slot_candidate(P.dm, 0, x0, y0);
-            huge = cp.d2 > P.dm.huge2;
-            if (!huge) cp = closest_point(P.dm, x0, y0, cp, stack, P.stack_stride);
-        }
-    }
-    unsigned long long hb = __ballot(huge);
-    while (hb) {
-        const int src = __builtin_ctzll(hb);
-        const Closest r = closest_point_wave(P.dm, __shfl(x0, src), __shfl(y0, src));
-        if ((int)(threadIdx.x & 63) == src) cp = r;
-        hb &= hb - 1;
-    }
+    if (alive) pcg_seed_pixel(L.rng, P.w.walk_seed_base + w, P.w.seed_width);
+    Closest cp = closest_point_lockstep(P.dm, x0, y0, alive, stack, P.stack_stride);
     L.x0 = x0; L.y0 = y0; L.px = x0; L.py = y0;
     L.hint = cp.slot;
     L.thp = 1.0f;
@@ -2323,18 +2293,13 @@ __global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
             c_nhits += (status >> 3) & 1u;
             if (status & STEP_ABSORBED) {
                 slot = L.hint;
-                const float4 a = P.dm.segA[slot];
-                const float inv = P.dm.segInv[slot];
-                const float wx = L.px - a.x, wy = L.py - a.y;
-                uv = dot2(wx, wy, a.z, a.w) * inv;
-                const float cr = cross2(a.z, a.w, wx, wy);
-                side = (0.0f < cr) - (cr < 0.0f);
+                segment_uv_side(P.dm, slot, L.px, L.py, uv, side);
             } else if (status & STEP_ENDED) {
                 thp = L.thp; br = L.sr; bg = L.sg; bb = L.sb;
             }
             if (status & STEP_ENDED) alive = false;
         }
-        huge = false;
+        bool huge = false;
         if (alive && has_d) {
             cp = slot_candidate(P.dm, L.hint, L.px, L.py);
             if (cp.d2 > P.dm.huge2) {
@@ -2351,13 +2316,7 @@ __global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
                 cp = T.best;
             }
         }
-        hb = __ballot(huge);
-        while (hb) {
-            const int src = __builtin_ctzll(hb);
-            const Closest r = closest_point_wave(P.dm, __shfl(L.px, src), __shfl(L.py, src));
-            if ((int)(threadIdx.x & 63) == src) cp = r;
-            hb &= hb - 1;
-        }
+        closest_point_scan_huge(P.dm, L.px, L.py, huge, cp);
     }
     if (owned) {
         const ExitRecords &R = P.w.rec;
@@ -2368,14 +2327,7 @@ __global__ __launch_bounds__(256) void exits2_kernel(ExitWalkParams P)
         R.thp()[w] = thp;
         R.base(2, 0)[w] = br; R.base(2, 1)[w] = bg; R.base(2, 2)[w] = bb;
     }
-    uint32_t v[5] = {c_steps, c_started, c_absorbed, c_truncated, c_nhits};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        uint32_t x = v[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-        if ((threadIdx.x & 63) == 0 && x) atomicAdd(P.w.counters + k, (unsigned long long)x);
-    }
+    wave_add_counters(P.w.counters, c_steps, c_started, c_absorbed, c_truncated, c_nhits);
 }
 
 }  // namespace wost

@@ -670,12 +670,16 @@ __global__ __launch_bounds__(256) void closest_point3_kernel(DevMesh3 m, const f
     if (i >= n) return;
     const V3 q = v3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
     const Closest cp = closest_triangle(m, q, -1, stk);
-    const float4 a = m.tri[3 * (size_t)cp.slot], b = m.tri[3 * (size_t)cp.slot + 1], c = m.tri[3 * (size_t)cp.slot + 2];
-    const V3 p0 = v3(a.x, a.y, a.z), e0 = v3(b.x, b.y, b.z) - p0, e1 = v3(c.x, c.y, c.z) - p0;
+    float u, v;
+    int32_t side;
+    triangle_uv_side(m, cp.slot, q, u, v, side);
     if (out_idx) out_idx[i] = m.triOrig[cp.slot];
     if (out_dist) out_dist[i] = sqrtf(cp.d2);
-    if (out_uv) tri_uv(p0, e0, e1, q, out_uv[2 * i], out_uv[2 * i + 1]);
-    if (out_side) out_side[i] = tri_side(p0, cross3(e0, e1), q);
+    if (out_uv) {
+        out_uv[2 * i] = u;
+        out_uv[2 * i + 1] = v;
+    }
+    if (out_side) out_side[i] = side;
 }
 
 // debug channels at the evaluation points of the frame
@@ -1214,12 +1218,12 @@ struct ExitWalk3Params {
     ExitWalk w;
 };
 
-// One lane per walk, in lock step to the walk's end, as exits2_kernel: the depth-0 query without a hint -- the scan by the wave
-// where the boxes of the root's children all lie beyond dm.huge2, the descent otherwise (depth0_distance3 of the gradient's
-// kernel in front makes the same choice; both answers are exact, lowest original index among equal distances) --, every later
-// query seeded with the lane's hint as walk3_kernel's begin_step seeds it, and between two queries the unchanged step3 with the
-// flags of the handle's point solve.  When step3_a absorbs (the lane's absorbed count moves; L.hint is the slot, L.p still the
-// absorbed position) the lane forms side, u and v again with the step's own expressions and writes the record.
+// One lane per walk, in lock step to the walk's end, as exits2_kernel: the depth-0 query without a hint, the steps of the
+// gradient's kernel in front (closest_triangle_lockstep: the scan by the wave where root_beyond_huge3 finds the boxes of the
+// root's children all beyond dm.huge2, the descent otherwise), every later query seeded with the lane's hint as walk3_kernel's begin_step seeds
+// it and scanned beyond dm.huge2 (closest_triangle_scan_huge), and between two queries the unchanged step3 with the flags of
+// the handle's point solve.  When step3_a absorbs (the lane's absorbed count moves; L.hint is the slot, L.p still the absorbed
+// position) the lane forms side, u and v as the batch query reports them (triangle_uv_side) and writes the record.
 // (One wave per SIMD asked for, as walk3_kernel: the instantiations take 114 to 133 registers.  The cap of 100 scalar registers:
 // with the default of 102 the instantiation with every flag set keeps a private segment of 36 bytes per lane for scalar spills
 // that end up in register lanes -- never addressed, but reserved per lane at launch; under the cap every instantiation reports
@@ -1250,13 +1254,12 @@ __global__ __launch_bounds__(kWalk3Threads, 1) __attribute__((amdgpu_num_sgpr(10
     int32_t slot = -1, side = 0;
     float u = finite ? 0.0f : __int_as_float(0x7fc00000), v = u, thp = u, base[3] = {u, u, u};
     // ---- the closest Dirichlet triangle of the evaluation point: no hint ----
+    // (closest_triangle_lockstep, written out: through the call two instantiations come out of register allocation with a
+    // private segment or a wave per SIMD less -- EXPERIMENTS 51)
     Trav T = trav_begin(Closest{WOST_INF, -1});
     bool huge = false;
     if (alive && has_d) {
-        const float4 LX = P.dm.nodes[0], LY = P.dm.nodes[1], LZ = P.dm.nodes[2], HX = P.dm.nodes[3], HY = P.dm.nodes[4], HZ = P.dm.nodes[5];
-        const float d0 = aabb_d2(LX.x, LY.x, LZ.x, HX.x, HY.x, HZ.x, q), d1 = aabb_d2(LX.y, LY.y, LZ.y, HX.y, HY.y, HZ.y, q);
-        const float d2 = aabb_d2(LX.z, LY.z, LZ.z, HX.z, HY.z, HZ.z, q), d3 = aabb_d2(LX.w, LY.w, LZ.w, HX.w, HY.w, HZ.w, q);
-        huge = fminf(fminf(d0, d1), fminf(d2, d3)) > P.dm.huge2;
+        huge = root_beyond_huge3(P.dm, q);
         if (!huge) {
             while (trav_visit3(P.dm, q, T, stk)) {
             }
@@ -1280,10 +1283,7 @@ __global__ __launch_bounds__(kWalk3Threads, 1) __attribute__((amdgpu_num_sgpr(10
             bool ended = step3<EMISSIVE, SOURCE, NTREE>(P, L, T.best, stk);
             if (L.c_absorbed != absorbed_before) {
                 slot = L.hint;
-                const float4 a = P.dm.tri[3 * (size_t)slot], b = P.dm.tri[3 * (size_t)slot + 1], c = P.dm.tri[3 * (size_t)slot + 2];
-                const V3 p0 = v3(a.x, a.y, a.z), e0 = v3(b.x, b.y, b.z) - p0, e1 = v3(c.x, c.y, c.z) - p0;
-                side = tri_side(p0, cross3(e0, e1), L.p);
-                tri_uv(p0, e0, e1, L.p, u, v);
+                triangle_uv_side(P.dm, slot, L.p, u, v, side);
             } else {
                 if (!ended) {
                     ++L.depth;
@@ -1315,13 +1315,7 @@ __global__ __launch_bounds__(kWalk3Threads, 1) __attribute__((amdgpu_num_sgpr(10
                 }
             }
         }
-        hb = __ballot(huge);
-        while (hb) {
-            const int src = __builtin_ctzll(hb);
-            const Closest r = closest_triangle_wave(P.dm, v3(__shfl(L.p.x, src), __shfl(L.p.y, src), __shfl(L.p.z, src)));
-            if (lane == src) T.best = r;
-            hb &= hb - 1;
-        }
+        closest_triangle_scan_huge(P.dm, L.p, huge, T.best);
     }
     if (owned) {
         const ExitRecords &R = X.w.rec;
@@ -1333,14 +1327,7 @@ __global__ __launch_bounds__(kWalk3Threads, 1) __attribute__((amdgpu_num_sgpr(10
 #pragma unroll
         for (int k = 0; k < 3; ++k) R.base(3, k)[w] = base[k];
     }
-    uint32_t cnt[5] = {L.c_steps, L.c_started, L.c_absorbed, L.c_truncated, L.c_nhits};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        uint32_t x = cnt[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-        if (lane == 0 && x) atomicAdd(X.w.counters + k, (unsigned long long)x);
-    }
+    wave_add_counters(X.w.counters, L.c_steps, L.c_started, L.c_absorbed, L.c_truncated, L.c_nhits);
 }
 
 }  // namespace wost

@@ -126,13 +126,17 @@ def _mixed_cube():
 
 
 def test_3d_blocks_match_the_emulation_and_a_cut_list_gives_the_same_bits(oracle):
-    """100 points in blocks of 32, 32, 32 and 4"""
+    """100 points in blocks of 32, 32, 32 and 4; one of them hundreds of extents away, where both queries of the kernel in front
+    are the scan by the wave: its radius has the bits of the handle's batch closest-point queries"""
     sd = _mixed_cube()
     pts = np.random.default_rng(7).uniform(0.05, 0.95, size=(100, 3)).astype(np.float32)
+    pts[3] = (300.0, -200.0, 40.0)
     it = _it3(sd, 16, 16, BOX["S"], BOX["depth"], BOX["eps"])
     out, stats = _gradient(it, pts, BOX["seed_base"], BOX["walk_seed_base"], BOX["seed_width"])
     joined = _cut(it, pts, 41, BOX["S"], BOX["seed_base"], BOX["walk_seed_base"], BOX["seed_width"])
+    dD, dN = it.closest_point(pts[3:4])[1][0], it.closest_point(pts[3:4], which=1)[1][0]
     it.close()
+    assert dD > 300.0 and out["radius"][3] == min(dD, ge.NEUMANN_SHRINK * dN)
     emu = ge.emulate(oracle, "cube", sd, pts, out["first_pts"], BOX["seed_base"], BOX["walk_seed_base"], BOX["seed_width"], BOX["depth"], BOX["eps"], 3)
     ge.assert_matches(out, stats, emu, pts)
     assert not emu["degenerate"].any() and stats["walks_started"] == 100 * BOX["S"]
