@@ -207,6 +207,7 @@ FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_double, C.PO
 _pf, _pi, _pu8, _pu64, _pd = (C.POINTER(t) for t in (C.c_float, C.c_int32, C.c_uint8, C.c_uint64, C.c_double))
 _h, _dev, _i32, _st, _gst = C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Stats), C.POINTER(GuidedStats)      # _dev: a device array or a stream
 _gco = C.POINTER(GradientCarriedOut)
+_pi64 = C.POINTER(C.c_int64)
 _BOTH = {
     "destroy": [_h],
     "solve": [_h, _i32, _i32, _pf, _st],
@@ -263,6 +264,14 @@ _BOTH = {
     "exits_apply_gradient_dev": [_h, _dev, _i32, _dev, _dev, _dev, _dev],
     "exits_adjoint_gradient": [_h, _pf, _i32, _pf],
     "exits_adjoint_gradient_dev": [_h, _dev, _i32, _dev, _dev],
+    # the index of the exit list and the ordered adjoints (wost_exits_index & co.)
+    "exits_index": [_h],
+    "exits_index_info": [_h, _pi64, _pi64],
+    "exits_index_records": [_h, _pi64, _pi],
+    "exits_adjoint_ordered": [_h, _pf, _i32, _pf],
+    "exits_adjoint_ordered_dev": [_h, _dev, _i32, _dev, _dev],
+    "exits_adjoint_gradient_ordered": [_h, _pf, _i32, _pf],
+    "exits_adjoint_gradient_ordered_dev": [_h, _dev, _i32, _dev, _dev],
     # the batch queries
     "render_sdf": [_h, C.c_int, _pf],
     "render_source": [_h, _pf],

@@ -6,7 +6,9 @@
 // list, the two kernels behind it and the bodies of the entry points are here and in wost_exits.hip.  The list of the gradient
 // (wost_exits_walk_gradient & co., "Exit lists of the gradient") is the same list walked from the first points of
 // the gradient's estimator (wost_grad.h) and kept with their directions and radii: grad u for any Dirichlet data and the
-// transpose of that map are two more kernels over the same records.  Not part of the C-ABI.
+// transpose of that map are two more kernels over the same records.  The index of a list by vertex (wost_exits_index & co., "Exit
+// lists: the index and the ordered adjoint"; built in wost_exits_index.hip) turns both transposes into gathers
+// with a fixed summation order.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,14 +42,27 @@ struct ExitRecords {
 // of the gradient (wost_exits_walk_gradient) has three more arrays in it, behind the records: per point the radius
 // of its first ball, per walk its direction and its first point, dim floats each, interleaved per walk as GradPrep writes them
 // -- 4 * (6 + 3 dim) bytes per walk and 4 per point in all.  A plain list has none of them (dirs == nullptr).
+// The index of a list by vertex (wost_exits_index), one allocation of its own: incidence w * DIM + j is corner j of
+// the primitive of absorbed walk w, its bin 2 v + (side < 0) with v the corner's vertex in the caller's numbering; a bin holds
+// its incidences ascending.  nbar (a list of the gradient only): per point and axis the mean direction as
+// exits_adjoint_gradient_kernel forms it.  mem == nullptr: no index stands.
+struct ExitIndex {
+    void *mem = nullptr;
+    int64_t *bin_begin = nullptr;      // 2 n_verts + 1
+    double *nbar = nullptr;            // n * DIM, or nullptr
+    int32_t *inc = nullptr;            // n_inc
+    int64_t n_inc = 0, longest_bin = 0;
+};
 struct ExitList {
     void *mem = nullptr;
     ExitRecords rec;
     int dim = 0;
     int32_t n = 0, S = 0;
     float *radius = nullptr, *dirs = nullptr, *first = nullptr;
+    ExitIndex index;                   // lives and dies with the list: whatever replaces or releases the list drops it
 };
 void exits_free(ExitList &l);
+void exits_index_free(ExitIndex &x);
 
 // One launch of a dimension's walk kernel: the `count` walks from walk `first_walk` of the list on, one lane each.  Walk w
 // belongs to point w / S of pts and runs on the stream of pixel walk_seed_base + w of a frame seed_width wide.  counters: five
@@ -117,6 +132,16 @@ int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &
 // grad is required, se and field may be nullptr
 int exits_apply_gradient(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, bool on_host, hipStream_t stream);
 int exits_adjoint_gradient(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
+
+// ---- the index and the ordered adjoints (include/wost.h "Exit lists: the index and the ordered adjoint") ----
+// a device allocation that may fail for want of memory: WOST_ERR_NOMEM then, WOST_ERR_DEVICE for anything else
+int exits_alloc(void **p, size_t bytes, const char *what);
+// the index of the bound list, built on the default stream (wost_exits_index.hip); the list's old index, if any, stays on failure
+int exits_index_build(const ExitCall &c);
+int exits_index_records(const ExitCall &c, int64_t *bin_begin, int32_t *inc);
+// the gathers over the index: the arguments and layouts of exits_adjoint and exits_adjoint_gradient
+int exits_adjoint_ordered(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
+int exits_adjoint_gradient_ordered(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
 
 // the bodies of the entry points, written once: H is the context (device, stream, exits), `call` what a dimension adds
 template <class H>
@@ -212,6 +237,56 @@ struct ExitCalls {
         if (rc == WOST_OK) rc = bound_gradient(h);
         if (rc != WOST_OK) return rc;
         return exits_adjoint_gradient(call(h), dgrad, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    // ---- the index and the ordered adjoints ----
+    static int indexed(const H *h)
+    {
+        if (!h->exits.index.mem)
+            return set_error(WOST_ERR_INVALID, "the exit list bound to the handle has no index (wost_exits_index builds one)");
+        return WOST_OK;
+    }
+    int index(H *h) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        const int rc = bound(h);
+        if (rc != WOST_OK) return rc;
+        const ExitCall c = call(h);
+        if (c.n_verts <= 0)
+            return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_index: the scene has no Dirichlet mesh, so no walk exits at a vertex");
+        if (h->exits.index.mem) return WOST_OK;
+        return exits_index_build(c);
+    }
+    int index_info(H *h, int64_t *n_incidences, int64_t *longest_bin) const
+    {
+        if (!h || !n_incidences || !longest_bin) return set_error(WOST_ERR_INVALID, "null argument");
+        *n_incidences = h->exits.index.mem ? h->exits.index.n_inc : 0;
+        *longest_bin = h->exits.index.mem ? h->exits.index.longest_bin : 0;
+        return WOST_OK;
+    }
+    int index_records(H *h, int64_t *bin_begin, int32_t *inc) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        int rc = bound(h);
+        if (rc == WOST_OK) rc = indexed(h);
+        if (rc != WOST_OK) return rc;
+        return exits_index_records(call(h), bin_begin, inc);
+    }
+    int adjoint_ordered(H *h, const float *dfield, int32_t K, float *dcolors, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, dfield, K, dcolors, "dfield", "dcolors");
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc == WOST_OK) rc = indexed(h);
+        if (rc != WOST_OK) return rc;
+        return exits_adjoint_ordered(call(h), dfield, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int adjoint_gradient_ordered(H *h, const float *dgrad, int32_t K, float *dcolors, bool on_host, void *stream) const
+    {
+        int rc = exits_check_apply(h, dgrad, K, dcolors, "dgrad", "dcolors");
+        if (rc == WOST_OK) rc = bound(h);
+        if (rc == WOST_OK) rc = indexed(h);
+        if (rc == WOST_OK) rc = bound_gradient(h);
+        if (rc != WOST_OK) return rc;
+        return exits_adjoint_gradient_ordered(call(h), dgrad, K, dcolors, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
     }
     int progress(H *h, int32_t *n_points, int32_t *walks) const
     {

@@ -314,15 +314,102 @@ __global__ __launch_bounds__(256) void exits_adjoint_gradient_kernel(ExitAdjoint
     }
 }
 
+// ---- the ordered adjoints: gathers over the index of the list -------------------------------------------------
+struct ExitOrderedParams {
+    ExitRecords rec;
+    const int32_t *verts;
+    const float *in;                 // dfield (K * n * 3) or dgrad (K * n * DIM * 3)
+    const float *radius, *dirs;      // the list's (the gradient form)
+    const double *nbar;              // the index's: n * DIM (the gradient form)
+    const int64_t *bin_begin;        // 2 * n_verts + 1
+    const int32_t *inc;
+    int32_t n, S, K, n_verts;
+    float intensity, eps;
+    float *out;                      // K * n_verts * 6
+};
+
+// One wave per (bin, set): the wave of bin b = 2 v + (side < 0) and set k owns the three entries dcolors[k][v][off + c].  Its
+// lanes take the bin's incidences at positions lane, lane + 64, ... in that order; for incidence w * DIM + j a lane forms the
+// term of walk w and corner j, factor by factor as the scatter kernels do, and adds it to its three fp64 sums, which start at
+// +0.0.  Then one wave_sum per channel, one rounding to fp32 and a plain store by lane 0: no scratch array, no atomic, and an
+// order that is a function of the list alone.  GRAD: the terms of exits_adjoint_gradient_kernel with nbar from the index; an
+// incidence of a degenerate point is skipped and its dgrad is not read.  An empty bin stores +0.0f.
+template <int DIM, bool GRAD>
+__device__ __forceinline__ void exits_ordered_wave(const ExitOrderedParams &P)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t bins = 2 * (size_t)P.n_verts;
+    const size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= bins * (size_t)P.K) return;      // (the whole wave)
+    const size_t k = g / bins, b = g % bins;
+    const int64_t begin = P.bin_begin[b], end = P.bin_begin[b + 1];
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t p = begin + lane; p < end; p += 64) {
+        const int32_t inc = P.inc[p];
+        const size_t w = (size_t)(inc / DIM);
+        const int j = inc % DIM;
+        const size_t i = w / (size_t)P.S;
+        const ExitRec<DIM> e = exit_load<DIM>(P.rec, P.verts, w);
+        float wgt[DIM];
+        exit_weights<DIM>(e, wgt);
+        const float w_v = j == 0 ? wgt[0] : (j == 1 ? wgt[1] : wgt[DIM - 1]);
+        if (GRAD) {
+            const float R = P.radius[i];
+            if (ball_degenerate(R, P.eps)) continue;
+            const double scale = grad_scale<DIM>(R, P.S);
+            double cen[DIM];
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) cen[a] = (double)P.dirs[DIM * w + a] - P.nbar[DIM * i + a];
+            const float *dg = P.in + (k * (size_t)P.n + i) * (DIM * 3);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                double q = (double)dg[c] * scale * cen[0];
+#pragma unroll
+                for (int a = 1; a < DIM; ++a) q += (double)dg[3 * a + c] * scale * cen[a];
+                acc[c] += q * (double)P.intensity * (double)e.thp * (double)w_v;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                acc[c] += (double)P.in[(k * (size_t)P.n + i) * 3 + c] / (double)P.S * (double)P.intensity * (double)e.thp * (double)w_v;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = wave_sum(acc[c]);
+    if (lane == 0) {
+        float *out = P.out + (k * (size_t)P.n_verts + (b >> 1)) * 6 + ((b & 1) ? 3 : 0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c] = (float)acc[c];
+    }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_adjoint_ordered_kernel(ExitOrderedParams P)
+{
+    exits_ordered_wave<DIM, false>(P);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_adjoint_gradient_ordered_kernel(ExitOrderedParams P)
+{
+    exits_ordered_wave<DIM, true>(P);
+}
+
 // ---- the driver -------------------------------------------------------------------------------------------------------------
+void exits_index_free(ExitIndex &x)
+{
+    if (x.mem) (void)hipFree(x.mem);
+    x = ExitIndex{};
+}
+
 void exits_free(ExitList &l)
 {
+    exits_index_free(l.index);
     if (l.mem) (void)hipFree(l.mem);
     l = ExitList{};
 }
 
-// a device allocation that may fail for want of memory: WOST_ERR_NOMEM then, WOST_ERR_DEVICE for anything else
-static int exits_alloc(void **p, size_t bytes, const char *what)
+int exits_alloc(void **p, size_t bytes, const char *what)
 {
     const hipError_t e = hipMalloc(p, bytes);
     if (e == hipErrorOutOfMemory) {
@@ -567,41 +654,83 @@ int exits_apply_gradient(const ExitCall &c, const float *colors, int32_t K, floa
     return b.finish();
 }
 
-// the frame both adjoints share: the zeroed fp64 sums, the input and the output staged for a host call, `launch` (the scatter
-// into acc from the input on the device), the rounding kernel, the fetch
-static int exits_adjoint_run(const ExitCall &c, const char *name, const float *in, size_t n_in, const char *in_name, int32_t K, float *dcolors, bool on_host,
-                             hipStream_t stream, const std::function<void(const float *d_in, double *acc)> &launch)
+// the frame all adjoints share: the input and the output staged for a host call, `launch` (the kernels from the input on the
+// device to dcolors on the device; it may hand the batch scratch of its own), the fetch
+static int exits_adjoint_frame(const ExitCall &c, const char *name, const float *in, size_t n_in, const char *in_name, int32_t K, float *dcolors, bool on_host,
+                               hipStream_t stream, const std::function<int(Batch &b, const float *d_in, float *d_out)> &launch)
 {
     if (c.n_verts <= 0)
         return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + name + ": the scene has no Dirichlet mesh, so there are no colours to differentiate by");
     WOST_TRY(hipSetDevice(c.device));
     const size_t n_colors = (size_t)K * c.n_verts * 6;
     Batch b{stream};
-    void *acc = nullptr;
-    int rc = exits_alloc(&acc, n_colors * sizeof(double), "the fp64 sums of the adjoint");
-    if (rc != WOST_OK) return rc;
-    b.scratch.ptrs.push_back(acc);
     const float *d_in = in;
     float *d_out = dcolors;
+    int rc = WOST_OK;
     if (on_host) {
         float *staged = nullptr;
         if ((rc = exits_stage(b, &staged, n_in, in_name)) != WOST_OK || (rc = exits_stage(b, &d_out, n_colors, "dcolors")) != WOST_OK) return rc;
         WOST_TRY(hipMemcpyAsync(staged, in, n_in * sizeof(float), hipMemcpyHostToDevice, stream));
         d_in = staged;
     }
-    WOST_TRY(hipMemsetAsync(acc, 0, n_colors * sizeof(double), stream));
-    launch(d_in, static_cast<double *>(acc));
-    rc = hipGetLastError() == hipSuccess ? WOST_OK : set_error(WOST_ERR_DEVICE, "the adjoint kernel could not be launched");
-    if (rc == WOST_OK) {
-        hipLaunchKernelGGL(exits_round_kernel, dim3((unsigned)((n_colors + 255) / 256)), dim3(256), 0, stream, static_cast<const double *>(acc), d_out, n_colors);
-        if (hipGetLastError() != hipSuccess) rc = set_error(WOST_ERR_DEVICE, "the rounding kernel of the adjoint could not be launched");
-    }
-    if (rc != WOST_OK) {
+    if ((rc = launch(b, d_in, d_out)) != WOST_OK) {
         (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
         return rc;
     }
     if (on_host) WOST_TRY(b.fetch(dcolors, d_out, n_colors));
     return b.finish();
+}
+
+// the scattering adjoints in that frame: the zeroed fp64 sums, `scatter` (the atomic adds into acc), the rounding kernel
+static int exits_adjoint_run(const ExitCall &c, const char *name, const float *in, size_t n_in, const char *in_name, int32_t K, float *dcolors, bool on_host,
+                             hipStream_t stream, const std::function<void(const float *d_in, double *acc)> &scatter)
+{
+    const size_t n_colors = (size_t)K * std::max(c.n_verts, 0) * 6;
+    return exits_adjoint_frame(c, name, in, n_in, in_name, K, dcolors, on_host, stream, [&](Batch &b, const float *d_in, float *d_out) {
+        void *acc = nullptr;
+        const int rc = exits_alloc(&acc, n_colors * sizeof(double), "the fp64 sums of the adjoint");
+        if (rc != WOST_OK) return rc;
+        b.scratch.ptrs.push_back(acc);
+        WOST_TRY(hipMemsetAsync(acc, 0, n_colors * sizeof(double), stream));
+        scatter(d_in, static_cast<double *>(acc));
+        if (hipGetLastError() != hipSuccess) return set_error(WOST_ERR_DEVICE, "the adjoint kernel could not be launched");
+        hipLaunchKernelGGL(exits_round_kernel, dim3((unsigned)((n_colors + 255) / 256)), dim3(256), 0, stream, static_cast<const double *>(acc), d_out, n_colors);
+        if (hipGetLastError() != hipSuccess) return set_error(WOST_ERR_DEVICE, "the rounding kernel of the adjoint could not be launched");
+        return (int)WOST_OK;
+    });
+}
+
+// the gathering adjoints in that frame: one kernel, one wave per (bin, set), straight into dcolors
+static int exits_ordered_run(const ExitCall &c, const char *name, const float *in, size_t n_in, const char *in_name, int32_t K, float *dcolors, bool on_host,
+                             hipStream_t stream, bool gradient)
+{
+    const ExitList &l = *c.list;
+    return exits_adjoint_frame(c, name, in, n_in, in_name, K, dcolors, on_host, stream, [&](Batch &, const float *d_in, float *d_out) {
+        const ExitOrderedParams P{l.rec, c.verts, d_in, l.radius, l.dirs, l.index.nbar, l.index.bin_begin, l.index.inc, l.n, l.S, K, c.n_verts,
+                                  c.dirichlet_intensity, c.eps, d_out};
+        const size_t waves = 2 * (size_t)c.n_verts * (size_t)K;
+        if ((waves + 3) / 4 > 0x7fffffffu) return set_error(WOST_ERR_INVALID, std::string(c.prefix) + name + ": K * n_verts is too large for one launch");
+        const dim3 grid((unsigned)((waves + 3) / 4));
+        if (gradient) {
+            if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_gradient_ordered_kernel<2>, grid, dim3(256), 0, stream, P);
+            else hipLaunchKernelGGL(exits_adjoint_gradient_ordered_kernel<3>, grid, dim3(256), 0, stream, P);
+        } else {
+            if (c.dim == 2) hipLaunchKernelGGL(exits_adjoint_ordered_kernel<2>, grid, dim3(256), 0, stream, P);
+            else hipLaunchKernelGGL(exits_adjoint_ordered_kernel<3>, grid, dim3(256), 0, stream, P);
+        }
+        if (hipGetLastError() != hipSuccess) return set_error(WOST_ERR_DEVICE, "the ordered adjoint kernel could not be launched");
+        return (int)WOST_OK;
+    });
+}
+
+int exits_adjoint_ordered(const ExitCall &c, const float *dfield, int32_t K, float *dcolors, bool on_host, hipStream_t stream)
+{
+    return exits_ordered_run(c, "exits_adjoint_ordered", dfield, (size_t)K * c.list->n * 3, "dfield", K, dcolors, on_host, stream, false);
+}
+
+int exits_adjoint_gradient_ordered(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream)
+{
+    return exits_ordered_run(c, "exits_adjoint_gradient_ordered", dgrad, (size_t)K * c.list->n * 3 * (size_t)c.dim, "dgrad", K, dcolors, on_host, stream, true);
 }
 
 int exits_adjoint_gradient(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream)

@@ -2429,4 +2429,30 @@ int wost_exits_adjoint_gradient_dev(wost_handle h, const float *dgrad_dev, int32
     return kExits.adjoint_gradient(h, dgrad_dev, K, dcolors_dev, false, stream);
 }
 
+int wost_exits_index(wost_handle h) { return kExits.index(h); }
+
+int wost_exits_index_info(wost_handle h, int64_t *n_incidences, int64_t *longest_bin) { return kExits.index_info(h, n_incidences, longest_bin); }
+
+int wost_exits_index_records(wost_handle h, int64_t *bin_begin, int32_t *inc) { return kExits.index_records(h, bin_begin, inc); }
+
+int wost_exits_adjoint_ordered(wost_handle h, const float *dfield, int32_t K, float *dcolors)
+{
+    return kExits.adjoint_ordered(h, dfield, K, dcolors, true, nullptr);
+}
+
+int wost_exits_adjoint_ordered_dev(wost_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits.adjoint_ordered(h, dfield_dev, K, dcolors_dev, false, stream);
+}
+
+int wost_exits_adjoint_gradient_ordered(wost_handle h, const float *dgrad, int32_t K, float *dcolors)
+{
+    return kExits.adjoint_gradient_ordered(h, dgrad, K, dcolors, true, nullptr);
+}
+
+int wost_exits_adjoint_gradient_ordered_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits.adjoint_gradient_ordered(h, dgrad_dev, K, dcolors_dev, false, stream);
+}
+
 }  // extern "C"

@@ -1430,4 +1430,30 @@ int wost3_exits_adjoint_gradient_dev(wost3_handle h, const float *dgrad_dev, int
     return kExits3.adjoint_gradient(h, dgrad_dev, K, dcolors_dev, false, stream);
 }
 
+int wost3_exits_index(wost3_handle h) { return kExits3.index(h); }
+
+int wost3_exits_index_info(wost3_handle h, int64_t *n_incidences, int64_t *longest_bin) { return kExits3.index_info(h, n_incidences, longest_bin); }
+
+int wost3_exits_index_records(wost3_handle h, int64_t *bin_begin, int32_t *inc) { return kExits3.index_records(h, bin_begin, inc); }
+
+int wost3_exits_adjoint_ordered(wost3_handle h, const float *dfield, int32_t K, float *dcolors)
+{
+    return kExits3.adjoint_ordered(h, dfield, K, dcolors, true, nullptr);
+}
+
+int wost3_exits_adjoint_ordered_dev(wost3_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits3.adjoint_ordered(h, dfield_dev, K, dcolors_dev, false, stream);
+}
+
+int wost3_exits_adjoint_gradient_ordered(wost3_handle h, const float *dgrad, int32_t K, float *dcolors)
+{
+    return kExits3.adjoint_gradient_ordered(h, dgrad, K, dcolors, true, nullptr);
+}
+
+int wost3_exits_adjoint_gradient_ordered_dev(wost3_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream)
+{
+    return kExits3.adjoint_gradient_ordered(h, dgrad_dev, K, dcolors_dev, false, stream);
+}
+
 }  // extern "C"

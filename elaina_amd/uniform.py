@@ -361,6 +361,62 @@ class UniformCalls:
         fn, name = self._fn("exits_adjoint_gradient_dev")
         _check(fn(self._handle, C.c_void_p(dgrad_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
 
+    # -- the index of the exit list and the ordered adjoints (wost_exits_index & co.) -------------
+    def exits_index(self):
+        """index the bound exit list by vertex (wost_exits_index; include/wost.h "Exit lists: the index and the ordered
+        adjoint"), once per walk of the list: the ordered adjoints gather over it.  A second call is a no-op; whatever replaces
+        or releases the list drops the index"""
+        fn, name = self._fn("exits_index")
+        _check(fn(self._handle), name)
+
+    @property
+    def exits_index_info(self):
+        """(incidences of the index, entries of its longest bin); (0, 0): no index stands"""
+        fn, name = self._fn("exits_index_info")
+        n_inc, longest = C.c_int64(0), C.c_int64(0)
+        _check(fn(self._handle, C.byref(n_inc), C.byref(longest)), name)
+        return n_inc.value, longest.value
+
+    def exits_index_records(self):
+        """the index: {"bin_begin" (2 n_verts + 1,) int64, "inc" (n_incidences,) int32}; bin 2 v + (side < 0) holds the
+        incidences w * dim + j at bin_begin[b] .. bin_begin[b + 1], ascending"""
+        fn, name = self._fn("exits_index_records")
+        begin = np.zeros(2 * self._exit_verts() + 1, np.int64)
+        inc = np.zeros(max(self.exits_index_info[0], 1), np.int32)      # (with no index the call says so; its pointers are still real ones)
+        _check(fn(self._handle, begin.ctypes.data_as(C.POINTER(C.c_int64)), capi._ip(inc)), name)
+        return {"bin_begin": begin, "inc": inc[:self.exits_index_info[0]]}
+
+    def exits_adjoint_ordered(self, dfield):
+        """exits_adjoint as a gather over the index, in a stated summation order: the same bits on every run and every stream"""
+        fn, name = self._fn("exits_adjoint_ordered")
+        d = self._exit_sets(dfield, self.exits_done[0], 3)
+        out = np.zeros((len(d), self._exit_verts(), 6), np.float32)
+        _check(fn(self._handle, _fp(d), len(d), _fp(out)), name)
+        return out
+
+    def exits_adjoint_ordered_dev(self, dfield_ptr, K, dcolors_ptr, stream_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n * 3 floats in, K * n_verts * 6 floats out"""
+        fn, name = self._fn("exits_adjoint_ordered_dev")
+        _check(fn(self._handle, C.c_void_p(dfield_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
+
+    def exits_adjoint_gradient_ordered(self, dgrad):
+        """exits_adjoint_gradient as a gather over the index, in a stated summation order: the same bits on every run"""
+        fn, name = self._fn("exits_adjoint_gradient_ordered")
+        n = self.exits_done[0]
+        d = np.ascontiguousarray(dgrad, dtype=np.float32)
+        if d.ndim == 3:
+            d = d[None]
+        if d.ndim != 4 or d.shape[1:] != (n, self._dim, 3) or len(d) < 1:
+            raise ValueError("expected [K, %d, %d, 3] floats, got %s" % (n, self._dim, d.shape))
+        out = np.zeros((len(d), self._exit_verts(), 6), np.float32)
+        _check(fn(self._handle, _fp(d), len(d), _fp(out)), name)
+        return out
+
+    def exits_adjoint_gradient_ordered_dev(self, dgrad_ptr, K, dcolors_ptr, stream_ptr=None):
+        """the same on device pointers (ints) on the caller's stream: K * n * dim * 3 floats in, K * n_verts * 6 floats out"""
+        fn, name = self._fn("exits_adjoint_gradient_ordered_dev")
+        _check(fn(self._handle, C.c_void_p(dgrad_ptr), int(K), C.c_void_p(dcolors_ptr), C.c_void_p(stream_ptr or 0)), name)
+
     # -- the continued frame solve (wost_solve_more & co.) ---------------------------------------
     def solve_more(self, more_spp):
         """more_spp samples per pixel on top of the carried frame solve; the field of all samples so far -- the solve()'s at

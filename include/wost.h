@@ -566,6 +566,57 @@ int wost_exits_apply_gradient_dev(wost_handle h, const float *colors_dev, int32_
 int wost_exits_adjoint_gradient(wost_handle h, const float *dgrad, int32_t K, float *dcolors);
 int wost_exits_adjoint_gradient_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
 
+/* Exit lists: the index and the ordered adjoint.  wost_exits_adjoint and wost_exits_adjoint_gradient scatter with
+ * atomic adds, so their last bits change from run to run.  wost_exits_index transposes the bound list once -- per vertex and
+ * side, the walks that exit there -- and the ordered adjoints gather over it in a stated order:
+ * dcolors IS A FUNCTION OF THE LIST AND THE ARGUMENT ALONE: THE SAME BITS ON EVERY RUN, EVERY STREAM AND EVERY DEVICE OF THIS
+ * KIND.  The reference has no counterpart.
+ *   1. The index.  An incidence is  inc = w * DIM + j:  walk w = i * S + s of the list, absorbed (prim >= 0), and corner j of its
+ *     primitive.  Its bin is  b = 2 * v + (side < 0 ? 1 : 0)  with v = segs[prim][j] (tris[prim][j]) of the caller: there are
+ *     2 * n_verts bins, and a bin holds its incidences ascending in inc.  The index is bin_begin (2 * n_verts + 1 offsets, int64)
+ *     and inc (int32, n_incidences = DIM * absorbed walks of them); bin b is inc[bin_begin[b] .. bin_begin[b + 1]).  For a list
+ *     of the gradient it also holds, per point and axis, the fp64 mean direction nbar that the sums below use: a lane l of 64
+ *     adds the directions of the point's walks s = l, l + 64, ... in that order to a sum that starts at +0.0, the 64 sums are
+ *     combined by the butterfly below, and the result is divided by (double)S.  The index is built on the device on the
+ *     default stream, without floating-point atomics: it is a function of the records.  It costs 16 * n_verts + 4 *
+ *     n_incidences bytes (+ 8 * DIM * n for a list of the gradient); the build's temporaries (about 4 * n * S + 16 *
+ *     n_incidences bytes) are freed before it returns.
+ *   2. The order.  Entry dcolors[k][v][off + c] (off = 0 for side >= 0, else 3) is the sum over bin b = 2 v + (off ? 1 : 0).
+ *     Lane l of 64 takes the bin's incidences at positions l, l + 64, ... of the bin, in that order, and adds the term of each
+ *     to an fp64 sum that starts at +0.0.  The term of incidence w * DIM + j, w = i * S + s, with w_v the fp32 weight of corner
+ *     j as apply forms it, every factor promoted to fp64 and the products taken from left to right:
+ *         wost_exits_adjoint_ordered            dfield[k][i][c] / S * dirichlet_intensity * thp * w_v
+ *         wost_exits_adjoint_gradient_ordered   q * dirichlet_intensity * thp * w_v,
+ *                                               q = dgrad[k][i][0][c] * scale * cen_0 + dgrad[k][i][1][c] * scale * cen_1 (+ ...),
+ *                                               scale = DIM / (R_i * (S - 1)),   cen_a = n_s,a - nbar_i,a,   the axes in that order
+ *     An incidence of a degenerate or non-finite point (R <= eps_shell or R not finite) is SKIPPED in the gradient form: it is
+ *     not added as zero, and its dgrad is not read.  The 64 sums x_0 .. x_63 are then combined by the butterfly
+ *         for off in 32, 16, 8, 4, 2, 1:   x_l = x_l + x_(l xor off)   on all lanes at once
+ *     and x_0 is rounded to fp32 once.  An empty bin gives +0.0f.  No contraction anywhere: numpy float64 reproduces the bits
+ *     (tests/exits_index_emulation.py does).  The values agree with the unordered calls within those calls' bounds.
+ *   - wost_exits_index: builds the index of the bound list; a second call is a no-op that returns WOST_OK.  The index lives and
+ *     dies with the list: a walk call that replaces the list or releases it (n == 0) drops the index, a walk that is refused or
+ *     fails leaves both as they were, wost_destroy frees it.  An allocation that fails is WOST_ERR_NOMEM, and the list and any
+ *     old index stay.  A scene without a Dirichlet mesh: WOST_ERR_UNSUPPORTED.
+ *   - wost_exits_index_info: n_incidences and the entries of the longest bin; 0, 0 with WOST_OK when no index stands.
+ *   - wost_exits_index_records: the index into host arrays of 2 * n_verts + 1 and n_incidences entries; either may be NULL.
+ *   - wost_exits_adjoint_ordered, wost_exits_adjoint_gradient_ordered: the arguments and layouts of wost_exits_adjoint and
+ *     wost_exits_adjoint_gradient, host arrays.  The _dev forms: DEVICE arrays, the work runs on the caller's stream and is
+ *     complete when the call returns.  One wave per (bin, set): plain loads and stores, no scratch array, no atomic.
+ *   The index and the ordered calls leave the list, the unordered calls and every neighbour of the list alone.
+ *   Refusals, in this order: a null handle; a null required array; K < 1; no list bound; no index built (WOST_ERR_INVALID, the
+ *     message names wost_exits_index); for the gradient form, a list without directions (the message names
+ *     wost_exits_walk_gradient); a scene without a Dirichlet mesh (WOST_ERR_UNSUPPORTED).
+ * Not built: a bin split across waves (it would change the order above), an ordered apply (apply is deterministic already),
+ * and what the exit lists themselves leave out. */
+int wost_exits_index(wost_handle h);
+int wost_exits_index_info(wost_handle h, int64_t *n_incidences, int64_t *longest_bin);
+int wost_exits_index_records(wost_handle h, int64_t *bin_begin, int32_t *inc);
+int wost_exits_adjoint_ordered(wost_handle h, const float *dfield, int32_t K, float *dcolors);
+int wost_exits_adjoint_ordered_dev(wost_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
+int wost_exits_adjoint_gradient_ordered(wost_handle h, const float *dgrad, int32_t K, float *dcolors);
+int wost_exits_adjoint_gradient_ordered_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
+
 /* renderDirichletSDF / renderSilhouetteSDF (integrator/common.h:52-123): one query per
  * pixel of the frame, out receives width*height distances. */
 int wost_render_sdf(wost_handle h, int which_mesh, float *out_dist);
@@ -1009,6 +1060,15 @@ int wost3_exits_apply_gradient_dev(wost3_handle h, const float *colors_dev, int3
                                    float *field_rgb_dev, void *stream);
 int wost3_exits_adjoint_gradient(wost3_handle h, const float *dgrad, int32_t K, float *dcolors);
 int wost3_exits_adjoint_gradient_dev(wost3_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
+/* The index and the ordered adjoint in 3-D: wost_exits_index & co. with the same rules in every clause (DIM = 3: three
+ * incidences per absorbed walk, v = tris[prim][j], three axes in q). */
+int wost3_exits_index(wost3_handle h);
+int wost3_exits_index_info(wost3_handle h, int64_t *n_incidences, int64_t *longest_bin);
+int wost3_exits_index_records(wost3_handle h, int64_t *bin_begin, int32_t *inc);
+int wost3_exits_adjoint_ordered(wost3_handle h, const float *dfield, int32_t K, float *dcolors);
+int wost3_exits_adjoint_ordered_dev(wost3_handle h, const float *dfield_dev, int32_t K, float *dcolors_dev, void *stream);
+int wost3_exits_adjoint_gradient_ordered(wost3_handle h, const float *dgrad, int32_t K, float *dcolors);
+int wost3_exits_adjoint_gradient_ordered_dev(wost3_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
 /* lbvh::nearest + checkPointSide + computeProjectionRatio for triangles (call sites integrator.cu:138,154-155):
  * winning triangle (lowest index on ties), distance, barycentric (u, v) of the projection, side */
 int wost3_closest_point(wost3_handle h, int which_mesh, const float *pts, int32_t n, int32_t *out_idx, float *out_dist,
