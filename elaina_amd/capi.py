@@ -262,6 +262,7 @@ _BOTH = {
     "exits_gradient_records": [_h, C.POINTER(ExitGradientRecords)],
     "exits_apply_gradient": [_h, _pf, _i32, _pf, _pf, _pf],
     "exits_apply_gradient_dev": [_h, _dev, _i32, _dev, _dev, _dev, _dev],
+    "exits_gradient_terms": [_h, _pd, _pd, _pd],
     "exits_adjoint_gradient": [_h, _pf, _i32, _pf],
     "exits_adjoint_gradient_dev": [_h, _dev, _i32, _dev, _dev],
     # the index of the exit list and the ordered adjoints (wost_exits_index & co.)

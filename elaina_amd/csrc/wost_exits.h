@@ -42,6 +42,10 @@ struct ExitRecords {
 // of the gradient (wost_exits_walk_gradient) has three more arrays in it, behind the records: per point the radius
 // of its first ball, per walk its direction and its first point, dim floats each, interleaved per walk as GradPrep writes them
 // -- 4 * (6 + 3 dim) bytes per walk and 4 per point in all.  A plain list has none of them (dirs == nullptr).
+// A list of the gradient walked on a scene with a source term (the option "exits_grad_source"; DESIGN 4.3i "The in-ball term")
+// has one more array behind those, 8-byte aligned: per point the in-ball term of the gradient's estimator, which does not depend
+// on the Dirichlet data -- 6 dim + 3 doubles, T (dim * 3), seT (dim * 3) and U (3), 8 * (6 dim + 3) bytes per point.  Every
+// other list has none (terms == nullptr): the mode is the list's, fixed at the walk.
 // The index of a list by vertex (wost_exits_index), one allocation of its own: incidence w * DIM + j is corner j of
 // the primitive of absorbed walk w, its bin 2 v + (side < 0) with v the corner's vertex in the caller's numbering; a bin holds
 // its incidences ascending.  nbar (a list of the gradient only): per point and axis the mean direction as
@@ -59,6 +63,7 @@ struct ExitList {
     int dim = 0;
     int32_t n = 0, S = 0;
     float *radius = nullptr, *dirs = nullptr, *first = nullptr;
+    double *terms = nullptr;
     ExitIndex index;                   // lives and dies with the list: whatever replaces or releases the list drops it
 };
 void exits_free(ExitList &l);
@@ -100,11 +105,14 @@ struct ExitCall {
     int32_t n_verts;
     float dirichlet_intensity;
     std::function<int(const ExitWalk &, hipStream_t)> walk;
-    // ... and for a list of the gradient: the kernel in front (grad_prep2 / grad_prep3 on the context's meshes), the shell, and
-    // whether the scene has a source term (refused: the in-ball term is not carried in the list)
+    // ... and for a list of the gradient: the kernel in front (grad_prep2 / grad_prep3 on the context's meshes), the shell,
+    // whether the scene has a source term, the handle's option "exits_grad_source" (without it such a scene is refused, with it
+    // the list carries the in-ball term) and the in-ball kernel on the context's source grid (grad_ball2 / grad_ball3)
     std::function<int(const GradPrep &, hipStream_t)> prep;
     float eps = 0.0f;
-    bool has_source = false;
+    bool has_source = false, source_term = false;
+    std::function<int(const GradBall &, hipStream_t)> ball;
+    bool in_ball() const { return has_source && source_term; }
 };
 
 // the argument rules that need no look at the handle (include/wost.h), in the order of the header
@@ -132,6 +140,10 @@ int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &
 // grad is required, se and field may be nullptr
 int exits_apply_gradient(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, bool on_host, hipStream_t stream);
 int exits_adjoint_gradient(const ExitCall &c, const float *dgrad, int32_t K, float *dcolors, bool on_host, hipStream_t stream);
+// the option "exits_grad_source" of a handle (wost_set_option, wost3_set_option): exactly 0 or 1
+int exits_grad_source_option(double value, bool *option);
+// the in-ball term the bound list carries into host arrays of n * dim * 3, n * dim * 3 and n * 3 doubles; any may be nullptr
+int exits_gradient_terms(const ExitCall &c, double *T, double *seT, double *U);
 
 // ---- the index and the ordered adjoints (include/wost.h "Exit lists: the index and the ordered adjoint") ----
 // a device allocation that may fail for want of memory: WOST_ERR_NOMEM then, WOST_ERR_DEVICE for anything else
@@ -230,6 +242,17 @@ struct ExitCalls {
         if (rc == WOST_OK) rc = bound_gradient(h);
         if (rc != WOST_OK) return rc;
         return exits_apply_gradient(call(h), colors, K, grad, se, field, on_host, on_host ? h->stream : reinterpret_cast<hipStream_t>(stream));
+    }
+    int gradient_terms(H *h, double *T, double *seT, double *U) const
+    {
+        if (!h) return set_error(WOST_ERR_INVALID, "null argument");
+        const int rc = bound_gradient(h);
+        if (rc != WOST_OK) return rc;
+        if (!h->exits.terms)
+            return set_error(WOST_ERR_INVALID, "the exit list bound to the handle carries no in-ball term (a walk of the gradient on a scene with a source "
+                                               "term under the option exits_grad_source binds one that does)");
+        if (!T && !seT && !U) return WOST_OK;
+        return exits_gradient_terms(call(h), T, seT, U);
     }
     int adjoint_gradient(H *h, const float *dgrad, int32_t K, float *dcolors, bool on_host, void *stream) const
     {

@@ -4,7 +4,9 @@
 // host and device forms of apply and adjoint.  Cold path beside the walk kernels, which do not know of it.  And the list of the
 // gradient (include/wost.h "Exit lists of the gradient"): the same list walked from the first points of the
 // gradient's estimator, kept with their directions and radii, and the two kernels that are its hot path -- grad u, its standard
-// error and the mean for K sets of colours, one wave per point, and the transpose of that map.
+// error and the mean for K sets of colours, one wave per point, and the transpose of that map.  On a scene with a source term
+// (the option "exits_grad_source") the walk also reduces the in-ball samples of the gradient's estimator to three fp64 terms per
+// point, which the list keeps and apply joins to every set (exits_ball_terms_kernel; DESIGN 4.3i "The in-ball term").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -184,6 +186,44 @@ __global__ __launch_bounds__(256) void exits_round_kernel(const double *acc, flo
     if (j < count) out[j] = (float)acc[j];
 }
 
+// ---- the list of the gradient: the in-ball term at walk time -----------------------------------------------------------------
+struct ExitBallTermsParams {
+    const float *ball;               // a block's in-ball samples as grad_ball_kernel leaves them, `stride` floats apart
+    size_t stride;
+    const float *radius;             // the block's radii
+    double *terms;                   // the block's part of the list's terms
+    int32_t count, S;
+    float eps;
+};
+
+// One wave per point of a block behind grad_ball_kernel: the two passes of grad_reduce_kernel over the point's S in-ball samples
+// (grad_ball_sums, grad_ball_variance, with its arguments) and, by lane 0, the three terms that kernel joins to the walk part,
+// kept in fp64 as it forms them:  T_e = (R / S) a_e,  seT_e = R sqrt(va_e / (S - 1) / S),  U_c = (R^2 / S) u_c  -- T (DIM * 3),
+// seT (DIM * 3), U (3) per point.  A degenerate point took no samples and has +0.0 in all of them.
+template <int DIM>
+__global__ __launch_bounds__(256) void exits_ball_terms_kernel(ExitBallTermsParams P)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (j >= P.count) return;      // (the whole wave)
+    const int S = P.S;
+    const double dS = (double)S;
+    double a[DIM * 3], u[3], va[DIM * 3];
+    grad_ball_sums<DIM>(P.ball + (size_t)j * S, P.stride, S, lane, a, u);
+    grad_ball_variance<DIM>(P.ball + (size_t)j * S, P.stride, S, lane, a, va);
+    if (lane == 0) {
+        const float R = P.radius[j];
+        const bool degenerate = ball_degenerate(R, P.eps);
+        double *out = P.terms + (size_t)(6 * DIM + 3) * j;
+#pragma unroll
+        for (int e = 0; e < DIM * 3; ++e) {
+            out[e] = degenerate ? 0.0 : ball_grad_term(R, S, a[e]);
+            out[DIM * 3 + e] = degenerate ? 0.0 : (double)R * sqrt(va[e] / (dS - 1.0) / dS);
+        }
+        for (int c = 0; c < 3; ++c) out[6 * DIM + c] = degenerate ? 0.0 : ball_field_term(R, S, u[c]);
+    }
+}
+
 // ---- the list of the gradient: apply -----------------------------------------------------------------------------------------
 struct ExitApplyGradParams {
     ExitRecords rec;
@@ -193,6 +233,7 @@ struct ExitApplyGradParams {
     int32_t n, S, K, n_verts;
     float intensity, eps;
     float *grad, *se, *field;        // K * n * DIM * 3, the same, K * n * 3; se and field may be nullptr
+    const double *terms;             // the list's in-ball term, 6 * DIM + 3 per point (BALL; nullptr without)
 };
 
 // One wave per point, its lanes over the point's S walks, per set the three passes of grad_reduce_kernel (the mean, the
@@ -201,7 +242,10 @@ struct ExitApplyGradParams {
 // walk in registers for all K sets and that walk's W for the three passes of a set: with S <= 64 every record and direction is
 // read once, and W is formed once per set.  The walks beyond the first 64 of a point are read again per pass (from the cache).
 // W never passes through memory.  Lane 0 writes the DIM * 3 + DIM * 3 + 3 results of a set.
-template <int DIM>
+// BALL (a list that carries the in-ball term): lane 0 joins the point's T, seT and U to every set as grad_reduce_kernel joins
+// them -- grad = walk part + T, stderr = sqrt(walk part^2 + seT^2), field = mean + U unless the point is degenerate, each still
+// rounded once --, and loads them where it uses them: nothing of them is live across the three passes.
+template <int DIM, bool BALL>
 __global__ __launch_bounds__(256) void exits_apply_gradient_kernel(ExitApplyGradParams P)
 {
     const int lane = threadIdx.x & 63;
@@ -243,13 +287,31 @@ __global__ __launch_bounds__(256) void exits_apply_gradient_kernel(ExitApplyGrad
         if (lane == 0) {
             const size_t o = (size_t)k * P.n + i;
             const double scale = grad_scale<DIM>(R, S), scale_se = (double)DIM / (double)R;
+            if (BALL) {
+                const double *terms = P.terms + (size_t)(6 * DIM + 3) * i;
 #pragma unroll
-            for (int e = 0; e < DIM * 3; ++e) {
-                P.grad[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
-                if (P.se) P.se[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale_se * sqrt(v[e] / (dS - 1.0) / dS));
+                for (int e = 0; e < DIM * 3; ++e) {
+                    double g = scale * t[e];
+                    g += terms[e];
+                    P.grad[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)g;
+                    if (P.se) {
+                        double se = scale_se * sqrt(v[e] / (dS - 1.0) / dS);
+                        const double se_t = terms[DIM * 3 + e];
+                        se = sqrt(se * se + se_t * se_t);
+                        P.se[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)se;
+                    }
+                }
+                if (P.field)
+                    for (int c = 0; c < 3; ++c) P.field[3 * o + c] = (float)(degenerate ? mean[c] : mean[c] + terms[6 * DIM + c]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < DIM * 3; ++e) {
+                    P.grad[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale * t[e]);
+                    if (P.se) P.se[(size_t)(DIM * 3) * o + e] = degenerate ? WOST_NAN : (float)(scale_se * sqrt(v[e] / (dS - 1.0) / dS));
+                }
+                if (P.field)
+                    for (int c = 0; c < 3; ++c) P.field[3 * o + c] = (float)mean[c];
             }
-            if (P.field)
-                for (int c = 0; c < 3; ++c) P.field[3 * o + c] = (float)mean[c];
         }
     }
 }
@@ -433,10 +495,13 @@ static int exits_stage(Batch &b, float **dev, size_t count, const char *what)
 
 // the arrays of a list of N walks, carved from one allocation: prim, slot, side, thp, DIM - 1 of uv and three of base, four
 // bytes an entry -- and behind them, for a list of the gradient, the radii (n), the directions and the first points (dim * N each)
-static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S, bool gradient)
+// -- and behind those, for one that carries the in-ball term, 6 dim + 3 doubles per point from the next multiple of 8 bytes on
+static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S, bool gradient, bool in_ball)
 {
     const size_t N = (size_t)n * S, records = N * (size_t)(6 + dim);
-    const int rc = exits_alloc(&l.mem, (records + (gradient ? (size_t)n + 2 * (size_t)dim * N : 0)) * 4, "the exit list");
+    const size_t words = records + (gradient ? (size_t)n + 2 * (size_t)dim * N : 0), terms_at = (words + 1) / 2 * 2;
+    const size_t bytes = in_ball ? terms_at * 4 + (size_t)n * (size_t)(6 * dim + 3) * sizeof(double) : words * 4;
+    const int rc = exits_alloc(&l.mem, bytes, "the exit list");
     if (rc != WOST_OK) return rc;
     l.rec = ExitRecords{static_cast<int32_t *>(l.mem), N};
     l.dim = dim; l.n = n; l.S = S;
@@ -445,6 +510,7 @@ static int exits_carve(ExitList &l, int dim, int32_t n, int32_t S, bool gradient
         l.dirs = l.radius + n;
         l.first = l.dirs + (size_t)dim * N;
     }
+    if (in_ball) l.terms = reinterpret_cast<double *>(static_cast<float *>(l.mem) + terms_at);
     return WOST_OK;
 }
 
@@ -510,19 +576,30 @@ struct ListGuard {
 // kernel in front first, in launches of at most n_pixels points, straight into the new list's radii, directions and first
 // points (GradPrep's pointers are the launch's own: offset per launch); then its walks are those of a plain list of the n * S
 // first points with one walk each -- walk w reads point w, seeds pixel walk_seed_base + w and writes record w.
+// in_ball (a list of the gradient on a scene with a source term, the handle's "exits_grad_source" on): between the kernel in
+// front and the walks, the in-ball passes, in blocks of max(1, floor(n_pixels / S)) points as the single call cuts them -- the
+// in-ball kernel of the single call (S samples per point from the directions' streams, reading the list's radii) into a
+// temporary of this call's own, dim + 8 arrays of max(n_pixels, S) floats, and exits_ball_terms_kernel behind it, which leaves
+// the block's terms in the list.  Two launches per block; the samples are no walks and count in none of the five counters.
 static int exits_walk_list(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, bool gradient,
                            hipStream_t stream, wost_stats *stats)
 {
     const int32_t walk_seed_base = seeds.walk_seed_base, seed_width = seeds.seed_width;
     const auto t0 = HostClock::now();
     WOST_TRY(hipSetDevice(c.device));
+    const bool in_ball = gradient && c.in_ball();
     ListGuard fresh;
-    int rc = exits_carve(fresh.l, c.dim, n, walks, gradient);
+    int rc = exits_carve(fresh.l, c.dim, n, walks, gradient, in_ball);
     if (rc != WOST_OK) return rc;
     Scratch scratch;
-    void *d_pts = nullptr, *d_counters = nullptr;
+    void *d_pts = nullptr, *d_counters = nullptr, *d_ball = nullptr;
     if ((rc = exits_alloc(&d_counters, 5 * sizeof(unsigned long long), "the counters of the walk")) != WOST_OK) return rc;
     scratch.ptrs.push_back(d_counters);
+    const size_t ball_stride = std::max(c.n_pixels, (size_t)walks);
+    if (in_ball) {
+        if ((rc = exits_alloc(&d_ball, ball_stride * (size_t)(c.dim + kBallArrays) * sizeof(float), "the in-ball samples of the walk")) != WOST_OK) return rc;
+        scratch.ptrs.push_back(d_ball);
+    }
     if (pts_on_host) {
         const size_t bytes = (size_t)n * c.dim * sizeof(float);
         if ((rc = exits_alloc(&d_pts, bytes, "the points")) != WOST_OK) return rc;
@@ -547,6 +624,26 @@ static int exits_walk_list(const ExitCall &c, const float *pts, bool pts_on_host
             if ((rc = c.prep(p, stream)) != WOST_OK) {
                 (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
                 return rc;
+            }
+        }
+        if (in_ball) {
+            const int64_t per_block = std::max<int64_t>(1, (int64_t)(c.n_pixels / (size_t)walks));
+            const size_t per_point_terms = (size_t)(6 * c.dim + 3);
+            for (int64_t a = 0; a < n; a += per_block, launches += 2) {
+                const int32_t m = (int32_t)std::min<int64_t>(per_block, n - a);
+                rc = c.ball(GradBall{walk_pts, (int32_t)a, m, walks, seeds.seed_base, seed_width, c.eps, l.radius + a, static_cast<float *>(d_ball), ball_stride},
+                            stream);
+                if (rc == WOST_OK) {
+                    const ExitBallTermsParams P{static_cast<const float *>(d_ball), ball_stride, l.radius + a, l.terms + per_point_terms * (size_t)a, m, walks, c.eps};
+                    const dim3 grid((unsigned)((m + 3) / 4));
+                    if (c.dim == 2) hipLaunchKernelGGL(exits_ball_terms_kernel<2>, grid, dim3(256), 0, stream, P);
+                    else hipLaunchKernelGGL(exits_ball_terms_kernel<3>, grid, dim3(256), 0, stream, P);
+                    if (hipGetLastError() != hipSuccess) rc = set_error(WOST_ERR_DEVICE, "the kernel of the in-ball terms could not be launched");
+                }
+                if (rc != WOST_OK) {
+                    (void)hipStreamSynchronize(stream);      // (the scratch arrays are freed on return)
+                    return rc;
+                }
             }
         }
         walk_pts = l.first;
@@ -588,10 +685,36 @@ int exits_walk(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n,
 int exits_walk_gradient(const ExitCall &c, const float *pts, bool pts_on_host, int32_t n, int32_t walks, const ExitSeeds &seeds, hipStream_t stream,
                         wost_stats *stats)
 {
-    if (c.has_source)
-        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_walk_gradient: a scene with a source term is not covered (the in-ball term of "
-                                                                        "the gradient does not depend on the Dirichlet data and is not carried in the list)");
+    if (c.has_source && !c.source_term)
+        return set_error(WOST_ERR_UNSUPPORTED, std::string(c.prefix) + "exits_walk_gradient: a scene with a source term is not covered without the option "
+                                                                        "exits_grad_source (the in-ball term of the gradient does not depend on the Dirichlet "
+                                                                        "data; with the option at 1 it is computed at the walk and carried in the list)");
     return exits_walk_list(c, pts, pts_on_host, n, walks, seeds, true, stream, stats);
+}
+
+int exits_grad_source_option(double value, bool *option)
+{
+    if (value != 0 && value != 1) return set_error(WOST_ERR_INVALID, "exits_grad_source must be 0 or 1");
+    *option = value == 1;
+    return WOST_OK;
+}
+
+int exits_gradient_terms(const ExitCall &c, double *T, double *seT, double *U)
+{
+    WOST_TRY(hipSetDevice(c.device));
+    const ExitList &l = *c.list;
+    const size_t n = (size_t)l.n, e3 = (size_t)l.dim * 3, per_point = 2 * e3 + 3;
+    // T, seT and U are interleaved per point in the list: fetched whole and sorted on the host
+    std::vector<double> terms(n * per_point);
+    WOST_TRY(hipMemcpyAsync(terms.data(), l.terms, terms.size() * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    WOST_TRY(hipStreamSynchronize(c.stream));
+    for (size_t i = 0; i < n; ++i) {
+        const double *t = terms.data() + i * per_point;
+        if (T) std::copy(t, t + e3, T + i * e3);
+        if (seT) std::copy(t + e3, t + 2 * e3, seT + i * e3);
+        if (U) std::copy(t + 2 * e3, t + per_point, U + i * 3);
+    }
+    return WOST_OK;
 }
 
 int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &out)
@@ -617,10 +740,16 @@ int exits_gradient_records(const ExitCall &c, const wost_exit_gradient_records &
 static int exits_apply_gradient_dev(const ExitCall &c, const float *colors, int32_t K, float *grad, float *se, float *field, hipStream_t stream)
 {
     const ExitList &l = *c.list;
-    const ExitApplyGradParams P{l.rec, c.verts, colors, l.radius, l.dirs, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, c.eps, grad, se, field};
+    const ExitApplyGradParams P{l.rec, c.verts, colors, l.radius, l.dirs, l.n, l.S, K, c.n_verts, c.dirichlet_intensity, c.eps, grad, se, field, l.terms};
     const dim3 grid((unsigned)((l.n + 3) / 4));
-    if (c.dim == 2) hipLaunchKernelGGL(exits_apply_gradient_kernel<2>, grid, dim3(256), 0, stream, P);
-    else hipLaunchKernelGGL(exits_apply_gradient_kernel<3>, grid, dim3(256), 0, stream, P);
+    // (the list's mode, not the handle's option: what the walk recorded)
+    if (l.terms) {
+        if (c.dim == 2) hipLaunchKernelGGL((exits_apply_gradient_kernel<2, true>), grid, dim3(256), 0, stream, P);
+        else hipLaunchKernelGGL((exits_apply_gradient_kernel<3, true>), grid, dim3(256), 0, stream, P);
+    } else {
+        if (c.dim == 2) hipLaunchKernelGGL((exits_apply_gradient_kernel<2, false>), grid, dim3(256), 0, stream, P);
+        else hipLaunchKernelGGL((exits_apply_gradient_kernel<3, false>), grid, dim3(256), 0, stream, P);
+    }
     WOST_TRY(hipGetLastError());
     return WOST_OK;
 }

@@ -1424,6 +1424,8 @@ int wost_set_option(wost_handle h, const char *key, double value)
         h->time_kernels = value != 0;
     } else if (k == "grad_source") {
         return grad_source_option(value, &h->grad_source);
+    } else if (k == "exits_grad_source") {
+        return exits_grad_source_option(value, &h->exits_grad_source);
     } else {
         return set_error(WOST_ERR_INVALID, "unknown option: " + k);
     }
@@ -2355,6 +2357,8 @@ static ExitCall exit_call(wost_context *c)
     e.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep2(c->dm.view, c->nm.view, p, stream); };
     e.eps = c->dst.eps;
     e.has_source = c->src.rgb != nullptr;
+    e.source_term = c->exits_grad_source;
+    e.ball = [c](const GradBall &p, hipStream_t stream) { return grad_ball2(c->src, p, stream); };
     return e;
 }
 
@@ -2418,6 +2422,8 @@ int wost_exits_apply_gradient_dev(wost_handle h, const float *colors_dev, int32_
 {
     return kExits.apply_gradient(h, colors_dev, K, grad_dev, grad_stderr_dev, field_rgb_dev, false, stream);
 }
+
+int wost_exits_gradient_terms(wost_handle h, double *T, double *seT, double *U) { return kExits.gradient_terms(h, T, seT, U); }
 
 int wost_exits_adjoint_gradient(wost_handle h, const float *dgrad, int32_t K, float *dcolors)
 {

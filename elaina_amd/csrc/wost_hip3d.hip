@@ -1070,6 +1070,7 @@ int wost3_set_option(wost3_handle h, const char *key, double value)
     if (!h || !key) return set_error(WOST_ERR_INVALID, "null argument");
     const std::string k(key);
     if (k == "grad_source") return grad_source_option(value, &h->grad_source);
+    if (k == "exits_grad_source") return exits_grad_source_option(value, &h->exits_grad_source);
     return set_error(WOST_ERR_INVALID, "unknown option: " + k);
 }
 
@@ -1356,6 +1357,8 @@ static ExitCall exit_call3(wost3_context *c)
     e.prep = [c](const GradPrep &p, hipStream_t stream) { return grad_prep3(c->dm.view, c->nm.view, p, stream); };
     e.eps = c->dst.eps;
     e.has_source = c->src.rgb != nullptr;
+    e.source_term = c->exits_grad_source;
+    e.ball = [c](const GradBall &p, hipStream_t stream) { return grad_ball3(c->src, p, stream); };
     return e;
 }
 
@@ -1419,6 +1422,8 @@ int wost3_exits_apply_gradient_dev(wost3_handle h, const float *colors_dev, int3
 {
     return kExits3.apply_gradient(h, colors_dev, K, grad_dev, grad_stderr_dev, field_rgb_dev, false, stream);
 }
+
+int wost3_exits_gradient_terms(wost3_handle h, double *T, double *seT, double *U) { return kExits3.gradient_terms(h, T, seT, U); }
 
 int wost3_exits_adjoint_gradient(wost3_handle h, const float *dgrad, int32_t K, float *dcolors)
 {

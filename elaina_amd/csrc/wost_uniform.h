@@ -35,6 +35,7 @@ struct HandleBase {
     GradScratch grad;               // the scratch of the gradient calls (wost_solve_gradient_points & co., wost_grad.h)
     GradList glist;                 // ... and the carried gradient list (wost_gradient_points_carry & co.), which shares it
     bool grad_source = false;       // the option "grad_source": the gradient calls take a scene with a source term (GradCall)
+    bool exits_grad_source = false; // the option "exits_grad_source": a walk of the gradient's exit list takes such a scene (ExitCall)
     ExitList exits;                 // the exit list (wost_exits_walk & co., wost_exits.h), beside the three carried states
     int32_t dirichlet_verts = 0;    // ... and the vertices of the Dirichlet mesh, which size a set of its colours (0: no such mesh)
 };

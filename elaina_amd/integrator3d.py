@@ -99,7 +99,8 @@ class UniformIntegrator3(UniformCalls):
         self.solution, self.last_stats = None, None
 
     def set_option(self, key, value):
-        """wost3_set_option: "grad_source" 1 lets the gradient calls take a scene with a source term (0, the default: refused)"""
+        """wost3_set_option: "grad_source" 1 lets the gradient calls take a scene with a source term (0, the default: refused);
+        "exits_grad_source" 1 lets exits_walk_gradient take one and carry the in-ball term in the list (0, the default: refused)"""
         _check(self.lib.wost3_set_option(self._handle, key.encode(), float(value)), "wost3_set_option")
 
     def render_sdf(self, which=0):

@@ -342,6 +342,17 @@ class UniformCalls:
         _check(fn(self._handle, C.c_void_p(colors_ptr), int(K), C.c_void_p(grad_ptr), C.c_void_p(stderr_ptr or 0), C.c_void_p(field_ptr or 0),
                   C.c_void_p(stream_ptr or 0)), name)
 
+    def exits_gradient_terms(self):
+        """the in-ball term a list of the gradient carries when it was walked on a scene with a source term under
+        set_option("exits_grad_source", 1) (wost_exits_gradient_terms; include/wost.h "Exit lists of the gradient", item 4):
+        (T, seT, U), float64 arrays shaped (n, dim, 3), (n, dim, 3) and (n, 3), as exits_apply_gradient joins them to every set of
+        colours; zeros at a degenerate point.  Any other list is refused"""
+        fn, name = self._fn("exits_gradient_terms")
+        n = self.exits_done[0]
+        T, seT, U = np.zeros((max(n, 1), self._dim, 3)), np.zeros((max(n, 1), self._dim, 3)), np.zeros((max(n, 1), 3))
+        _check(fn(self._handle, *[a.ctypes.data_as(C.POINTER(C.c_double)) for a in (T, seT, U)]), name)
+        return T[:n], seT[:n], U[:n]
+
     def exits_adjoint_gradient(self, dgrad):
         """the transposed map of exits_apply_gradient's grad: dgrad ([K, n, dim, 3] floats; [n, dim, 3] is one set) -> the
         derivative of sum(grad * dgrad) by the colours, (K, n_verts, 6) float32"""

@@ -528,6 +528,31 @@ int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks);
  *     of M terms is within (M + S + 12) * 2^-52 * sum 2 |a| + 2^-24 |value| of the exact sum, a the term without its direction
  *     factor.  A scene without a Dirichlet mesh: WOST_ERR_UNSUPPORTED.  The derivative of field_rgb is wost_exits_adjoint on the
  *     same list.
+ *   4. The in-ball term on a scene with a source term ("The gradient on a scene with a source term" above).  The
+ *     handle's option "exits_grad_source" (wost_set_option, wost3_set_option; exactly 0, the default, or 1) is the door: with 0
+ *     a walk on such a scene is refused, with 1 it runs and THE LIST CARRIES THE TERM.  T, seT and U of that section do not depend
+ *     on the Dirichlet data, so the walk computes them once: after the kernels in front, in blocks of max(1, floor(width *
+ *     height / S)) points, the S in-ball samples per point of wost_solve_gradient_points (the same kernel, the same streams,
+ *     behind the direction draws) and a reduction that keeps per point, in fp64 and unrounded,
+ *         T_kc = (R / S) sum_s a_s,   seT_kc = R sqrt(sum_s (a_s - mean a)^2 / (S - 1) / S),   U_c = (R^2 / S) sum_s wu_s ms_sc
+ *     as that call forms them; a degenerate or non-finite point takes no samples and keeps +0.0 in all 6 DIM + 3.  Apply joins
+ *     them to every one of the K sets before the one rounding, in that call's order:  grad = walk part + T,  grad_stderr =
+ *     sqrt(walk part^2 + seT^2),  field_rgb = mean + U  (a degenerate point: NaN, NaN and its mean without U).  WITH THE HANDLE'S
+ *     OWN COLOURS THE THREE OUTPUTS ARE THOSE OF wost_solve_gradient_points AT spp = S WITH "grad_source" 1, BIT FOR BIT, and
+ *     with other colours those of a handle created with them -- S is still not bound by the frame.  The term is constant in the
+ *     colours: wost_exits_adjoint_gradient, wost_exits_index and the ordered adjoints are what they are without it, and
+ *     wost_exits_apply on such a list is the mean of the walks from the first points, without U.  The mode is the list's,
+ *     recorded at the walk: a later change of the option does not reach a bound list.  On a scene without a source term the
+ *     option changes nothing -- the same records, outputs and kernel_launches, no allocation and no launch more.  The term costs
+ *     8 * (6 * DIM + 3) bytes per point in the list; the samples of a block pass through a temporary of the call's own,
+ *     (DIM + 8) * max(width * height, S) floats, freed before it returns, so wost_solve_gradient_points and the carried gradient
+ *     list between walk and apply change nothing, nor does the walk change anything for them.  wost_stats of such a walk: the
+ *     five counters as without the term (the in-ball samples are no walks); kernel_ms includes the new launches;
+ *     kernel_launches = ceil(n / (width * height)) + 2 * ceil(n / B) + ceil(n * S / (width * height)), B the block above.
+ *   - wost_exits_gradient_terms: the term of the bound list into host arrays, T and seT n * DIM * 3 doubles, entry [i][axis][c],
+ *     U n * 3; any pointer may be NULL.  Refused, in this order: a null handle; no list bound; a plain list (the message names
+ *     wost_exits_walk_gradient); a list without the term (WOST_ERR_INVALID; the message names exits_grad_source).  With all
+ *     three pointers NULL it answers whether the bound list carries the term.
  *   - wost_exits_walk_gradient: host points; a non-finite coordinate is refused.  wost_exits_walk_gradient_dev: DEVICE points and
  *     the caller's stream (NULL = default stream); both return when the list stands.  n == 0 (pts may be NULL) releases the list.
  *     A call that is refused or fails leaves the old list as it was; an allocation that fails is WOST_ERR_NOMEM.  The list costs
@@ -544,10 +569,10 @@ int wost_exits_progress(wost_handle h, int32_t *n_points, int32_t *walks);
  *     with null points; walks < 2; seed_width <= 0; a negative seed; seed_base + n > 2^28; walk_seed_base + n * walks > 2^28 (in
  *     64 bits); [seed_base, seed_base + n) overlapping [walk_seed_base, walk_seed_base + n * walks); in the host form, the first
  *     non-finite point.  With the handle: a scene with a source term is WOST_ERR_UNSUPPORTED whatever the option "grad_source"
- *     says (the in-ball term does not depend on the Dirichlet data and is not carried in the list).  Of apply and adjoint: a null
+ *     says, unless the option "exits_grad_source" is 1 (item 4; the message names it).  Of apply and adjoint: a null
  *     handle, a null required array, K < 1, no list bound, a bound list without directions (WOST_ERR_INVALID; the message names
  *     wost_exits_walk_gradient) -- which wost_exits_gradient_records answers on a plain list too.
- * Not built: the in-ball term and scenes with a source term, adding walks to a list, shards of one list, saving a list, the
+ * Not built: adding walks to a list, shards of one list, saving a list, the
  * carried gradient list on top of exit lists, the guided integrators, the C++ host mirror, and Neumann or source data as
  * variables. */
 typedef struct wost_exit_gradient_records {   /* host arrays; any may be NULL */
@@ -563,6 +588,7 @@ int wost_exits_gradient_records(wost_handle h, const wost_exit_gradient_records 
 int wost_exits_apply_gradient(wost_handle h, const float *colors, int32_t K, float *grad, float *grad_stderr, float *field_rgb);
 int wost_exits_apply_gradient_dev(wost_handle h, const float *colors_dev, int32_t K, float *grad_dev, float *grad_stderr_dev,
                                   float *field_rgb_dev, void *stream);
+int wost_exits_gradient_terms(wost_handle h, double *T, double *seT, double *U);
 int wost_exits_adjoint_gradient(wost_handle h, const float *dgrad, int32_t K, float *dcolors);
 int wost_exits_adjoint_gradient_dev(wost_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
 
@@ -929,7 +955,9 @@ int wost_last_launches(wost_handle h, wost_launch_info *out, int32_t capacity, i
  * the total, so solving with spp = k reproduces the state of a longer solve after k samples: the
  * host mirror uses this for saveSppMetrics frames).
  * "grad_source" (exactly 0, the default, or 1) is no tuning knob: 1 lets the gradient calls take a scene with a source term
- * ("The gradient on a scene with a source term" above). */
+ * ("The gradient on a scene with a source term" above).
+ * "exits_grad_source" (exactly 0, the default, or 1) is none either: 1 lets wost_exits_walk_gradient take such a scene and carry
+ * the in-ball term in the list ("Exit lists of the gradient", item 4); a key of its own, read at the walk alone. */
 int wost_set_option(wost_handle h, const char *key, double value);
 
 int wost_destroy(wost_handle h);
@@ -1058,6 +1086,7 @@ int wost3_exits_gradient_records(wost3_handle h, const wost_exit_gradient_record
 int wost3_exits_apply_gradient(wost3_handle h, const float *colors, int32_t K, float *grad, float *grad_stderr, float *field_rgb);
 int wost3_exits_apply_gradient_dev(wost3_handle h, const float *colors_dev, int32_t K, float *grad_dev, float *grad_stderr_dev,
                                    float *field_rgb_dev, void *stream);
+int wost3_exits_gradient_terms(wost3_handle h, double *T, double *seT, double *U);
 int wost3_exits_adjoint_gradient(wost3_handle h, const float *dgrad, int32_t K, float *dcolors);
 int wost3_exits_adjoint_gradient_dev(wost3_handle h, const float *dgrad_dev, int32_t K, float *dcolors_dev, void *stream);
 /* The index and the ordered adjoint in 3-D: wost_exits_index & co. with the same rules in every clause (DIM = 3: three
@@ -1109,8 +1138,8 @@ int wost3_vmm_loss_gradients(int device, const float *raw, const float *dir, con
  * out_rgb width*height*3 floats (zeros without a source term) */
 int wost3_render_sdf(wost3_handle h, int which_mesh, float *out_dist);
 int wost3_render_source(wost3_handle h, float *out_rgb);
-/* The options of a 3-D handle, as wost_set_option: "grad_source" (0 / 1, the rules of wost_set_option's) is the only key; any other
- * is WOST_ERR_INVALID "unknown option: KEY", a null handle or key WOST_ERR_INVALID "null argument". */
+/* The options of a 3-D handle, as wost_set_option: "grad_source" and "exits_grad_source" (0 / 1 each, the rules of
+ * wost_set_option's) are the only keys; any other is WOST_ERR_INVALID "unknown option: KEY", a null handle or key WOST_ERR_INVALID "null argument". */
 int wost3_set_option(wost3_handle h, const char *key, double value);
 int wost3_destroy(wost3_handle h);
 
